@@ -12,14 +12,19 @@ on: **Quadruped (Unitree A1, flat terrain) Predictive Sampling, 16384 candidates
 out its own 16384 candidates of a global batch of N*16384 (weak scaling) and the ranks exchange
 (best cost, index) + the winner's spline.
 
-The same JSON line carries, in `extra`, one entry per further single-GPU BASELINE config so that one
-driver run covers them all: configs[1] (Cartpole PS 4096 x 128 fp64), configs[2] through the Cross-Entropy
-planner, configs[3] (Humanoid tracking PS, one GPU's 8192-candidate share, fp32) and configs[4] (one iLQG
-iteration on the Quadruped, with the CPU port's iteration time beside it).
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write the last step's
+outputs if --dump-outputs DIR is given, and print ONE JSON line (rank 0) with the fields of the driver
+contract plus `config` and `roofline` (both from the same timed steps).
 
-Prints ONE JSON line (rank 0) with the fields of the driver contract plus `roofline`, `cpu_baseline`, `extra`.
+--full adds everything else, each measured after the headline's timed steps or around them: `gpu_clock`
+(sclk / power sampled over the timed region, and a box probe), `cpu_baseline` and `target_check` (the CPU
+oracle on the host cores), and, in `extra`, one entry per further single-GPU BASELINE config: configs[1]
+(Cartpole PS 4096 x 128 fp64), configs[2] through the Cross-Entropy planner, configs[3] (Humanoid tracking
+PS, one GPU's 8192-candidate share, fp32), configs[0] (testspeed closed loop) and configs[4] (one iLQG
+iteration on the Quadruped, with the CPU port's iteration time beside it).
 """
 import argparse
+import contextlib
 import hashlib
 import json
 import os
@@ -53,9 +58,15 @@ def parse():
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="one GPU: time the share of every rank of a W-rank strong-scaling run in turn (N / W candidates at that rank's "
                          "candidate offset) -- what the per-rank time of --scaling strong will be before the hardware shows up")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the `extra` configs (they only run at --gpus 1)")
-    ap.add_argument("--no-box-probe", action="store_true", help="skip gpu_clock.box_probe (three library-kernel figures that tell the pool's kinds of box apart)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: gpu_clock, cpu_baseline + target_check and the `extra` configs (off by default: a plain run "
+                         "only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (the planner's policy and best trajectory) as DIR/<name>.npy, "
+                         "float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the `extra` configs (they only run at --gpus 1)")
+    ap.add_argument("--no-box-probe", action="store_true", help="with --full: skip gpu_clock.box_probe (three library-kernel figures that tell the pool's kinds of box apart)")
     ap.add_argument("--cpu-seconds", type=float, default=6.0)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher self-test without a device: rendezvous over gloo, the unique-id broadcast, the candidate split, the "
@@ -358,11 +369,36 @@ class ClockSampler:
         return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_outputs(planner, horizon):
+    """what a caller of the timed path receives after its last step: the policy (nominal spline) and the best trajectory with its
+    return, plus the winner's index and score, all as float64 arrays"""
+    times, nodes = planner.policy()
+    best = planner.best_trajectory(cap=max(512, horizon))
+    out = {"policy_times": times, "policy_values": nodes}
+    if best is not None:
+        out.update({"best_states": best["states"], "best_actions": best["actions"], "best_times": best["times"],
+                    "best_costs": best["costs"], "best_total_return": np.array([best["total_return"]])})
+    out["winner"] = np.array([planner.winner], np.float64)
+    out["best_score"] = np.array([planner.best_score])
+    return {k: np.ascontiguousarray(v, np.float64) for k, v in out.items()}
+
+
+def dump_outputs(directory, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def run_config(args, task_name, kind, candidates, horizon, precision, steps, warmup, world, local_rank, group, want_cpu, rank, native=None,
-               total=None):
+               total=None, dump_dir=None):
     """one BASELINE config through the C++ planner over the C ABI; returns the fields of a bench line. candidates: this rank's share;
-    total: the global batch (default candidates * world)"""
-    import torch
+    total: the global batch (default candidates * world); dump_dir: where rank 0 writes the last timed step's outputs"""
     from mujoco_mpc_amd import capi
     from mujoco_mpc_amd.hostplanner import HostPlanner
     from mujoco_mpc_amd.task import load_task
@@ -395,18 +431,21 @@ def run_config(args, task_name, kind, candidates, horizon, precision, steps, war
     P = planner.num_spline_points
     planner.set_state(qpos, qvel, 0.0, mocap_pos=mocap_pos, mocap_quat=mocap_quat)
 
+    torch = sys.modules.get("torch")   # (imported by main() for several ranks and for --full; a plain one-GPU run does without it)
+
     def fence():
         if group is not None:
             group.barrier()
         planner.sync()
-        if torch.cuda.is_available():
+        if torch is not None and torch.cuda.is_available():
             torch.cuda.synchronize()
 
     for _ in range(warmup):
         planner.optimize_policy(H)
     fence()
     planner.timing_reset()
-    with ClockSampler(local_rank) as clocks:
+    clocks = ClockSampler(local_rank) if args.full else None
+    with clocks or contextlib.nullcontext():
         t0 = time.perf_counter()
         for _ in range(steps):
             planner.optimize_policy(H)
@@ -422,6 +461,8 @@ def run_config(args, task_name, kind, candidates, horizon, precision, steps, war
     if rank != 0:
         planner.close()
         return None
+    if dump_dir is not None:
+        dump_outputs(dump_dir, last_step_outputs(planner, H))
     bytes_per_launch = planner.algorithmic_bytes(H, P) * candidates
     avg_kernel_s = main_ms / max(launches, 1) * 1e-3      # the kernel that rolls the batch out (the roofline's kernel)
     avg_rollout_s = kernel_ms / max(launches, 1) * 1e-3   # + the pass over the candidates it handed on / the lane family's sensor stage
@@ -450,9 +491,10 @@ def run_config(args, task_name, kind, candidates, horizon, precision, steps, war
                              "wavefront-per-candidate kernel. The contact models are latency / issue-bound, not HBM-bound (DESIGN.md 4): see `valu`"},
     }
     del interp
-    out["gpu_clock"] = clocks.summary()
-    if out["gpu_clock"] is not None and not getattr(args, "no_box_probe", False):
-        out["gpu_clock"]["box_probe"] = box_probe(local_rank)
+    if clocks is not None:
+        out["gpu_clock"] = clocks.summary()
+        if out["gpu_clock"] is not None and not getattr(args, "no_box_probe", False):
+            out["gpu_clock"]["box_probe"] = box_probe(local_rank)
     pmc = pmc_summary(task_name, candidates, H, precision)
     if pmc is not None:
         out["roofline"]["traffic"] = pmc.get("hbm_bytes_per_launch")
@@ -812,7 +854,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
     if args.dry_run:
         return dry_run(args, rank, world)
-    import torch
+    if world > 1 or args.full:
+        import torch
 
     group = None
     native = None
@@ -832,7 +875,7 @@ def main():
                 uid.copy_(torch.frombuffer(bytearray(comm_unique_id()), dtype=torch.uint8))
             dist.broadcast(uid, src=0)
             native = (bytes(uid.cpu().numpy().tobytes()), rank, world)
-    elif torch.cuda.is_available():
+    elif args.full and torch.cuda.is_available():
         torch.cuda.set_device(local_rank)
 
     n0, h0, _ = BASELINE_SIZE.get(args.task, (4096, 128, ""))
@@ -845,12 +888,15 @@ def main():
     if args.emulate_world > 1 and world == 1:
         return emulate_strong(args, candidates, H, local_rank)
     main_line = run_config(args, args.task, args.planner, candidates, H, args.precision, args.steps, args.warmup, world, local_rank,
-                           group, want_cpu=not args.no_cpu_baseline and world == 1, rank=rank, native=native, total=total)
+                           group, want_cpu=args.full and not args.no_cpu_baseline and world == 1, rank=rank, native=native, total=total,
+                           dump_dir=args.dump_outputs)
     if rank == 0:
         out = {"metric": "candidate-trajectory rollouts/sec (fixed horizon)", "value": main_line["value"], "unit": "rollouts/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_line["ms_per_step"],
                "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": main_line["dtype"], "data": "synthetic",
-               "config": main_line["config"], "roofline": main_line["roofline"], "gpu_clock": main_line.get("gpu_clock")}
+               "config": main_line["config"], "roofline": main_line["roofline"]}
+        if args.full:
+            out["gpu_clock"] = main_line.get("gpu_clock")
         if "cpu_baseline" in main_line:
             out["cpu_baseline"] = main_line["cpu_baseline"]
             cb = main_line["cpu_baseline"]
@@ -861,7 +907,7 @@ def main():
                                            "and the whole probe are in cpu_baseline.host / .probe"}
         default_run = (args.task == "QuadrupedFlat" and args.planner == "sampling" and not args.candidates and not args.horizon
                        and args.precision == 64)
-        if world == 1 and default_run and not args.no_extra:
+        if world == 1 and default_run and args.full and not args.no_extra:
             extra = []
             for name, task_name, kind, prec, steps in (("configs[1]", "Cartpole", "sampling", 64, 50),
                                                        ("configs[2] (Cross-Entropy planner)", "QuadrupedFlat", "cross_entropy", 64, 5),

@@ -6,7 +6,7 @@
 #   stamps  phase stamps of wavefront 0 of the quad kernel over the first plan steps of the bench (MJPCX_QUAD_STAMPS), and of the limb kernel on
 #           configs[3] (MJPCX_LIMB_STAMPS)
 #   fuzz    the random-state parity sweeps (tools/fuzz_quad.py, fuzz_humanoid.py through both Humanoid kernels, fuzz_ilqg.py)
-#   bench   the default bench line with its extras
+#   bench   the full bench line (--full: gpu_clock, cpu_baseline and the extras)
 #   trace   rocprofv3 --kernel-trace --stats of the bench command
 #   ilqg    kernel trace of the iLQG iteration
 # Files land in gpurun_out/$ROUND/ (merged back by gpurun); copy them to profiles/ and commit.
@@ -25,7 +25,7 @@ fi
 cd $R
 if has stamps; then MJPCX_QUAD_STAMPS=1 timeout 300 python bench.py --steps 10 --warmup 0 --no-extra --no-cpu-baseline > $O/stamps_line.json 2> $O/quad_stamps.log; grep -c "cycles of wavefront" $O/quad_stamps.log; fi
 if has stamps; then MJPCX_LIMB_STAMPS=1 MJPCX_QUAD_STATS=1 timeout 300 python bench.py --task HumanoidTrack --precision 32 --steps 6 --warmup 1 --no-extra --no-cpu-baseline > $O/limb_stamps_line.json 2> $O/limb_stamps.log; grep -c "cycles of wavefront" $O/limb_stamps.log; fi
-if has bench; then timeout 900 python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 1500 $O/bench_line.json; fi
+if has bench; then timeout 900 python bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -c 1500 $O/bench_line.json; fi
 cd /tmp && export TMPDIR=/tmp
 if has trace; then
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --no-extra --no-cpu-baseline > $O/trace.log 2>&1
