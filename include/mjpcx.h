@@ -397,6 +397,17 @@ int mjpcx_backward_pass(mjpcx_ctx* ctx, int n, int m, int T, double mu, int reg_
                         double* Vx, double* Vxx, double* K, double* du, double* dV, int32_t* status,
                         double* kernel_ms);
 
+/* The Gradient planner's first-order pass (mjpc/planners/gradient): Gradient::Compute (gradient.cc:43-108) -- Vx[T-1] = cx[T-1],
+ * Qx = cx[t] + A[t]^T Vx[t+1], Qu = cu[t] + B[t]^T Vx[t+1], k[t] = -Qu, Vx[t] = Qx, dV[0] += k[t] . Qu for t = T-2..0, k[T-1] = k[T-2] --
+ * and its projection onto the spline parameters, gradient = M^T k (gradient/planner.cc:247-257), M the representation's spline
+ * mapping (spline_mapping.cc; 0 zero-order, 1 linear, 2 cubic) from the P node_times to the first T-1 step_times. A, B, cx, cu as
+ * for mjpcx_backward_pass; outputs Vx (T x n), k (T x m), dV[2] (dV[1] = 0), gradient (P x m). One launch, fp64 on every context.
+ * MJPCX_EUNSUPPORTED beyond n <= 48, m <= 16, P <= 25, T <= 512; MJPCX_EINVAL for n, m, P < 1, T < 2, another representation, or
+ * node_times not strictly increasing. kernel_ms (optional): HIP-event time of the kernel. */
+int mjpcx_gradient_pass(mjpcx_ctx* ctx, int n, int m, int T, const double* A, const double* B, const double* cx,
+                        const double* cu, int representation, int P, const double* node_times, const double* step_times,
+                        double* Vx, double* k, double* dV, double* gradient, double* kernel_ms);
+
 /* ---- measurement --------------------------------------------------------------
  * HIP-event timing of the rollout kernel on the context's own stream.
  * mjpcx_timing_reset zeroes the accumulators; mjpcx_timing_read synchronises and

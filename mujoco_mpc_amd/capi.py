@@ -25,7 +25,7 @@ EXPORTS = [
     "mjpcx_kernel_name", "mjpcx_set_state", "mjpcx_set_task_params", "mjpcx_set_residual_state", "mjpcx_rollout_splines",
     "mjpcx_rollout_noise", "mjpcx_rollout_splines_noisy", "mjpcx_kinematics", "mjpcx_sync", "mjpcx_get_returns", "mjpcx_get_return_at", "mjpcx_best", "mjpcx_topk", "mjpcx_elite_moments", "mjpcx_fetch_trajectory",
     "mjpcx_fetch_spline", "mjpcx_rollout_feedback", "mjpcx_transition_fd", "mjpcx_cost_derivatives",
-    "mjpcx_backward_pass", "mjpcx_timing_reset", "mjpcx_timing_read", "mjpcx_timing_read_main", "mjpcx_quad_stats", "mjpcx_algorithmic_bytes",
+    "mjpcx_backward_pass", "mjpcx_gradient_pass", "mjpcx_timing_reset", "mjpcx_timing_read", "mjpcx_timing_read_main", "mjpcx_quad_stats", "mjpcx_algorithmic_bytes",
     "mjpcx_device_buffer", "mjpcx_comm_unique_id", "mjpcx_comm_init", "mjpcx_comm_info", "mjpcx_exchange_best", "mjpcx_merge_topk",
     "mjpcx_elite_allreduce", "mjpcx_comm_barrier", "mjpcx_comm_destroy",
 ]
@@ -80,6 +80,8 @@ def lib():
         L.mjpcx_cost_derivatives.argtypes = [vp, C.c_int] + [c_f64p] * 8
         L.mjpcx_backward_pass.argtypes = ([vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [c_f64p] * 14 +
                                           [c_i32p, C.POINTER(C.c_double)])
+        L.mjpcx_gradient_pass.argtypes = ([vp, C.c_int, C.c_int, C.c_int] + [c_f64p] * 4 + [C.c_int, C.c_int] + [c_f64p] * 6 +
+                                          [C.POINTER(C.c_double)])
         L.mjpcx_timing_reset.argtypes = [vp]
         L.mjpcx_timing_read.argtypes = [vp, c_f64p, C.POINTER(C.c_int64)]
         L.mjpcx_timing_read_main.argtypes = [vp, c_f64p, C.POINTER(C.c_int64)]
@@ -309,6 +311,16 @@ class Context:
                                             as_f64p(Vx), as_f64p(Vxx), as_f64p(K), as_f64p(du), as_f64p(dV), as_i32p(st),
                                             C.byref(ms)))
         return dict(ok=bool(st[0]), Vx=Vx, Vxx=Vxx, K=K, du=du, dV=dV, kernel_ms=ms.value)
+
+    def gradient_pass(self, A, B, cx, cu, representation, node_times, step_times):
+        """Gradient::Compute + the spline-mapping projection (mjpcx_gradient_pass): Vx, k, dV, gradient (P x m)"""
+        T, n, m, P = A.shape[0], A.shape[1], B.shape[2], len(node_times)
+        Vx, k, dV, g = np.zeros((T, n)), np.zeros((T, m)), np.zeros(2), np.zeros((P, m))
+        ms = C.c_double()
+        args = [as_f64p(_f(x).reshape(-1)) for x in (A, B, cx, cu)]
+        self._chk(lib().mjpcx_gradient_pass(self.handle, n, m, T, *args, int(representation), P, as_f64p(_f(node_times)),
+                                            as_f64p(_f(step_times)), as_f64p(Vx), as_f64p(k), as_f64p(dV), as_f64p(g), C.byref(ms)))
+        return dict(Vx=Vx, k=k, dV=dV, gradient=g, kernel_ms=ms.value)
 
     def timing_reset(self):
         self._chk(lib().mjpcx_timing_reset(self.handle))

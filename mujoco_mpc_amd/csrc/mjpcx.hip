@@ -18,6 +18,7 @@
 #include "rollout_lane.h"
 #include "lane_registry.h"
 #include "ilqg_dense.h"
+#include "gradient_pass.h"
 #include "rollout_wave.h"
 #include "quad_launch.h"
 #include "limb_launch.h"
@@ -1974,6 +1975,52 @@ int mjpcx_backward_pass(mjpcx_ctx* c, int n, int m, int T, double mu, int reg_ty
     std::fprintf(stderr, "backward_pass phase cycles (second step): stage %lld gemm %lld reg %lld du/qp %lld Kcols %lld update %lld write %lld\n",
                  h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3], h[5] - h[4], h[6] - h[5], h[7] - h[6]);
   }
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  if (kernel_ms) *kernel_ms = ms;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return MJPCX_OK;
+}
+
+int mjpcx_gradient_pass(mjpcx_ctx* c, int n, int m, int T, const double* A, const double* B, const double* cx, const double* cu,
+                        int representation, int P, const double* node_times, const double* step_times, double* Vx, double* k,
+                        double* dV, double* gradient, double* kernel_ms) {
+  if (!c || !A || !B || !cx || !cu || !node_times || !step_times || !Vx || !k || !dV || !gradient)
+    return fail(c, MJPCX_EINVAL, "null argument");
+  if (n < 1 || m < 1 || T < 2 || P < 1) return fail(c, MJPCX_EINVAL, "gradient pass needs n >= 1, m >= 1, T >= 2, P >= 1");
+  if (n > kGradMaxN || m > kGradMaxM || P > kGradMaxP || T > kGradMaxT)
+    return fail(c, MJPCX_EUNSUPPORTED, "gradient pass kernel covers n <= 48, m <= 16, P <= 25 (kMaxGradientSplinePoints), T <= 512 (kMaxTrajectoryHorizon)");
+  if (representation < 0 || representation > 2) return fail(c, MJPCX_EINVAL, "representation must be 0 (zero-order), 1 (linear) or 2 (cubic)");
+  for (int i = 1; i < P; i++)
+    if (!(node_times[i] > node_times[i - 1])) return fail(c, MJPCX_EINVAL, "node times must be strictly increasing");
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double*> d;
+  int rc;
+  const size_t sn = n, sm = m, sT = T, sP = P;
+  if ((rc = upload_arrays<double>(c, c->d_ilqg, {{A, sT * sn * sn}, {B, sT * sn * sm}, {cx, sT * sn}, {cu, sT * sm}, {node_times, sP},
+                                                 {step_times, sT}}, &d)) != MJPCX_OK)
+    return rc;
+  const size_t n_out = sT * (sn + sm) + 2 + sP * sm;
+  HIPCHK(c, c->d_ilqg_out.reserve(n_out * 8));
+  GradientArgs a{};
+  a.n = n; a.m = m; a.T = T; a.P = P; a.representation = representation;
+  a.A = d[0]; a.B = d[1]; a.cx = d[2]; a.cu = d[3]; a.node_times = d[4]; a.step_times = d[5];
+  a.Vx = (double*)c->d_ilqg_out.p; a.k = a.Vx + sT * sn; a.dV = a.k + sT * sm; a.gradient = a.dV + 2;
+  const size_t lds = gradient_pass_lds_bytes(T, m, P);
+  HIPCHK(c, hipFuncSetAttribute((const void*)gradient_pass_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipEvent_t e0, e1;
+  HIPCHK(c, hipEventCreate(&e0));
+  HIPCHK(c, hipEventCreate(&e1));
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  hipLaunchKernelGGL(gradient_pass_kernel, dim3(1), dim3(64), lds, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, hipMemcpyAsync(Vx, a.Vx, sT * sn * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(k, a.k, sT * sm * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dV, a.dV, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(gradient, a.gradient, sP * sm * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   float ms = 0;
   (void)hipEventElapsedTime(&ms, e0, e1);
   if (kernel_ms) *kernel_ms = ms;

@@ -130,47 +130,6 @@ void GpuILQGPlanner::NominalTrajectory(int horizon, ThreadPool& pool) {
   nominal_compute_time = GetDuration(start);
 }
 
-// ModelDerivatives::Compute with skip + linear interpolation (model_derivatives.cc:45-165)
-void GpuILQGPlanner::ModelDerivatives(const Trajectory& tr, int T) {
-  const int n = dim_state_derivative, m = dim_action, nr = dim_sensor, ds = dim_state;
-  const int s = derivative_skip_ + 1;
-  std::vector<int> evaluate;
-  evaluate.push_back(0);
-  for (int t = s; t < T - s; t += s) evaluate.push_back(t);
-  evaluate.push_back(T - 2);
-  evaluate.push_back(T - 1);
-  std::sort(evaluate.begin(), evaluate.end());
-  evaluate.erase(std::unique(evaluate.begin(), evaluate.end()), evaluate.end());
-  evaluate.erase(std::remove_if(evaluate.begin(), evaluate.end(), [T](int e) { return e < 0 || e >= T; }), evaluate.end());
-  const int E = (int)evaluate.size();
-  etimes_.resize(E); estates_.resize((size_t)E * ds); eactions_.resize((size_t)E * m);
-  for (int k = 0; k < E; k++) {
-    const int t = evaluate[k];
-    etimes_[k] = tr.times[t];
-    std::copy_n(tr.states.begin() + (size_t)t * ds, ds, estates_.begin() + (size_t)k * ds);
-    std::copy_n(tr.actions.begin() + (size_t)t * m, m, eactions_.begin() + (size_t)k * m);
-  }
-  const size_t sA = (size_t)n * n, sB = (size_t)n * m, sC = (size_t)nr * n, sD = (size_t)nr * m;
-  eA_.resize(E * sA); eB_.resize(E * sB); eC_.resize(E * sC); eD_.resize(E * sD);
-  ctx_->Check(mjpcx_transition_fd(ctx_->handle(), E, etimes_.data(), estates_.data(), eactions_.data(), settings.fd_tolerance,
-                                  settings.fd_mode != 0, eA_.data(), eB_.data(), eC_.data(), eD_.data()));
-  A_.assign(T * sA, 0.0); B_.assign(T * sB, 0.0); C_.assign(T * sC, 0.0); D_.assign(T * sD, 0.0);
-  int k = 0;
-  for (int t = 0; t < T; t++) {
-    while (k + 1 < E && evaluate[k + 1] <= t) k++;
-    const int e0 = k, e1 = std::min(k + 1, E - 1);
-    const double tt = (evaluate[e0] == t || e0 == e1) ? 0.0 : double(t - evaluate[e0]) / double(evaluate[e1] - evaluate[e0]);
-    auto mix = [&](std::vector<double>& full, const std::vector<double>& ev, size_t sz) {
-      for (size_t i = 0; i < sz; i++) full[t * sz + i] = ev[e0 * sz + i] * (1.0 - tt) + ev[e1 * sz + i] * tt;
-    };
-    mix(A_, eA_, sA); mix(B_, eB_, sB); mix(C_, eC_, sC); mix(D_, eD_, sD);
-  }
-  // the last step has no transition: model_derivatives.cc:88-92 computes only C there
-  std::fill(A_.begin() + (T - 1) * sA, A_.end(), 0.0);
-  std::fill(B_.begin() + (T - 1) * sB, B_.end(), 0.0);
-  std::fill(D_.begin() + (T - 1) * sD, D_.end(), 0.0);
-}
-
 // ilqg/planner.cc:377-627
 void GpuILQGPlanner::Iteration(int horizon, ThreadPool& pool) {
   iLQGPolicy& c0 = candidate_policy0;
@@ -181,14 +140,15 @@ void GpuILQGPlanner::Iteration(int horizon, ThreadPool& pool) {
   ctx_->SyncTask(*task);
 
   auto start = std::chrono::steady_clock::now();
-  ModelDerivatives(tr, T);
+  model_derivative_.Compute(ctx_.get(), tr, T, derivative_skip_, settings.fd_tolerance, settings.fd_mode != 0, n, m, dim_sensor,
+                            dim_state);
   model_derivative_compute_time = GetDuration(start);
 
   start = std::chrono::steady_clock::now();
   cx_.resize((size_t)T * n); cu_.resize((size_t)T * m); cxx_.resize((size_t)T * n * n); cxu_.resize((size_t)T * n * m);
   cuu_.resize((size_t)T * m * m);
-  ctx_->Check(mjpcx_cost_derivatives(ctx_->handle(), T, tr.residual.data(), C_.data(), D_.data(), cx_.data(), cu_.data(),
-                                     cxx_.data(), cxu_.data(), cuu_.data()));
+  ctx_->Check(mjpcx_cost_derivatives(ctx_->handle(), T, tr.residual.data(), model_derivative_.C.data(), model_derivative_.D.data(),
+                                     cx_.data(), cu_.data(), cxx_.data(), cxu_.data(), cuu_.data()));
   cost_derivative_compute_time = GetDuration(start);
 
   // ---- backward pass with regularisation retries (planner.cc:429-520)
@@ -200,7 +160,8 @@ void GpuILQGPlanner::Iteration(int horizon, ThreadPool& pool) {
   while (reg_iter < settings.max_regularization_iterations && !ok) {
     std::int32_t status = 0;
     ctx_->Check(mjpcx_backward_pass(ctx_->handle(), n, m, T, regularization, settings.regularization_type, settings.action_limits,
-                                    A_.data(), B_.data(), cx_.data(), cu_.data(), cxx_.data(), cxu_.data(), cuu_.data(),
+                                    model_derivative_.A.data(), model_derivative_.B.data(), cx_.data(), cu_.data(), cxx_.data(),
+                                    cxu_.data(), cuu_.data(),
                                     tr.actions.data(), model->actuator_ctrlrange, Vx_.data(), Vxx_.data(), K_.data(), du_.data(),
                                     dv, &status, nullptr));
     ok = status != 0;

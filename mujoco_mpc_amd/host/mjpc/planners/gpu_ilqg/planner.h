@@ -6,13 +6,15 @@
 //   CostDerivatives::Compute           cost_derivatives.cc:112-230 -> mjpcx_cost_derivatives
 //   iLQGBackwardPass::Riccati          ilqg/backward_pass.cc:253-324 -> mjpcx_backward_pass (MFMA f64)
 // On the host, as in the reference: the regularisation schedule (backward_pass.cc:327-356), BestRollout
-// (planner.cc:727-740), derivative skip + interpolation (model_derivatives.cc:108-165), policy bookkeeping.
+// (planner.cc:727-740), derivative skip + interpolation (model_derivatives.cc:108-165, GpuModelDerivatives), policy
+// bookkeeping.
 #pragma once
 #include <memory>
 #include <shared_mutex>
 #include <vector>
 
 #include "../../gpu/context.h"
+#include "../gpu_model_derivatives.h"
 #include "../planner.h"
 #include "policy.h"
 #include "settings.h"
@@ -68,12 +70,11 @@ class GpuILQGPlanner : public Planner {
 
  private:
   void LineSearchSteps();
-  void ModelDerivatives(const Trajectory& tr, int T);
   void TakeTrajectory(iLQGPolicy* p, int index);
   int device_, precision_;
   std::unique_ptr<gpu::Context> ctx_;
-  std::vector<double> A_, B_, C_, D_, cx_, cu_, cxx_, cxu_, cuu_, Vx_, Vxx_, K_, du_;
-  std::vector<double> eA_, eB_, eC_, eD_, etimes_, estates_, eactions_;
+  GpuModelDerivatives model_derivative_;
+  std::vector<double> cx_, cu_, cxx_, cxu_, cuu_, Vx_, Vxx_, K_, du_;
   std::vector<double> returns_;
   std::vector<std::int32_t> failure_;
   iLQGPolicy winner_policy_;

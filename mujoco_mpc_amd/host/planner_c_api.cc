@@ -1,11 +1,12 @@
 // planner_c_api.cc -- a thin extern "C" view of the C++ GPU planners (mjpc::GpuSamplingPlanner,
-// mjpc::GpuCrossEntropyPlanner, mjpc::GpuILQGPlanner) for non-C++ drivers: bench.py and the pytest suite drive the
-// C++ planners through it with ctypes; the planner logic itself stays in C++.
+// mjpc::GpuCrossEntropyPlanner, mjpc::GpuILQGPlanner, mjpc::GpuGradientPlanner, ...) for non-C++ drivers: bench.py and the pytest
+// suite drive the C++ planners through it with ctypes; the planner logic itself stays in C++.
 #include <cstring>
 #include <memory>
 #include <string>
 
 #include "mjpc/planners/gpu_cross_entropy/planner.h"
+#include "mjpc/planners/gpu_gradient/planner.h"
 #include "mjpc/planners/gpu_ilqg/planner.h"
 #include "mjpc/planners/gpu_sampling/planner.h"
 #include "mjpc/planners/gpu_robust/robust_planner.h"
@@ -22,12 +23,15 @@ struct Handle {
   mjpc::GpuSamplingPlanner* ps = nullptr;       // exactly one of these three is set
   mjpc::GpuCrossEntropyPlanner* ce = nullptr;
   mjpc::GpuILQGPlanner* ilqg = nullptr;
+  mjpc::GpuGradientPlanner* gradient = nullptr;
   mjpc::GpuRobustPlanner* robust = nullptr;
   mjpc::GpuSampleGradientPlanner* sg = nullptr;     // wraps a GpuSamplingPlanner: `ps` then points at its delegate
   mjpc::State state;
   mjpc::ThreadPool pool{1};
   std::string error;
-  mjpc::gpu::Context* context() { return ps ? ps->context() : ce ? ce->context() : sg ? sg->context() : ilqg->context(); }
+  mjpc::gpu::Context* context() {
+    return ps ? ps->context() : ce ? ce->context() : sg ? sg->context() : gradient ? gradient->context() : ilqg->context();
+  }
 };
 thread_local std::string g_error;
 }  // namespace
@@ -36,7 +40,8 @@ extern "C" {
 
 const char* mjpc_planner_last_error(void* h) { return h ? static_cast<Handle*>(h)->error.c_str() : g_error.c_str(); }
 
-// kind: "sampling" | "cross_entropy" | "ilqg". num_trajectory > 0 overrides the model's custom numeric.
+// kind: "sampling" | "cross_entropy" | "ilqg" | "gradient" | "sample_gradient" | "robust". num_trajectory > 0 overrides the
+// model's custom numeric.
 void* mjpc_planner_create_kind(const char* kind, const char* blob_path, const char* task_name, int device, int precision,
                                unsigned long long seed, int num_trajectory) {
   try {
@@ -56,6 +61,9 @@ void* mjpc_planner_create_kind(const char* kind, const char* blob_path, const ch
     } else if (k == "ilqg") {
       h->ilqg = new mjpc::GpuILQGPlanner(device, precision);
       h->planner.reset(h->ilqg);
+    } else if (k == "gradient") {
+      h->gradient = new mjpc::GpuGradientPlanner(device, precision);
+      h->planner.reset(h->gradient);
     } else if (k == "sample_gradient") {
       h->sg = new mjpc::GpuSampleGradientPlanner(device, precision, seed);
       h->planner.reset(h->sg);
@@ -73,6 +81,7 @@ void* mjpc_planner_create_kind(const char* kind, const char* blob_path, const ch
       if (h->sg) h->sg->num_trajectory_ = num_trajectory;
       if (h->ce) { h->ce->num_trajectory_ = num_trajectory; h->ce->n_elite_ = std::max(num_trajectory / 10, 2); }
       if (h->ilqg) h->ilqg->num_rollouts_gui_ = h->ilqg->num_trajectory_ = num_trajectory;
+      if (h->gradient) h->gradient->num_trajectory = num_trajectory;
     }
     h->planner->Allocate();
     h->state.Allocate(h->storage->model());
@@ -168,6 +177,16 @@ int mjpc_planner_task_transition_state(void* h, double time, int mode, double* q
 void mjpc_host_gaussian_pair(unsigned long long seed, unsigned cand, unsigned pair, unsigned iter, double* z) {
   mjpc::HostGaussianPair(seed, cand, pair, iter, z);
 }
+// GradientPolicy::Action before the clamp (gradient/policy.cc:81-103) with the reference's interpolators (utilities.h), exported for
+// the tests that pin the spline mapping and the device's spline semantics to them
+void mjpc_gradient_policy_interpolation(int representation, double x, const double* xs, const double* ys, int dim, int length,
+                                        double* out) {
+  int b[2];
+  mjpc::FindInterval(b, xs, x, length);
+  if (b[0] == b[1] || representation == 0) mjpc::ZeroInterpolation(out, x, xs, ys, dim, length);
+  else if (representation == 1) mjpc::LinearInterpolation(out, x, xs, ys, dim, length);
+  else mjpc::CubicInterpolation(out, x, xs, ys, dim, length);
+}
 // SampleGradientPlanner: number of gradient candidates / filter; its last gradient estimate and winner type
 int mjpc_planner_sample_gradient_config(void* h, int num_gradient, double gradient_filter) {
   GUARD(h, {
@@ -182,6 +201,48 @@ int mjpc_planner_sample_gradient_result(void* h, int* winner_type, double* gradi
     *winner_type = H->sg->winner_type_;
     for (int i = 0; i < n && i < (int)H->sg->gradient.size(); i++) gradient[i] = H->sg->gradient[i];
     for (int i = 0; i < nret && i < (int)H->sg->returns.size(); i++) returns[i] = H->sg->returns[i];
+  });
+}
+// GradientPlanner: settings (negative keeps the current value) and the outcome of its last OptimizePolicy; gradient = the
+// parameter_update M^T k of the resampled nominal (P x nu, up to n values)
+int mjpc_planner_gradient_set(void* h, int representation, int derivative_skip, int num_spline_points, int num_trajectory) {
+  GUARD(h, {
+    if (!H->gradient) throw std::runtime_error("not a gradient planner");
+    auto* p = H->gradient;
+    if (representation >= 0) {
+      if (representation > 2) throw std::runtime_error("representation must be 0, 1 or 2");
+      for (auto* q : {&p->policy, &p->previous_policy, &p->candidate_policy0}) q->representation = (mjpc::spline::SplineInterpolation)representation;
+    }
+    if (derivative_skip >= 0) p->derivative_skip_ = derivative_skip;
+    if (num_spline_points > 0) {
+      if (num_spline_points > mjpc::kMaxGradientSplinePoints) throw std::runtime_error("at most 25 spline points");
+      for (auto* q : {&p->policy, &p->previous_policy, &p->candidate_policy0}) q->num_spline_points = num_spline_points;
+    }
+    if (num_trajectory > 0) p->num_trajectory = num_trajectory;
+  });
+}
+int mjpc_planner_gradient_result(void* h, int* winner, double* action_step, double* expected, double* improvement, double* gradient,
+                                 int n) {
+  GUARD(h, {
+    if (!H->gradient) throw std::runtime_error("not a gradient planner");
+    auto* p = H->gradient;
+    *winner = p->winner;
+    *action_step = p->action_step;
+    *expected = p->expected;
+    *improvement = p->improvement;
+    const int np = p->candidate_policy0.num_spline_points * p->dim_action;
+    for (int i = 0; i < n && i < np; i++) gradient[i] = p->candidate_policy0.parameter_update[i];
+  });
+}
+// GradientPlanner: per-stage times of the last OptimizePolicy [us] (nominal, model derivatives, cost derivatives, gradient,
+// rollouts, policy update) and the HIP-event time of its gradient-pass kernel [ms]
+int mjpc_planner_gradient_timers(void* h, double* out) {
+  GUARD(h, {
+    if (!H->gradient) throw std::runtime_error("not a gradient planner");
+    auto* p = H->gradient;
+    const double v[7] = {p->nominal_compute_time, p->model_derivative_compute_time, p->cost_derivative_compute_time,
+                         p->gradient_compute_time, p->rollouts_compute_time, p->policy_update_compute_time, p->gradient_kernel_ms};
+    std::memcpy(out, v, sizeof v);
   });
 }
 // RobustPlanner knobs and the outcome of its last OptimizePolicy (scores: ncandidates mean perturbed returns)
@@ -218,16 +279,19 @@ int mjpc_planner_action_state(void* h, const double* state, double time, int use
 int mjpc_planner_num_parameters(void* h) { return static_cast<Handle*>(h)->planner->NumParameters(); }
 int mjpc_planner_num_spline_points(void* h) {
   Handle* H = static_cast<Handle*>(h);
+  if (H->gradient) return H->gradient->policy.num_spline_points;
   return H->ps ? H->ps->policy.num_spline_points : H->ce ? H->ce->policy.num_spline_points : H->sg ? H->sg->policy.num_spline_points : 0;
 }
 int mjpc_planner_winner(void* h) {
   Handle* H = static_cast<Handle*>(h);
   if (H->sg) return H->sg->winner;
+  if (H->gradient) return H->gradient->winner;
   return H->ps ? H->ps->winner : H->ilqg ? H->ilqg->winner : (H->ce->trajectory_order.empty() ? -1 : H->ce->trajectory_order[0]);
 }
 double mjpc_planner_improvement(void* h) {
   Handle* H = static_cast<Handle*>(h);
   if (H->sg) return H->sg->improvement;
+  if (H->gradient) return H->gradient->improvement;
   return H->ps ? H->ps->improvement : H->ce ? H->ce->improvement : H->ilqg->improvement;
 }
 double mjpc_planner_best_score(void* h) {
@@ -235,10 +299,20 @@ double mjpc_planner_best_score(void* h) {
   if (H->sg) return H->sg->returns.empty() ? 0.0 : H->sg->returns[H->sg->winner];
   return H->ps ? H->ps->CandidateScore(0) : 0.0;
 }
-// policy spline nodes (sampling / cross-entropy): returns the node count; copies up to `cap` nodes
+// policy spline nodes (sampling / cross-entropy / gradient): returns the node count; copies up to `cap` nodes
 int mjpc_planner_policy(void* h, double* times, double* values, int cap) {
   Handle* H = static_cast<Handle*>(h);
   if (H->ilqg) return 0;
+  if (H->gradient) {
+    const std::shared_lock<std::shared_mutex> lock(H->gradient->mtx_);
+    const auto& p = H->gradient->policy;
+    const int nu = H->storage->model()->nu;
+    for (int k = 0; k < p.num_spline_points && k < cap; k++) {
+      times[k] = p.times[k];
+      std::memcpy(values + (size_t)k * nu, p.parameters.data() + (size_t)k * nu, sizeof(double) * nu);
+    }
+    return p.num_spline_points;
+  }
   const auto& plan = H->ps ? H->ps->policy.plan : H->sg ? H->sg->policy.plan : H->ce->policy.plan;
   const int n = (int)plan.Size(), nu = H->storage->model()->nu;
   for (int k = 0; k < n && k < cap; k++) {

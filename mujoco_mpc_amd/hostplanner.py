@@ -1,4 +1,5 @@
-"""ctypes view of the C++ planners `mjpc::GpuSamplingPlanner`, `mjpc::GpuCrossEntropyPlanner` and `mjpc::GpuILQGPlanner`
+"""ctypes view of the C++ planners `mjpc::GpuSamplingPlanner`, `mjpc::GpuCrossEntropyPlanner`, `mjpc::GpuILQGPlanner`,
+`mjpc::GpuGradientPlanner` and the others
 (mujoco_mpc_amd/host, planner_c_api.cc).
 
 The planner logic (nominal resampling, policy bookkeeping, C-ABI calls) is the C++ host layer; Python
@@ -14,7 +15,7 @@ import numpy as np
 
 from . import capi, mjcf
 from .build import build_host
-from .cstructs import as_f64p, c_f64p
+from .cstructs import MjpcxTrajView, as_f64p, c_f64p
 
 _LIB = None
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int)
@@ -53,6 +54,11 @@ def lib():
         L.mjpc_planner_robust_config.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double]
         L.mjpc_planner_sample_gradient_config.argtypes = [vp, C.c_int, C.c_double]
         L.mjpc_planner_sample_gradient_result.argtypes = [vp, C.POINTER(C.c_int), c_f64p, C.c_int, c_f64p, C.c_int]
+        L.mjpc_planner_gradient_set.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.mjpc_planner_gradient_result.argtypes = [vp, C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 3 + [c_f64p, C.c_int]
+        L.mjpc_planner_gradient_timers.argtypes = [vp, c_f64p]
+        L.mjpc_gradient_policy_interpolation.argtypes = [C.c_int, C.c_double, c_f64p, c_f64p, C.c_int, C.c_int, c_f64p]
+        L.mjpc_gradient_policy_interpolation.restype = None
         L.mjpc_planner_robust_result.argtypes = [vp, C.POINTER(C.c_int), c_f64p, C.c_int]
         L.mjpc_planner_task_set_parameter.argtypes = [vp, C.c_int, C.c_double]
         L.mjpc_planner_destroy.argtypes = [vp]
@@ -218,6 +224,40 @@ class HostPlanner:
         self._chk(lib().mjpc_planner_sample_gradient_result(self.h, C.byref(wt), as_f64p(g), num_parameters, as_f64p(r), num_trajectory))
         return wt.value, g, r
 
+    # ---- gradient
+    def gradient_set(self, representation=-1, derivative_skip=-1, num_spline_points=-1, num_trajectory=-1):
+        self._chk(lib().mjpc_planner_gradient_set(self.h, int(representation), int(derivative_skip), int(num_spline_points),
+                                                  int(num_trajectory)))
+
+    def fetch_trajectory(self, candidate, horizon):
+        """candidate `candidate` of the planner's last device rollout, in the reference's Trajectory layout"""
+        m = self.task.model
+        tr = capi.Trajectory(m.nq + m.nv + m.na, self.nu, self.task.num_residual, self.task.num_trace, horizon)
+        v = MjpcxTrajView()
+        v.horizon = horizon
+        v.states, v.actions, v.times = as_f64p(tr.states), as_f64p(tr.actions), as_f64p(tr.times)
+        v.residual, v.costs, v.trace = as_f64p(tr.residual), as_f64p(tr.costs), as_f64p(tr.trace)
+        rc = capi.lib().mjpcx_fetch_trajectory(self._ctx(), int(candidate), C.byref(v))
+        if rc != 0:
+            raise capi.MjpcxError(rc, capi.lib().mjpcx_last_error(self._ctx()).decode())
+        tr.total_return, tr.failure = v.total_return, bool(v.failure)
+        return tr
+
+    def gradient_result(self):
+        """the last OptimizePolicy of mjpc::GpuGradientPlanner: winner, action_step, expected, improvement and the parameter
+        update M^T k (P x nu)"""
+        w, s, e, i = C.c_int(-1), C.c_double(), C.c_double(), C.c_double()
+        g = np.zeros((max(self.num_spline_points, 1), self.nu))
+        self._chk(lib().mjpc_planner_gradient_result(self.h, C.byref(w), C.byref(s), C.byref(e), C.byref(i), as_f64p(g), g.size))
+        return dict(winner=w.value, action_step=s.value, expected=e.value, improvement=i.value, gradient=g)
+
+    def gradient_timers(self):
+        """per-stage times of the last OptimizePolicy [us] and the gradient-pass kernel's HIP-event time [ms]"""
+        v = np.zeros(7)
+        self._chk(lib().mjpc_planner_gradient_timers(self.h, as_f64p(v)))
+        keys = ("nominal", "model_derivative", "cost_derivative", "gradient", "rollouts", "policy_update", "gradient_kernel_ms")
+        return dict(zip(keys, v))
+
     def robust_config(self, ncandidates=0, nrepetitions=0, xfrc_std=-1.0, xfrc_rate=0.0):
         self._chk(lib().mjpc_planner_robust_config(self.h, int(ncandidates), int(nrepetitions), float(xfrc_std), float(xfrc_rate)))
 
@@ -346,3 +386,12 @@ class HostPlanner:
     @property
     def kernel_name(self):
         return capi.lib().mjpcx_kernel_name(self._ctx()).decode()
+
+
+def gradient_policy_interpolation(representation, x, xs, ys):
+    """GradientPolicy::Action before the clamp with the reference's interpolators (the C++ host's utilities.h)"""
+    xs, ys = np.ascontiguousarray(xs, float), np.ascontiguousarray(ys, float)
+    dim = ys.shape[1] if ys.ndim > 1 else 1
+    out = np.zeros(dim)
+    lib().mjpc_gradient_policy_interpolation(int(representation), float(x), as_f64p(xs), as_f64p(ys), dim, len(xs), as_f64p(out))
+    return out

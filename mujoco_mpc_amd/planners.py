@@ -585,6 +585,27 @@ def normalize_state_quaternions(model, x):
     return x
 
 
+def model_derivatives(ctx, tr, T, derivative_skip, fd_tolerance, fd_mode):
+    """ModelDerivatives::Compute incl. skip + interpolation, model_derivatives.cc:45-165 (the gradient-based planners' shared
+    step; the caller zeroes A, B, D at the last step, which has no transition)"""
+    s = derivative_skip + 1
+    evaluate = [0] + list(range(s, T - s, s)) + [T - 2, T - 1]
+    evaluate = sorted(set(e for e in evaluate if 0 <= e < T))
+    A, B, C, D = ctx.transition_fd(tr.times[evaluate], tr.states[evaluate], tr.actions[evaluate], fd_tolerance, int(fd_mode))
+    if len(evaluate) == T:
+        return A, B, C, D
+    full = [np.zeros((T,) + x.shape[1:]) for x in (A, B, C, D)]
+    ev = np.array(evaluate)
+    for t in range(T):
+        k = int(np.searchsorted(ev, t, side="right")) - 1
+        e0 = k
+        e1 = min(k + 1, len(ev) - 1)
+        tt = 0.0 if (ev[e0] == t or e0 == e1) else (t - ev[e0]) / (ev[e1] - ev[e0])
+        for f, x in zip(full, (A, B, C, D)):
+            f[t] = x[e0] * (1.0 - tt) + x[e1] * tt
+    return full
+
+
 class ILQGSettings:
     """iLQGSettings, mjpc/planners/ilqg/settings.h."""
     min_linesearch_step = 1.0e-3
@@ -794,25 +815,8 @@ class GpuILQGPlanner:
             getattr(tr, name)[:horizon] = getattr(got, name)
         tr.horizon, tr.total_return, tr.failure = horizon, got.total_return, got.failure
 
-    # ---- ModelDerivatives::Compute incl. skip + interpolation, model_derivatives.cc:45-165
     def _model_derivatives(self, tr, T):
-        s = self.derivative_skip_ + 1
-        evaluate = [0] + list(range(s, T - s, s)) + [T - 2, T - 1]
-        evaluate = sorted(set(e for e in evaluate if 0 <= e < T))
-        A, B, C, D = self.ctx.transition_fd(tr.times[evaluate], tr.states[evaluate], tr.actions[evaluate],
-                                            self.settings.fd_tolerance, int(self.settings.fd_mode))
-        if len(evaluate) == T:
-            return A, B, C, D
-        full = [np.zeros((T,) + x.shape[1:]) for x in (A, B, C, D)]
-        ev = np.array(evaluate)
-        for t in range(T):
-            k = int(np.searchsorted(ev, t, side="right")) - 1
-            e0 = k
-            e1 = min(k + 1, len(ev) - 1)
-            tt = 0.0 if (ev[e0] == t or e0 == e1) else (t - ev[e0]) / (ev[e1] - ev[e0])
-            for f, x in zip(full, (A, B, C, D)):
-                f[t] = x[e0] * (1.0 - tt) + x[e1] * tt
-        return full
+        return model_derivatives(self.ctx, tr, T, self.derivative_skip_, self.settings.fd_tolerance, self.settings.fd_mode)
 
     # ---- Iteration, planner.cc:377-627
     def iteration(self, horizon, pool=None):
@@ -891,3 +895,222 @@ class GpuILQGPlanner:
 
     def num_parameters(self):
         return self.dim_action * K_MAX_TRAJECTORY_HORIZON
+
+
+# ====================================================================================== Gradient
+K_MAX_GRADIENT_SPLINE_POINTS = 25  # gradient/spline_mapping.h:27
+
+
+class GradientSettings:
+    """GradientPlannerSettings, mjpc/planners/gradient/settings.h."""
+    max_rollout = 1
+    min_linesearch_step = 1.0e-8
+    fd_tolerance = 1.0e-5
+    fd_mode = 0
+    action_limits = 1
+
+
+class GradientPolicy:
+    """GradientPolicy, mjpc/planners/gradient/policy.{h,cc}: P spline points of nu parameters, sampled as the rollout kernels
+    sample them (spline.TimeSpline semantics) and clamped. This equals the reference's Zero / Linear / CubicInterpolation except for a
+    cubic on two points, where the reference's FiniteDifferenceSlope takes the second point's slope as 0."""
+
+    def __init__(self, model, task, horizon_cap=K_MAX_TRAJECTORY_HORIZON):
+        self.model = model
+        nu = model.nu
+        self.k = np.zeros((horizon_cap, nu))
+        self.parameters = np.zeros((horizon_cap, nu))
+        self.parameter_update = np.zeros((horizon_cap, nu))
+        self.times = np.zeros(horizon_cap)
+        self.num_parameters = nu * horizon_cap
+        # the reference's default is kMaxTrajectoryHorizon, its mappings hold 25 points: clamped to [1, 25]
+        P = int(model.get_number("gradient_spline_points", K_MAX_TRAJECTORY_HORIZON))
+        self.num_spline_points = min(max(P, 1), K_MAX_GRADIENT_SPLINE_POINTS)
+        self.representation = int(model.get_number("gradient_representation", LINEAR))
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.k[:horizon] = 0
+        self.parameters[:horizon] = 0 if initial_repeated_action is None else np.asarray(initial_repeated_action, float)
+        self.parameter_update[:horizon] = 0
+        self.times[:horizon] = 0
+
+    def copy_from(self, other, horizon=None):
+        for name in ("k", "parameters", "parameter_update", "times"):
+            getattr(self, name)[...] = getattr(other, name)
+        self.num_spline_points, self.num_parameters, self.representation = (other.num_spline_points, other.num_parameters,
+                                                                            other.representation)
+
+    def sample(self, time):
+        """the spline before the clamp: FindInterval, then TimeSpline::Sample's interpolation and node slopes (spline.cc:103-156,
+        269-287); after Reset every node time is 0 and the last node holds, as in the reference"""
+        P, xs, ys = self.num_spline_points, self.times, self.parameters
+        b0, b1 = find_interval(xs, time, P)
+        if b0 == b1 or self.representation == ZERO:
+            return ys[b0].copy()
+        span = xs[b1] - xs[b0]
+        t = (time - xs[b0]) / span
+        if self.representation == LINEAR:
+            return ys[b0] * (1.0 - t) + ys[b1] * t
+
+        def slope(i):
+            if i == 0:
+                return (ys[1] - ys[0]) / (xs[1] - xs[0])
+            if i == P - 1:
+                return (ys[i] - ys[i - 1]) / (xs[i] - xs[i - 1])
+            return 0.5 * (ys[i + 1] - ys[i]) / (xs[i + 1] - xs[i]) + 0.5 * (ys[i] - ys[i - 1]) / (xs[i] - xs[i - 1])
+        c0, c1 = 2.0 * t * t * t - 3.0 * t * t + 1.0, (t * t * t - 2.0 * t * t + t) * span
+        c2, c3 = -2.0 * t * t * t + 3 * t * t, (t * t * t - t * t) * span
+        return c0 * ys[b0] + c1 * slope(b0) + c2 * ys[b1] + c3 * slope(b1)
+
+    def action(self, action, state, time):
+        """policy.cc:81-103 with the device's spline semantics"""
+        action[:] = self.sample(time)
+        return clamp(action, self.model.actuator_ctrlrange)
+
+
+class GpuGradientPlanner:
+    """mjpc::GradientPlanner (mjpc/planners/gradient/planner.{h,cc}, max_rollout = 1) with its device work on the GPU: the
+    nominal and line-search rollouts (mjpcx_rollout_splines), finite-difference model derivatives (mjpcx_transition_fd), cost
+    derivatives (mjpcx_cost_derivatives), and the adjoint sweep with its spline-mapping projection (mjpcx_gradient_pass).
+    Host side: ResamplePolicy, the line-search steps, the selection, policy bookkeeping. Failed rollouts never win; the
+    128-candidate cap is lifted; gradient_spline_points is clamped to [1, 25]."""
+
+    def __init__(self, device=0, precision=64, backend_factory=None):
+        self.device, self.precision = device, precision
+        self._backend_factory = backend_factory
+        self.settings = GradientSettings()
+        self.mtx_ = threading.RLock()
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        self.dim_state = model.nq + model.nv + model.na
+        self.dim_state_derivative = 2 * model.nv + model.na
+        self.dim_action = model.nu
+        self.num_trajectory = int(model.get_number("gradient_num_trajectory", 32))
+
+    def allocate(self):
+        m = self.model
+        self.state = np.zeros(self.dim_state)
+        self.mocap = np.zeros(7 * m.nmocap)
+        self.userdata = np.zeros(m.nuserdata)
+        self.time = 0.0
+        self.policy = GradientPolicy(m, self.task)
+        self.previous_policy = GradientPolicy(m, self.task)
+        self.candidate0 = GradientPolicy(m, self.task)      # candidate_policy[0]
+        self.trajectory0 = None                             # trajectory[0]
+        self.differentiable_ = bool(int(m.get_number("agent_differentiable", 1)))
+        self.ctx = (self._backend_factory(self.task) if self._backend_factory   # test backends: see tests/oracle_backend.py
+                    else capi.Context(self.task.packed_model(differentiable=self.differentiable_), self.task.packed(), self.device,
+                                      self.precision))
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.state[:] = 0; self.mocap[:] = 0; self.userdata[:] = 0
+        self.time = 0.0
+        for p in (self.policy, self.previous_policy, self.candidate0):
+            p.reset(horizon, initial_repeated_action)
+        self.trajectory0 = None
+        self.dV = np.zeros(2)
+        self.action_step = self.expected = self.improvement = self.surprise = 0.0
+        self.winner = -1
+        self.derivative_skip_ = int(self.model.get_number("derivative_skip", 0))
+        self.linesearch_steps = np.zeros(0)
+        self.timers = {}
+
+    def set_state(self, state: State):
+        self.state, self.mocap, self.userdata, self.time = state.copy_to()
+
+    # ---- ResamplePolicy, planner.cc:355-381
+    def resample_policy(self, horizon):
+        c0 = self.candidate0
+        P, nu = c0.num_spline_points, self.model.nu
+        timestep = self.model.get_number("agent_timestep", self.model.timestep)   # the planning model's opt.timestep
+        time_shift = max((horizon - 1) * timestep / (P - 1), 1.0e-5) if P > 1 else 0.0
+        params = np.zeros((P, nu))
+        nominal_time = self.time
+        for t in range(P):
+            c0.action(params[t], None, nominal_time)
+            nominal_time += time_shift
+        c0.parameters[:P] = params
+        c0.times[:P] = self.time + np.arange(P) * time_shift     # LinearRange
+
+    # ---- NominalTrajectory, planner.cc:300-311
+    def nominal_trajectory(self, horizon, pool=None):
+        c0 = self.candidate0
+        P = c0.num_spline_points
+        sync_task(self.ctx, self.task)
+        self.ctx.set_state(self.state, self.time, self.mocap, self.userdata)
+        self.ctx.rollout_splines(horizon, c0.representation, c0.times[:P], c0.parameters[:P])
+        self.trajectory0 = self.ctx.fetch_trajectory(0)
+
+    # ---- OptimizePolicy, planner.cc:159-327
+    def optimize_policy(self, horizon, pool=None):
+        N = self.num_trajectory                             # the reference clamps to kMaxTrajectory = 128 (lifted)
+        if N < 1:
+            return
+        T = horizon
+        c0 = self.candidate0
+        t0 = _time.perf_counter()
+        with self.mtx_:
+            c0.copy_from(self.policy)
+        self.resample_policy(horizon)
+        self.nominal_trajectory(horizon)
+        tr = self.trajectory0
+        c_prev = c_best = tr.total_return
+        self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
+        t0 = _time.perf_counter()
+        st = self.settings
+        A, B, C, D = model_derivatives(self.ctx, tr, T, self.derivative_skip_, st.fd_tolerance, st.fd_mode)
+        A[T - 1] = 0; B[T - 1] = 0; D[T - 1] = 0
+        self.timers["model_derivative"] = (_time.perf_counter() - t0) * 1e6
+        t0 = _time.perf_counter()
+        cx, cu, _, _, _ = self.ctx.cost_derivatives(tr.residual[:T], C, D)
+        self.timers["cost_derivative"] = (_time.perf_counter() - t0) * 1e6
+        t0 = _time.perf_counter()
+        P = c0.num_spline_points
+        out = self.ctx.gradient_pass(A, B, cx, cu, c0.representation, c0.times[:P], tr.times[:T])
+        self.dV = out["dV"]
+        c0.k[:T] = out["k"]
+        c0.parameter_update[:P] = out["gradient"]
+        self.timers["gradient"] = (_time.perf_counter() - t0) * 1e6
+        # ---- Rollouts, planner.cc:384-418: theta + s_i * parameter_update, one batch
+        t0 = _time.perf_counter()
+        steps = np.zeros(N)
+        if N > 1:
+            steps[:N - 1] = log_scale(1.0, st.min_linesearch_step, N - 1)
+        self.linesearch_steps = steps
+        nodes = c0.parameters[:P][None] + steps[:, None, None] * c0.parameter_update[:P][None]
+        self.ctx.set_state(self.state, self.time, self.mocap, self.userdata)
+        self.ctx.rollout_splines(T, c0.representation, c0.times[:P], nodes)
+        ret, fail = self.ctx.returns()
+        # strict < from the last candidate down, starting from the nominal's return; failed rollouts never win
+        winner = N - 1
+        for j in range(N - 1, -1, -1):
+            if fail[j]:
+                continue
+            if ret[j] < c_best:
+                c_best, winner = float(ret[j]), j
+        if c_best < c_prev:
+            c0.parameters[:P] = nodes[winner]
+            self.trajectory0 = self.ctx.fetch_trajectory(winner)
+        self.winner = winner
+        self.action_step = float(steps[winner])
+        self.expected = -self.action_step * self.dV[0] - 1.0e-16
+        self.improvement = c_prev - c_best
+        self.surprise = min(max(0.0, self.improvement / self.expected), 2.0)
+        self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
+        if c_best >= c_prev:
+            self.winner = N - 1
+        with self.mtx_:
+            self.previous_policy.copy_from(self.policy)
+            self.policy.parameters[:P] = c0.parameters[:P]
+            self.policy.times[:P] = c0.times[:P]
+
+    def action_from_policy(self, action, state, time, use_previous=False):
+        with self.mtx_:
+            return (self.previous_policy if use_previous else self.policy).action(action, state, time)
+
+    def best_trajectory(self):
+        return self.trajectory0
+
+    def num_parameters(self):
+        return self.policy.num_spline_points * self.model.nu
