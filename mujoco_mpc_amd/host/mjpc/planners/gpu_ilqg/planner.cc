@@ -30,8 +30,8 @@ void GpuILQGPlanner::Allocate() {
   for (iLQGPolicy* p : {&policy, &previous_policy, &candidate_policy0, &winner_policy_})
     p->Allocate(model, *task, kMaxTrajectoryHorizon);
   // gradient-based planners plan on the differentiable model copy unless agent_differentiable says otherwise (agent.cc:156-164)
-  const bool differentiable = GetNumberOrDefault(1, model, "agent_differentiable") != 0;
-  ctx_ = std::make_unique<gpu::Context>(model, *task, device_, precision_, differentiable);
+  const bool use_differentiable = differentiable >= 0 ? differentiable != 0 : GetNumberOrDefault(1, model, "agent_differentiable") != 0;
+  ctx_ = std::make_unique<gpu::Context>(model, *task, device_, precision_, use_differentiable);
 }
 
 // ilqg/planner.cc:116-153 + iLQGBackwardPass::Reset (backward_pass.cc:50-62)
@@ -52,6 +52,8 @@ void GpuILQGPlanner::Reset(int horizon, const double* initial_repeated_action) {
   regularization_factor = 2.0;
   dV[0] = dV[1] = 0;
   action_step = feedback_scaling = improvement = expected = surprise = 0.0;
+  winner_return = linesearch0_return = 0.0;
+  iteration_completed = false;
   derivative_skip_ = GetNumberOrDefault(0, model, "derivative_skip");
   winner = 0;
 }
@@ -136,6 +138,7 @@ void GpuILQGPlanner::Iteration(int horizon, ThreadPool& pool) {
   Trajectory& tr = c0.trajectory;
   const int T = horizon, n = dim_state_derivative, m = dim_action;
   const double previous_return = tr.total_return;
+  iteration_completed = false;
   LineSearchSteps();
   ctx_->SyncTask(*task);
 
@@ -188,9 +191,11 @@ void GpuILQGPlanner::Iteration(int horizon, ThreadPool& pool) {
   returns_.resize(num_trajectory_);
   failure_.resize(num_trajectory_);
   ctx_->Check(mjpcx_get_returns(ctx_->handle(), returns_.data(), failure_.data()));
+  linesearch0_return = returns_[0];
   const int best = BestRollout(returns_, failure_);
   if (best == -1) return;
   winner = best;
+  winner_return = returns_[best];
   // candidate_policy[winner]: the nominal trajectory with actions += step * improvement, NOT re-rolled
   // (planner.cc:556-572 copies candidate_policy[0] into every candidate before the rollouts overwrite trajectory[i])
   winner_policy_.CopyFrom(c0, T);
@@ -215,6 +220,7 @@ void GpuILQGPlanner::Iteration(int horizon, ThreadPool& pool) {
     policy.feedback_scaling = 1.0;
   }
   policy_update_compute_time = GetDuration(start);
+  iteration_completed = true;
 }
 
 void GpuILQGPlanner::ActionFromPolicy(double* action, const double* s, double t, bool use_previous) {

@@ -66,6 +66,12 @@ class GpuILQGPlanner : public Planner {
   int winner = 0, num_trajectory_ = 0, num_rollouts_gui_ = 0, derivative_skip_ = 0;
   double nominal_compute_time = 0, model_derivative_compute_time = 0, cost_derivative_compute_time = 0,
          backward_pass_compute_time = 0, rollouts_compute_time = 0, policy_update_compute_time = 0;
+  // the last Iteration's line search: trajectory[winner].total_return, trajectory[0].total_return, and whether it got as far as a
+  // policy update (false when the backward pass failed or every line-search rollout failed; the returns are then stale)
+  double winner_return = 0, linesearch0_return = 0;
+  bool iteration_completed = false;
+  // the differentiable model copy: < 0 reads agent_differentiable (default 1, agent.cc:156-164); set before Allocate
+  int differentiable = -1;
   mutable std::shared_mutex mtx_;
 
  private:

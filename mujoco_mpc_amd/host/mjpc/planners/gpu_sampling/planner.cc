@@ -33,7 +33,7 @@ void GpuSamplingPlanner::Allocate() {
   plan_scratch = TimeSpline(model->nu);
   best_.Initialize((int)state.size(), model->nu, task->num_residual, task->num_trace, kMaxTrajectoryHorizon);
   best_.Allocate(kMaxTrajectoryHorizon);
-  ctx_ = std::make_unique<gpu::Context>(model, *task, device_, precision_);  // throws if no device kernel covers the model
+  ctx_ = std::make_unique<gpu::Context>(model, *task, device_, precision_, differentiable);  // throws if no device kernel covers the model
 }
 
 void GpuSamplingPlanner::Reset(int horizon, const double* initial_repeated_action) {
@@ -51,6 +51,7 @@ void GpuSamplingPlanner::Reset(int horizon, const double* initial_repeated_actio
   best_.Reset(kMaxTrajectoryHorizon);
   best_valid_ = false;
   improvement = 0.0;
+  best_return = nominal_return = 0.0;
   winner = 0;
 }
 
@@ -226,6 +227,8 @@ void GpuSamplingPlanner::OptimizePolicy(int horizon, ThreadPool& pool) {
   iteration++;
   const auto update_start = std::chrono::steady_clock::now();
   SetWinner(index, values);
+  this->best_return = best_return;
+  this->nominal_return = nominal_return;
   improvement = mju_max(nominal_return - best_return, 0.0);
   policy_update_compute_time = GetDuration(update_start);
 }

@@ -72,6 +72,7 @@ class GpuSamplingPlanner : public RankedPlanner {
   int rank() const { return rank_; }
   int world() const { return world_; }
   gpu::Context* context() { return ctx_.get(); }
+  double PlanningTimestep() const;  // agent_timestep if the model defines it (agent.cc:288-291)
 
   // ----- members (names as in the reference) ----- //
   mjModel* model = nullptr;
@@ -92,10 +93,14 @@ class GpuSamplingPlanner : public RankedPlanner {
   std::uint8_t sliding_plan_ = false;
   int num_trajectory_ = 0;
   std::uint32_t iteration = 0;
+  // the last OptimizePolicy's mjpcx_best: trajectory[winner].total_return and trajectory[0].total_return
+  double best_return = 0, nominal_return = 0;
+  // plan on the differentiable model copy (MakeDifferentiable, agent.cc:156-164); set before Allocate. Off, as in the reference,
+  // for sampling on its own; GpuILQSPlanner turns it on so that both of its halves plan on one model.
+  bool differentiable = false;
   mutable std::shared_mutex mtx_;
 
  private:
-  double PlanningTimestep() const;  // agent_timestep if the model defines it (agent.cc:288-291)
   void SetWinner(int index, const std::vector<double>& values);
   void LoadCandidatePlan(int index, SamplingPolicy* out);
   void LoadRankedPlan(int candidate, SamplingPolicy* out);

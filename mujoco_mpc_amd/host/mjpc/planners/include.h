@@ -12,7 +12,7 @@ enum PlannerType : int {
   kSamplingPlanner = 0,   // -> GpuSamplingPlanner
   kGradientPlanner,       // not ported (empty slot)
   kILQGPlanner,           // -> GpuILQGPlanner
-  kILQSPlanner,           // not ported
+  kILQSPlanner,           // not in the registry: GpuILQSPlanner via mjpc_planner_create_kind("ilqs")
   kRobustPlanner,         // -> GpuRobustPlanner(GpuSamplingPlanner)
   kCrossEntropyPlanner,   // -> GpuCrossEntropyPlanner
   kSampleGradientPlanner, // -> GpuSampleGradientPlanner

@@ -1,6 +1,7 @@
 // planner_c_api.cc -- a thin extern "C" view of the C++ GPU planners (mjpc::GpuSamplingPlanner,
 // mjpc::GpuCrossEntropyPlanner, mjpc::GpuILQGPlanner, mjpc::GpuGradientPlanner, ...) for non-C++ drivers: bench.py and the pytest
 // suite drive the C++ planners through it with ctypes; the planner logic itself stays in C++.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -8,6 +9,7 @@
 #include "mjpc/planners/gpu_cross_entropy/planner.h"
 #include "mjpc/planners/gpu_gradient/planner.h"
 #include "mjpc/planners/gpu_ilqg/planner.h"
+#include "mjpc/planners/gpu_ilqs/planner.h"
 #include "mjpc/planners/gpu_sampling/planner.h"
 #include "mjpc/planners/gpu_robust/robust_planner.h"
 #include "mjpc/planners/gpu_sample_gradient/planner.h"
@@ -26,10 +28,12 @@ struct Handle {
   mjpc::GpuGradientPlanner* gradient = nullptr;
   mjpc::GpuRobustPlanner* robust = nullptr;
   mjpc::GpuSampleGradientPlanner* sg = nullptr;     // wraps a GpuSamplingPlanner: `ps` then points at its delegate
+  mjpc::GpuILQSPlanner* ilqs = nullptr;             // its two halves are reached through it, never through `ps` / `ilqg`
   mjpc::State state;
   mjpc::ThreadPool pool{1};
   std::string error;
   mjpc::gpu::Context* context() {
+    if (ilqs) return ilqs->sampling.context();
     return ps ? ps->context() : ce ? ce->context() : sg ? sg->context() : gradient ? gradient->context() : ilqg->context();
   }
 };
@@ -40,8 +44,8 @@ extern "C" {
 
 const char* mjpc_planner_last_error(void* h) { return h ? static_cast<Handle*>(h)->error.c_str() : g_error.c_str(); }
 
-// kind: "sampling" | "cross_entropy" | "ilqg" | "gradient" | "sample_gradient" | "robust". num_trajectory > 0 overrides the
-// model's custom numeric.
+// kind: "sampling" | "cross_entropy" | "ilqg" | "gradient" | "sample_gradient" | "robust" | "ilqs". num_trajectory > 0 overrides the
+// model's custom numeric (for "ilqs": the sampling half's; its iLQG half keeps ilqg_num_rollouts).
 void* mjpc_planner_create_kind(const char* kind, const char* blob_path, const char* task_name, int device, int precision,
                                unsigned long long seed, int num_trajectory) {
   try {
@@ -67,6 +71,9 @@ void* mjpc_planner_create_kind(const char* kind, const char* blob_path, const ch
     } else if (k == "sample_gradient") {
       h->sg = new mjpc::GpuSampleGradientPlanner(device, precision, seed);
       h->planner.reset(h->sg);
+    } else if (k == "ilqs") {
+      h->ilqs = new mjpc::GpuILQSPlanner(device, precision, seed);
+      h->planner.reset(h->ilqs);
     } else if (k == "robust") {
       h->robust = new mjpc::GpuRobustPlanner(std::make_unique<mjpc::GpuSamplingPlanner>(device, precision, seed), device, precision, seed);
       h->planner.reset(h->robust);
@@ -82,6 +89,7 @@ void* mjpc_planner_create_kind(const char* kind, const char* blob_path, const ch
       if (h->ce) { h->ce->num_trajectory_ = num_trajectory; h->ce->n_elite_ = std::max(num_trajectory / 10, 2); }
       if (h->ilqg) h->ilqg->num_rollouts_gui_ = h->ilqg->num_trajectory_ = num_trajectory;
       if (h->gradient) h->gradient->num_trajectory = num_trajectory;
+      if (h->ilqs) h->ilqs->sampling.num_trajectory_ = num_trajectory;
     }
     h->planner->Allocate();
     h->state.Allocate(h->storage->model());
@@ -103,12 +111,13 @@ void mjpc_planner_destroy(void* h) { delete static_cast<Handle*>(h); }
   try { __VA_ARGS__; return 0; } catch (const std::exception& e) { H->error = e.what(); return -1; }
 
 int mjpc_planner_set_sharding(void* h, int rank, int world, mjpc::GpuSamplingPlanner::ExchangeFn fn, void* user) {
-  GUARD(h, { if (!H->ps) throw std::runtime_error("not a sampling planner"); H->ps->SetSharding(rank, world, fn, user); });
+  GUARD(h, { if (H->ilqs) throw std::runtime_error("the ilqs planner is not sharded (replicas only)"); if (!H->ps) throw std::runtime_error("not a sampling planner"); H->ps->SetSharding(rank, world, fn, user); });
 }
 // the ranked interface of a sampling planner (the robust planner's delegate): top-k merge + sum callbacks, as the Cross-Entropy planner's
 int mjpc_planner_set_sharding_ranked(void* h, int rank, int world, mjpc::GpuSamplingPlanner::MergeTopkFn merge,
                                      mjpc::GpuSamplingPlanner::SumFn sum, void* user) {
   GUARD(h, {
+    if (H->ilqs) throw std::runtime_error("the ilqs planner is not sharded (replicas only)");
     if (!H->ps) throw std::runtime_error("not a sampling planner");
     H->ps->SetSharding(rank, world, nullptr, nullptr);
     H->ps->SetRankedSharding(merge, sum, user);
@@ -123,6 +132,7 @@ int mjpc_planner_set_sharding_ce(void* h, int rank, int world, mjpc::GpuCrossEnt
 int mjpc_comm_unique_id(void* id_out) { return mjpcx_comm_unique_id(id_out); }
 int mjpc_planner_comm_init(void* h, const void* unique_id, int rank, int world) {
   GUARD(h, {
+    if (H->ilqs) throw std::runtime_error("the ilqs planner is not sharded (replicas only)");
     mjpc::gpu::Context* ctx = H->ps ? H->ps->context() : (H->ce ? H->ce->context() : nullptr);
     if (!ctx) throw std::runtime_error("this planner kind is not sharded (replicas only)");
     ctx->Check(mjpcx_comm_init(ctx->handle(), unique_id, rank, world));
@@ -279,23 +289,28 @@ int mjpc_planner_action_state(void* h, const double* state, double time, int use
 int mjpc_planner_num_parameters(void* h) { return static_cast<Handle*>(h)->planner->NumParameters(); }
 int mjpc_planner_num_spline_points(void* h) {
   Handle* H = static_cast<Handle*>(h);
+  if (H->ilqs) return H->ilqs->sampling.policy.num_spline_points;
   if (H->gradient) return H->gradient->policy.num_spline_points;
   return H->ps ? H->ps->policy.num_spline_points : H->ce ? H->ce->policy.num_spline_points : H->sg ? H->sg->policy.num_spline_points : 0;
 }
 int mjpc_planner_winner(void* h) {
   Handle* H = static_cast<Handle*>(h);
+  if (H->ilqs) return H->ilqs->active_policy == mjpc::GpuILQSPlanner::kSampling ? H->ilqs->sampling.winner : H->ilqs->ilqg.winner;
   if (H->sg) return H->sg->winner;
   if (H->gradient) return H->gradient->winner;
   return H->ps ? H->ps->winner : H->ilqg ? H->ilqg->winner : (H->ce->trajectory_order.empty() ? -1 : H->ce->trajectory_order[0]);
 }
 double mjpc_planner_improvement(void* h) {
   Handle* H = static_cast<Handle*>(h);
+  if (H->ilqs)
+    return H->ilqs->active_policy == mjpc::GpuILQSPlanner::kSampling ? H->ilqs->sampling.improvement : H->ilqs->ilqg.improvement;
   if (H->sg) return H->sg->improvement;
   if (H->gradient) return H->gradient->improvement;
   return H->ps ? H->ps->improvement : H->ce ? H->ce->improvement : H->ilqg->improvement;
 }
 double mjpc_planner_best_score(void* h) {
   Handle* H = static_cast<Handle*>(h);
+  if (H->ilqs) return H->ilqs->sampling.CandidateScore(0);
   if (H->sg) return H->sg->returns.empty() ? 0.0 : H->sg->returns[H->sg->winner];
   return H->ps ? H->ps->CandidateScore(0) : 0.0;
 }
@@ -303,6 +318,16 @@ double mjpc_planner_best_score(void* h) {
 int mjpc_planner_policy(void* h, double* times, double* values, int cap) {
   Handle* H = static_cast<Handle*>(h);
   if (H->ilqg) return 0;
+  if (H->ilqs) {  // the sampling half's spline, whichever half is active
+    const std::shared_lock<std::shared_mutex> lock(H->ilqs->sampling.mtx_);
+    const auto& plan = H->ilqs->sampling.policy.plan;
+    const int n = (int)plan.Size(), nu = H->storage->model()->nu;
+    for (int k = 0; k < n && k < cap; k++) {
+      times[k] = plan.times()[k];
+      std::memcpy(values + (size_t)k * nu, plan.values().data() + (size_t)k * nu, sizeof(double) * nu);
+    }
+    return n;
+  }
   if (H->gradient) {
     const std::shared_lock<std::shared_mutex> lock(H->gradient->mtx_);
     const auto& p = H->gradient->policy;
@@ -349,8 +374,8 @@ int mjpc_planner_ce_set(void* h, int n_elite, double std_initial, double std_min
 // winner, policy.trajectory.total_return}
 int mjpc_planner_ilqg_info(void* h, double* out) {
   Handle* H = static_cast<Handle*>(h);
-  if (!H->ilqg) return -1;
-  auto* p = H->ilqg;
+  mjpc::GpuILQGPlanner* p = H->ilqs ? &H->ilqs->ilqg : H->ilqg;
+  if (!p) return -1;
   const double v[10] = {p->regularization, p->dV[0], p->dV[1], p->action_step, p->feedback_scaling, p->improvement,
                         p->expected, p->surprise, (double)p->winner, p->policy.trajectory.total_return};
   std::memcpy(out, v, sizeof v);
@@ -359,8 +384,8 @@ int mjpc_planner_ilqg_info(void* h, double* out) {
 int mjpc_planner_ilqg_set(void* h, int regularization_type, int action_limits, int fd_mode, int derivative_skip,
                           int representation) {
   Handle* H = static_cast<Handle*>(h);
-  if (!H->ilqg) return -1;
-  auto* p = H->ilqg;
+  mjpc::GpuILQGPlanner* p = H->ilqs ? &H->ilqs->ilqg : H->ilqg;
+  if (!p) return -1;
   if (regularization_type >= 0) p->settings.regularization_type = regularization_type;
   if (action_limits >= 0) p->settings.action_limits = action_limits;
   if (fd_mode >= 0) p->settings.fd_mode = fd_mode;
@@ -371,14 +396,59 @@ int mjpc_planner_ilqg_set(void* h, int regularization_type, int action_limits, i
 // iLQG policy arrays for T steps: actions (T x nu), states (T x dim_state), times (T), gains (T x nu x ndx)
 int mjpc_planner_ilqg_policy(void* h, int T, double* times, double* states, double* actions, double* gains) {
   Handle* H = static_cast<Handle*>(h);
-  if (!H->ilqg) return -1;
-  const auto& p = H->ilqg->policy;
-  const int nu = H->ilqg->dim_action, ds = H->ilqg->dim_state, ndx = H->ilqg->dim_state_derivative;
+  mjpc::GpuILQGPlanner* q = H->ilqs ? &H->ilqs->ilqg : H->ilqg;
+  if (!q) return -1;
+  const auto& p = q->policy;
+  const int nu = q->dim_action, ds = q->dim_state, ndx = q->dim_state_derivative;
   if (times) std::memcpy(times, p.trajectory.times.data(), sizeof(double) * T);
   if (states) std::memcpy(states, p.trajectory.states.data(), sizeof(double) * T * ds);
   if (actions) std::memcpy(actions, p.trajectory.actions.data(), sizeof(double) * T * nu);
   if (gains) std::memcpy(gains, p.feedback_gain.data(), sizeof(double) * T * nu * ndx);
   return p.trajectory.horizon;
+}
+// iLQS: out[0..16] = {active_policy, previous_active_policy (0 sampling, 1 iLQG), iLQG iteration ran, iteration_completed, sampling
+// winner, its best_return, its nominal_return, iLQG winner, its return, line-search candidate 0's return, fit status (-1 none, 0 ok,
+// 1 unreached nodes, 2 not positive definite: the sampling nominal was kept), unreached nodes, and the per-stage times [us] of the last
+// OptimizePolicy: iLQG nominal, fit, sampling, handoff, iLQG iteration}
+int mjpc_planner_ilqs_info(void* h, double* out) {
+  GUARD(h, {
+    if (!H->ilqs) throw std::runtime_error("not an ilqs planner");
+    const auto* p = H->ilqs;
+    const double v[17] = {(double)p->active_policy.load(), (double)p->previous_active_policy.load(), (double)p->ilqg_ran,
+                          (double)p->ilqg.iteration_completed, (double)p->sampling.winner, p->sampling.best_return,
+                          p->sampling.nominal_return, (double)p->ilqg.winner, p->ilqg.winner_return, p->ilqg.linesearch0_return,
+                          (double)p->fit_status, (double)p->fit_unreached, p->nominal_compute_time, p->fit_compute_time,
+                          p->sampling_compute_time, p->handoff_compute_time, p->iteration_compute_time};
+    std::memcpy(out, v, sizeof v);
+  });
+}
+// iLQS: the last conversion -- node times (P) and values (P x nu), step times (T-1) and the actions ((T-1) x nu) it fitted; any
+// output may be NULL. Returns P * 65536 + (T-1) (0 before the first conversion), or -1.
+int mjpc_planner_ilqs_last_fit(void* h, double* node_times, double* values, double* step_times, double* actions) {
+  Handle* H = static_cast<Handle*>(h);
+  if (!H->ilqs) { H->error = "not an ilqs planner"; return -1; }
+  const auto* p = H->ilqs;
+  const int P = (int)p->fit_times.size(), T = (int)p->fit_step_times.size();
+  if (node_times) std::copy(p->fit_times.begin(), p->fit_times.end(), node_times);
+  if (values) std::copy(p->fit_values.begin(), p->fit_values.end(), values);
+  if (step_times) std::copy(p->fit_step_times.begin(), p->fit_step_times.end(), step_times);
+  if (actions) std::copy(p->fit_actions.begin(), p->fit_actions.end(), actions);
+  return P * 65536 + T;
+}
+// the iLQS policy conversion (mjpc::SplineFit) on its own, for the tests: returns its SplineFitStatus, or -1 on bad input
+int mjpc_ilqs_fit_spline(int interpolation, int num_nodes, const double* node_times, int num_steps, const double* step_times,
+                         const double* actions, int nu, const double* ctrlrange, double* values, int* num_unreached) {
+  try {
+    if (interpolation < 0 || interpolation > 2) throw std::invalid_argument("spline fit: interpolation must be 0, 1 or 2");
+    mjpc::SplineFit fit;
+    const int status = fit.Fit((mjpc::spline::SplineInterpolation)interpolation, num_nodes, node_times, num_steps, step_times, actions,
+                               nu, ctrlrange, values);
+    if (num_unreached) *num_unreached = fit.num_unreached;
+    return status;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+    return -1;
+  }
 }
 // BestTrajectory(): horizon or -1; any output may be NULL
 int mjpc_planner_best_trajectory(void* h, double* states, double* actions, double* times, double* costs, double* total_return) {

@@ -1,5 +1,5 @@
 """ctypes view of the C++ planners `mjpc::GpuSamplingPlanner`, `mjpc::GpuCrossEntropyPlanner`, `mjpc::GpuILQGPlanner`,
-`mjpc::GpuGradientPlanner` and the others
+`mjpc::GpuGradientPlanner`, `mjpc::GpuILQSPlanner` and the others
 (mujoco_mpc_amd/host, planner_c_api.cc).
 
 The planner logic (nominal resampling, policy bookkeeping, C-ABI calls) is the C++ host layer; Python
@@ -59,6 +59,10 @@ def lib():
         L.mjpc_planner_gradient_timers.argtypes = [vp, c_f64p]
         L.mjpc_gradient_policy_interpolation.argtypes = [C.c_int, C.c_double, c_f64p, c_f64p, C.c_int, C.c_int, c_f64p]
         L.mjpc_gradient_policy_interpolation.restype = None
+        L.mjpc_planner_ilqs_info.argtypes = [vp, c_f64p]
+        L.mjpc_planner_ilqs_last_fit.argtypes = [vp, c_f64p, c_f64p, c_f64p, c_f64p]
+        L.mjpc_ilqs_fit_spline.argtypes = [C.c_int, C.c_int, c_f64p, C.c_int, c_f64p, c_f64p, C.c_int, c_f64p, c_f64p,
+                                           C.POINTER(C.c_int)]
         L.mjpc_planner_robust_result.argtypes = [vp, C.POINTER(C.c_int), c_f64p, C.c_int]
         L.mjpc_planner_task_set_parameter.argtypes = [vp, C.c_int, C.c_double]
         L.mjpc_planner_destroy.argtypes = [vp]
@@ -320,6 +324,32 @@ class HostPlanner:
         lib().mjpc_planner_ilqg_policy(self.h, T, as_f64p(t), as_f64p(x), as_f64p(u), as_f64p(K))
         return t, x, u, K
 
+    # ---- iLQS
+    ILQS_INFO_KEYS = ("active", "previous_active", "ilqg_ran", "iteration_completed", "sampling_winner", "sampling_best_return",
+                      "sampling_nominal_return", "ilqg_winner", "ilqg_winner_return", "ilqg_linesearch0_return", "fit_status",
+                      "fit_unreached", "nominal_us", "fit_us", "sampling_us", "handoff_us", "iteration_us")
+
+    def ilqs_info(self):
+        """the last OptimizePolicy of mjpc::GpuILQSPlanner: active and previous half (0 sampling, 1 iLQG), whether the iLQG
+        iteration ran and completed, both halves' winners and returns, the fit status and the per-stage times [us]"""
+        v = np.zeros(len(self.ILQS_INFO_KEYS))
+        self._chk(lib().mjpc_planner_ilqs_info(self.h, as_f64p(v)))
+        return {k: (int(x) if k in ("active", "previous_active", "ilqg_ran", "iteration_completed", "sampling_winner", "ilqg_winner",
+                                    "fit_status", "fit_unreached") else float(x)) for k, x in zip(self.ILQS_INFO_KEYS, v)}
+
+    def ilqs_last_fit(self):
+        """the last iLQG -> sampling conversion: node times (P), node values (P x nu), and the step times (T-1) and actions
+        ((T-1) x nu) it was fitted to; None before the first conversion"""
+        code = lib().mjpc_planner_ilqs_last_fit(self.h, None, None, None, None)
+        if code < 0:
+            raise RuntimeError(lib().mjpc_planner_last_error(self.h).decode())
+        P, T = divmod(code, 65536)
+        if P == 0:
+            return None
+        t, v, st, a = np.zeros(P), np.zeros((P, self.nu)), np.zeros(T), np.zeros((T, self.nu))
+        lib().mjpc_planner_ilqs_last_fit(self.h, as_f64p(t), as_f64p(v), as_f64p(st), as_f64p(a))
+        return dict(node_times=t, values=v, step_times=st, actions=a)
+
     def best_trajectory(self, cap=512):
         m = self.task.model
         ds = m.nq + m.nv + m.na
@@ -395,3 +425,19 @@ def gradient_policy_interpolation(representation, x, xs, ys):
     out = np.zeros(dim)
     lib().mjpc_gradient_policy_interpolation(int(representation), float(x), as_f64p(xs), as_f64p(ys), dim, len(xs), as_f64p(out))
     return out
+
+
+def ilqs_fit_spline(interpolation, node_times, step_times, actions, ctrlrange=None):
+    """the iLQS policy conversion of the C++ host (mjpc::SplineFit): least-squares spline nodes for `actions` at `step_times`;
+    returns (values P x nu, status, unreached nodes) -- status 0 ok, 1 unreached nodes, 2 not positive definite (values zero)"""
+    nt, st = np.ascontiguousarray(node_times, float), np.ascontiguousarray(step_times, float)
+    a = np.ascontiguousarray(actions, float).reshape(len(st), -1)
+    nu = a.shape[1]
+    out = np.zeros((len(nt), nu))
+    cr = None if ctrlrange is None else np.ascontiguousarray(ctrlrange, float).reshape(nu, 2)
+    unreached = C.c_int(0)
+    status = lib().mjpc_ilqs_fit_spline(int(interpolation), len(nt), as_f64p(nt), len(st), as_f64p(st), as_f64p(a), nu,
+                                        None if cr is None else as_f64p(cr), as_f64p(out), C.byref(unreached))
+    if status < 0:
+        raise ValueError(lib().mjpc_planner_last_error(None).decode())
+    return out, status, unreached.value

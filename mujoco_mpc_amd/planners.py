@@ -105,14 +105,17 @@ class GpuSamplingPlanner:
     `group`: optional rank group (see distributed.py) sharding the candidates over
     GPUs; every rank keeps an identical host policy."""
 
-    def __init__(self, device=0, precision=64, seed=0, group=None, backend_factory=None):
+    def __init__(self, device=0, precision=64, seed=0, group=None, backend_factory=None, differentiable=False):
         self.device, self.precision, self.seed = device, precision, seed
         self.group = group
         self._backend_factory = backend_factory
+        # plan on the differentiable model copy (agent.cc:156-164): off for sampling on its own, on in GpuILQSPlanner
+        self.differentiable = differentiable
         self.model = None
         self.task = None
         self.ctx = None
         self.mtx_ = threading.RLock()
+        self.best_return = self.nominal_return = 0.0    # the last optimize_policy's trajectory[winner] / trajectory[0] returns
         self.noise_exploration = [0.0, 0.0]
         self.iteration = 0
         self.winner = 0
@@ -151,7 +154,8 @@ class GpuSamplingPlanner:
         if self._backend_factory is not None:
             self.ctx = self._backend_factory(self.task)
         else:
-            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+            self.ctx = capi.Context(self.task.packed_model(differentiable=self.differentiable), self.task.packed(), self.device,
+                                    self.precision)
 
     # ---- Planner::Reset, planner.cc:110-147
     def reset(self, horizon, initial_repeated_action=None):
@@ -269,6 +273,7 @@ class GpuSamplingPlanner:
         self.iteration += 1
         t0 = _time.perf_counter()
         self._set_winner(int(idx), values)
+        self.best_return, self.nominal_return = float(best_ret), float(nominal_ret)
         self.improvement = max(nominal_ret - best_ret, 0.0)
         self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
 
@@ -733,6 +738,9 @@ class GpuILQGPlanner:
         self.action_step = self.feedback_scaling = self.improvement = self.expected = self.surprise = 0.0
         self.derivative_skip_ = int(self.model.get_number("derivative_skip", 0))
         self.winner = 0
+        # the last iteration's trajectory[winner] / trajectory[0] returns, and whether it reached the policy update
+        self.winner_return = self.linesearch0_return = 0.0
+        self.iteration_completed = False
         self.timers = {}
 
     def set_state(self, state: State):
@@ -825,6 +833,7 @@ class GpuILQGPlanner:
         tr = c0.trajectory
         T, n, m = horizon, self.dim_state_derivative, self.dim_action
         previous_return = tr.total_return
+        self.iteration_completed = False
         steps = self._linesearch_steps()
         t0 = _time.perf_counter()
         A, B, C, D = self._model_derivatives(tr, T)
@@ -860,10 +869,12 @@ class GpuILQGPlanner:
         self.ctx.rollout_feedback(T, 0, 0, 1, tr.times[:T], tr.states[:T], tr.actions[:T], c0.feedback_gain[:T],
                                   c0.action_improvement[:T], steps)
         ret, fail = self.ctx.returns()
+        self.linesearch0_return = float(ret[0])
         best = self.best_rollout(ret, fail)
         if best == -1:
             return
         self.winner = best
+        self.winner_return = float(ret[best])
         # candidate_policy[winner]: the nominal trajectory with actions += step * improvement (NOT re-rolled)
         import copy
         winner_policy = ILQGPolicy.__new__(ILQGPolicy)
@@ -884,6 +895,7 @@ class GpuILQGPlanner:
             self.previous_policy.feedback_scaling = self.policy.feedback_scaling
             self.policy.copy_from(winner_policy, T)
             self.policy.feedback_scaling = 1.0
+        self.iteration_completed = True
 
     def action_from_policy(self, action, state, time, use_previous=False):
         with self.mtx_:
@@ -1114,3 +1126,169 @@ class GpuGradientPlanner:
 
     def num_parameters(self):
         return self.policy.num_spline_points * self.model.nu
+
+
+# ====================================================================================== iLQS
+SPLINE_FIT_NONE, SPLINE_FIT_OK, SPLINE_FIT_UNREACHED, SPLINE_FIT_NOT_POSITIVE_DEFINITE = -1, 0, 1, 2
+SPLINE_FIT_UNREACHED_TOLERANCE = 1.0e-9   # SplineFit::kUnreachedTolerance
+
+
+def fit_spline(interpolation, node_times, step_times, actions, ctrlrange=None):
+    """mjpc::SplineFit (host/mjpc/planners/gpu_ilqs/spline_fit.h) in numpy: spline nodes fitted to `actions` at `step_times` by least
+    squares, M built by sampling a TimeSpline of unit node vectors. An unreached node (column norm <= 1e-9 of the largest) takes
+    the action at the nearest step time; the others solve the reduced normal equations. Returns (values P x nu, status, unreached)."""
+    nt, st = np.asarray(node_times, float), np.asarray(step_times, float)
+    a = np.asarray(actions, float).reshape(len(st), -1)
+    P, nu = len(nt), a.shape[1]
+    basis = TimeSpline(P, interpolation)
+    for k in range(P):
+        basis.add_node(nt[k], np.eye(P)[k])
+    M = np.array([basis.sample(t) for t in st])
+    norm = np.sqrt((M * M).sum(axis=0))
+    reached = norm > SPLINE_FIT_UNREACHED_TOLERANCE * norm.max()
+    unreached = int(P - reached.sum())
+    x = np.zeros((P, nu))
+    for k in np.flatnonzero(~reached):
+        x[k] = a[int(np.argmin(np.abs(st - nt[k])))]
+    R = M[:, reached]
+    try:
+        L = np.linalg.cholesky(R.T @ R)
+    except np.linalg.LinAlgError:
+        return np.zeros((P, nu)), SPLINE_FIT_NOT_POSITIVE_DEFINITE, unreached
+    rhs = R.T @ (a - M[:, ~reached] @ x[~reached])
+    x[reached] = np.linalg.solve(L.T, np.linalg.solve(L, rhs))
+    if ctrlrange is not None:
+        for k in range(P):
+            clamp(x[k], ctrlrange)
+    return x, (SPLINE_FIT_UNREACHED if unreached else SPLINE_FIT_OK), unreached
+
+
+class GpuILQSPlanner:
+    """mjpc::iLQSPlanner (mjpc/planners/ilqs/planner.{h,cc}) over the sampling and iLQG mirrors, each with its own context, both on
+    the differentiable model unless agent_differentiable = 0. Deviations (host/mjpc/planners/gpu_ilqs/planner.h): the fit goes
+    into the sampling winner's plan at the node times its update uses; unreached nodes are defined; an iLQG iteration that
+    stopped early never activates iLQG; no cap on the spline points."""
+    SAMPLING, ILQG = 0, 1
+
+    def __init__(self, device=0, precision=64, seed=0, backend_factory=None):
+        self.sampling = GpuSamplingPlanner(device, precision, seed, backend_factory=backend_factory)
+        self.ilqg = GpuILQGPlanner(device, precision, backend_factory=backend_factory)
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        self.sampling.initialize(model, task)
+        self.ilqg.initialize(model, task)
+
+    def allocate(self):
+        # the iLQG mirror reads agent_differentiable (default 1) itself; the sampling half is told the same
+        self.sampling.differentiable = bool(int(self.model.get_number("agent_differentiable", 1)))
+        self.sampling.allocate()
+        self.ilqg.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.sampling.reset(horizon, initial_repeated_action)
+        self.ilqg.reset(horizon, initial_repeated_action)
+        self.active_policy = self.previous_active_policy = self.SAMPLING
+        self.ilqg_ran = False
+        self.fit_status, self.fit_unreached = SPLINE_FIT_NONE, 0
+        self.last_fit = None
+        self.timers = {}
+
+    def set_state(self, state: State):
+        self.sampling.set_state(state)
+        self.ilqg.set_state(state)
+
+    def convert_policy(self, horizon):
+        """iLQG's nominal actions -> the sampling spline, at the node times the sampling update lays out"""
+        s = self.sampling
+        P, nu = s.policy.num_spline_points, self.model.nu
+        time_horizon = (horizon - 1) * s._timestep()
+        if not s.sliding_plan_ and s.interpolation_ == ZERO:
+            shift = max(time_horizon / P, 1.0e-5)
+        else:
+            shift = max(time_horizon / (P - 1), 1.0e-5) if P > 1 else float("inf")
+        node_times, t = np.zeros(P), s.time
+        for k in range(P):
+            node_times[k] = t
+            t += shift
+        tr = self.ilqg.candidate0.trajectory
+        step_times, actions = tr.times[:horizon - 1].copy(), tr.actions[:horizon - 1].copy()
+        values, self.fit_status, self.fit_unreached = fit_spline(s.interpolation_, node_times, step_times, actions,
+                                                                 self.model.actuator_ctrlrange)
+        self.last_fit = dict(node_times=node_times, values=values, step_times=step_times, actions=actions)
+        if self.fit_status == SPLINE_FIT_NOT_POSITIVE_DEFINITE:
+            return
+        plan = TimeSpline(nu, s.interpolation_)
+        for k in range(P):
+            plan.add_node(node_times[k], values[k])
+        if s.sliding_plan_:
+            with s.mtx_:
+                s.policy.plan = plan
+        else:
+            s.winner_policy.plan = plan
+            s.winner_policy.num_spline_points = P
+
+    def _handoff(self, horizon):
+        """ilqg.candidate_policy[0].trajectory = sampling.trajectory[0] (buffers keep their capacity)"""
+        got = self.sampling.ctx.fetch_trajectory(0)
+        tr = self.ilqg.candidate0.trajectory
+        for name in ("states", "actions", "times", "residual", "costs", "trace"):
+            getattr(tr, name)[:horizon] = getattr(got, name)[:horizon]
+        tr.horizon, tr.total_return, tr.failure = horizon, got.total_return, got.failure
+        # its nominal_trajectory did not run, so its context has not seen this plan's state (the derivatives read its mocap)
+        g = self.ilqg
+        g.ctx.set_state(g.state, g.time, g.mocap, g.userdata)
+
+    # ---- OptimizePolicy, planner.cc:87-214
+    def optimize_policy(self, horizon, pool=None):
+        s, g = self.sampling, self.ilqg
+        previous = self.previous_active_policy = self.active_policy
+        g.num_trajectory_ = g.num_rollouts_gui_
+        self.ilqg_ran = False
+        self.fit_status, self.fit_unreached = SPLINE_FIT_NONE, 0
+        self.timers = {}
+        if previous == self.ILQG:
+            t0 = _time.perf_counter()
+            g.nominal_trajectory(horizon)
+            self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
+            t0 = _time.perf_counter()
+            self.convert_policy(horizon)
+            self.timers["fit"] = (_time.perf_counter() - t0) * 1e6
+        t0 = _time.perf_counter()
+        s.optimize_policy(horizon)
+        self.timers["sampling"] = (_time.perf_counter() - t0) * 1e6
+        reference = s.nominal_return if previous == self.SAMPLING else g.candidate0.trajectory.total_return
+        if s.winner > 0 and s.best_return < reference:
+            self.active_policy = self.SAMPLING
+            return
+        if previous == self.SAMPLING:
+            self._handoff(horizon)
+        t0 = _time.perf_counter()
+        g.iteration(horizon)
+        self.timers["iteration"] = (_time.perf_counter() - t0) * 1e6
+        self.ilqg_ran = True
+        reference = s.best_return if previous == self.SAMPLING else g.linesearch0_return
+        if g.iteration_completed and g.winner_return < reference:
+            self.active_policy = self.ILQG
+
+    def nominal_trajectory(self, horizon, pool=None):
+        if self.active_policy == self.SAMPLING:
+            return self.sampling.nominal_trajectory(horizon)
+        return self.ilqg.nominal_trajectory(horizon)
+
+    # ---- ActionFromPolicy, planner.cc:228-253
+    def action_from_policy(self, action, state, time, use_previous=False):
+        if use_previous:
+            if self.previous_active_policy == self.SAMPLING:
+                return self.sampling.action_from_policy(action, state, time, True)
+            # iLQG was previously active: if the last plan stopped after sampling, iLQG's current policy is the previous one
+            return self.ilqg.action_from_policy(action, state, time, self.active_policy == self.ILQG)
+        if self.active_policy == self.SAMPLING:
+            return self.sampling.action_from_policy(action, state, time, False)
+        return self.ilqg.action_from_policy(action, state, time, False)
+
+    def best_trajectory(self):
+        return self.sampling.best_trajectory() if self.active_policy == self.SAMPLING else self.ilqg.best_trajectory()
+
+    def num_parameters(self):
+        return self.sampling.num_parameters() + self.ilqg.num_parameters()
