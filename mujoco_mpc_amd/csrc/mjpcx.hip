@@ -953,16 +953,17 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
       le = launch_tree<TreeCfgHumanoid, float>(c, wm, wt, a, c->wh.dev_image32, c->wh.blob_bytes32, N, P);
       if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
     } else {
-    // (the Jacobian-free constraint path in fp32 for the models it covers that are not RK4 -- the Humanoid of configs[3] --, in two
-    // passes as in fp64)
-    const bool tree = c->wh.tree_ok && !c->no_tree && wm.integrator != MJPCX_INT_RK4;
-    const bool two_pass = tree && !c->no_second_pass;
+    // (the Jacobian-free constraint path in fp32 for the models it covers, as in fp64: in two passes under Euler, in one with the long
+    // contact lists under RK4 -- the row-table kernel's lists overflow on a folded Humanoid)
+    const bool tree = c->wh.tree_ok && !c->no_tree;
+    const bool rk4 = wm.integrator == MJPCX_INT_RK4;
+    const bool two_pass = tree && !rk4 && !c->no_second_pass;
     auto tree_lds = [&](int caps, int capc) { return (4 * w32::wave_lds_elems_tree(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, a.xfrc_scale > 0, caps, capc) + 15) & ~(size_t)15; };
     const size_t lds_big = tree ? tree_lds(w32::kTreeMaxSimpleBig, w32::kTreeMaxConeBig)
                                 : (4 * w32::wave_lds_elems(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, wm.cone, /*nodes_in_lds=*/false, a.xfrc_scale > 0) + 15) & ~(size_t)15;
     const size_t lds = two_pass ? tree_lds(w32::kTreeMaxSimple, w32::kTreeMaxCone) : lds_big;
     if (lds_big > 160 * 1024) return fail(c, MJPCX_EUNSUPPORTED, "model state does not fit the 160 KB LDS of a CU");
-    const int kern_big = wm.integrator == MJPCX_INT_RK4 ? kW32Rk4 : tree ? kW32Tree
+    const int kern_big = rk4 ? (tree ? kW32TreeRk4 : kW32Rk4) : tree ? kW32Tree
                        : wm.nv <= 18 ? kW32Rows18 : wm.nv <= 20 ? kW32Rows20 : wm.nv <= 28 ? kW32Rows28 : kW32Rows32;
     le = launch_wave_kernel_f32(two_pass ? kW32TreeSmall : kern_big, N, lds, wm, wt, a, c->stream);  // (the fp32 kernels live in wave32.hip)
     if (two_pass && le == hipSuccess) {

@@ -15,6 +15,7 @@ hipError_t launch_wave_kernel_f32(int which, int N, size_t lds, const WaveModelT
   // the register-resident Cholesky is unrolled to NMAX columns: row-table instantiations at the widths of the shipped models; the
   // Jacobian-free path at one width (the shipped tree models are registered), in its small-list and long-list forms
   auto kern = which == kW32Rk4 ? w32::rollout_wave_kernel<32, false, true>
+            : which == kW32TreeRk4 ? w32::rollout_wave_kernel<32, true, true>
             : which == kW32Tree ? w32::rollout_wave_kernel<32, true>
             : which == kW32TreeSmall ? w32::rollout_wave_kernel<32, true, false, true>
             : which == kW32Rows18 ? w32::rollout_wave_kernel<18> : which == kW32Rows20 ? w32::rollout_wave_kernel<20>

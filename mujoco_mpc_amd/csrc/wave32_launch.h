@@ -8,7 +8,7 @@
 
 namespace mjpcx {
 // generic kernels (rollout_wave_kernel<NMAX, TREE, RK4, SMALL>): which instantiation a model takes
-enum Wave32Kernel { kW32Rk4 = 0, kW32Tree, kW32TreeSmall, kW32Rows18, kW32Rows20, kW32Rows28, kW32Rows32 };
+enum Wave32Kernel { kW32Rk4 = 0, kW32Tree, kW32TreeSmall, kW32Rows18, kW32Rows20, kW32Rows28, kW32Rows32, kW32TreeRk4 };
 hipError_t launch_wave_kernel_f32(int which, int N, size_t lds, const WaveModelT<float>& m, const WaveTaskT<float>& wt, const RolloutArgs<float>& a,
                                   hipStream_t stream);
 // registered models (rollout_tree_kernel<C, BIG>): config 0 = TreeCfgA1, 1 = TreeCfgHumanoid (tree_registry.h)

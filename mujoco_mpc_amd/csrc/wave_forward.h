@@ -1108,7 +1108,7 @@ __device__ __forceinline__ void wf_constraint_newton(const MODEL& m, WaveData& d
   for (int iter = 0; iter < m.solver_iterations; iter++) {
     if (stamp && lane == 0) tacc = (long long)__builtin_readcyclecounter();
     // gradient = M (qacc - qacc_smooth) - J' force
-    wreal g = 0;
+    wreal g = 0, gparts = 0;
     if (lane < nv) {
       wreal s = 0;
 #pragma unroll 6
@@ -1117,18 +1117,17 @@ __device__ __forceinline__ void wf_constraint_newton(const MODEL& m, WaveData& d
       g = s;
 #pragma unroll 8
       for (int r = 0; r < ne; r++) g -= d.efc_J[r * nv + lane] * d.efc_force[r];
+      gparts = s * s + (s - g) * (s - g);
       d.grad[lane] = g;
       d.search[lane] = -g;
     }
     const wreal gnorm = sqrt(wave_sum(lane < nv ? g * g : WL(0.0)));
     if (gnorm == 0) break;
     // termination as in MuJoCo's primal solvers (engine_solver.c): the test uses the gradient AFTER the update, so it sits
-    // between the gradient and the Hessian work of the next pass. float: tolerance floored at what float resolves of a cost
-    // of this size
-    {
-      const wreal tol = sizeof(wreal) == 4 ? fmax((wreal)m.solver_tolerance, WL(1e-7)) : (wreal)m.solver_tolerance;
-      if (iter > 0 && (scale * improvement < tol || scale * gnorm < tol)) break;
-    }
+    // between the gradient and the Hessian work of the next pass. float: the gradient's rounding residue (its two cancelling parts,
+    // M (qacc - qacc_smooth) and J' force) is a floor under the gradient test; the tolerance is not raised (wave_tree.h says why)
+    if (iter > 0 && (scale * improvement < (wreal)m.solver_tolerance || scale * gnorm < (wreal)m.solver_tolerance)) break;
+    if (sizeof(wreal) == 4 && iter > 0 && gnorm <= WL(16.0) * (wreal)__FLT_EPSILON__ * sqrt(wave_sum(gparts))) break;
     if (stamp && lane == 0 && iter == 0) stamp[21] = (long long)__builtin_readcyclecounter();
     WACC(32);
     // H = M + J' (d2s) J depends on the rows' zones only -- and on jar for a cone in its middle (sliding) zone. When no row

@@ -9,6 +9,7 @@ import pytest
 from mujoco_mpc_amd import capi
 from mujoco_mpc_amd.task import load_task
 from oracle import pyoracle
+from step_bank import contact_census, humanoid_census
 
 pytestmark = pytest.mark.gpu
 
@@ -20,71 +21,6 @@ def close(a, b, tol):
 
 def mocap7(mpos):
     return np.concatenate([np.concatenate([p, [1, 0, 0, 0]]) for p in np.asarray(mpos).reshape(-1, 3)])
-
-
-def contact_census(task, mocap, states):
-    """Which kinds of contact the oracle sees along recorded rollouts (states [n, H, nq + nv]): per candidate, whether some step carries a
-    contact between geoms of two different LEGS, and whether one involves a hip CYLINDER and a geom of another moving body -- the cases
-    the quad kernel's solver pays most for (super-leg elimination, the thin-solid narrow phase). Legs: the chains below the free-joint body."""
-    m = task.model
-    gb, gt, parent = m.arrays["geom_bodyid"], m.arrays["geom_type"], m.arrays["body_parentid"]
-    trunk = next(b for b in range(m.nbody) if m.arrays["body_dofnum"][b] == 6)
-
-    def leg_of(b):  # the child of the trunk the body hangs under (-1: the trunk itself or a body outside the robot)
-        while b > 0 and parent[b] != trunk:
-            b = parent[b]
-        return int(b) if b > 0 else -1
-    legs = [leg_of(int(b)) for b in gb]
-    ph = pyoracle.Physics(task.packed_model())
-    leg_leg, hip_cyl = set(), set()
-    nq = m.nq
-    for k in range(states.shape[0]):
-        for t in range(states.shape[1]):
-            s = states[k, t]
-            ph.set_state(s[:nq], s[nq:], 0.0, mocap)
-            ph.forward()
-            nc = int(ph.get("ncon")[0])
-            if nc == 0:
-                continue
-            for r in ph.get("contact").reshape(-1, 11)[:nc]:
-                g1, g2 = int(r[7]), int(r[8])
-                if legs[g1] < 0 or legs[g2] < 0:
-                    continue  # (a static geom or the trunk on one side)
-                if legs[g1] != legs[g2]:
-                    leg_leg.add(k)
-                if 5 in (gt[g1], gt[g2]):  # MJPCX_GEOM_CYLINDER: the A1's hips (against another leg's geom, or the own calf / foot)
-                    hip_cyl.add(k)
-    return leg_leg, hip_cyl
-
-
-def humanoid_census(task, mocap, states, times, lds_cones=16):
-    """What the oracle sees along recorded Humanoid rollouts (states [n, H, nq + nv]): candidates with a contact between two MOVING bodies
-    (self-collision: frictionless rows that couple two limbs), with an active fixed-tendon limit row (the hamstrings), and with more
-    pyramidal cones at one step than the tree kernel's LDS list holds (csrc/wave_tree.h kTreeMaxCone: the rest go through its HBM slab)."""
-    m = task.model
-    ph = pyoracle.Physics(task.packed_model())
-    static = [int(b) == 0 or m.arrays["body_mocapid"][int(b)] >= 0 for b in m.arrays["geom_bodyid"]]
-    selfc, tendon, beyond = set(), set(), set()
-    nq = m.nq
-    for k in range(states.shape[0]):
-        for t in range(states.shape[1]):
-            s = states[k, t]
-            ph.set_state(s[:nq], s[nq:], float(times[k, t]), mocap)
-            ph.forward()
-            nc = int(ph.get("ncon")[0])
-            cones = 0
-            if nc:
-                for r in ph.get("contact").reshape(-1, 11)[:nc]:
-                    g1, g2 = int(r[7]), int(r[8])
-                    if not static[g1] and not static[g2]:
-                        selfc.add(k)
-                    if int(r[9]) > 1:
-                        cones += 1
-            if cones > lds_cones:
-                beyond.add(k)
-            if int(ph.get("nefc")[0]) and 5 in ph.get("efc_type").astype(int):   # contact.inc EFC_TENDON
-                tendon.add(k)
-    return selfc, tendon, beyond
 
 
 def full_size_properties(task, state, mocap, N, H, P, interp, mode, precision, tol, sample_stride, expect_quad=False, census=False):
@@ -182,25 +118,27 @@ def test_north_star_quadruped_predictive_sampling_n16384_h100():
 _HUMANOID_RETURNS = {}
 
 
+@pytest.mark.parametrize("motion", [0, 9])   # Jump, Walk
 @pytest.mark.parametrize("precision,tol", [(64, 1e-8), (32, 2e-3)])
-def test_config4_humanoid_tracking_n8192_h64(precision, tol):
+def test_config4_humanoid_tracking_n8192_h64(precision, tol, motion):
     """fp64 at the A1 configs' tolerance (1e-8 on 128 sampled candidates, with a census of what the sample exercises); fp32 -- the
     precision configs[3] is quoted in -- at 2e-3 on returns, and test_config4_fp32_ranking_equals_fp64 says what that means for a planner"""
     t = load_task("HumanoidTrack")
-    e = t.transition(0.0, mode=9)
-    _HUMANOID_RETURNS[precision] = full_size_properties(
+    e = t.transition(0.0, mode=motion)
+    _HUMANOID_RETURNS[motion, precision] = full_size_properties(
         t, np.concatenate([e["qpos"], e["qvel"]]), mocap7(e["mocap_pos"]), N=8192, H=64, P=16, interp=2,
         mode=capi.NOISE_SAMPLING, precision=precision, tol=tol, sample_stride=64, census="humanoid" if precision == 64 else False)
 
 
-def test_config4_fp32_ranking_equals_fp64():
+@pytest.mark.parametrize("motion", [0, 9])
+def test_config4_fp32_ranking_equals_fp64(motion):
     """What a 2e-3 tolerance on fp32 returns means for the planner (sampling/planner.cc:184-188 sorts by total_return and keeps the best):
     on the full 8192-candidate batch the fp32 kernel must pick the fp64 kernel's winner, its eight best must be the fp64 eight best (as a
     set; the order inside may swap where two returns differ by less than the fp32 error), and the rank correlation over the whole batch
-    is stated. Runs after the two parametrised cases above (same batch, same seed) and reuses their returns."""
-    if 32 not in _HUMANOID_RETURNS or 64 not in _HUMANOID_RETURNS:
+    is stated. Runs after the parametrised cases above (same batch, same seed) and reuses their returns."""
+    if (motion, 32) not in _HUMANOID_RETURNS or (motion, 64) not in _HUMANOID_RETURNS:
         pytest.skip("needs the fp32 and fp64 runs of test_config4_humanoid_tracking_n8192_h64 in the same session")
-    r32, r64 = _HUMANOID_RETURNS[32], _HUMANOID_RETURNS[64]
+    r32, r64 = _HUMANOID_RETURNS[motion, 32], _HUMANOID_RETURNS[motion, 64]
     N = len(r64)
     o32, o64 = np.lexsort((np.arange(N), r32)), np.lexsort((np.arange(N), r64))
     rank64 = np.empty(N, int); rank64[o64] = np.arange(N)
@@ -209,7 +147,7 @@ def test_config4_fp32_ranking_equals_fp64():
     gap = float(r64[o64[1]] - r64[o64[0]]) / (1 + abs(float(r64[o64[0]])))        # how far the fp64 runner-up is behind the winner
     err = float(np.max(np.abs(r32 - r64) / (1 + np.abs(r64))))
     top_overlap = len(set(o32[:8].tolist()) & set(o64[:8].tolist()))
-    print(f"fp32 vs fp64 on 8192 x 64: worst relative return difference {err:.2e}, winner's margin {gap:.2e}, fp32 winner has fp64 rank "
+    print(f"motion {motion}: fp32 vs fp64 on 8192 x 64: worst relative return difference {err:.2e}, winner's margin {gap:.2e}, fp32 winner has fp64 rank "
           f"{int(rank64[o32[0]])}, top-8 overlap {top_overlap}/8, Spearman rho {rho:.6f}, worst rank displacement {int(np.max(np.abs(rank32 - rank64)))}")
     # (the WORST of all 8192 candidates: chaotic contact dynamics amplify fp32 rounding over 64 steps -- 3.1e-3 observed with the limb kernel, the
     # 128 sampled candidates against the oracle stay within 2e-3 above; what matters to the planner is the ranking, asserted below)

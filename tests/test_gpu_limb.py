@@ -170,7 +170,7 @@ def test_collapse_keeps_tendon_limit_rows_in_the_limb_kernel():
     the limb form covers stay in the limb kernel, the others are handed on -- and the oracle's census of the rollouts says that candidates with
     an active tendon-limit row and with contacts between moving geoms are among those the limb kernel KEPT (its tendon row and its Woodbury
     terms are exercised on the device, not only in the emulator)"""
-    from test_gpu_full_size import humanoid_census
+    from step_bank import humanoid_census
     t = load_task("HumanoidTrack")
     e = t.transition(0.0, mode=4)   # Crouch Flip
     v = np.zeros(27)
