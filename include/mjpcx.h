@@ -323,6 +323,45 @@ int mjpcx_rollout_noise(mjpcx_ctx* ctx, int num_candidates, int horizon,
  * Either pointer may be NULL (keep). */
 int mjpcx_set_residual_state(mjpcx_ctx* ctx, const int32_t* residual_int, const double* residual_real);
 
+/* ---- several environments in one launch ---------------------------------------
+ * An environment is one robot: its own state, clock, mocap pose, userdata and nominal spline. All environments of a context
+ * share the model, the task weights and parameters, the horizon and the spline shape (P nodes, interpolation); the frozen
+ * residual state is shared unless mjpcx_set_residual_states gives one per environment. Candidates are environment-major: global
+ * candidate c = e * n_per_env + i, and every getter (mjpcx_get_returns, mjpcx_get_return_at, mjpcx_fetch_trajectory,
+ * mjpcx_fetch_spline, mjpcx_device_buffer) takes the global index. The rollout kernel is chosen from the TOTAL E * n_per_env, by the
+ * thresholds of the plain calls: a fleet's shares run together on the kernel a batch of that size runs on.
+ *   - n_per_env must be a positive multiple of 64 (every wavefront then serves one environment) and E >= 1: MJPCX_EINVAL otherwise;
+ *   - a batched rollout needs a preceding mjpcx_set_states with the same E: MJPCX_EINVAL otherwise;
+ *   - on a context sharded with mjpcx_comm_init (world > 1), or with xfrc noise: MJPCX_EUNSUPPORTED.
+ * The plain entry points are the one-environment case of the same launch code and kernels; they keep using the state of
+ * mjpcx_set_state, which mjpcx_set_states does not touch. */
+
+/* E x Planner::SetState: states E x (nq+nv+na), times E, mocap E x 7*nmocap (NULL: every environment keeps the context's
+ * pose), userdata E x nuserdata. */
+int mjpcx_set_states(mjpcx_ctx* ctx, int num_envs, const double* states, const double* times, const double* mocap,
+                     const double* userdata);
+
+/* mjpcx_set_residual_state per environment (E x residual_int, E x residual_real; either may be NULL: keep), for fleets whose
+ * robots are not in the same mode or gait phase. After mjpcx_set_states with the same E. A later plain
+ * mjpcx_set_residual_state applies to all environments again. */
+int mjpcx_set_residual_states(mjpcx_ctx* ctx, int num_envs, const int32_t* residual_int, const double* residual_real);
+
+/* mjpcx_rollout_splines for E environments: node_times E x P, node_values E x n_per_env x P x nu. */
+int mjpcx_rollout_splines_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,
+                                  const double* node_times, const double* node_values);
+
+/* mjpcx_rollout_noise for E environments: node_times E x P, nominal_values E x P x nu. Environment e draws exactly the noise
+ * that mjpcx_rollout_noise draws with noise->seed + e and the same remaining fields; candidate_offset and nominal_candidate
+ * are local to the environment -- so E plain calls reproduce a batched one. param_variance (CE) is shared. */
+int mjpcx_rollout_noise_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,
+                                const double* node_times, const double* nominal_values, const mjpcx_noise_spec* noise);
+
+/* mjpcx_best, segmented: one launch and one sync give, per environment, the argmin over its n_per_env returns (ties by
+ * index) as a LOCAL index -> index[E], best_return[E]; the return of local candidate ref_candidate (-1: skip) -> ref_return[E];
+ * the winner's spline values -> spline_values (E x P x nu). Any output but index may be NULL. */
+int mjpcx_best_batched(mjpcx_ctx* ctx, int num_envs, int ref_candidate, int32_t* index, double* best_return,
+                       double* ref_return, double* spline_values);
+
 /* Block until everything queued on the context's stream has finished. */
 int mjpcx_sync(mjpcx_ctx* ctx);
 

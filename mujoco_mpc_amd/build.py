@@ -36,9 +36,9 @@ SOURCES = [("mjpcx.hip", PRESSURE), ("ilqg_wave.hip", []), ("wave32.hip", PRESSU
 # re-compile the wavefront-per-candidate kernels, and vice versa)
 QUAD_ONLY = ["quad_step.h", "quad_kernel.h", "quad_model.h", "limb_step.h", "limb_kernel.h", "limb_model.h"]
 # likewise the limb kernel's unit (the Humanoid of configs[3])
-LIMB_DEPS = ["limb_step.h", "limb_kernel.h", "limb_model.h", "limb_abi.h", "limb_launch.h", "limb_kernel.hip", "pair_cull.h", "solid_pairs.h",
+LIMB_DEPS = ["env_select.h", "limb_step.h", "limb_kernel.h", "limb_model.h", "limb_abi.h", "limb_launch.h", "limb_kernel.hip", "pair_cull.h", "solid_pairs.h",
              os.path.join("..", "..", "include", "mjpcx.h")]
-QUAD_DEPS = ["quad_step.h", "quad_kernel.h", "quad_model.h", "quad_abi.h", "quad_launch.h", "quad_kernel.hip", "solid_pairs.h", "pair_cull.h",
+QUAD_DEPS = ["env_select.h", "quad_step.h", "quad_kernel.h", "quad_model.h", "quad_abi.h", "quad_launch.h", "quad_kernel.hip", "solid_pairs.h", "pair_cull.h",
              os.path.join("..", "..", "include", "mjpcx.h")]
 HEADERS = ["device_common.h", "rollout_lane.h", "lane_registry.h", os.path.join("generated", "static_models.h"),
            os.path.join("..", "..", "include", "mjpcx.h")]

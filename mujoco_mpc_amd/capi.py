@@ -28,6 +28,7 @@ EXPORTS = [
     "mjpcx_backward_pass", "mjpcx_gradient_pass", "mjpcx_timing_reset", "mjpcx_timing_read", "mjpcx_timing_read_main", "mjpcx_quad_stats", "mjpcx_algorithmic_bytes",
     "mjpcx_device_buffer", "mjpcx_comm_unique_id", "mjpcx_comm_init", "mjpcx_comm_info", "mjpcx_exchange_best", "mjpcx_merge_topk",
     "mjpcx_elite_allreduce", "mjpcx_comm_barrier", "mjpcx_comm_destroy",
+    "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
 ]
 
 _LIB = None
@@ -67,6 +68,11 @@ def lib():
         L.mjpcx_rollout_splines_noisy.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_f64p, c_f64p, C.c_double, C.c_double,
                                                   C.c_uint64, C.c_int]
         L.mjpcx_kinematics.argtypes = [vp] + [c_f64p] * 7
+        L.mjpcx_set_states.argtypes = [vp, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]
+        L.mjpcx_set_residual_states.argtypes = [vp, C.c_int, c_i32p, c_f64p]
+        L.mjpcx_rollout_splines_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p]
+        L.mjpcx_rollout_noise_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
+        L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_sync.argtypes = [vp]
         L.mjpcx_get_returns.argtypes = [vp, c_f64p, c_i32p]
         L.mjpcx_get_return_at.argtypes = [vp, C.c_int, C.POINTER(C.c_double), c_i32p]
@@ -218,6 +224,58 @@ class Context:
         self._chk(lib().mjpcx_rollout_noise(self.handle, int(num_candidates), int(horizon), P, int(interp),
                                             as_f64p(nt), as_f64p(nom), C.byref(noise_spec)))
         self.N, self.H, self.P = int(num_candidates), int(horizon), P
+
+    # ---- several environments in one launch (candidates environment-major: global c = e * n_per_env + i)
+    def set_states(self, states, times, mocap=None, userdata=None):
+        """E x set_state: states E x dim_state, times E, mocap E x 7*nmocap (None: the context's pose for all)."""
+        st = _f(states).reshape(-1, self.dim_state)
+        E = st.shape[0]
+        tm = _f(times).reshape(-1)
+        assert tm.size == E
+        mc = None if mocap is None else _f(mocap).reshape(E, -1)
+        ud = None if userdata is None else _f(userdata).reshape(E, -1)
+        self._chk(lib().mjpcx_set_states(self.handle, E, as_f64p(st), as_f64p(tm), None if mc is None else as_f64p(mc),
+                                         None if ud is None else as_f64p(ud)))
+        self.E = E
+
+    def set_residual_states(self, residual_int=None, residual_real=None):
+        """set_residual_state per environment: E x residual_int, E x residual_real (None: keep)."""
+        ri = None if residual_int is None else np.ascontiguousarray(residual_int, dtype=np.int32)
+        rr = None if residual_real is None else _f(residual_real)
+        E = (ri if ri is not None else rr).shape[0] if (ri is not None or rr is not None) else getattr(self, "E", 0)
+        self._chk(lib().mjpcx_set_residual_states(self.handle, int(E), None if ri is None else ri.ctypes.data_as(c_i32p),
+                                                  None if rr is None else as_f64p(rr)))
+
+    def rollout_splines_batched(self, horizon, interp, node_times, node_values, num_envs=None, n_per_env=None):
+        """node_times E x P, node_values E x n_per_env x P x nu."""
+        nt = _f(node_times)
+        nv = _f(node_values)
+        E = int(num_envs) if num_envs is not None else (nt.shape[0] if nt.ndim == 2 else 1)
+        P = nt.size // E if E > 0 else nt.size
+        n = int(n_per_env) if n_per_env is not None else nv.size // max(E * P * self.nu, 1)
+        assert nv.size == E * n * P * self.nu
+        self._chk(lib().mjpcx_rollout_splines_batched(self.handle, E, n, int(horizon), P, int(interp), as_f64p(nt), as_f64p(nv)))
+        self.N, self.H, self.P, self.n_per_env = E * n, int(horizon), P, n
+
+    def rollout_noise_batched(self, n_per_env, horizon, interp, node_times, nominal, noise_spec, num_envs=None):
+        """node_times E x P, nominal E x P x nu; environment e draws the noise of a plain call with seed + e."""
+        nt, nom = _f(node_times), _f(nominal)
+        E = int(num_envs) if num_envs is not None else (nt.shape[0] if nt.ndim == 2 else 1)
+        P = nt.size // E if E > 0 else nt.size
+        assert E < 1 or nom.size == E * P * self.nu
+        self._chk(lib().mjpcx_rollout_noise_batched(self.handle, E, int(n_per_env), int(horizon), P, int(interp), as_f64p(nt),
+                                                    as_f64p(nom), C.byref(noise_spec)))
+        self.N, self.H, self.P, self.n_per_env = E * int(n_per_env), int(horizon), P, int(n_per_env)
+
+    def best_batched(self, num_envs, ref_candidate=0, with_spline=True):
+        """per environment: local argmin, its return, the return of local ref_candidate, the winner's spline (E x P x nu)."""
+        E = int(num_envs)
+        idx = np.zeros(max(E, 1), np.int32)
+        br, rr = np.zeros(max(E, 1)), np.zeros(max(E, 1))
+        sp = np.zeros((max(E, 1), self.P, self.nu)) if with_spline else None
+        self._chk(lib().mjpcx_best_batched(self.handle, E, int(ref_candidate), as_i32p(idx), as_f64p(br), as_f64p(rr),
+                                           as_f64p(sp) if with_spline else None))
+        return idx, br, rr, sp
 
     def sync(self):
         self._chk(lib().mjpcx_sync(self.handle))

@@ -60,6 +60,33 @@ struct LaneTask {
   T mocap_pos[kLaneMaxMocap][3], mocap_quat[kLaneMaxMocap][4];
 };
 
+// The initial condition as the rollout kernels of the lane family read it: one LaneInit per environment, staged behind the plan's
+// node times and nominal spline (mjpcx.hip, stage_plan_inputs) -- E of them do not fit the kernel-argument segment. The environment is
+// wave-uniform, so these are scalar loads like the kernel arguments they replace. (LaneTask keeps its copy for the feedback and
+// finite-difference kernels, which serve one environment.)
+template <typename T>
+struct LaneInit {
+  T qpos[kLaneMaxDof], qvel[kLaneMaxDof];
+  T time;
+  T mocap_pos[kLaneMaxMocap][3], mocap_quat[kLaneMaxMocap][4];
+};
+// wave-uniform read-only data behind a global pointer, read through the constant address space: s_load, whatever the kernel stores elsewhere
+template <typename T> using const_as_ptr = const __attribute__((address_space(4))) T*;
+template <typename T>
+__device__ __forceinline__ void lane_task_init(LaneTask<T>& tk, const LaneInit<T>* init) {
+  const_as_ptr<LaneInit<T>> p = (const_as_ptr<LaneInit<T>>)init;
+#pragma unroll
+  for (int k = 0; k < kLaneMaxDof; k++) { tk.qpos[k] = p->qpos[k]; tk.qvel[k] = p->qvel[k]; }
+  tk.time = p->time;
+#pragma unroll
+  for (int i = 0; i < kLaneMaxMocap; i++) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) tk.mocap_pos[i][k] = p->mocap_pos[i][k];
+#pragma unroll
+    for (int k = 0; k < 4; k++) tk.mocap_quat[i][k] = p->mocap_quat[i][k];
+  }
+}
+
 // ---- small fixed-size math; all indices are compile-time after unrolling ----
 template <typename T> __device__ __forceinline__ void quat_mul(T (&r)[4], const T (&a)[4], const T (&b)[4]) {
   T t0 = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];

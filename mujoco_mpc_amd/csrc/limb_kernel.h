@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "env_select.h"
 #include "limb_model.h"
 
 namespace mjpcx { namespace limb {
@@ -169,8 +170,15 @@ constexpr size_t wave_reals(int LS) { return wave_con(LS) + wave_ml(LS) + wave_m
 
 // Workgroup = W wavefronts sharing one model image. stats[0]: candidates handed to the fallback kernel, stats[1 + b]: by reason bit b.
 template <typename R, int LS>
-__global__ __launch_bounds__(256) void rollout_limb_kernel(const LimbModelT<R>* __restrict__ gm, const R* __restrict__ blob, const LBlob bo, const LArgs<R> a,
+__global__ __launch_bounds__(256) void rollout_limb_kernel(const LimbModelT<R>* __restrict__ gm, const R* __restrict__ blob0, const LBlob bo, const LArgs<R> a0,
                                                            const R* __restrict__ key_mpos, int* __restrict__ stats) {
+  // the workgroup's environment (env_select.h; 0 of one unless a0.env_n is set), from its first candidate: that environment's blob, node
+  // times, nominal spline and noise stream. The cost terms staged below are then the environment's.
+  const int env = env_of(a0, (int)((blockIdx.x * blockDim.x) >> 6) * (a0.cpw > 0 && a0.cpw <= LS / 4 ? a0.cpw : LS / 4));
+  const R* __restrict__ blob = env_ptr(blob0, env, a0.env_stride);
+  LArgs<R> a = a0;
+  env_rebase(a, env);
+  a.seed += (uint64_t)env; a.candidate_offset -= env * a0.env_n;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   LimbModelT<R>& sm = *reinterpret_cast<LimbModelT<R>*>(lds_raw);
   {

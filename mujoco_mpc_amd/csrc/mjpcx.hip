@@ -170,6 +170,7 @@ __global__ __launch_bounds__(1024) void argmin_kernel(const double* __restrict__
 // nominal candidate's return (`improvement`, planner.cc:207-208). One launch writes them all
 // into a pinned, device-mapped host record, so the host pays exactly one stream sync per plan step.
 struct BestRecord { double best_return, ref_return; int best_index, ref_failure; double spline[1]; };
+static_assert(offsetof(BestRecord, spline) == 24, "mjpcx_best_batched packs the records at 24 bytes + the spline values");
 template <typename T>
 __global__ __launch_bounds__(1024) void best_kernel(const double* __restrict__ ret, const int* __restrict__ fail,
                                                      const T* __restrict__ nodes, int n, int np, int ref, BestRecord* out) {
@@ -213,6 +214,61 @@ __global__ __launch_bounds__(1024) void best_kernel(const double* __restrict__ r
   const int w = winner;
   if (w >= 0 && w < n)
     for (int j = threadIdx.x; j < np; j += blockDim.x) out->spline[j] = (double)nodes[(size_t)j * n + w];
+}
+
+// The same reads for E environments in one launch (mjpcx_best_batched): one workgroup per environment over its n_env returns,
+// environment-major. The wavefront reduction is a butterfly of (return, index) minima: the steps inside a row of 16 lanes are DPP
+// moves (no LDS traffic) -- quad_perm [1,0,3,2] and [2,3,0,1] leave a quad's minimum in its four lanes, row_half_mirror and row_mirror
+// then pair whole quads and whole halves -- and the two steps across rows go through the LDS crossbar. less_ri is a total order
+// (NaN last, ties to the lower index), so every lane ends with the same minimum whatever the pairing.
+template <int CTRL> __device__ __forceinline__ RetIdx dpp_ri(const RetIdx& v) {
+  RetIdx o;
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v.r), CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v.r), CTRL, 0xf, 0xf, true);
+  o.r = __hiloint2double(hi, lo);
+  o.i = __builtin_amdgcn_update_dpp(0, v.i, CTRL, 0xf, 0xf, true);
+  return o;
+}
+__device__ __forceinline__ RetIdx wave_argmin(RetIdx best) {  // every lane of the wavefront active
+  RetIdx o;
+  o = dpp_ri<0xB1>(best); if (less_ri(o, best)) best = o;   // quad_perm:[1,0,3,2]
+  o = dpp_ri<0x4E>(best); if (less_ri(o, best)) best = o;   // quad_perm:[2,3,0,1]
+  o = dpp_ri<0x141>(best); if (less_ri(o, best)) best = o;  // row_half_mirror
+  o = dpp_ri<0x140>(best); if (less_ri(o, best)) best = o;  // row_mirror
+#pragma unroll
+  for (int off = 16; off <= 32; off <<= 1) {
+    o.r = __shfl_xor(best.r, off, 64);
+    o.i = __shfl_xor(best.i, off, 64);
+    if (less_ri(o, best)) best = o;
+  }
+  return best;
+}
+constexpr size_t kBestHeader = 24;  // bytes of a BestRecord before its spline values
+template <typename T>
+__global__ __launch_bounds__(256) void best_segmented_kernel(const double* __restrict__ ret, const int* __restrict__ fail, const T* __restrict__ nodes,
+                                                              int N, int n_env, int np, int ref, unsigned char* out, unsigned rec_bytes) {
+  __shared__ RetIdx sm[4];
+  const int env = blockIdx.x, first = env * n_env;
+  RetIdx best{NAN, 0x7fffffff};  // (sorts behind every candidate)
+  for (int i = threadIdx.x; i < n_env; i += 256) {
+    const RetIdx c{ret[first + i], i};
+    if (less_ri(c, best)) best = c;
+  }
+  best = wave_argmin(best);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) sm[wave] = best;
+  __syncthreads();
+  best = wave_argmin(lane < 4 ? sm[lane] : RetIdx{NAN, 0x7fffffff});  // (every wavefront: the winner without a second barrier)
+  BestRecord* rec = reinterpret_cast<BestRecord*>(out + (size_t)env * rec_bytes);
+  if (threadIdx.x == 0) {
+    rec->best_return = best.r;
+    rec->best_index = best.i;  // local to the environment
+    rec->ref_return = (ref >= 0 && ref < n_env) ? ret[first + ref] : NAN;
+    rec->ref_failure = (ref >= 0 && ref < n_env) ? fail[first + ref] : 0;
+  }
+  const int w = best.i;
+  if (w >= 0 && w < n_env)
+    for (int j = threadIdx.x; j < np; j += 256) rec->spline[j] = (double)nodes[(size_t)j * N + first + w];
 }
 
 // elite moments: one workgroup per spline parameter j, fixed-shape tree reduction (deterministic)
@@ -344,6 +400,11 @@ struct mjpcx_ctx {
   int nsite_model = 0;
   double xfrc_std = 0, xfrc_rate = 1; uint64_t xfrc_seed = 0; int xfrc_offset = 0;  // pending NoisyRollout request (0: plain Rollout)  // layout of the last rollout's Trajectory buffers (true: wavefront-per-candidate kernels)
   int N = 0, H = 0, P = 0;  // shape of the last rollout
+  // several environments (mjpcx_set_states): E x [state | time | mocap] and, when given, E x the frozen residual state
+  int env_E = 0;
+  std::vector<double> env_state, env_time, env_mocap, env_rreal;
+  std::vector<int32_t> env_rint;
+  int env_n = 0;  // candidates per environment of the last rollout (0: not a batched one)
   bool have_rollout = false;
   // wavefront-per-candidate family
   bool wave = false;
@@ -518,17 +579,20 @@ int reserve_rollout(mjpcx_ctx* c, int N, int H, int P) {
   return MJPCX_OK;
 }
 
-// Stage [node_times (T) | nominal (T) | variance (f64)] into the next pinned slot and enqueue ONE
-// asynchronous H2D copy. The slot is recycled only after the kernel that reads it has finished.
+// Stage E records [node_times (T) | nominal (T) | variance (f64) | blob] into the next pinned slot, `*stride` bytes apart, and enqueue ONE
+// asynchronous H2D copy. The slot is recycled only after the kernel that reads it has finished. The blob is the per-plan blob of the
+// wavefront-per-candidate family (wave_model.h) or the lane family's initial condition (LaneInit). E = 0: the plain call -- one record
+// from the state of mjpcx_set_state; E >= 1: node_times is E x P, nominal E x P*nu, the states are those of mjpcx_set_states.
 template <typename T>
-int stage_plan_inputs(mjpcx_ctx* c, int P, const double* node_times, const double* nominal, const double* variance,
+int stage_plan_inputs(mjpcx_ctx* c, int P, int E, const double* node_times, const double* nominal, const double* variance,
                       const T** d_times, const T** d_nominal, const double** d_variance, mjpcx_ctx::Slot** used,
-                      const void** d_blob = nullptr) {
-  const int np = P * c->nu;
+                      const void** d_blob, unsigned* stride) {
+  const int np = P * c->nu, nrec = E > 0 ? E : 1;
   const size_t off_nom = ((size_t)P * sizeof(T) + 15) & ~(size_t)15;
   const size_t off_var = (off_nom + (size_t)np * sizeof(T) + 15) & ~(size_t)15;
   const size_t off_blob = (off_var + (size_t)np * 8 + 15) & ~(size_t)15;
-  const size_t bytes = off_blob + (c->wave ? (sizeof(T) == 4 ? c->wh.blob_bytes32 : c->wh.blob_bytes) : 0);
+  const size_t rec = (off_blob + (c->wave ? (sizeof(T) == 4 ? c->wh.blob_bytes32 : c->wh.blob_bytes) : sizeof(LaneInit<T>)) + 15) & ~(size_t)15;
+  const size_t bytes = rec * nrec;
   mjpcx_ctx::Slot& s = c->slots[c->next_slot];
   c->next_slot = (c->next_slot + 1) % mjpcx_ctx::kSlots;
   if (s.pending) { HIPCHK(c, hipEventSynchronize(s.done)); s.pending = false; }
@@ -540,20 +604,48 @@ int stage_plan_inputs(mjpcx_ctx* c, int P, const double* node_times, const doubl
     s.cap = bytes;
   }
   HIPCHK(c, s.dev.reserve(bytes));
-  char* h = (char*)s.host;
-  T* ht = (T*)h;
-  for (int p = 0; p < P; p++) ht[p] = (T)node_times[p];
-  T* hn = (T*)(h + off_nom);
-  if (nominal) for (int j = 0; j < np; j++) hn[j] = (T)nominal[j];
-  if (variance) std::memcpy(h + off_var, variance, (size_t)np * 8);
-  if (c->wave) {
-    if (sizeof(T) == 4) c->wh.fill_blob32(h + off_blob); else c->wh.fill_blob(h + off_blob);
-    if (d_blob) *d_blob = (const char*)s.dev.p + off_blob;
+  const int nst = c->nq + c->nv;
+  for (int e = 0; e < nrec; e++) {
+    char* h = (char*)s.host + rec * e;
+    T* ht = (T*)h;
+    for (int p = 0; p < P; p++) ht[p] = (T)node_times[(size_t)e * P + p];
+    T* hn = (T*)(h + off_nom);
+    if (nominal) for (int j = 0; j < np; j++) hn[j] = (T)nominal[(size_t)e * np + j];
+    if (variance) std::memcpy(h + off_var, variance, (size_t)np * 8);
+    T* hb = (T*)(h + off_blob);
+    const double* st = E > 0 ? c->env_state.data() + (size_t)e * nst : nullptr;
+    const double* mo = E > 0 && !c->env_mocap.empty() ? c->env_mocap.data() + (size_t)e * 7 * c->nmocap : nullptr;
+    if (c->wave) {
+      if (sizeof(T) == 4) c->wh.fill_blob32(hb); else c->wh.fill_blob(hb);
+      if (E > 0) {  // the environment's own state, clock, mocap pose and (if given) frozen residual state over the context's
+        const WaveTask& t = c->wh.t;
+        for (int i = 0; i < nst; i++) hb[i] = (T)st[i];
+        hb[t.off_time] = (T)c->env_time[e];
+        if (mo) for (int i = 0; i < 7 * c->nmocap; i++) hb[t.off_mocap + i] = (T)mo[i];
+        if (!c->env_rreal.empty()) for (int i = 0; i < t.nrr; i++) hb[t.off_rreal + i] = (T)c->env_rreal[(size_t)e * t.nrr + i];
+        if (!c->env_rint.empty()) std::memcpy(hb + t.off_rint, c->env_rint.data() + (size_t)e * t.nri, sizeof(int32_t) * t.nri);
+      }
+    } else {
+      LaneInit<T>& li = *reinterpret_cast<LaneInit<T>*>(hb);
+      const LaneTask<double>& k = c->ht64;
+      for (int i = 0; i < kLaneMaxDof; i++) {
+        li.qpos[i] = (T)(st && i < c->nq ? st[i] : k.qpos[i]);
+        li.qvel[i] = (T)(st && i < c->nv ? st[c->nq + i] : k.qvel[i]);
+      }
+      li.time = (T)(E > 0 ? c->env_time[e] : k.time);
+      for (int i = 0; i < kLaneMaxMocap; i++) {
+        const bool own = mo && i < c->nmocap;
+        for (int q = 0; q < 3; q++) li.mocap_pos[i][q] = (T)(own ? mo[7 * i + q] : k.mocap_pos[i][q]);
+        for (int q = 0; q < 4; q++) li.mocap_quat[i][q] = (T)(own ? mo[7 * i + 3 + q] : k.mocap_quat[i][q]);
+      }
+    }
   }
   HIPCHK(c, hipMemcpyAsync(s.dev.p, s.host, bytes, hipMemcpyHostToDevice, c->stream));
   *d_times = (const T*)s.dev.p;
   *d_nominal = (const T*)((char*)s.dev.p + off_nom);
   *d_variance = (const double*)((char*)s.dev.p + off_var);
+  *d_blob = (const char*)s.dev.p + off_blob;
+  *stride = (unsigned)rec;
   *used = &s;
   return MJPCX_OK;
 }
@@ -592,11 +684,16 @@ hipError_t launch_tree_pass(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTas
   W = std::max(1, std::min(W, (N + c->num_cu - 1) / c->num_cu));  // small batches: spread over the CUs first
   int grid = std::min(c->num_cu, (N + W - 1) / W);
   if (BIG) grid = std::min(grid, 64);  // the second pass scans the failure flags; a handful of rollouts at most
+  // several environments: a workgroup holds ONE environment's blob, so the workgroups are dealt to the environments in equal shares
+  // (tree_kernel.h) -- a chip's worth of them over all environments, one each at least
+  const int E = a.env_n > 0 ? N / a.env_n : 1;
+  if (E > 1) grid = E * std::max(1, std::min(grid / E, (a.env_n + W - 1) / W));
   const int mode = (BIG ? (c->tree_mode & 8) : c->tree_mode) | (only_flagged && !BIG ? 32 : 0);  // 32: only the candidates the quad kernel handed on
   const size_t lds = fixed + (size_t)W * arena;
-  hipError_t e = c->d_work.reserve(16);
+  const size_t work_bytes = (8 + 4 * (size_t)E + 15) & ~(size_t)15;  // [-, self-check count, one work counter per environment]
+  hipError_t e = c->d_work.reserve(work_bytes);
   if (e != hipSuccess) return e;
-  if (mode & (2 | 16)) if ((e = hipMemsetAsync(c->d_work.p, 0, 16, c->stream)) != hipSuccess) return e;  // self-check count / work counter
+  if (mode & (2 | 16)) if ((e = hipMemsetAsync(c->d_work.p, 0, work_bytes, c->stream)) != hipSuccess) return e;  // self-check count / work counters
   // first pass: one slab per wavefront for the cones beyond the LDS list (wave_tree.h; a few tens of MB, never touched in the common case)
   void* slabs = nullptr;
   if (!BIG && !c->no_cone_slabs) {
@@ -646,6 +743,7 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
   q.param_variance = a.noise.param_variance;
   q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
   q.total_return = a.total_return; q.failure = a.failure; q.con_cap = c->quad_con_cap; q.cpw = c->quad_cpw;
+  q.env_n = a.env_n; q.env_stride = a.env_stride;
   const quad::QBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
   hipError_t e;
   if (quad::quad_uses_ovf_slab()) {  // (a build with QEXP_OVF_SLAB: contacts beyond a lane's LDS slots in global memory, 150 KB per wavefront)
@@ -749,6 +847,7 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
   q.param_variance = a.noise.param_variance;
   q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
   q.total_return = a.total_return; q.failure = a.failure; q.cpw = c->limb_cpw;
+  q.env_n = a.env_n; q.env_stride = a.env_stride;
   const limb::LBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
   hipError_t e;
   if ((e = hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream)) != hipSuccess) return e;  // (how many candidates are handed on, by reason: mjpcx_quad_stats)
@@ -804,7 +903,9 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
 
 template <typename T>
 int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node_times,
-               const double* node_values, const double* nominal, const mjpcx_noise_spec* ns) {
+               const double* node_values, const double* nominal, const mjpcx_noise_spec* ns, int E = 0) {
+  // E = 0: the plain entry points (one environment, the state of mjpcx_set_state). E >= 1: N = E x n_per_env candidates, environment-major,
+  // from the states of mjpcx_set_states; node_times is E x P and nominal E x P*nu. Same launch code, same kernels.
   int rc;
   if ((rc = reserve_rollout(c, N, H, P)) != MJPCX_OK) return rc;
   const int np = P * c->nu;
@@ -817,8 +918,10 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   const bool ce = ns && ns->mode == MJPCX_NOISE_CROSS_ENTROPY;
   if (ce && !ns->param_variance) return fail(c, MJPCX_EINVAL, "cross-entropy noise needs param_variance");
   const void* d_blob = nullptr;
-  if ((rc = stage_plan_inputs<T>(c, P, node_times, nominal, ce ? ns->param_variance : nullptr, &a.node_times,
-                                 &a.nominal, &d_var, &slot, &d_blob)) != MJPCX_OK) return rc;
+  if ((rc = stage_plan_inputs<T>(c, P, E, node_times, nominal, ce ? ns->param_variance : nullptr, &a.node_times,
+                                 &a.nominal, &d_var, &slot, &d_blob, &a.env_stride)) != MJPCX_OK) return rc;
+  a.env_n = E > 1 ? N / E : 0;
+  if (!c->wave) a.init = (const LaneInit<T>*)d_blob;
   if (node_values) {
     // candidate-major host splines -> [node][actuator][candidate] on the device (not the hot path:
     // the planner generates candidates on the device; this entry serves tests and NominalTrajectory)
@@ -985,6 +1088,7 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   HIPCHK(c, hipEventRecord(slot->done, c->stream));
   slot->pending = true;
   c->N = N; c->H = H; c->P = P;
+  c->env_n = E > 0 ? N / E : 0;
   c->have_rollout = true;
   c->traj_candidate_major = c->wave;
   return MJPCX_OK;
@@ -1335,7 +1439,8 @@ int mjpcx_set_task_params(mjpcx_ctx* c, const double* weight, const double* norm
 int mjpcx_set_residual_state(mjpcx_ctx* c, const int32_t* residual_int, const double* residual_real) {
   if (!c) return MJPCX_EINVAL;
   if (!c->wave) return (residual_int || residual_real) ? fail(c, MJPCX_EUNSUPPORTED, "this task's residual has no frozen state") : MJPCX_OK;
-  if (residual_int) c->wh.residual_int.assign(residual_int, residual_int + c->wh.t.nri);
+  if (residual_int) { c->wh.residual_int.assign(residual_int, residual_int + c->wh.t.nri); c->env_rint.clear(); }  // (all environments again)
+  if (residual_real) c->env_rreal.clear();
   if (residual_int && c->quad_ok)  // the quad model bakes the ids Task::Reset resolves; a caller that changes them gets the generic path
     for (int k = 0; k < 7; k++) if (residual_int[1 + k] != c->quad_ids[k]) { c->quad_ok = false; c->kernel = &kTreeEntryA1; }
   if (residual_int && c->limb_ok)  // likewise the limb model: the tracking sites and mocap bodies (the motion's first / last key may change)
@@ -1374,6 +1479,111 @@ int mjpcx_rollout_noise(mjpcx_ctx* c, int N, int H, int P, int interp, const dou
   if (ns->mode != MJPCX_NOISE_SAMPLING && ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "unknown noise mode");
   return c->precision == 64 ? do_rollout<double>(c, N, H, P, interp, node_times, nullptr, nominal, ns)
                             : do_rollout<float>(c, N, H, P, interp, node_times, nullptr, nominal, ns);
+}
+
+// ---- several environments per launch
+int mjpcx_set_states(mjpcx_ctx* c, int E, const double* states, const double* times, const double* mocap, const double* userdata) {
+  if (!c || !states || !times) return fail(c, MJPCX_EINVAL, "null argument");
+  if (E < 1) return fail(c, MJPCX_EINVAL, "mjpcx_set_states: the number of environments must be >= 1");
+  (void)userdata;  // nuserdata == 0 for every supported model
+  const size_t nst = (size_t)c->nq + c->nv + c->na;
+  c->env_state.assign(states, states + nst * E);
+  c->env_time.assign(times, times + E);
+  if (mocap) c->env_mocap.assign(mocap, mocap + (size_t)7 * c->nmocap * E);  // (NULL: every environment keeps the context's pose)
+  else c->env_mocap.clear();
+  if (c->env_E != E) { c->env_rint.clear(); c->env_rreal.clear(); }  // (per-environment residual state of another fleet size)
+  c->env_E = E;
+  return MJPCX_OK;
+}
+
+int mjpcx_set_residual_states(mjpcx_ctx* c, int E, const int32_t* residual_int, const double* residual_real) {
+  if (!c) return MJPCX_EINVAL;
+  if (E < 1) return fail(c, MJPCX_EINVAL, "mjpcx_set_residual_states: the number of environments must be >= 1");
+  if (!c->wave) return (residual_int || residual_real) ? fail(c, MJPCX_EUNSUPPORTED, "this task's residual has no frozen state") : MJPCX_OK;
+  if (E != c->env_E) return fail(c, MJPCX_EINVAL, "mjpcx_set_residual_states: " + std::to_string(E) + " environments, but mjpcx_set_states gave " + std::to_string(c->env_E));
+  const int nri = c->wh.t.nri, nrr = c->wh.t.nrr;
+  if (residual_int) {
+    c->env_rint.assign(residual_int, residual_int + (size_t)nri * E);
+    // the quad / limb models bake the ids Task::Reset resolves; a caller that changes them in any environment gets the generic path
+    for (int e = 0; e < E; e++) {
+      const int32_t* ri = residual_int + (size_t)e * nri;
+      if (c->quad_ok) for (int k = 0; k < 7; k++) if (ri[1 + k] != c->quad_ids[k]) { c->quad_ok = false; c->kernel = &kTreeEntryA1; break; }
+      if (c->limb_ok) for (int k = 0; k < 32; k++) if (ri[2 + k] != c->limb_ids[k]) { c->limb_ok = false; c->kernel = &kTreeEntryHumanoid; break; }
+    }
+  }
+  if (residual_real) c->env_rreal.assign(residual_real, residual_real + (size_t)nrr * E);
+  return MJPCX_OK;
+}
+
+namespace {
+int check_batched_args(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times) {
+  if (!c || !node_times) return fail(c, MJPCX_EINVAL, "null argument");
+  if (E < 1) return fail(c, MJPCX_EINVAL, "batched rollout: the number of environments must be >= 1");
+  if (n < 64 || n % 64 != 0)
+    return fail(c, MJPCX_EINVAL, "batched rollout: n_per_env = " + std::to_string(n) + " must be a positive multiple of 64 (a wavefront serves one environment)");
+  if ((long long)E * n > 0x7fffffffLL / 64) return fail(c, MJPCX_EINVAL, "batched rollout: too many candidates");
+  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, "batched rollouts on a context sharded with mjpcx_comm_init are not implemented");
+  if (c->xfrc_std > 0) return fail(c, MJPCX_EUNSUPPORTED, "batched rollouts with xfrc noise (NoisyRollout) are not implemented");
+  if (c->env_E != E)
+    return fail(c, MJPCX_EINVAL, c->env_E == 0 ? std::string("batched rollout before mjpcx_set_states")
+                                               : "batched rollout of " + std::to_string(E) + " environments after mjpcx_set_states of " + std::to_string(c->env_E));
+  for (int e = 0; e < E; e++) {
+    const int rc = check_rollout_args(c, E * n, H, P, interp, node_times + (size_t)e * (P > 0 ? P : 0));
+    if (rc != MJPCX_OK) return rc;
+  }
+  return MJPCX_OK;
+}
+}  // namespace
+
+int mjpcx_rollout_splines_batched(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* node_values) {
+  int rc = check_batched_args(c, E, n, H, P, interp, node_times);
+  if (rc != MJPCX_OK) return rc;
+  if (!node_values) return fail(c, MJPCX_EINVAL, "null node_values");
+  return c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E)
+                            : do_rollout<float>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E);
+}
+
+int mjpcx_rollout_noise_batched(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* nominal,
+                                const mjpcx_noise_spec* ns) {
+  int rc = check_batched_args(c, E, n, H, P, interp, node_times);
+  if (rc != MJPCX_OK) return rc;
+  if (!nominal || !ns) return fail(c, MJPCX_EINVAL, "null argument");
+  if (ns->mode != MJPCX_NOISE_SAMPLING && ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "unknown noise mode");
+  return c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E)
+                            : do_rollout<float>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E);
+}
+
+int mjpcx_best_batched(mjpcx_ctx* c, int E, int ref_candidate, int32_t* index, double* best_return, double* ref_return, double* spline_values) {
+  if (!c || !index) return fail(c, MJPCX_EINVAL, "null argument");
+  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N)
+    return fail(c, MJPCX_EINVAL, "mjpcx_best_batched: the last rollout was not a batched one of " + std::to_string(E) + " environments");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int np = c->P * c->nu;
+  const size_t rec = kBestHeader + (size_t)np * 8, bytes = rec * E;
+  if (bytes > c->best_cap) {
+    if (c->best_host) (void)hipHostFree(c->best_host);
+    c->best_host = nullptr; c->best_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
+    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
+    c->best_cap = bytes;
+  }
+  if (c->precision == 64)
+    hipLaunchKernelGGL((best_segmented_kernel<double>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
+                       (const double*)c->d_nodes.p, c->N, c->env_n, np, ref_candidate, (unsigned char*)c->best_dev, (unsigned)rec);
+  else
+    hipLaunchKernelGGL((best_segmented_kernel<float>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
+                       (const float*)c->d_nodes.p, c->N, c->env_n, np, ref_candidate, (unsigned char*)c->best_dev, (unsigned)rec);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int e = 0; e < E; e++) {
+    const BestRecord* r = (const BestRecord*)((const char*)c->best_host + rec * e);
+    index[e] = r->best_index;
+    if (best_return) best_return[e] = r->best_return;
+    if (ref_return) ref_return[e] = r->ref_return;
+    if (spline_values) std::memcpy(spline_values + (size_t)e * np, r->spline, (size_t)np * 8);
+  }
+  return MJPCX_OK;
 }
 
 int mjpcx_sync(mjpcx_ctx* c) {

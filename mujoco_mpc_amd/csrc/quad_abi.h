@@ -30,6 +30,8 @@ struct QArgs {
   double* ovf_slab;   // builds with QEXP_OVF_SLAB only (nullptr otherwise): per wavefront, (kQMaxCon - kQLdsSlots) x kQConRec x 64 doubles ([slot][field][lane], as the
                       // LDS store): a lane's contacts beyond the LDS slots (quad_ovf_doubles_per_wave / quad_waves: quad_launch.h)
   int con_cap;        // a lane that collects more contacts than this hands its candidate on (0: kQMaxCon, the store's capacity; MJPCX_QUAD_CON_CAP lowers it, for tests of the hand-on)
+  int env_n;          // several environments in one launch (env_select.h): candidates per environment, a multiple of 64 (0: one environment) ...
+  unsigned env_stride;  // ... and the bytes between the plan records of consecutive environments (node_times, nominal and the blob are environment 0's)
 };
 
 // the feedback policy of the iLQG rollouts (FeedbackArgs of ilqg_kernels.h): nullptr members = the spline policy of QArgs

@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "env_select.h"
 #include "quad_model.h"
 
 namespace mjpcx { namespace quad {
@@ -202,8 +203,15 @@ constexpr size_t kQWaveLds = (kQWaveCon + kQWaveMl + kQWaveMt) * sizeof(double);
 // Workgroup = W wavefronts (W = 4 for the large batches: one per SIMD of a CU, sharing one model image; W = 1 spreads small batches
 // over the CUs). stats[0]: candidates handed to the fallback kernel, stats[1 + log2(flag)]: by reason.
 template <bool FEEDBACK>
-__device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob,
-                                                 const QBlob& bo, const QArgs& a, const QFeedback& fb, int* __restrict__ stats) {
+__device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob0,
+                                                 const QBlob& bo, const QArgs& a0, const QFeedback& fb, int* __restrict__ stats) {
+  // the workgroup's environment (env_select.h; 0 of one unless a0.env_n is set), from its first candidate: that environment's blob, node
+  // times, nominal spline and noise stream. What the workgroup shares below (static_pose from the mocap pose) is then the environment's.
+  const int env = env_of(a0, (int)((blockIdx.x * blockDim.x) >> 6) * (a0.cpw > 0 ? a0.cpw : 16));
+  const double* __restrict__ blob = env_ptr(blob0, env, a0.env_stride);
+  QArgs a = a0;
+  env_rebase(a, env);
+  a.seed += (uint64_t)env; a.candidate_offset -= env * a0.env_n;
   __shared__ QuadModel sm;
   __shared__ QStaticPose sp[kQStatic];
   extern __shared__ __attribute__((aligned(16))) double con_lds[];

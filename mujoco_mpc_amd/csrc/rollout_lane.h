@@ -27,6 +27,7 @@
 #include <utility>
 
 #include "device_common.h"
+#include "env_select.h"
 
 namespace mjpcx {
 
@@ -130,7 +131,23 @@ struct RolloutArgs {
   uint64_t xfrc_seed;
   // generic Jacobian-free kernels, second pass: roll out only the candidates whose failure[] carries the list-overflow warning (bit 32 << 8)
   int only_overflowed;
+  // several environments in one launch (mjpcx_rollout_*_batched): global candidate c = e * env_n + i is candidate i of environment e,
+  // whose plan record [node_times | nominal | variance | blob] lies e * env_stride bytes behind environment 0's (node_times, nominal,
+  // init and the wave kernels' blob point into record 0). env_n = 0: one environment. env_n is a multiple of 64, so the environment
+  // is uniform over a wavefront and over a workgroup of the lane, quad and limb kernels.
+  int env_n;
+  unsigned env_stride;
+  const LaneInit<T>* init;  // lane family: the initial condition (in the record)
 };
+
+template <typename T> __device__ __forceinline__ RolloutArgs<T> env_view(const RolloutArgs<T>& a, int env) {
+  RolloutArgs<T> r = a;
+  env_rebase(r, env);
+  r.init = env_ptr(a.init, env, a.env_stride);
+  r.noise.seed = a.noise.seed + (uint64_t)env;
+  r.noise.candidate_offset = a.noise.candidate_offset - env * a.env_n;
+  return r;
+}
 
 // weighted sum of norms over the (compile-time) term partition of the residual
 template <class TK, typename T, int... K>
@@ -720,9 +737,13 @@ struct StaticModel {  // returns the constexpr object BY VALUE: a local constant
 // NOISY = true: Trajectory::NoisyRollout -- Ornstein-Uhlenbeck xfrc_applied noise on every body (its own instantiation, so the
 // plain rollout carries neither the 6 NB force registers nor the Philox draws).
 template <class TP, class TK, typename T, class MC, bool SPLIT = false, bool NOISY = false>
-__global__ __launch_bounds__(64) void rollout_lane_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk,
-                                                           const RolloutArgs<T> a) {
+__global__ __launch_bounds__(64) void rollout_lane_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk_karg,
+                                                           const RolloutArgs<T> a_karg) {
   decltype(auto) m = MC::template get<T>(m_karg);
+  // the workgroup's environment (one wavefront, 64 consecutive candidates): its plan record and initial condition
+  const RolloutArgs<T> a = env_view(a_karg, env_of(a_karg, blockIdx.x * 64));
+  LaneTask<T> tk = tk_karg;
+  lane_task_init(tk, a.init);
   constexpr int NB = TP::NB, NV = TP::NV, NU = TP::NU, NS = TP::NSITE;
   [[maybe_unused]] constexpr int NR = TK::NR, NTR = TK::NTRACE, DS = 2 * NV;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -950,13 +971,17 @@ __global__ __launch_bounds__(64) void rollout_lane_kernel(const LaneModel<T> m_k
 // state / action, redoes the position stage (what remains of lane_forward once only site_xpos is used), evaluates the residual
 // and the cost exactly as the fused loop does, and applies its recording rules: nothing after the first bad step, no cost AT it.
 template <class TP, class TK, typename T, class MC>
-__global__ __launch_bounds__(256) void cost_lane_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk, const RolloutArgs<T> a) {
+__global__ __launch_bounds__(256) void cost_lane_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk_karg, const RolloutArgs<T> a) {
   decltype(auto) m = MC::template get<T>(m_karg);
   constexpr int NV = TP::NV, NU = TP::NU, NS = TP::NSITE, NR = TK::NR, DS = 2 * NV;
   const size_t N = (size_t)a.N;
   const size_t item = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (item >= N * (size_t)a.H) return;
   const int t = (int)(item / N), cand = (int)(item - (size_t)t * N);
+  // the mocap pose the residual reads is the environment's (with several environments N is a multiple of 64: a wavefront's 64 items are
+  // one step of 64 consecutive candidates, all of one environment)
+  LaneTask<T> tk = tk_karg;
+  lane_task_init(tk, env_ptr(a.init, env_of(a, cand), a.env_stride));
   const int fb = a.failure[cand];
   if (fb && t > fb - 1) return;
   T qpos[NV], qvel[NV], ctrl[NU];

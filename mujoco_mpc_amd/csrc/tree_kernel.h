@@ -22,11 +22,18 @@ __global__ __launch_bounds__(TREE_KERNEL_THREADS) void rollout_tree_kernel(const
                                                            int* work, int mode, wreal* __restrict__ cone_slabs) {
   typedef LdsLayout<C, wreal> L;
   const int tid = threadIdx.x, nth = blockDim.x;
+  // Several environments (a.env_n set; rollout_lane.h): the workgroups are dealt to the environments in equal shares (the host launches
+  // a multiple of their number), and a workgroup rolls out only candidates of the environment whose blob it staged. One environment:
+  // every workgroup, all candidates -- the launch as it always was.
+  const int num_env = a.env_n > 0 ? a.N / a.env_n : 1, wg_per_env = (int)gridDim.x / num_env;
+  const int env = (int)blockIdx.x / wg_per_env, env_block = (int)blockIdx.x - env * wg_per_env;
+  const int env_count = a.env_n > 0 ? a.env_n : a.N, env_first = env * env_count;
+  if (env >= num_env) return;  // (never with the host's grid; the whole workgroup leaves)
   {
     const uint4* src = reinterpret_cast<const uint4*>(image);
     uint4* dst = reinterpret_cast<uint4*>(mjpcx_lds);
     for (unsigned i = tid; i < L::kBytes / 16; i += nth) dst[i] = src[i];
-    const uint4* bs = reinterpret_cast<const uint4*>(tk_in.blob);
+    const uint4* bs = reinterpret_cast<const uint4*>(env_ptr(tk_in.blob, env, a.env_stride));
     uint4* bd = reinterpret_cast<uint4*>(mjpcx_lds + L::kBytes);
     for (unsigned i = tid; i < blob_bytes / 16; i += nth) bd[i] = bs[i];
   }
@@ -60,30 +67,36 @@ __global__ __launch_bounds__(TREE_KERNEL_THREADS) void rollout_tree_kernel(const
     return;
   }
   // Persistent wavefronts. Every wavefront starts on candidate (workgroup, wavefront); after that, mode bit 4 (16) hands the
-  // remaining candidates out through one atomic counter (work[2], zeroed by the host before the launch) -- a wavefront that drew
+  // remaining candidates out through one atomic counter (work[2 + environment], zeroed by the host before the launch) -- a wavefront that drew
   // cheap rollouts (few Newton iterations) takes more of them, so the launch ends with the mean, not with the unluckiest
   // stride; without the bit, the static grid stride. Results do not depend on which wavefront rolls a candidate out.
   // cones beyond the LDS list go to this wavefront's slab in global memory (wave_tree.h)
-  const int total_waves = gridDim.x * (nth >> 6);
+  const int total_waves = wg_per_env * (nth >> 6);  // (of this environment)
   wreal* slab = cone_slabs ? cone_slabs + (size_t)(blockIdx.x * (nth >> 6) + wave) * (size_t)((kTreeMaxConeTotal - kTreeMaxCone) * kConeRec) : nullptr;
   const bool dynamic = !BIG && (mode & 16);
-  int cand = blockIdx.x * (nth >> 6) + wave;
-  while (cand < a.N) {
+  const int env_end = env_first + env_count;
+  int cand = env_first + env_block * (nth >> 6) + wave;  // the counter of environment e is work[2 + e]
+  while (cand < env_end) {
+    // the request as this environment sees it, rebuilt per candidate from the kernel arguments (the asm keeps the optimiser from hoisting it:
+    // five more scalars alive over the whole rollout cost vector registers through the scalar spills)
+    int env_here = env;
+    asm volatile("" : "+s"(env_here));
+    const RolloutArgs<wreal> ae = env_view(a, env_here);
     if (mode & 8) {  // bring-up aid (MJPCX_TREE_MODE=8): poison the arena -- a read of storage this rollout never wrote shows up as NaN / -1
       for (unsigned i = lane; i < arena_bytes / 4; i += 64) reinterpret_cast<unsigned*>(arena)[i] = 0xFFFFFFFFu;
       WSYNC();
     }
     if constexpr (BIG) {
       if (a.failure[cand] & (32 << 8))  // wave-uniform
-        wave_rollout_body<C::NMAX, true, kTreeMaxSimpleBig, kTreeMaxConeBig>(m, tk, a, arena, cand, lane);
+        wave_rollout_body<C::NMAX, true, kTreeMaxSimpleBig, kTreeMaxConeBig>(m, tk, ae, arena, cand, lane);
     } else {
       if (!(mode & 32) || (a.failure[cand] & kQFallback))  // wave-uniform
-        wave_rollout_body<C::NMAX, true>(m, tk, a, arena, cand, lane, slab);
+        wave_rollout_body<C::NMAX, true>(m, tk, ae, arena, cand, lane, slab);
     }
     if (dynamic) {
       int next = 0;
-      if (lane == 0) next = atomicAdd(work + 2, 1);
-      cand = total_waves + __builtin_amdgcn_readfirstlane(next);
+      if (lane == 0) next = atomicAdd(work + 2 + env, 1);
+      cand = env_first + total_waves + __builtin_amdgcn_readfirstlane(next);
     } else {
       cand += total_waves;
     }

@@ -309,7 +309,12 @@ __global__ __launch_bounds__(64) WAVE_KERNEL_ATTR void rollout_wave_kernel(const
   // The model and task structs stay in the kernel-argument segment (scalar loads). Staging the model allocation into
   // LDS was tried: no shorter step, fewer candidates per CU, and a run-time-rebased copy of this struct
   // ends up in the private segment -- every pointer fetch becomes a scratch load. (Registered models: tree_kernel.h.)
-  wave_rollout_body<NMAX, TREE, SMALL ? kTreeMaxSimple : kTreeMaxSimpleBig, SMALL ? kTreeMaxCone : kTreeMaxConeBig, RK4>(m, tk, a, smem_raw, blockIdx.x, threadIdx.x);
+  // the candidate's environment (0 of one unless a.env_n is set): its own blob, node times, nominal spline and noise stream
+  // (rollout_lane.h, env_view). WTask and RolloutArgs hold scalars and pointers only: the rebased copies stay in SGPRs.
+  const int env = env_of(a, blockIdx.x);
+  WTask tke = tk;
+  tke.blob = env_ptr(tk.blob, env, a.env_stride);
+  wave_rollout_body<NMAX, TREE, SMALL ? kTreeMaxSimple : kTreeMaxSimpleBig, SMALL ? kTreeMaxCone : kTreeMaxConeBig, RK4>(m, tke, env_view(a, env), smem_raw, blockIdx.x, threadIdx.x);
 }
 
 } }  // namespace mjpcx::WAVE_NS

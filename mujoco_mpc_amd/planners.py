@@ -354,6 +354,135 @@ class GpuSamplingPlanner:
         self._set_winner(self.trajectory_order[candidate], p.plan.values())
 
 
+class GpuBatchSamplingPlanner:
+    """Predictive Sampling for `num_envs` environments (robots) on ONE context: every plan step is one `set_states`, one
+    `rollout_noise_batched` over all E x n candidates, one `best_batched` and one sync, instead of E plan steps one after the
+    other. The environments share the model and the task (weights, parameters); each has its own state, clock, mocap pose
+    and policy. Environment e with seed s behaves exactly like a GpuSamplingPlanner with seed s + e: the per-environment
+    logic (nominal resampling, policy copy, ActionFromPolicy) IS that planner's, one member per environment."""
+
+    def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
+        if int(num_envs) < 1:
+            raise ValueError("GpuBatchSamplingPlanner needs at least one environment")
+        self.num_envs, self.device, self.precision, self.seed = int(num_envs), device, precision, seed
+        self._backend_factory = backend_factory
+        self.model = self.task = self.ctx = None
+        self.iteration = 0
+        self.rollouts_compute_time = self.policy_update_compute_time = 0.0
+        self._last = None  # what the context's last rollout was: "plan" (n candidates per environment) or "nominal"
+        # the members never roll out themselves: they are handed the shared context instead of creating their own
+        self.envs = [GpuSamplingPlanner(device, precision, seed + e, backend_factory=lambda task: self.ctx) for e in range(self.num_envs)]
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        for p in self.envs:
+            p.initialize(model, task)
+
+    @property
+    def num_trajectory_(self):
+        return self.envs[0].num_trajectory_
+
+    @num_trajectory_.setter
+    def num_trajectory_(self, n):
+        for p in self.envs:
+            p.num_trajectory_ = int(n)
+
+    def _check_n(self, n):
+        if n < 64 or n % 64 != 0:
+            raise ValueError(f"GpuBatchSamplingPlanner: {n} candidates per environment; a batched launch needs a positive multiple "
+                             "of 64 (every wavefront serves one environment) -- set sampling_trajectories / num_trajectory_ accordingly")
+
+    def allocate(self):
+        if self._backend_factory is not None:
+            self.ctx = self._backend_factory(self.task)
+        else:
+            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+        for p in self.envs:
+            p.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        for p in self.envs:
+            p.reset(horizon, initial_repeated_action)
+        self._last = None
+
+    def set_states(self, states):
+        """one State per environment (Planner::SetState for each)"""
+        if len(states) != self.num_envs:
+            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
+        for p, st in zip(self.envs, states):
+            p.set_state(st)
+
+    def _push_states(self):
+        sync_task(self.ctx, self.task)
+        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
+                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
+                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+
+    def optimize_policy(self, horizon, pool=None):
+        n = self.num_trajectory_
+        self._check_n(n)
+        for p in self.envs:
+            p.update_nominal_policy(horizon)
+            p.policy.plan.set_interpolation(p.interpolation_)
+        t0 = _time.perf_counter()
+        plans = [p.policy.plan for p in self.envs]
+        exploration = self.envs[0].noise_exploration
+        ns = capi.make_noise_spec(seed=self.seed, iteration=self.iteration, mode=capi.NOISE_SAMPLING, candidate_offset=0,
+                                  nominal_candidate=0, std0=exploration[0], std1=exploration[1])
+        self._push_states()
+        self.ctx.rollout_noise_batched(n, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
+                                       np.stack([pl.values() for pl in plans]), ns, num_envs=self.num_envs)
+        idx, best_ret, nominal_ret, values = self.ctx.best_batched(self.num_envs, 0)
+        self._last = "plan"
+        self._n = n
+        self.rollouts_compute_time = (_time.perf_counter() - t0) * 1e6
+        self.iteration += 1
+        t0 = _time.perf_counter()
+        for e, p in enumerate(self.envs):
+            p._offset, p._n_local = 0, n
+            p.trajectory_order, p._scores = [int(idx[e])], [float(best_ret[e])]
+            p.iteration = self.iteration
+            p._set_winner(int(idx[e]), values[e])
+            p.best_return, p.nominal_return = float(best_ret[e]), float(nominal_ret[e])
+            p.improvement = max(float(nominal_ret[e] - best_ret[e]), 0.0)
+        self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
+
+    @property
+    def winners(self):
+        return [p.winner for p in self.envs]
+
+    def nominal_trajectory(self, horizon, pool=None):
+        """NominalTrajectory of every environment in one launch: 64 candidates per environment, candidate 0 carrying the policy"""
+        plans = [(p.winner_policy.plan if p.winner_policy.plan.size() else p.policy.plan) for p in self.envs]
+        if any(pl.size() != plans[0].size() for pl in plans):
+            raise ValueError("the environments' policies have different numbers of spline nodes")
+        self._push_states()
+        if plans[0].size() == 0:
+            times = np.array([[p.time] for p in self.envs])
+            values = np.zeros((self.num_envs, 64, 1, self.model.nu))
+        else:
+            times = np.stack([pl.times() for pl in plans])
+            values = np.stack([np.broadcast_to(pl.values()[None], (64,) + pl.values().shape) for pl in plans])
+        self.ctx.rollout_splines_batched(horizon, plans[0].interpolation(), times, values, num_envs=self.num_envs, n_per_env=64)
+        self._last = "nominal"
+        out = [self.ctx.fetch_trajectory(64 * e) for e in range(self.num_envs)]
+        for p, tr in zip(self.envs, out):
+            p._best = tr
+        return out
+
+    def action_from_policy(self, env, action, state, time, use_previous=False):
+        return self.envs[env].action_from_policy(action, state, time, use_previous)
+
+    def best_trajectory(self, env):
+        p = self.envs[env]
+        if p._best is None and self._last == "plan":
+            p._best = self.ctx.fetch_trajectory(env * self._n + p.winner)
+        return p._best
+
+    def num_parameters(self):
+        return self.envs[0].num_parameters()
+
+
 class GpuCrossEntropyPlanner:
     """mjpc::CrossEntropyPlanner (mjpc/planners/cross_entropy/planner.{h,cc}) with the candidate
     fan-out, the sort and the elite statistics on the GPU. Differences forced by SURVEY F4/F5 as for

@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""What many environments per launch buy: for each shape E x n, the time of (a) E sequential plan steps (set_state, rollout_noise, best:
+each ends in its own sync) and (b) one batched plan step (set_states, rollout_noise_batched, best_batched: one sync) on the same context,
+alternating in one process. Host clock around work that ends in a sync; warm-up for every shape; median and spread over the timed steps.
+
+  python tools/batch_sweep.py [--steps 12] [--warmup 2] [--out profiles/batch_sweep.jsonl] [--only QuadrupedFlat]
+
+Kernel thresholds are the library's defaults: the sequential side of 8 x 2048 runs eight launches of the kernel a 2048-candidate batch gets,
+the batched side one launch of the kernel a 16384-candidate batch gets -- that is the feature."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from mujoco_mpc_amd import capi  # noqa: E402
+from mujoco_mpc_amd.task import load_task  # noqa: E402
+
+# (task, precision, horizon, [(E, n), ...])
+SHAPES = [("QuadrupedFlat", 64, 100, [(8, 2048), (4, 4096), (1, 16384)]),
+          ("HumanoidTrack", 32, 64, [(4, 2048), (1, 8192)]),
+          ("Cartpole", 64, 128, [(64, 64), (1, 4096)])]
+
+
+def initial(task, name, E, rng):
+    """E states (perturbed around the task's start), clocks and mocap poses"""
+    m = task.model
+    if name == "QuadrupedFlat":
+        task.transition(0.0)
+        q0, v0 = np.asarray(m.keyframes["home"]["qpos"], float), np.zeros(m.nv)
+        mocap = np.array([0.3, 0, 0.26, 1, 0, 0, 0, -2.5, 0, 0, 1, 0, 0, 0.0])
+    elif name == "HumanoidTrack":
+        e = task.transition(0.0, mode=9)
+        q0, v0 = np.asarray(e["qpos"], float), np.asarray(e["qvel"], float)
+        mocap = np.concatenate([np.concatenate([p, [1, 0, 0, 0]]) for p in np.asarray(e["mocap_pos"]).reshape(-1, 3)])
+    else:
+        q0, v0, mocap = np.zeros(m.nq), np.zeros(m.nv), None
+    states = []
+    for e in range(E):
+        q = q0.copy()
+        if name == "Cartpole":
+            q += rng.uniform(-0.5, 0.5, m.nq)
+        else:
+            q[7:] += rng.normal(0, 0.02, m.nq - 7)   # joints only: the base pose and its quaternion stay
+        states.append(np.concatenate([q, v0]))
+    return np.stack(states), np.zeros(E), None if mocap is None else np.stack([mocap] * E)
+
+
+def sweep(name, precision, H, shapes, steps, warmup, out):
+    task = load_task(name)
+    m = task.model
+    rng = np.random.default_rng(1)
+    ctx = capi.Context(task.packed_model(), task.packed(), 0, precision)
+    P = int(m.get_number("sampling_spline_points", 6))
+    interp = int(m.get_number("sampling_representation", capi.SPLINE_CUBIC))
+    std = float(m.get_number("sampling_exploration", 0.1))
+    dt = m.get_number("agent_timestep", m.timestep)
+    times1 = np.arange(P) * ((H - 1) * dt / max(P - 1, 1))
+    for E, n in shapes:
+        states, clocks, mocap = initial(task, name, E, rng)
+        times, nominal = np.stack([times1] * E), np.zeros((E, P, m.nu))
+        it = [0]
+
+        def sequential():
+            it[0] += 1
+            for e in range(E):
+                ctx.set_state(states[e], clocks[e], None if mocap is None else mocap[e])
+                ctx.rollout_noise(n, H, interp, times[e], nominal[e], capi.make_noise_spec(seed=7 + e, iteration=it[0], std0=std))
+                ctx.best(0)
+
+        def batched():
+            ctx.set_states(states, clocks, mocap)
+            ctx.rollout_noise_batched(n, H, interp, times, nominal, capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_envs=E)
+            ctx.best_batched(E, 0)
+
+        for _ in range(warmup):
+            sequential()
+            batched()
+        ts, tb = [], []
+        for _ in range(steps):   # alternating: both sides see the same clocks and the same neighbours on the machine
+            t0 = time.perf_counter(); sequential(); t1 = time.perf_counter(); batched(); t2 = time.perf_counter()
+            ts.append((t1 - t0) * 1e3)
+            tb.append((t2 - t1) * 1e3)
+        rec = {"task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps, "warmup": warmup,
+               "kernel": ctx.kernel_name.split(" (")[0],
+               "sequential_ms": {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))},
+               "batched_ms": {"median": float(np.median(tb)), "min": float(np.min(tb)), "max": float(np.max(tb))},
+               "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)),
+               "beyond_spread": bool(np.max(tb) < np.min(ts))}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+        out.flush()
+    ctx.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=12)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_sweep.jsonl"))
+    ap.add_argument("--only", default=None)
+    a = ap.parse_args()
+    if a.steps < 10:
+        raise SystemExit("batch_sweep.py: at least 10 timed steps")
+    with open(a.out, "w") as out:
+        for name, precision, H, shapes in SHAPES:
+            if a.only is None or a.only == name:
+                sweep(name, precision, H, shapes, a.steps, a.warmup, out)
+
+
+if __name__ == "__main__":
+    main()
