@@ -352,9 +352,33 @@ int mjpcx_rollout_splines_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, i
 
 /* mjpcx_rollout_noise for E environments: node_times E x P, nominal_values E x P x nu. Environment e draws exactly the noise
  * that mjpcx_rollout_noise draws with noise->seed + e and the same remaining fields; candidate_offset and nominal_candidate
- * are local to the environment -- so E plain calls reproduce a batched one. param_variance (CE) is shared. */
+ * are local to the environment -- so E plain calls reproduce a batched one. noise->param_variance (CE) is shared by all
+ * environments; mjpcx_rollout_noise_batched_ce takes one row per environment. */
 int mjpcx_rollout_noise_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,
                                 const double* node_times, const double* nominal_values, const mjpcx_noise_spec* noise);
+
+/* mjpcx_rollout_noise_batched for a cross-entropy fleet: every environment has its own variance. param_variance is E x P*nu, row e
+ * for environment e; noise->mode must be MJPCX_NOISE_CROSS_ENTROPY (MJPCX_EINVAL otherwise) and noise->param_variance is ignored.
+ * Environment e draws exactly the noise mjpcx_rollout_noise draws with noise->seed + e, row e as param_variance and the same
+ * remaining fields; candidate_offset, nominal_candidate and explore_count are local to the environment. Validation and error
+ * codes as mjpcx_rollout_noise_batched. */
+int mjpcx_rollout_noise_batched_ce(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,
+                                   const double* node_times, const double* nominal_values, const double* param_variance,
+                                   const mjpcx_noise_spec* noise);
+
+/* The cross-entropy update, segmented: one launch and one sync give, per environment over the n_per_env returns of the last
+ * batched rollout (either kind), what mjpcx_topk(n_elite + 1) without the nominal, 2 x mjpcx_elite_moments and the host's
+ * divisions give for one:
+ *   index (E x n_elite, LOCAL), total_return (E x n_elite): the n_elite best candidates, ascending (NaN last, ties to the lower
+ *     index); local candidate skip_candidate (the nominal rollout; -1: none) is never one of them;
+ *   mean (E x P*nu): the elites' spline parameters, summed in rank order in fp64 and divided by n_elite;
+ *   variance (E x P*nu): the sum of (p - mean)^2 divided by n_elite - 1 (n_elite == 1: inf / NaN, as the reference);
+ *   avg_return (E): the elites' mean return.
+ * Any output but index may be NULL. Deterministic: two calls on the same rollout give the same bits. MJPCX_EINVAL when the last
+ * rollout was not a batched one of num_envs environments, when n_elite < 1, or when n_elite exceeds the candidates of an
+ * environment that are left after the skip. */
+int mjpcx_ce_update_batched(mjpcx_ctx* ctx, int num_envs, int n_elite, int skip_candidate, int32_t* index, double* total_return,
+                            double* mean, double* variance, double* avg_return);
 
 /* mjpcx_best, segmented: one launch and one sync give, per environment, the argmin over its n_per_env returns (ties by
  * index) as a LOCAL index -> index[E], best_return[E]; the return of local candidate ref_candidate (-1: skip) -> ref_return[E];

@@ -29,6 +29,7 @@ EXPORTS = [
     "mjpcx_device_buffer", "mjpcx_comm_unique_id", "mjpcx_comm_init", "mjpcx_comm_info", "mjpcx_exchange_best", "mjpcx_merge_topk",
     "mjpcx_elite_allreduce", "mjpcx_comm_barrier", "mjpcx_comm_destroy",
     "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
+    "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched",
 ]
 
 _LIB = None
@@ -73,6 +74,8 @@ def lib():
         L.mjpcx_rollout_splines_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p]
         L.mjpcx_rollout_noise_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
+        L.mjpcx_rollout_noise_batched_ce.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
+        L.mjpcx_ce_update_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_sync.argtypes = [vp]
         L.mjpcx_get_returns.argtypes = [vp, c_f64p, c_i32p]
         L.mjpcx_get_return_at.argtypes = [vp, C.c_int, C.POINTER(C.c_double), c_i32p]
@@ -266,6 +269,29 @@ class Context:
         self._chk(lib().mjpcx_rollout_noise_batched(self.handle, E, int(n_per_env), int(horizon), P, int(interp), as_f64p(nt),
                                                     as_f64p(nom), C.byref(noise_spec)))
         self.N, self.H, self.P, self.n_per_env = E * int(n_per_env), int(horizon), P, int(n_per_env)
+
+    def rollout_noise_batched_ce(self, n_per_env, horizon, interp, node_times, nominal, param_variance, noise_spec, num_envs=None):
+        """rollout_noise_batched in cross-entropy mode with one variance row per environment: param_variance E x P x nu
+        (noise_spec.param_variance is ignored)."""
+        nt, nom, var = _f(node_times), _f(nominal), _f(param_variance)
+        E = int(num_envs) if num_envs is not None else (nt.shape[0] if nt.ndim == 2 else 1)
+        P = nt.size // E if E > 0 else nt.size
+        assert E < 1 or (nom.size == E * P * self.nu and var.size == E * P * self.nu)
+        self._chk(lib().mjpcx_rollout_noise_batched_ce(self.handle, E, int(n_per_env), int(horizon), P, int(interp), as_f64p(nt),
+                                                       as_f64p(nom), as_f64p(var), C.byref(noise_spec)))
+        self.N, self.H, self.P, self.n_per_env = E * int(n_per_env), int(horizon), P, int(n_per_env)
+
+    def ce_update_batched(self, num_envs, n_elite, skip_candidate=-1):
+        """the cross-entropy update of every environment in one launch / one sync: the n_elite best local candidates (without
+        skip_candidate) and their returns (E x n_elite), the elites' mean and variance (E x P x nu), their mean return (E)."""
+        E, k = int(num_envs), int(n_elite)
+        shape = (max(E, 1), max(k, 1))
+        idx, ret = np.zeros(shape, np.int32), np.zeros(shape)
+        mean, var = np.zeros((max(E, 1), self.P, self.nu)), np.zeros((max(E, 1), self.P, self.nu))
+        avg = np.zeros(max(E, 1))
+        self._chk(lib().mjpcx_ce_update_batched(self.handle, E, k, int(skip_candidate), as_i32p(idx), as_f64p(ret), as_f64p(mean),
+                                                as_f64p(var), as_f64p(avg)))
+        return idx, ret, mean, var, avg
 
     def best_batched(self, num_envs, ref_candidate=0, with_spline=True):
         """per environment: local argmin, its return, the return of local ref_candidate, the winner's spline (E x P x nu)."""

@@ -271,30 +271,131 @@ __global__ __launch_bounds__(256) void best_segmented_kernel(const double* __res
     for (int j = threadIdx.x; j < np; j += 256) rec->spline[j] = (double)nodes[(size_t)j * N + first + w];
 }
 
-// elite moments: one workgroup per spline parameter j, fixed-shape tree reduction (deterministic)
+// elite moments: one workgroup per spline parameter j, fixed-shape tree reduction (deterministic). elite_reduce is the reduction of
+// both elite kernels (this one and ce_update_kernel): 256 strided partial sums over the elites in rank order, then the halving tree.
+// `t` is the thread's place among the 256 of its reduction, `sm` their 256 doubles; every thread of the workgroup calls it. The
+// candidate indices are relative to `nodes_j` (row j of the [P*nu][N] spline nodes) and `ret`; mean_j == nullptr: plain sums.
+template <typename T>
+__device__ __forceinline__ double elite_reduce(const T* __restrict__ nodes_j, const double* __restrict__ ret, const int* cand, int n,
+                                               const double* mean_j, int t, double* sm) {
+  double acc = 0;
+  for (int i = t; i < n; i += 256) {
+    const int c = cand[i];
+    if (nodes_j) {
+      const double p = (double)nodes_j[c];
+      if (mean_j) { const double d = p - mean_j[0]; acc += d * d; } else acc += p;
+    } else {
+      acc += ret[c];
+    }
+  }
+  sm[t] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) sm[t] += sm[t + s];
+    __syncthreads();
+  }
+  return sm[0];
+}
 template <typename T>
 __global__ __launch_bounds__(256) void elite_moments_kernel(const T* __restrict__ nodes, const double* __restrict__ ret,
                                                             const int* __restrict__ cand, int n, int N, int np,
                                                             const double* __restrict__ mean, double* out) {
   __shared__ double sm[256];
   const int j = blockIdx.x;  // j == np: the return sum
-  double acc = 0;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int c = cand[i];
-    if (j < np) {
-      const double p = (double)nodes[(size_t)j * N + c];
-      if (mean) { const double d = p - mean[j]; acc += d * d; } else acc += p;
-    } else {
-      acc += ret[c];
-    }
+  const double r = elite_reduce<T>(j < np ? nodes + (size_t)j * N : nullptr, ret, cand, n, mean && j < np ? mean + j : nullptr, threadIdx.x, sm);
+  if (threadIdx.x == 0) out[j] = r;
+}
+
+// The cross-entropy update of E environments in one launch (mjpcx_ce_update_batched): one workgroup of 16 wavefronts per environment.
+//  1. Selection: a bitonic sort of the environment's (return, local index) keys by less_ri, padded to n2 = 2^m >= 1024 with keys that
+//     sort last; the candidate to skip (the nominal rollout) is one of them. Split layout, returns [n2] then indices [n2]: 12 bytes a
+//     key, so n2 <= 8192 sorts in 96 KiB of LDS (IN_LDS); larger environments sort in a global scratch slab of the same layout.
+//     Element i belongs to thread i % 1024, so a compare-exchange at distance j < 64 pairs two lanes of one wavefront: those steps run
+//     on registers -- DPP quad_perm for j = 1, 2, ds_bpermute above -- six of them between two barriers. Only the steps at distance
+//     >= 64 go through memory with a barrier each: 45 barriers for 16384 keys instead of 105.
+//  2. Moments: the elites are the first n_elite keys. The four quarters of the workgroup take the parameters j in turn, each with
+//     elite_reduce -- the sum, the mean from it, then the squares about that mean, all fp64 -- so the result equals
+//     mjpcx_topk + 2 x mjpcx_elite_moments + the host's divisions. No atomics: a second call gives the same bits.
+// Everything goes to the environment's pinned, device-mapped record [avg_return | index | total_return | mean | variance].
+template <int JJ> __device__ __forceinline__ RetIdx lane_xor_ri(const RetIdx& v) {
+  if constexpr (JJ == 1) return dpp_ri<0xB1>(v);       // quad_perm:[1,0,3,2]
+  else if constexpr (JJ == 2) return dpp_ri<0x4E>(v);  // quad_perm:[2,3,0,1]
+  else { RetIdx o; o.r = __shfl_xor(v.r, JJ, 64); o.i = __shfl_xor(v.i, JJ, 64); return o; }
+}
+// compare-exchange of element i with element i ^ JJ (a lane of the same wavefront) in the merge of blocks of k
+template <int JJ> __device__ __forceinline__ void lane_cmpx(RetIdx& v, int i, int k) {
+  const RetIdx o = lane_xor_ri<JJ>(v);
+  const bool keep_min = ((i & JJ) == 0) == ((i & k) == 0);
+  if (keep_min ? less_ri(o, v) : less_ri(v, o)) v = o;
+}
+__device__ __forceinline__ void lane_merge(RetIdx& v, int i, int k) {  // the steps of distance < 64 of the merge of blocks of k
+  if (k > 32) lane_cmpx<32>(v, i, k);
+  if (k > 16) lane_cmpx<16>(v, i, k);
+  if (k > 8) lane_cmpx<8>(v, i, k);
+  if (k > 4) lane_cmpx<4>(v, i, k);
+  if (k > 2) lane_cmpx<2>(v, i, k);
+  lane_cmpx<1>(v, i, k);
+}
+constexpr int kCeLdsKeys = 8192;  // 12 bytes a key: 96 KiB of a CU's 160 KiB of LDS
+struct CeRecord { size_t bytes, off_index, off_ret, off_mean, off_var; };  // avg_return at 0
+template <typename T, bool IN_LDS>
+__global__ __launch_bounds__(1024) void ce_update_kernel(const double* __restrict__ ret, const T* __restrict__ nodes, int N, int n_env, int n2, int np,
+                                                          int n_elite, int skip, double* scratch, unsigned char* out, CeRecord rec) {
+  extern __shared__ __attribute__((aligned(16))) double ce_lds[];
+  __shared__ double sm[4][256];
+  __shared__ double sm_mean[4];
+  const int env = blockIdx.x, first = env * n_env, tid = threadIdx.x;
+  double* keys;
+  int* idx;
+  if constexpr (IN_LDS) { keys = ce_lds; idx = reinterpret_cast<int*>(ce_lds + n2); }
+  else { keys = scratch + (size_t)env * (n2 + n2 / 2); idx = reinterpret_cast<int*>(keys + n2); }
+  // n2 is a multiple of 1024: every lane is active in every round of the loops over i
+  for (int i = tid; i < n2; i += 1024) {
+    RetIdx v = i < n_env && i != skip ? RetIdx{ret[first + i], i} : RetIdx{NAN, 0x7fffffff};
+    for (int k = 2; k <= 64; k <<= 1) lane_merge(v, i, k);
+    keys[i] = v.r; idx[i] = v.i;
   }
-  sm[threadIdx.x] = acc;
   __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+  for (int k = 128; k <= n2; k <<= 1) {
+    for (int j = k >> 1; j >= 64; j >>= 1) {
+      for (int i = tid; i < n2; i += 1024) {
+        const int l = i ^ j;
+        if (l > i) {
+          const bool up = (i & k) == 0;
+          const RetIdx a{keys[i], idx[i]}, b{keys[l], idx[l]};
+          if (less_ri(b, a) == up) { keys[i] = b.r; idx[i] = b.i; keys[l] = a.r; idx[l] = a.i; }
+        }
+      }
+      __syncthreads();
+    }
+    for (int i = tid; i < n2; i += 1024) {
+      RetIdx v{keys[i], idx[i]};
+      lane_merge(v, i, k);
+      keys[i] = v.r; idx[i] = v.i;
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) out[j] = sm[0];
+  unsigned char* r = out + (size_t)env * rec.bytes;
+  int* o_index = reinterpret_cast<int*>(r + rec.off_index);
+  double* o_ret = reinterpret_cast<double*>(r + rec.off_ret);
+  double* o_mean = reinterpret_cast<double*>(r + rec.off_mean);
+  double* o_var = reinterpret_cast<double*>(r + rec.off_var);
+  for (int i = tid; i < n_elite; i += 1024) { o_index[i] = idx[i]; o_ret[i] = keys[i]; }
+  const int g = tid >> 8, t = tid & 255;  // quarter g reduces parameter j0 + g; j == np: the returns
+  for (int j0 = 0; j0 <= np; j0 += 4) {
+    const int j = j0 + g;
+    const bool live = j <= np;
+    const T* nodes_j = live && j < np ? nodes + (size_t)j * N + first : nullptr;
+    const double sum = elite_reduce<T>(nodes_j, ret + first, idx, live ? n_elite : 0, nullptr, t, sm[g]);
+    if (t == 0) sm_mean[g] = sum / n_elite;
+    __syncthreads();
+    const double sq = elite_reduce<T>(nodes_j, ret + first, idx, live && j < np ? n_elite : 0, &sm_mean[g], t, sm[g]);
+    if (t == 0 && live) {
+      if (j < np) { o_mean[j] = sm_mean[g]; o_var[j] = sq / (n_elite - 1); }
+      else reinterpret_cast<double*>(r)[0] = sm_mean[g];
+    }
+    __syncthreads();
+  }
 }
 
 // single-workgroup bitonic sort of (return, index) pairs in global memory (n2 = pow2 >= n)
@@ -583,8 +684,9 @@ int reserve_rollout(mjpcx_ctx* c, int N, int H, int P) {
 // asynchronous H2D copy. The slot is recycled only after the kernel that reads it has finished. The blob is the per-plan blob of the
 // wavefront-per-candidate family (wave_model.h) or the lane family's initial condition (LaneInit). E = 0: the plain call -- one record
 // from the state of mjpcx_set_state; E >= 1: node_times is E x P, nominal E x P*nu, the states are those of mjpcx_set_states.
+// variance: one row of P*nu copied into every record, or (variance_rows) E rows, row e into record e.
 template <typename T>
-int stage_plan_inputs(mjpcx_ctx* c, int P, int E, const double* node_times, const double* nominal, const double* variance,
+int stage_plan_inputs(mjpcx_ctx* c, int P, int E, const double* node_times, const double* nominal, const double* variance, bool variance_rows,
                       const T** d_times, const T** d_nominal, const double** d_variance, mjpcx_ctx::Slot** used,
                       const void** d_blob, unsigned* stride) {
   const int np = P * c->nu, nrec = E > 0 ? E : 1;
@@ -611,7 +713,7 @@ int stage_plan_inputs(mjpcx_ctx* c, int P, int E, const double* node_times, cons
     for (int p = 0; p < P; p++) ht[p] = (T)node_times[(size_t)e * P + p];
     T* hn = (T*)(h + off_nom);
     if (nominal) for (int j = 0; j < np; j++) hn[j] = (T)nominal[(size_t)e * np + j];
-    if (variance) std::memcpy(h + off_var, variance, (size_t)np * 8);
+    if (variance) std::memcpy(h + off_var, variance + (variance_rows ? (size_t)e * np : 0), (size_t)np * 8);
     T* hb = (T*)(h + off_blob);
     const double* st = E > 0 ? c->env_state.data() + (size_t)e * nst : nullptr;
     const double* mo = E > 0 && !c->env_mocap.empty() ? c->env_mocap.data() + (size_t)e * 7 * c->nmocap : nullptr;
@@ -903,9 +1005,10 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
 
 template <typename T>
 int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node_times,
-               const double* node_values, const double* nominal, const mjpcx_noise_spec* ns, int E = 0) {
+               const double* node_values, const double* nominal, const mjpcx_noise_spec* ns, int E = 0, const double* variance_rows = nullptr) {
   // E = 0: the plain entry points (one environment, the state of mjpcx_set_state). E >= 1: N = E x n_per_env candidates, environment-major,
-  // from the states of mjpcx_set_states; node_times is E x P and nominal E x P*nu. Same launch code, same kernels.
+  // from the states of mjpcx_set_states; node_times is E x P and nominal E x P*nu. Same launch code, same kernels. variance_rows
+  // (mjpcx_rollout_noise_batched_ce): E x P*nu cross-entropy variances, one row per environment, instead of ns->param_variance for all.
   int rc;
   if ((rc = reserve_rollout(c, N, H, P)) != MJPCX_OK) return rc;
   const int np = P * c->nu;
@@ -916,9 +1019,9 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   const double* d_var = nullptr;
   mjpcx_ctx::Slot* slot = nullptr;
   const bool ce = ns && ns->mode == MJPCX_NOISE_CROSS_ENTROPY;
-  if (ce && !ns->param_variance) return fail(c, MJPCX_EINVAL, "cross-entropy noise needs param_variance");
+  if (ce && !ns->param_variance && !variance_rows) return fail(c, MJPCX_EINVAL, "cross-entropy noise needs param_variance");
   const void* d_blob = nullptr;
-  if ((rc = stage_plan_inputs<T>(c, P, E, node_times, nominal, ce ? ns->param_variance : nullptr, &a.node_times,
+  if ((rc = stage_plan_inputs<T>(c, P, E, node_times, nominal, !ce ? nullptr : variance_rows ? variance_rows : ns->param_variance, variance_rows != nullptr, &a.node_times,
                                  &a.nominal, &d_var, &slot, &d_blob, &a.env_stride)) != MJPCX_OK) return rc;
   a.env_n = E > 1 ? N / E : 0;
   if (!c->wave) a.init = (const LaneInit<T>*)d_blob;
@@ -1551,6 +1654,70 @@ int mjpcx_rollout_noise_batched(mjpcx_ctx* c, int E, int n, int H, int P, int in
   if (ns->mode != MJPCX_NOISE_SAMPLING && ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "unknown noise mode");
   return c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E)
                             : do_rollout<float>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E);
+}
+
+int mjpcx_rollout_noise_batched_ce(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* nominal,
+                                   const double* variance, const mjpcx_noise_spec* ns) {
+  int rc = check_batched_args(c, E, n, H, P, interp, node_times);
+  if (rc != MJPCX_OK) return rc;
+  if (!nominal || !variance || !ns) return fail(c, MJPCX_EINVAL, "null argument");
+  if (ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "mjpcx_rollout_noise_batched_ce: the noise mode must be MJPCX_NOISE_CROSS_ENTROPY");
+  return c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E, variance)
+                            : do_rollout<float>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E, variance);
+}
+
+int mjpcx_ce_update_batched(mjpcx_ctx* c, int E, int n_elite, int skip_candidate, int32_t* index, double* total_return, double* mean,
+                            double* variance, double* avg_return) {
+  if (!c || !index) return fail(c, MJPCX_EINVAL, "null argument");
+  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N)
+    return fail(c, MJPCX_EINVAL, "mjpcx_ce_update_batched: the last rollout was not a batched one of " + std::to_string(E) + " environments");
+  const int n = c->env_n, left = n - (skip_candidate >= 0 && skip_candidate < n ? 1 : 0);
+  if (n_elite < 1 || n_elite > left)
+    return fail(c, MJPCX_EINVAL, "mjpcx_ce_update_batched: n_elite = " + std::to_string(n_elite) + " outside 1.." + std::to_string(left) +
+                                 " (the candidates of an environment without the skipped one)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int np = c->P * c->nu;
+  int n2 = 1024;  // (a multiple of the workgroup: ce_update_kernel)
+  while (n2 < n) n2 <<= 1;
+  CeRecord rec;
+  rec.off_index = 8;
+  rec.off_ret = (rec.off_index + (size_t)n_elite * 4 + 7) & ~(size_t)7;
+  rec.off_mean = rec.off_ret + (size_t)n_elite * 8;
+  rec.off_var = rec.off_mean + (size_t)np * 8;
+  rec.bytes = rec.off_var + (size_t)np * 8;
+  const size_t bytes = rec.bytes * E;
+  if (bytes > c->best_cap) {
+    if (c->best_host) (void)hipHostFree(c->best_host);
+    c->best_host = nullptr; c->best_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
+    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
+    c->best_cap = bytes;
+  }
+  const bool in_lds = n2 <= kCeLdsKeys;
+  const size_t lds = in_lds ? (size_t)n2 * 12 : 0;
+  if (!in_lds) HIPCHK(c, c->d_sort.reserve((size_t)E * n2 * 12));
+  auto launch = [&](auto kern, auto* nodes) {
+    hipError_t e = in_lds ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(E), dim3(1024), lds, c->stream, (const double*)c->d_ret.p, nodes, c->N, n, n2, np, n_elite, skip_candidate,
+                       in_lds ? nullptr : (double*)c->d_sort.p, (unsigned char*)c->best_dev, rec);
+    return hipGetLastError();
+  };
+  hipError_t le;
+  if (c->precision == 64) le = in_lds ? launch(ce_update_kernel<double, true>, (const double*)c->d_nodes.p) : launch(ce_update_kernel<double, false>, (const double*)c->d_nodes.p);
+  else le = in_lds ? launch(ce_update_kernel<float, true>, (const float*)c->d_nodes.p) : launch(ce_update_kernel<float, false>, (const float*)c->d_nodes.p);
+  HIPCHK(c, le);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int e = 0; e < E; e++) {
+    const char* r = (const char*)c->best_host + rec.bytes * e;
+    std::memcpy(index + (size_t)e * n_elite, r + rec.off_index, (size_t)n_elite * 4);
+    if (total_return) std::memcpy(total_return + (size_t)e * n_elite, r + rec.off_ret, (size_t)n_elite * 8);
+    if (mean) std::memcpy(mean + (size_t)e * np, r + rec.off_mean, (size_t)np * 8);
+    if (variance) std::memcpy(variance + (size_t)e * np, r + rec.off_var, (size_t)np * 8);
+    if (avg_return) std::memcpy(avg_return + e, r, 8);
+  }
+  return MJPCX_OK;
 }
 
 int mjpcx_best_batched(mjpcx_ctx* c, int E, int ref_candidate, int32_t* index, double* best_return, double* ref_return, double* spline_values) {

@@ -211,6 +211,7 @@ __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ g
   const double* __restrict__ blob = env_ptr(blob0, env, a0.env_stride);
   QArgs a = a0;
   env_rebase(a, env);
+  a.param_variance = env_ptr(a.param_variance, env, a0.env_stride);  // (CE: the environment's own variance row)
   a.seed += (uint64_t)env; a.candidate_offset -= env * a0.env_n;
   __shared__ QuadModel sm;
   __shared__ QStaticPose sp[kQStatic];

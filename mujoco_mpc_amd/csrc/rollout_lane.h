@@ -140,10 +140,12 @@ struct RolloutArgs {
   const LaneInit<T>* init;  // lane family: the initial condition (in the record)
 };
 
-template <typename T> __device__ __forceinline__ RolloutArgs<T> env_view(const RolloutArgs<T>& a, int env) {
+// NOISE = false: a pass that draws no noise (noise.mode < 0) and so has no use for the variance pointer
+template <bool NOISE = true, typename T> __device__ __forceinline__ RolloutArgs<T> env_view(const RolloutArgs<T>& a, int env) {
   RolloutArgs<T> r = a;
   env_rebase(r, env);
   r.init = env_ptr(a.init, env, a.env_stride);
+  if constexpr (NOISE) r.noise.param_variance = env_ptr(a.noise.param_variance, env, a.env_stride);  // (CE: the environment's own variance row)
   r.noise.seed = a.noise.seed + (uint64_t)env;
   r.noise.candidate_offset = a.noise.candidate_offset - env * a.env_n;
   return r;

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(TREE_KERNEL_THREADS) void rollout_tree_kernel(const
     // five more scalars alive over the whole rollout cost vector registers through the scalar spills)
     int env_here = env;
     asm volatile("" : "+s"(env_here));
-    const RolloutArgs<wreal> ae = env_view(a, env_here);
+    const RolloutArgs<wreal> ae = env_view<!BIG>(a, env_here);  // (the second pass draws no noise: the host sets noise.mode = -1)
     if (mode & 8) {  // bring-up aid (MJPCX_TREE_MODE=8): poison the arena -- a read of storage this rollout never wrote shows up as NaN / -1
       for (unsigned i = lane; i < arena_bytes / 4; i += 64) reinterpret_cast<unsigned*>(arena)[i] = 0xFFFFFFFFu;
       WSYNC();

@@ -655,6 +655,162 @@ class GpuCrossEntropyPlanner:
         return self.policy.num_spline_points * self.model.nu
 
 
+def _fleet_setting(name):
+    """a planner setting that all environments of a batch planner share: read from the first member, written to every member"""
+    def fget(self):
+        return getattr(self.envs[0], name)
+
+    def fset(self, value):
+        for p in self.envs:
+            setattr(p, name, value)
+    return property(fget, fset)
+
+
+class GpuBatchCrossEntropyPlanner:
+    """Cross-Entropy for `num_envs` environments (robots) on ONE context: every plan step is one `set_states`, one
+    `rollout_noise_batched_ce` over all E x (n + 1) candidates with a variance row per environment, one `ce_update_batched`
+    (selection of the elites, their mean, variance and mean return, on the device) and one sync -- instead of E plan steps of
+    four host round trips each. The environments share the model, the task and n_elite_, std_initial_, std_min_,
+    explore_fraction_; each has its own state, clock, mocap pose, policy and variance. Environment e with seed s behaves exactly
+    like a GpuCrossEntropyPlanner with seed s + e: the per-environment logic (ResamplePolicy, policy copy, ActionFromPolicy) IS
+    that planner's, one member per environment. The nominal rollout rides along as each environment's last candidate, so
+    num_trajectory_ + 1 must be a positive multiple of 64."""
+
+    def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
+        if int(num_envs) < 1:
+            raise ValueError("GpuBatchCrossEntropyPlanner needs at least one environment")
+        self.num_envs, self.device, self.precision, self.seed = int(num_envs), device, precision, seed
+        self._backend_factory = backend_factory
+        self.model = self.task = self.ctx = None
+        self.iteration = 0
+        self.rollouts_compute_time = self.policy_update_compute_time = 0.0
+        self._last = None  # what the context's last rollout was: "plan" (n + 1 candidates per environment) or "nominal"
+        # the members never roll out themselves: they are handed the shared context instead of creating their own
+        self.envs = [GpuCrossEntropyPlanner(device, precision, seed + e, backend_factory=lambda task: self.ctx) for e in range(self.num_envs)]
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        for p in self.envs:
+            p.initialize(model, task)
+
+    num_trajectory_ = _fleet_setting("num_trajectory_")
+    n_elite_ = _fleet_setting("n_elite_")
+    std_initial_ = _fleet_setting("std_initial_")
+    std_min_ = _fleet_setting("std_min_")
+    explore_fraction_ = _fleet_setting("explore_fraction_")
+
+    def _check_n(self, n):
+        if n < 64 or n % 64 != 0:
+            raise ValueError(f"GpuBatchCrossEntropyPlanner: num_trajectory_ = {n - 1}; with the nominal rollout every environment launches "
+                             "num_trajectory_ + 1 candidates, and a batched launch needs a positive multiple of 64 (every wavefront "
+                             "serves one environment) -- set sampling_trajectories / num_trajectory_ to 63, 127, ..., 2047, ...")
+
+    def allocate(self):
+        if self._backend_factory is not None:
+            self.ctx = self._backend_factory(self.task)
+        else:
+            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+        for p in self.envs:
+            p.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        for p in self.envs:
+            p.reset(horizon, initial_repeated_action)
+        self._last = None
+
+    def set_states(self, states):
+        """one State per environment (Planner::SetState for each)"""
+        if len(states) != self.num_envs:
+            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
+        for p, st in zip(self.envs, states):
+            p.set_state(st)
+
+    def _push_states(self):
+        sync_task(self.ctx, self.task)
+        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
+                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
+                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+
+    # ---- OptimizePolicy, cross_entropy/planner.cc:168-291, for every environment
+    def optimize_policy(self, horizon, pool=None):
+        num_trajectory = int(self.num_trajectory_)
+        n = num_trajectory + 1                               # the nominal rollout is local candidate num_trajectory
+        self._check_n(n)
+        self.n_elite_ = min(self.n_elite_, num_trajectory)
+        n_elite = self.n_elite_
+        for p in self.envs:
+            p.resampled_policy.plan.set_interpolation(p.interpolation_)
+            with p.mtx_:
+                p.resampled_policy.copy_from(p.policy, p.policy.num_spline_points)
+            p.resample_policy(horizon)
+        t0 = _time.perf_counter()
+        first = self.envs[0]
+        P, nu = first.resampled_policy.num_spline_points, self.model.nu
+        np_ = P * nu
+        explore_count = int(np.sum(np.arange(num_trajectory) < num_trajectory * self.explore_fraction_))
+        ns = capi.make_noise_spec(seed=self.seed, iteration=self.iteration, mode=capi.NOISE_CROSS_ENTROPY, candidate_offset=0,
+                                  nominal_candidate=num_trajectory, explore_count=explore_count, std0=self.std_initial_,
+                                  std1=self.std_min_)
+        plans = [p.resampled_policy.plan for p in self.envs]
+        self._push_states()
+        self.ctx.rollout_noise_batched_ce(n, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
+                                          np.stack([pl.values() for pl in plans]), np.stack([p.variance[:np_] for p in self.envs]),
+                                          ns, num_envs=self.num_envs)
+        idx, ret, mean, var, avg = self.ctx.ce_update_batched(self.num_envs, n_elite, num_trajectory)
+        self._last = "plan"
+        self._n = n
+        self.rollouts_compute_time = (_time.perf_counter() - t0) * 1e6
+        self.iteration += 1
+        # ---- the elites' mean becomes the policy, their variance the next step's noise (planner.cc:216-290)
+        t0 = _time.perf_counter()
+        for e, p in enumerate(self.envs):
+            p._offset, p._n_local = 0, n
+            p.trajectory_order = [int(i) for i in idx[e]]
+            p.variance[:] = 0.0
+            p.variance[:np_] = np.asarray(var[e]).reshape(-1)
+            m = np.asarray(mean[e]).reshape(P, nu)
+            p.parameters_scratch[:np_] = m.reshape(-1)
+            with p.mtx_:
+                p.previous_policy.copy_from(p.policy)
+                p.policy.plan.clear()
+                p.policy.plan.set_interpolation(p.interpolation_)
+                for t in range(P):
+                    p.policy.plan.add_node(p.times_scratch[t], m[t])
+            p.improvement = max(float(avg[e]) - float(ret[e][0]), 0.0)
+            p._nominal = None
+            p.iteration = self.iteration
+        self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
+
+    def nominal_trajectory(self, horizon, pool=None):
+        """NominalTrajectory of every environment in one launch: 64 candidates per environment, candidate 0 carrying the policy"""
+        plans = [p.resampled_policy.plan for p in self.envs]
+        if any(pl.size() != plans[0].size() for pl in plans):
+            raise ValueError("the environments' policies have different numbers of spline nodes")
+        self._push_states()
+        times = np.stack([pl.times() for pl in plans])
+        values = np.stack([np.broadcast_to(pl.values()[None], (64,) + pl.values().shape) for pl in plans])
+        self.ctx.rollout_splines_batched(horizon, plans[0].interpolation(), times, values, num_envs=self.num_envs, n_per_env=64)
+        self._last = "nominal"
+        out = [self.ctx.fetch_trajectory(64 * e) for e in range(self.num_envs)]
+        for p, tr in zip(self.envs, out):
+            p._nominal = tr
+            p._n_local = 0
+        return out
+
+    def action_from_policy(self, env, action, state, time, use_previous=False):
+        return self.envs[env].action_from_policy(action, state, time, use_previous)
+
+    # ---- BestTrajectory, planner.cc:446-448: the NOMINAL rollout, the environment's last candidate
+    def best_trajectory(self, env):
+        p = self.envs[env]
+        if p._nominal is None and self._last == "plan":
+            p._nominal = self.ctx.fetch_trajectory(env * self._n + self._n - 1)
+        return p._nominal
+
+    def num_parameters(self):
+        return self.envs[0].num_parameters()
+
+
 # ====================================================================================== iLQG
 def log_scale(max_value, min_value, steps):
     """LogScale, mjpc/utilities.cc:819-826 (ascending from min_value to max_value)."""

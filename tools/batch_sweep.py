@@ -3,7 +3,13 @@
 each ends in its own sync) and (b) one batched plan step (set_states, rollout_noise_batched, best_batched: one sync) on the same context,
 alternating in one process. Host clock around work that ends in a sync; warm-up for every shape; median and spread over the timed steps.
 
-  python tools/batch_sweep.py [--steps 12] [--warmup 2] [--out profiles/batch_sweep.jsonl] [--only QuadrupedFlat]
+  python tools/batch_sweep.py [--steps 12] [--warmup 2] [--out profiles/batch_sweep.jsonl] [--only QuadrupedFlat] [--shapes 8x2048,1x16384]
+
+--planner cross_entropy: the Cross-Entropy plan step instead. (a) per environment set_state, rollout_noise (CE), topk, elite_moments twice
+-- four round trips, three of them syncs -- against (b) set_states, rollout_noise_batched_ce with a variance row per environment and
+ce_update_batched: one sync. n counts the nominal rollout (the last candidate of every environment), n_elite = n / 10. The record also
+splits the batched step, in a loop of its own: the rollout up to its sync, and the update call alone (launch + sync) after it. Default
+output profiles/batch_sweep_ce.jsonl.
 
 Kernel thresholds are the library's defaults: the sequential side of 8 x 2048 runs eight launches of the kernel a 2048-candidate batch gets,
 the batched side one launch of the kernel a 16384-candidate batch gets -- that is the feature."""
@@ -51,7 +57,7 @@ def initial(task, name, E, rng):
     return np.stack(states), np.zeros(E), None if mocap is None else np.stack([mocap] * E)
 
 
-def sweep(name, precision, H, shapes, steps, warmup, out):
+def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling"):
     task = load_task(name)
     m = task.model
     rng = np.random.default_rng(1)
@@ -78,6 +84,34 @@ def sweep(name, precision, H, shapes, steps, warmup, out):
             ctx.rollout_noise_batched(n, H, interp, times, nominal, capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_envs=E)
             ctx.best_batched(E, 0)
 
+        ce = planner == "cross_entropy"
+        n_elite = max(n // 10, 2)
+        variance = np.stack([np.full((P, m.nu), (std * (1 + 0.1 * e)) ** 2) for e in range(E)])   # every robot its own
+
+        def ce_spec(e, row):
+            return capi.make_noise_spec(seed=7 + e, iteration=it[0], mode=capi.NOISE_CROSS_ENTROPY, nominal_candidate=n - 1,
+                                        explore_count=n // 10, std0=std, std1=0.1 * std, param_variance=row)
+
+        def ce_sequential():   # GpuCrossEntropyPlanner.optimize_policy's calls
+            it[0] += 1
+            for e in range(E):
+                ctx.set_state(states[e], clocks[e], None if mocap is None else mocap[e])
+                ctx.rollout_noise(n, H, interp, times[e], nominal[e], ce_spec(e, variance[e]))
+                idx, _ = ctx.topk(n_elite + 1)
+                idx = idx[idx != n - 1][:n_elite]
+                s, _ = ctx.elite_moments(idx)
+                ctx.elite_moments(idx, s / n_elite)
+
+        def ce_rollout():
+            ctx.set_states(states, clocks, mocap)
+            ctx.rollout_noise_batched_ce(n, H, interp, times, nominal, variance, ce_spec(0, None), num_envs=E)
+
+        def ce_batched():      # GpuBatchCrossEntropyPlanner.optimize_policy's calls
+            ce_rollout()
+            ctx.ce_update_batched(E, n_elite, n - 1)
+
+        if ce:
+            sequential, batched = ce_sequential, ce_batched
         for _ in range(warmup):
             sequential()
             batched()
@@ -92,6 +126,16 @@ def sweep(name, precision, H, shapes, steps, warmup, out):
                "batched_ms": {"median": float(np.median(tb)), "min": float(np.min(tb)), "max": float(np.max(tb))},
                "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)),
                "beyond_spread": bool(np.max(tb) < np.min(ts))}
+        if ce:
+            tr, tu = [], []
+            for _ in range(steps):
+                t0 = time.perf_counter(); ce_rollout(); ctx.sync(); t1 = time.perf_counter()
+                ctx.ce_update_batched(E, n_elite, n - 1); t2 = time.perf_counter()
+                tr.append((t1 - t0) * 1e3)
+                tu.append((t2 - t1) * 1e3)
+            rec.update(planner="cross_entropy", n_elite=n_elite,
+                       batched_rollout_ms={"median": float(np.median(tr)), "min": float(np.min(tr)), "max": float(np.max(tr))},
+                       batched_update_ms={"median": float(np.median(tu)), "min": float(np.min(tu)), "max": float(np.max(tu))})
         print(json.dumps(rec), flush=True)
         out.write(json.dumps(rec) + "\n")
         out.flush()
@@ -102,15 +146,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=12)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_sweep.jsonl"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--planner", choices=["sampling", "cross_entropy"], default="sampling")
+    ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "batch_sweep_ce.jsonl" if a.planner == "cross_entropy" else "batch_sweep.jsonl")
+    keep = None if a.shapes is None else {tuple(int(x) for x in sh.split("x")) for sh in a.shapes.split(",")}
     if a.steps < 10:
         raise SystemExit("batch_sweep.py: at least 10 timed steps")
     with open(a.out, "w") as out:
         for name, precision, H, shapes in SHAPES:
-            if a.only is None or a.only == name:
-                sweep(name, precision, H, shapes, a.steps, a.warmup, out)
+            shapes = [sh for sh in shapes if keep is None or sh in keep]
+            if shapes and (a.only is None or a.only == name):
+                sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner)
 
 
 if __name__ == "__main__":
