@@ -471,6 +471,31 @@ int mjpcx_gradient_pass(mjpcx_ctx* ctx, int n, int m, int T, const double* A, co
                         const double* cu, int representation, int P, const double* node_times, const double* step_times,
                         double* Vx, double* k, double* dV, double* gradient, double* kernel_ms);
 
+/* The Gradient planner's derivative chain for E environments, chained on the device after a batched rollout (mjpcx_rollout_splines_batched
+ * or mjpcx_rollout_noise_batched) of num_envs environments with horizon >= T: for every environment e, local candidate `candidate` of that
+ * rollout is the nominal trajectory; its times, states, actions and residual are read from the device Trajectory buffers in whichever
+ * layout the rollout kernel left them -- nothing of it passes through the host. Enqueued on the context's stream:
+ *   ModelDerivatives::Compute (mjpcx_transition_fd: eps, centered) at the num_eval steps of `evaluate` (strictly increasing, within
+ *     [0, T); the list of model_derivatives.cc:45-106 for derivative_skip), every environment's items with that environment's record
+ *     from mjpcx_set_states / mjpcx_set_residual_states (clock, mocap pose, frozen residual state), restaged by this call;
+ *   their linear interpolation to all T steps (model_derivatives.cc:108-165; a step outside the list's range takes the nearest
+ *     evaluated one), two products and a sum, not contracted; A, B and D of step T - 1 set to zero (gradient/planner.cc:211-216);
+ *   CostDerivatives::Compute (mjpcx_cost_derivatives; cx and cu only) on the rollout's residual;
+ *   Gradient::Compute with the projection M^T k (mjpcx_gradient_pass), per environment with its node times (E x P) and step times.
+ * ONE sync at the end. Outputs: nominal_return (E, may be NULL), k (E x T x m), gradient (E x P x m), dV (E x 2); A (E x T x n x n),
+ * B (E x T x n x m), cx (E x T x n), cu (E x T x m) are optional (NULL: they never visit the host), n = 2 nv, m = nu.
+ * With every step evaluated the results equal, bit for bit, those of mjpcx_transition_fd -> mjpcx_cost_derivatives ->
+ * mjpcx_gradient_pass fed with mjpcx_fetch_trajectory of the same candidates. Deterministic. Both precisions of the lane family
+ * (fp32: the finite differences in fp32, the rest in fp64, as the plain calls); fp32 contexts of the wavefront-per-candidate family
+ * are refused like mjpcx_transition_fd refuses them.
+ * MJPCX_EINVAL: the last rollout was not a batched one of num_envs environments, candidate outside [0, n_per_env), T < 2 or beyond the
+ * rollout's horizon, a bad evaluate list, eps <= 0, an unknown representation, P < 1, node times of any environment not strictly
+ * increasing. MJPCX_EUNSUPPORTED: beyond n <= 48, m <= 16, P <= 25, T <= 512, 32 cost terms of 32 residuals; a context sharded with
+ * mjpcx_comm_init (world > 1); fp32 contexts of the wavefront-per-candidate family. */
+int mjpcx_gradient_step_batched(mjpcx_ctx* ctx, int num_envs, int candidate, int T, int num_eval, const int32_t* evaluate, double eps,
+                                int centered, int representation, int P, const double* node_times, double* nominal_return, double* k,
+                                double* gradient, double* dV, double* A, double* B, double* cx, double* cu);
+
 /* ---- measurement --------------------------------------------------------------
  * HIP-event timing of the rollout kernel on the context's own stream.
  * mjpcx_timing_reset zeroes the accumulators; mjpcx_timing_read synchronises and

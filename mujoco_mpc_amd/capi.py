@@ -29,7 +29,7 @@ EXPORTS = [
     "mjpcx_device_buffer", "mjpcx_comm_unique_id", "mjpcx_comm_init", "mjpcx_comm_info", "mjpcx_exchange_best", "mjpcx_merge_topk",
     "mjpcx_elite_allreduce", "mjpcx_comm_barrier", "mjpcx_comm_destroy",
     "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
-    "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched",
+    "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched", "mjpcx_gradient_step_batched",
 ]
 
 _LIB = None
@@ -76,6 +76,7 @@ def lib():
         L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_rollout_noise_batched_ce.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_ce_update_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p]
+        L.mjpcx_gradient_step_batched.argtypes = ([vp] + [C.c_int] * 4 + [c_i32p, C.c_double] + [C.c_int] * 3 + [c_f64p] * 9)
         L.mjpcx_sync.argtypes = [vp]
         L.mjpcx_get_returns.argtypes = [vp, c_f64p, c_i32p]
         L.mjpcx_get_return_at.argtypes = [vp, C.c_int, C.POINTER(C.c_double), c_i32p]
@@ -292,6 +293,26 @@ class Context:
         self._chk(lib().mjpcx_ce_update_batched(self.handle, E, k, int(skip_candidate), as_i32p(idx), as_f64p(ret), as_f64p(mean),
                                                 as_f64p(var), as_f64p(avg)))
         return idx, ret, mean, var, avg
+
+    def gradient_step_batched(self, num_envs, candidate, T, evaluate, eps, centered, representation, node_times, with_matrices=False):
+        """the Gradient planner's derivative chain for every environment of the last batched rollout, on the device, one sync
+        (mjpcx_gradient_step_batched): dict of nominal_return (E), k (E x T x nu), gradient (E x P x nu), dV (E x 2) and, with
+        with_matrices (tests), A, B, cx, cu."""
+        E, T = int(num_envs), int(T)
+        ev = np.ascontiguousarray(evaluate, dtype=np.int32).reshape(-1)
+        nt = _f(node_times)
+        P = nt.size // max(E, 1)
+        n, m, Ea = 2 * self.nv, self.nu, max(E, 1)
+        out = dict(nominal_return=np.zeros(Ea), k=np.zeros((Ea, max(T, 1), m)), gradient=np.zeros((Ea, max(P, 1), m)), dV=np.zeros((Ea, 2)))
+        if with_matrices:
+            out.update(A=np.zeros((Ea, max(T, 1), n, n)), B=np.zeros((Ea, max(T, 1), n, m)), cx=np.zeros((Ea, max(T, 1), n)),
+                       cu=np.zeros((Ea, max(T, 1), m)))
+        opt = [as_f64p(out[key]) if with_matrices else None for key in ("A", "B", "cx", "cu")]
+        self._chk(lib().mjpcx_gradient_step_batched(self.handle, E, int(candidate), T, ev.size, as_i32p(ev) if ev.size else as_i32p(np.zeros(1, np.int32)),
+                                                    float(eps), int(centered), int(representation), P, as_f64p(nt),
+                                                    as_f64p(out["nominal_return"]), as_f64p(out["k"]), as_f64p(out["gradient"]),
+                                                    as_f64p(out["dV"]), *opt))
+        return out
 
     def best_batched(self, num_envs, ref_candidate=0, with_spline=True):
         """per environment: local argmin, its return, the return of local ref_candidate, the winner's spline (E x P x nu)."""

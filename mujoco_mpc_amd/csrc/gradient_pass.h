@@ -59,8 +59,7 @@ __device__ __forceinline__ void lds_sync() {  // LDS ordering inside one wavefro
 }
 }  // namespace grad_detail
 
-__global__ __launch_bounds__(64) void gradient_pass_kernel(const GradientArgs a) {
-  extern __shared__ double lds[];
+__device__ __forceinline__ void gradient_pass_body(const GradientArgs& a, double* lds) {
   const int lane = threadIdx.x, n = a.n, m = a.m, T = a.T, P = a.P;
   double* vx = lds;                                    // Vx[t], broadcast to every lane
   double* ks = vx + kGradMaxN;                         // k, T x m
@@ -166,6 +165,24 @@ __global__ __launch_bounds__(64) void gradient_pass_kernel(const GradientArgs a)
     }
     a.gradient[o] = g;
   }
+}
+
+__global__ __launch_bounds__(64) void gradient_pass_kernel(const GradientArgs a) {
+  extern __shared__ double lds[];
+  gradient_pass_body(a, lds);
+}
+
+// E trajectories in one launch (mjpcx_gradient_step_batched): workgroup e, one wavefront, runs the pass above on environment e's block of
+// every array -- A, B, cx, cu, step_times, Vx and k are E x T x ..., node_times E x P, dV E x 2, gradient E x P x m. The environments
+// are independent, so the grid hides the latency of the T dependent steps that one trajectory alone exposes.
+__global__ __launch_bounds__(64) void gradient_pass_batched_kernel(const GradientArgs a0) {
+  extern __shared__ double lds[];
+  const size_t e = blockIdx.x, n = a0.n, m = a0.m, T = a0.T, P = a0.P;
+  GradientArgs a = a0;
+  a.A += e * T * n * n; a.B += e * T * n * m; a.cx += e * T * n; a.cu += e * T * m;
+  a.node_times += e * P; a.step_times += e * T;
+  a.Vx += e * T * n; a.k += e * T * m; a.dV += e * 2; a.gradient += e * P * m;
+  gradient_pass_body(a, lds);
 }
 
 }  // namespace mjpcx

@@ -15,7 +15,8 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------- norm value + gradient + Hessian
 // mjpc::Norm with g and H (mjpc/norm.cc:50-210); n <= 32; H row-major n x n (zeroed here)
-__device__ inline double norm_grad_hess(double* g, double* H, const double* x, double p, double q, int n, int type) {
+// (forced inline: with cost_gradient_kernel as a second caller the compiler would otherwise call it out of line from both)
+__device__ __forceinline__ double norm_grad_hess(double* g, double* H, const double* x, double p, double q, int n, int type) {
   double y = 0;
   for (int i = 0; i < n * n; i++) H[i] = 0;
   switch (type) {
@@ -177,6 +178,46 @@ __global__ __launch_bounds__(64) void cost_derivatives_kernel(const CostSpec cs,
     for (int e = lane; e < ndx * ndx; e += 64) cxx_t[e] = cxx_t[e] * s + cs.risk * s * cx_t[e / ndx] * cx_t[e % ndx];
     for (int e = lane; e < ndx * nu; e += 64) cxu_t[e] = cxu_t[e] * s + cs.risk * s * cx_t[e / nu] * cu_t[e % nu];
     for (int e = lane; e < nu * nu; e += 64) cuu_t[e] = cuu_t[e] * s + cs.risk * s * cu_t[e / nu] * cu_t[e % nu];
+  }
+}
+
+// The first-order half of cost_derivatives_kernel for E trajectories in one launch (mjpcx_gradient_step_batched): workgroup e * T + t
+// forms cx and cu of step t of environment e over environment-major arrays, by the operations of the kernel above in its order, so
+// the results equal its cx / cu bit for bit; cxx, cxu, cuu and the H rx / H ru products they need are not formed. T is the horizon
+// the weights are divided by.
+__global__ __launch_bounds__(64) void cost_gradient_kernel(const CostSpec cs, const double* __restrict__ r, const double* __restrict__ C,
+                                                            const double* __restrict__ D, int T, int ndx, int nu, double* cx, double* cu) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* g = reinterpret_cast<double*>(smem_raw);  // [32]
+  double* Hn = g + 32;                              // [32*32]
+  __shared__ double cval;
+  const int lane = threadIdx.x;
+  const size_t t = blockIdx.x;
+  const int nr = cs.num_residual;
+  double* cx_t = cx + t * ndx; double* cu_t = cu + t * nu;
+  for (int i = lane; i < ndx; i += 64) cx_t[i] = 0;
+  for (int i = lane; i < nu; i += 64) cu_t[i] = 0;
+  if (lane == 0) cval = 0;
+  __syncthreads();
+  int shift = 0;
+  for (int k = 0; k < cs.num_term; k++) {
+    const int nk = cs.dim[k];
+    const double w = cs.weight[k] / T;  // weights[i] / T, cost_derivatives.cc:151
+    const double* rk = r + t * nr + shift;
+    const double* rx = C + (t * nr + shift) * ndx;  // nk x ndx
+    const double* ru = D + (t * nr + shift) * nu;   // nk x nu
+    if (lane == 0) cval += w * norm_grad_hess(g, Hn, rk, cs.p[k], cs.q[k], nk, cs.norm[k]);
+    __syncthreads();
+    for (int i = lane; i < ndx; i += 64) { double s = 0; for (int a = 0; a < nk; a++) s += rx[a * ndx + i] * g[a]; cx_t[i] += w * s; }
+    for (int i = lane; i < nu; i += 64) { double s = 0; for (int a = 0; a < nk; a++) s += ru[a * nu + i] * g[a]; cu_t[i] += w * s; }
+    __syncthreads();
+    shift += nk;
+  }
+  if (fabs(cs.risk) >= 1.0e-6) {  // exponential risk transformation of the gradient, cost_derivatives.cc:156-226
+    const double s = exp(cs.risk * cval);
+    __syncthreads();
+    for (int i = lane; i < ndx; i += 64) cx_t[i] *= s;
+    for (int i = lane; i < nu; i += 64) cu_t[i] *= s;
   }
 }
 

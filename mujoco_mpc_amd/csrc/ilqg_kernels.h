@@ -200,20 +200,36 @@ struct FdArgs {
   T eps;
   T* next;      // [Tn][NC][NDX]  next state of each perturbed step
   T* sensor;    // [Tn][NC][NR]   residual (the leading user sensors) of each perturbed step
+  // several environments in one launch (mjpcx_gradient_step_batched): the arrays above hold num_envs x Tn steps, environment-major, and
+  // environment e's items are [e * env_items, e * env_items + Tn * NC). env_items is a multiple of 64, so a wavefront serves one
+  // environment, whose initial-condition record (the mocap pose the residual reads) is init moved by e * env_stride bytes
+  // (env_select.h). num_envs = 0: one environment, the LaneTask of the kernel arguments.
+  int num_envs, env_items;
+  unsigned env_stride;
+  const LaneInit<T>* init;
 };
 
 // columns: 0 nominal | 1..NDX: +eps on x_j | NDX+1..2NDX: -eps | then +eps on u_k | then -eps on u_k
 template <class TP> constexpr int fd_columns() { return 1 + 2 * (2 * TP::NV + TP::NU); }
 
-template <class TP, class TK, typename T, class MC>
-__global__ __launch_bounds__(64) void transition_fd_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk,
+// ENVS: the instantiation mjpcx_gradient_step_batched launches (FdArgs::num_envs > 0); the plain one is the kernel of mjpcx_transition_fd
+template <class TP, class TK, typename T, class MC, bool ENVS = false>
+__global__ __launch_bounds__(64) void transition_fd_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk_karg,
                                                             const FdArgs<T> f) {
   decltype(auto) m = MC::template get<T>(m_karg);
   constexpr int NV = TP::NV, NU = TP::NU, NS = TP::NSITE, NR = TK::NR, DS = 2 * NV, NDX = 2 * NV;
   constexpr int NC = fd_columns<TP>();
-  const int item = blockIdx.x * 64 + threadIdx.x;
+  int item = blockIdx.x * 64 + threadIdx.x;
+  int t0 = 0;
+  LaneTask<T> tk = tk_karg;
+  if constexpr (ENVS) {  // the wavefront's environment (wave-uniform): its record, its block of steps
+    const int env = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 64)) / f.env_items;
+    lane_task_init(tk, env_ptr(f.init, env, f.env_stride));
+    item -= env * f.env_items;
+    t0 = env * f.Tn;
+  }
   if (item >= f.Tn * NC) return;
-  const int t = item / NC, c = item % NC;
+  const int t = t0 + item / NC, c = item % NC;
   T qpos[NV], qvel[NV], ctrl[NU];
 #pragma unroll
   for (int i = 0; i < NV; i++) { qpos[i] = f.states[t * DS + i]; qvel[i] = f.states[t * DS + NV + i]; }

@@ -62,6 +62,10 @@ hipError_t launch_feedback_impl(const LaneModel<T>& m, const LaneTask<T>& tk, co
 }
 template <class TP, class TK, typename T, class MC>
 hipError_t launch_fd_impl(const LaneModel<T>& m, const LaneTask<T>& tk, const FdArgs<T>& f, hipStream_t s) {
+  if (f.num_envs > 0) {  // several environments (mjpcx_gradient_step_batched): every environment's items padded to whole wavefronts
+    hipLaunchKernelGGL((transition_fd_kernel<TP, TK, T, MC, true>), dim3((unsigned)f.num_envs * (f.env_items / 64)), dim3(64), 0, s, m, tk, f);
+    return hipGetLastError();
+  }
   const int items = f.Tn * fd_columns<TP>();
   hipLaunchKernelGGL((transition_fd_kernel<TP, TK, T, MC>), dim3((items + 63) / 64), dim3(64), 0, s, m, tk, f);
   return hipGetLastError();

@@ -19,6 +19,7 @@
 #include "lane_registry.h"
 #include "ilqg_dense.h"
 #include "gradient_pass.h"
+#include "gradient_batched.h"
 #include "rollout_wave.h"
 #include "quad_launch.h"
 #include "limb_launch.h"
@@ -496,6 +497,8 @@ struct mjpcx_ctx {
   void* best_host = nullptr; void* best_dev = nullptr; size_t best_cap = 0;
   // rollout buffers
   DevBuf d_nodes, d_in_nodes, d_ilqg, d_ilqg_out, d_wblob;
+  DevBuf d_grad;                                  // workspace of mjpcx_gradient_step_batched: inputs, every intermediate, the result block
+  void* grad_host = nullptr; size_t grad_cap = 0; // its pinned [inputs | result block]
   DevBuf d_states, d_actions, d_times, d_residual, d_costs, d_trace, d_ret, d_fail, d_sort, d_stage;
   bool traj_candidate_major = false;
   int nsite_model = 0;
@@ -1492,9 +1495,10 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   }
   if (c->best_host) (void)hipHostFree(c->best_host);
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
+  if (c->grad_host) (void)hipHostFree(c->grad_host);
   (void)mjpcx_comm_destroy(c);
   c->wh.release();
-  DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_ilqg, &c->d_ilqg_out, &c->d_wblob, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
+  DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_wblob, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
                     &c->d_states, &c->d_actions, &c->d_times, &c->d_residual, &c->d_costs, &c->d_trace, &c->d_ret,
                     &c->d_fail, &c->d_sort, &c->d_stage};
   for (DevBuf* b : bufs) b->release();
@@ -2210,6 +2214,22 @@ int do_transition_fd_wave(mjpcx_ctx* c, int Tn, const double* times, const doubl
 }
 }  // namespace
 
+namespace {
+// the context's current cost specification as the cost-derivative kernel takes it
+int make_cost_spec(mjpcx_ctx* c, CostSpec* out) {
+  if (c->nterm > 32) return fail(c, MJPCX_EUNSUPPORTED, "more than 32 cost terms");
+  CostSpec& cs = *out;
+  cs.num_term = c->nterm; cs.num_residual = c->nr; cs.risk = c->wave ? c->wh.risk : c->ht64.risk;
+  for (int k = 0; k < c->nterm; k++) {
+    if (c->dim_norm_residual[k] > 32) return fail(c, MJPCX_EUNSUPPORTED, "cost term wider than 32 residuals");
+    cs.dim[k] = c->dim_norm_residual[k];
+    if (c->wave) { cs.norm[k] = c->wh.norm_types[k]; cs.weight[k] = c->wh.weight[k]; cs.p[k] = c->wh.norm_p[k]; cs.q[k] = c->wh.norm_q[k]; }
+    else { cs.norm[k] = c->ht64.norm[k]; cs.weight[k] = c->ht64.weight[k]; cs.p[k] = c->ht64.norm_p[k]; cs.q[k] = c->ht64.norm_q[k]; }
+  }
+  return MJPCX_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int mjpcx_rollout_feedback(mjpcx_ctx* c, int N, int H, int mode, int representation, int use_state, int Tn,
@@ -2266,19 +2286,12 @@ int mjpcx_cost_derivatives(mjpcx_ctx* c, int T, const double* residual, const do
                            double* cu, double* cxx, double* cxu, double* cuu) {
   if (!c || !residual || !C || !D || !cx || !cu || !cxx || !cxu || !cuu) return fail(c, MJPCX_EINVAL, "null argument");
   if (T < 1) return fail(c, MJPCX_EINVAL, "T must be >= 1");
-  if (c->nterm > 32) return fail(c, MJPCX_EUNSUPPORTED, "more than 32 cost terms");
   HIPCHK(c, hipSetDevice(c->device));
   const size_t ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr;
   CostSpec cs{};
-  cs.num_term = c->nterm; cs.num_residual = c->nr; cs.risk = c->wave ? c->wh.risk : c->ht64.risk;
-  for (int k = 0; k < c->nterm; k++) {
-    if (c->dim_norm_residual[k] > 32) return fail(c, MJPCX_EUNSUPPORTED, "cost term wider than 32 residuals");
-    cs.dim[k] = c->dim_norm_residual[k];
-    if (c->wave) { cs.norm[k] = c->wh.norm_types[k]; cs.weight[k] = c->wh.weight[k]; cs.p[k] = c->wh.norm_p[k]; cs.q[k] = c->wh.norm_q[k]; }
-    else { cs.norm[k] = c->ht64.norm[k]; cs.weight[k] = c->ht64.weight[k]; cs.p[k] = c->ht64.norm_p[k]; cs.q[k] = c->ht64.norm_q[k]; }
-  }
-  std::vector<double*> d;
   int rc;
+  if ((rc = make_cost_spec(c, &cs)) != MJPCX_OK) return rc;
+  std::vector<double*> d;
   if ((rc = upload_arrays<double>(c, c->d_ilqg, {{residual, T * nr}, {C, T * nr * ndx}, {D, T * nr * nu}}, &d)) != MJPCX_OK) return rc;
   const size_t n_out = T * (ndx + nu + ndx * ndx + ndx * nu + nu * nu);
   HIPCHK(c, c->d_ilqg_out.reserve(n_out * 8));
@@ -2405,6 +2418,165 @@ int mjpcx_gradient_pass(mjpcx_ctx* c, int n, int m, int T, const double* A, cons
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return MJPCX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// mjpcx_gradient_step_batched after validation: stage, launch the chain, one sync, unpack
+template <typename T>
+int do_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int Tn, int ne, const int32_t* evaluate, double eps, int centered, int representation,
+                             int P, const double* node_times, double* nominal_return, double* k, double* gradient, double* dV, double* A,
+                             double* B, double* cx, double* cu) {
+  int rc;
+  CostSpec cs{};
+  if ((rc = make_cost_spec(c, &cs)) != MJPCX_OK) return rc;
+  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, nc = 1 + 2 * (ndx + nu);
+  const size_t sE = E, sT = Tn, sne = ne, sP = P, rows = sE * sne;
+  if (sE * std::max(sne * nc, sT) * (ndx + nr) * (ndx + nu) > 0x7fffffffULL) return fail(c, MJPCX_EUNSUPPORTED, "mjpcx_gradient_step_batched: too many environments x steps");
+  // the environments' plan records, restaged: the preceding rollout's slot may have been recycled since
+  const T *d_rec_times, *d_rec_nominal;
+  const double* d_rec_var;
+  const void* d_blob = nullptr;
+  mjpcx_ctx::Slot* slot = nullptr;
+  unsigned stride = 0;
+  if ((rc = stage_plan_inputs<T>(c, P, E, node_times, nullptr, nullptr, false, &d_rec_times, &d_rec_nominal, &d_rec_var, &slot, &d_blob, &stride)) != MJPCX_OK)
+    return rc;
+  // ---- workspace carve: [evaluate | ctrllimited | ctrlrange | node_times] (one upload), the stages' arrays, [nominal_return | k | gradient | dV] (one download)
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+  const size_t o_eval = carve(sne * 4), o_lim = carve(nu * 4), o_range = carve(2 * nu * sizeof(T)), o_nodes = carve(sE * sP * 8), in_bytes = off;
+  const size_t o_ft = carve(rows * sizeof(T)), o_fs = carve(rows * ds * sizeof(T)), o_fa = carve(rows * nu * sizeof(T));
+  const size_t o_st = carve(sE * sT * 8), o_res = carve(sE * sT * nr * 8);
+  const size_t o_next = carve(rows * nc * (c->wave ? ds : ndx) * sizeof(T)), o_tan = carve(c->wave ? rows * nc * ndx * 8 : 0), o_sens = carve(rows * nc * nr * sizeof(T));
+  const size_t sA = ndx * ndx, sB = ndx * nu, sC = nr * ndx, sD = nr * nu;
+  const size_t o_Ae = carve(rows * sA * 8), o_Be = carve(rows * sB * 8), o_Ce = carve(rows * sC * 8), o_De = carve(rows * sD * 8);
+  const size_t o_A = carve(sE * sT * sA * 8), o_B = carve(sE * sT * sB * 8), o_C = carve(sE * sT * sC * 8), o_D = carve(sE * sT * sD * 8);
+  const size_t o_cx = carve(sE * sT * ndx * 8), o_cu = carve(sE * sT * nu * 8), o_Vx = carve(sE * sT * ndx * 8);
+  const size_t o_out = off, o_ret = carve(sE * 8), o_k = carve(sE * sT * nu * 8), o_g = carve(sE * sP * nu * 8), o_dV = carve(sE * 2 * 8), out_bytes = off - o_out;
+  HIPCHK(c, c->d_grad.reserve(off));
+  if (in_bytes + out_bytes > c->grad_cap) {
+    if (c->grad_host) (void)hipHostFree(c->grad_host);
+    c->grad_host = nullptr; c->grad_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->grad_host, in_bytes + out_bytes, hipHostMallocDefault));
+    c->grad_cap = in_bytes + out_bytes;
+  }
+  char* base = (char*)c->d_grad.p;
+  char* hin = (char*)c->grad_host;
+  char* hout = hin + in_bytes;
+  std::memcpy(hin + o_eval, evaluate, sne * 4);
+  std::memcpy(hin + o_lim, c->ctrllimited.data(), nu * 4);
+  for (size_t i = 0; i < 2 * nu; i++) ((T*)(hin + o_range))[i] = (T)c->ctrlrange[i];
+  std::memcpy(hin + o_nodes, node_times, sE * sP * 8);
+  HIPCHK(c, hipMemcpyAsync(base, hin, in_bytes, hipMemcpyHostToDevice, c->stream));
+  const int* d_eval = (const int*)(base + o_eval);
+  // ---- gather the nominal candidates
+  GatherNominalArgs<T> g{};
+  g.states = (const T*)c->d_states.p; g.actions = (const T*)c->d_actions.p; g.times = (const T*)c->d_times.p; g.residual = (const T*)c->d_residual.p;
+  g.total_return = (const double*)c->d_ret.p;
+  g.N = c->N; g.H = c->H; g.n_per_env = c->env_n; g.cand = cand; g.candidate_major = c->traj_candidate_major ? 1 : 0;
+  g.E = E; g.Tn = Tn; g.ne = ne; g.evaluate = d_eval;
+  g.ds_roll = c->nq + c->nv + c->na; g.ds = (int)ds; g.nu = (int)nu; g.nr = (int)nr;
+  g.fd_times = (T*)(base + o_ft); g.fd_states = (T*)(base + o_fs); g.fd_actions = (T*)(base + o_fa);
+  g.step_times = (double*)(base + o_st); g.residual_out = (double*)(base + o_res); g.nominal_return = (double*)(base + o_ret);
+  const size_t g_items = sE * (sne * (1 + ds + nu) + sT * (1 + nr) + 1);
+  hipLaunchKernelGGL((gather_nominal_kernel<T>), dim3((unsigned)std::min<size_t>((g_items + 255) / 256, 2048)), dim3(256), 0, c->stream, g);
+  HIPCHK(c, hipGetLastError());
+  // ---- ModelDerivatives::Compute at the evaluated steps of every environment
+  const T* fd_next = (const T*)(base + o_next);
+  if (c->wave) {
+    if constexpr (sizeof(T) == 8) {
+      WaveTask wt = c->wh.t;
+      wt.blob = (const double*)d_blob;
+      wt.stamps = nullptr;
+      wt.stamp_step = 0;
+      w64::FdWaveArgs f{g.fd_times, g.fd_states, g.fd_actions, (int)rows, (int)nc, eps, (double*)(base + o_next), (double*)(base + o_sens), ne, stride};
+      const bool tree = c->wh.tree_ok && !c->no_tree;
+      HIPCHK(c, launch_transition_fd_wave(c->wh.m, wt, f, (unsigned)(rows * nc), wave_lds_bytes(c, 1, tree), tree, c->wh.m.integrator == MJPCX_INT_RK4, c->stream));
+      HIPCHK(c, launch_fd_tangent(c->wh.m, (const double*)(base + o_next), (double*)(base + o_tan), (int)rows, (int)nc, c->stream));
+      fd_next = (const T*)(base + o_tan);
+    }
+  } else {
+    FdArgs<T> f{g.fd_times, g.fd_states, g.fd_actions, ne, (T)eps, (T*)(base + o_next), (T*)(base + o_sens)};
+    f.num_envs = E; f.env_items = (int)((sne * nc + 63) / 64 * 64); f.env_stride = stride; f.init = (const LaneInit<T>*)d_blob;
+    hipError_t le;
+    if constexpr (sizeof(T) == 8) le = c->kernel->fd64(c->hm64, c->ht64, f, c->stream);
+    else { convert_task(c->ht32, c->ht64); le = c->kernel->fd32(c->hm32, c->ht32, f, c->stream); }
+    if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("fd kernel launch: ") + hipGetErrorString(le));
+  }
+  double *dAe = (double*)(base + o_Ae), *dBe = (double*)(base + o_Be), *dCe = (double*)(base + o_Ce), *dDe = (double*)(base + o_De);
+  double *dA = (double*)(base + o_A), *dB = (double*)(base + o_B), *dC = (double*)(base + o_C), *dD = (double*)(base + o_D);
+  const size_t a_items = rows * (ndx + nr) * (ndx + nu);
+  hipLaunchKernelGGL((fd_assemble_kernel<T>), dim3((unsigned)std::min<size_t>((a_items + 255) / 256, 1024)), dim3(256), 0, c->stream, fd_next,
+                     (const T*)(base + o_sens), (const T*)g.fd_actions, (const T*)(base + o_range), (const int*)(base + o_lim), (int)rows, (int)ndx,
+                     (int)nu, (int)nr, (T)eps, centered, dAe, dBe, dCe, dDe);
+  HIPCHK(c, hipGetLastError());
+  const size_t i_items = sE * sT * (sA + sB + sC + sD);
+  hipLaunchKernelGGL(fd_interpolate_kernel, dim3((unsigned)std::min<size_t>((i_items + 255) / 256, 4096)), dim3(256), 0, c->stream, dAe, dBe, dCe, dDe,
+                     d_eval, E, ne, Tn, (int)sA, (int)sB, (int)sC, (int)sD, dA, dB, dC, dD);
+  HIPCHK(c, hipGetLastError());
+  // ---- CostDerivatives::Compute (first order) and Gradient::Compute with the projection, per environment
+  double *dcx = (double*)(base + o_cx), *dcu = (double*)(base + o_cu);
+  hipLaunchKernelGGL(cost_gradient_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32) * 8, c->stream, cs, (const double*)g.residual_out,
+                     (const double*)dC, (const double*)dD, Tn, (int)ndx, (int)nu, dcx, dcu);
+  HIPCHK(c, hipGetLastError());
+  GradientArgs ga{};
+  ga.n = (int)ndx; ga.m = (int)nu; ga.T = Tn; ga.P = P; ga.representation = representation;
+  ga.A = dA; ga.B = dB; ga.cx = dcx; ga.cu = dcu; ga.node_times = (const double*)(base + o_nodes); ga.step_times = g.step_times;
+  ga.Vx = (double*)(base + o_Vx); ga.k = (double*)(base + o_k); ga.dV = (double*)(base + o_dV); ga.gradient = (double*)(base + o_g);
+  const size_t lds = gradient_pass_lds_bytes(Tn, (int)nu, P);
+  HIPCHK(c, hipFuncSetAttribute((const void*)gradient_pass_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(gradient_pass_batched_kernel, dim3(E), dim3(64), lds, c->stream, ga);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(slot->done, c->stream));
+  slot->pending = true;
+  // ---- results: one block into pinned memory; the optional matrices straight to the caller; ONE sync
+  HIPCHK(c, hipMemcpyAsync(hout, base + o_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (A) HIPCHK(c, hipMemcpyAsync(A, dA, sE * sT * sA * 8, hipMemcpyDeviceToHost, c->stream));
+  if (B) HIPCHK(c, hipMemcpyAsync(B, dB, sE * sT * sB * 8, hipMemcpyDeviceToHost, c->stream));
+  if (cx) HIPCHK(c, hipMemcpyAsync(cx, dcx, sE * sT * ndx * 8, hipMemcpyDeviceToHost, c->stream));
+  if (cu) HIPCHK(c, hipMemcpyAsync(cu, dcu, sE * sT * nu * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (nominal_return) std::memcpy(nominal_return, hout + (o_ret - o_out), sE * 8);
+  std::memcpy(k, hout + (o_k - o_out), sE * sT * nu * 8);
+  std::memcpy(gradient, hout + (o_g - o_out), sE * sP * nu * 8);
+  std::memcpy(dV, hout + (o_dV - o_out), sE * 2 * 8);
+  return MJPCX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mjpcx_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int T, int ne, const int32_t* evaluate, double eps, int centered, int representation,
+                                int P, const double* node_times, double* nominal_return, double* k, double* gradient, double* dV, double* A,
+                                double* B, double* cx, double* cu) {
+  const char* who = "mjpcx_gradient_step_batched: ";
+  if (!c || !evaluate || !node_times || !k || !gradient || !dV) return fail(c, MJPCX_EINVAL, std::string(who) + "null argument");
+  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N || c->env_E != E)
+    return fail(c, MJPCX_EINVAL, std::string(who) + "the last rollout was not a batched one of " + std::to_string(E) + " environments");
+  if (cand < 0 || cand >= c->env_n) return fail(c, MJPCX_EINVAL, std::string(who) + "candidate outside [0, n_per_env)");
+  if (T < 2 || T > c->H) return fail(c, MJPCX_EINVAL, std::string(who) + "T must be >= 2 and within the rollout's horizon");
+  if (ne < 1 || ne > T) return fail(c, MJPCX_EINVAL, std::string(who) + "num_eval outside [1, T]");
+  for (int i = 0; i < ne; i++)
+    if (evaluate[i] < 0 || evaluate[i] >= T || (i > 0 && evaluate[i] <= evaluate[i - 1]))
+      return fail(c, MJPCX_EINVAL, std::string(who) + "the evaluate list must be strictly increasing and within [0, T)");
+  if (!(eps > 0)) return fail(c, MJPCX_EINVAL, std::string(who) + "epsilon must be > 0");
+  if (representation < 0 || representation > 2) return fail(c, MJPCX_EINVAL, std::string(who) + "representation must be 0 (zero-order), 1 (linear) or 2 (cubic)");
+  if (P < 1) return fail(c, MJPCX_EINVAL, std::string(who) + "P must be >= 1");
+  for (int e = 0; e < E; e++)
+    for (int i = 1; i < P; i++)
+      if (!(node_times[(size_t)e * P + i] > node_times[(size_t)e * P + i - 1]))
+        return fail(c, MJPCX_EINVAL, std::string(who) + "node times must be strictly increasing (environment " + std::to_string(e) + ")");
+  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "not implemented on a context sharded with mjpcx_comm_init");
+  if (c->wave && c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+  if (2 * c->nv > kGradMaxN || c->nu > kGradMaxM || P > kGradMaxP || T > kGradMaxT)
+    return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "covers n <= 48, m <= 16, P <= 25 (kMaxGradientSplinePoints), T <= 512 (kMaxTrajectoryHorizon)");
+  HIPCHK(c, hipSetDevice(c->device));
+  return c->precision == 64 ? do_gradient_step_batched<double>(c, E, cand, T, ne, evaluate, eps, centered, representation, P, node_times, nominal_return, k,
+                                                               gradient, dV, A, B, cx, cu)
+                            : do_gradient_step_batched<float>(c, E, cand, T, ne, evaluate, eps, centered, representation, P, node_times, nominal_return, k,
+                                                              gradient, dV, A, B, cx, cu);
 }
 
 }  // extern "C"

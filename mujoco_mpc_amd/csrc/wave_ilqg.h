@@ -55,10 +55,13 @@ __device__ __forceinline__ void w_state_diff(const MODEL& m, wreal* dx, const wr
 // TREE: the Jacobian-free forward pass of wave_tree.h (its LDS layout, its contact lists at the large capacities) instead of the
 // row-table one -- the same step function the rollout kernels of such a model use
 template <int NMAX, bool TREE = false, bool RK4 = false>
-__global__ __launch_bounds__(64) void transition_fd_wave_kernel(const WModel m, const WTask tk, const FdWaveArgs f) {
+__global__ __launch_bounds__(64) void transition_fd_wave_kernel(const WModel m, const WTask tk_karg, const FdWaveArgs f) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x;
   const int t = blockIdx.x / f.ncol, col = blockIdx.x % f.ncol;
+  // the step's environment (0 of one unless f.env_T is set): its own blob -- mocap pose and frozen residual state (rollout_wave_kernel)
+  WTask tk = tk_karg;
+  if (f.env_T > 0) tk.blob = env_ptr(tk_karg.blob, t / f.env_T, f.env_stride);
   const int nq = m.nq, nv = m.nv, nu = m.nu, ndx = 2 * nv, ds = nq + nv, nr = tk.nr;
   wreal *lnodes, *ltimes;
   TreeData tree;

@@ -15,6 +15,10 @@ struct FdWaveArgs {
   double eps;
   double* next;    // [Tn][ncol][nq+nv] raw next states
   double* sensor;  // [Tn][ncol][nr]
+  // several environments in one launch (mjpcx_gradient_step_batched): Tn = num_envs x env_T steps, environment-major; step t belongs to
+  // environment t / env_T, whose plan blob is the task's moved by that many env_stride bytes (env_select.h). env_T = 0: one environment.
+  int env_T;
+  unsigned env_stride;
 };
 struct FeedbackWaveArgs {
   const double *times, *states, *actions, *gains, *improvement, *alpha;  // as FeedbackArgs (ilqg_kernels.h)

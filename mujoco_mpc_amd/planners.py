@@ -878,9 +878,7 @@ def normalize_state_quaternions(model, x):
 def model_derivatives(ctx, tr, T, derivative_skip, fd_tolerance, fd_mode):
     """ModelDerivatives::Compute incl. skip + interpolation, model_derivatives.cc:45-165 (the gradient-based planners' shared
     step; the caller zeroes A, B, D at the last step, which has no transition)"""
-    s = derivative_skip + 1
-    evaluate = [0] + list(range(s, T - s, s)) + [T - 2, T - 1]
-    evaluate = sorted(set(e for e in evaluate if 0 <= e < T))
+    evaluate = derivative_steps(T, derivative_skip)
     A, B, C, D = ctx.transition_fd(tr.times[evaluate], tr.states[evaluate], tr.actions[evaluate], fd_tolerance, int(fd_mode))
     if len(evaluate) == T:
         return A, B, C, D
@@ -1352,7 +1350,7 @@ class GpuGradientPlanner:
         self.resample_policy(horizon)
         self.nominal_trajectory(horizon)
         tr = self.trajectory0
-        c_prev = c_best = tr.total_return
+        c_prev = tr.total_return
         self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
         t0 = _time.perf_counter()
         st = self.settings
@@ -1371,14 +1369,27 @@ class GpuGradientPlanner:
         self.timers["gradient"] = (_time.perf_counter() - t0) * 1e6
         # ---- Rollouts, planner.cc:384-418: theta + s_i * parameter_update, one batch
         t0 = _time.perf_counter()
-        steps = np.zeros(N)
-        if N > 1:
-            steps[:N - 1] = log_scale(1.0, st.min_linesearch_step, N - 1)
-        self.linesearch_steps = steps
+        steps = self._linesearch_steps(N)
         nodes = c0.parameters[:P][None] + steps[:, None, None] * c0.parameter_update[:P][None]
         self.ctx.set_state(self.state, self.time, self.mocap, self.userdata)
         self.ctx.rollout_splines(T, c0.representation, c0.times[:P], nodes)
         ret, fail = self.ctx.returns()
+        self._select(c_prev, ret, fail, nodes, steps, self.ctx.fetch_trajectory)
+        self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
+
+    def _linesearch_steps(self, N):
+        steps = np.zeros(N)
+        if N > 1:
+            steps[:N - 1] = log_scale(1.0, self.settings.min_linesearch_step, N - 1)
+        self.linesearch_steps = steps
+        return steps
+
+    def _select(self, c_prev, ret, fail, nodes, steps, fetch):
+        """the winner among the line-search rollouts and the policy update (planner.cc:262-327). fetch(winner) returns the winner's
+        trajectory; None (a batch planner) leaves trajectory0 to be fetched when it is asked for."""
+        N, c0 = len(steps), self.candidate0
+        P = c0.num_spline_points
+        c_best = c_prev
         # strict < from the last candidate down, starting from the nominal's return; failed rollouts never win
         winner = N - 1
         for j in range(N - 1, -1, -1):
@@ -1388,13 +1399,12 @@ class GpuGradientPlanner:
                 c_best, winner = float(ret[j]), j
         if c_best < c_prev:
             c0.parameters[:P] = nodes[winner]
-            self.trajectory0 = self.ctx.fetch_trajectory(winner)
+            self.trajectory0 = fetch(winner) if fetch is not None else None
         self.winner = winner
         self.action_step = float(steps[winner])
         self.expected = -self.action_step * self.dV[0] - 1.0e-16
         self.improvement = c_prev - c_best
         self.surprise = min(max(0.0, self.improvement / self.expected), 2.0)
-        self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
         if c_best >= c_prev:
             self.winner = N - 1
         with self.mtx_:
@@ -1411,6 +1421,155 @@ class GpuGradientPlanner:
 
     def num_parameters(self):
         return self.policy.num_spline_points * self.model.nu
+
+
+def derivative_steps(T, derivative_skip):
+    """the steps ModelDerivatives::Compute evaluates for derivative_skip (model_derivatives.cc:45-106; model_derivatives above)"""
+    s = derivative_skip + 1
+    evaluate = [0] + list(range(s, T - s, s)) + [T - 2, T - 1]
+    return sorted(set(e for e in evaluate if 0 <= e < T))
+
+
+class GpuBatchGradientPlanner:
+    """The Gradient planner for `num_envs` environments (robots) on ONE context: a plan step is one `set_states`, one
+    `rollout_splines_batched` of the resampled policies (64 candidates per environment, candidate 0 the nominal), one
+    `gradient_step_batched` -- model derivatives, cost derivatives and the adjoint sweep of every environment chained on the device,
+    the first sync --, one `rollout_splines_batched` of theta + s_i * parameter_update for all environments and `returns()`, the
+    second sync: two host round trips for the fleet instead of six per robot. The environments share the model, the task and the
+    settings; each has its own state, clock, mocap pose and policy. The per-environment logic (ResamplePolicy, the line-search
+    steps, the selection rule with its ties toward the higher index, the policy bookkeeping) IS GpuGradientPlanner's, one member
+    per environment. gradient_num_trajectory must be a positive multiple of 64."""
+
+    def __init__(self, num_envs, device=0, precision=64, backend_factory=None):
+        if int(num_envs) < 1:
+            raise ValueError("GpuBatchGradientPlanner needs at least one environment")
+        self.num_envs, self.device, self.precision = int(num_envs), device, precision
+        self._backend_factory = backend_factory
+        self.model = self.task = self.ctx = None
+        self.timers = {}
+        self._last = None  # what the context's last rollout was: "plan" (the line search) or "nominal"
+        # the members never roll out themselves: they are handed the shared context instead of creating their own
+        self.envs = [GpuGradientPlanner(device, precision, backend_factory=lambda task: self.ctx) for _ in range(self.num_envs)]
+        for p in self.envs:
+            p.settings = self.envs[0].settings      # one GradientSettings for the fleet
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        for p in self.envs:
+            p.initialize(model, task)
+
+    num_trajectory = _fleet_setting("num_trajectory")
+    derivative_skip_ = _fleet_setting("derivative_skip_")
+    settings = _fleet_setting("settings")
+
+    def _check_n(self, n):
+        if n < 64 or n % 64 != 0:
+            raise ValueError(f"GpuBatchGradientPlanner: {n} candidates per environment; a batched launch needs a positive multiple "
+                             "of 64 (every wavefront serves one environment) -- set gradient_num_trajectory / num_trajectory accordingly")
+
+    def allocate(self):
+        if self._backend_factory is not None:
+            self.ctx = self._backend_factory(self.task)
+        else:
+            differentiable = bool(int(self.model.get_number("agent_differentiable", 1)))
+            self.ctx = capi.Context(self.task.packed_model(differentiable=differentiable), self.task.packed(), self.device, self.precision)
+        for p in self.envs:
+            p.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        for p in self.envs:
+            p.reset(horizon, initial_repeated_action)
+        self._last = None
+        self.timers = {}
+
+    def set_states(self, states):
+        """one State per environment (Planner::SetState for each)"""
+        if len(states) != self.num_envs:
+            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
+        for p, st in zip(self.envs, states):
+            p.set_state(st)
+
+    def _push_states(self):
+        sync_task(self.ctx, self.task)
+        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
+                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
+                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+
+    def _rollout_nominal(self, horizon):
+        """candidate0 of every environment in one launch: 64 candidates per environment, candidate 0 carrying the policy"""
+        c0s = [p.candidate0 for p in self.envs]
+        P = c0s[0].num_spline_points
+        if any(c.num_spline_points != P or c.representation != c0s[0].representation for c in c0s):
+            raise ValueError("the environments' policies have different spline shapes")
+        self._push_states()
+        times = np.stack([c.times[:P] for c in c0s])
+        values = np.stack([np.broadcast_to(c.parameters[:P][None], (64, P, self.model.nu)) for c in c0s])
+        self.ctx.rollout_splines_batched(horizon, c0s[0].representation, times, values, num_envs=self.num_envs, n_per_env=64)
+        self._last = "nominal"
+        return times
+
+    # ---- OptimizePolicy, gradient/planner.cc:159-327, for every environment
+    def optimize_policy(self, horizon, pool=None):
+        N = int(self.num_trajectory)
+        self._check_n(N)
+        T, E = horizon, self.num_envs
+        t0 = _time.perf_counter()
+        for p in self.envs:
+            with p.mtx_:
+                p.candidate0.copy_from(p.policy)
+            p.resample_policy(horizon)
+        times = self._rollout_nominal(horizon)
+        self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
+        t0 = _time.perf_counter()
+        first = self.envs[0]
+        st, c0 = first.settings, first.candidate0
+        P, rep = c0.num_spline_points, c0.representation
+        out = self.ctx.gradient_step_batched(E, 0, T, derivative_steps(T, first.derivative_skip_), st.fd_tolerance, int(st.fd_mode), rep, times)
+        self.timers["derivatives"] = (_time.perf_counter() - t0) * 1e6
+        # ---- Rollouts, planner.cc:384-418: theta + s_i * parameter_update of every environment, one batch
+        t0 = _time.perf_counter()
+        nodes = []
+        for e, p in enumerate(self.envs):
+            p.dV = np.array(out["dV"][e])
+            p.candidate0.k[:T] = out["k"][e]
+            p.candidate0.parameter_update[:P] = out["gradient"][e]
+            steps = p._linesearch_steps(N)
+            nodes.append(p.candidate0.parameters[:P][None] + steps[:, None, None] * p.candidate0.parameter_update[:P][None])
+        nodes = np.stack(nodes)
+        self.ctx.rollout_splines_batched(T, rep, times, nodes, num_envs=E, n_per_env=N)
+        ret, fail = self.ctx.returns()
+        self._last, self._n = "plan", N
+        for e, p in enumerate(self.envs):
+            p.trajectory0 = None          # the winner's (or, without one, the zero step's = the nominal's) rollout: best_trajectory fetches it
+            p._select(float(out["nominal_return"][e]), ret[e * N:(e + 1) * N], fail[e * N:(e + 1) * N], nodes[e], p.linesearch_steps, None)
+        self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
+
+    def nominal_trajectory(self, horizon, pool=None):
+        """NominalTrajectory of every environment in one launch"""
+        self._rollout_nominal(horizon)
+        out = [self.ctx.fetch_trajectory(64 * e) for e in range(self.num_envs)]
+        for p, tr in zip(self.envs, out):
+            p.trajectory0 = tr
+        return out
+
+    def action_from_policy(self, env, action, state, time, use_previous=False):
+        return self.envs[env].action_from_policy(action, state, time, use_previous)
+
+    def best_trajectory(self, env):
+        p = self.envs[env]
+        if p.trajectory0 is None and self._last == "plan":
+            p.trajectory0 = self.ctx.fetch_trajectory(env * self._n + p.winner)
+        return p.trajectory0
+
+    def num_parameters(self):
+        return self.envs[0].num_parameters()
+
+    winner = property(lambda self: [p.winner for p in self.envs])
+    dV = property(lambda self: [p.dV for p in self.envs])
+    action_step = property(lambda self: [p.action_step for p in self.envs])
+    improvement = property(lambda self: [p.improvement for p in self.envs])
+    expected = property(lambda self: [p.expected for p in self.envs])
+    surprise = property(lambda self: [p.surprise for p in self.envs])
 
 
 # ====================================================================================== iLQS
