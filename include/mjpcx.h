@@ -330,7 +330,8 @@ int mjpcx_set_residual_state(mjpcx_ctx* ctx, const int32_t* residual_int, const 
  * candidate c = e * n_per_env + i, and every getter (mjpcx_get_returns, mjpcx_get_return_at, mjpcx_fetch_trajectory,
  * mjpcx_fetch_spline, mjpcx_device_buffer) takes the global index. The rollout kernel is chosen from the TOTAL E * n_per_env, by the
  * thresholds of the plain calls: a fleet's shares run together on the kernel a batch of that size runs on.
- *   - n_per_env must be a positive multiple of 64 (every wavefront then serves one environment) and E >= 1: MJPCX_EINVAL otherwise;
+ *   - n_per_env must be a positive multiple of 64 (every wavefront then serves one environment) and E >= 1: MJPCX_EINVAL otherwise
+ *     (mjpcx_rollout_feedback_batched alone takes any n_per_env >= 1);
  *   - a batched rollout needs a preceding mjpcx_set_states with the same E: MJPCX_EINVAL otherwise;
  *   - on a context sharded with mjpcx_comm_init (world > 1), or with xfrc noise: MJPCX_EUNSUPPORTED.
  * The plain entry points are the one-environment case of the same launch code and kernels; they keep using the state of
@@ -495,6 +496,22 @@ int mjpcx_gradient_pass(mjpcx_ctx* ctx, int n, int m, int T, const double* A, co
 int mjpcx_gradient_step_batched(mjpcx_ctx* ctx, int num_envs, int candidate, int T, int num_eval, const int32_t* evaluate, double eps,
                                 int centered, int representation, int P, const double* node_times, double* nominal_return, double* k,
                                 double* gradient, double* dV, double* A, double* B, double* cx, double* cu);
+
+/* mjpcx_rollout_feedback for E environments in one launch: for every environment e exactly mjpcx_rollout_feedback(n_per_env, ...) with
+ * row e of every array -- times E x Tn, states E x Tn x (nq+nv), actions E x Tn x nu, gains E x Tn x nu x ndx, improvement E x Tn x nu,
+ * alpha E x n_per_env -- from the state, clock, mocap pose, userdata and frozen residual state mjpcx_set_states /
+ * mjpcx_set_residual_states gave environment e (restaged by this call). Candidates are environment-major, c = e * n_per_env + i, and
+ * every getter takes the global index afterwards. n_per_env is ANY positive number here (iLQG uses 10), not a multiple of 64: the lane
+ * family pads every environment to whole wavefronts, and on the other feedback kernels a workgroup is one candidate. E plain calls
+ * reproduce a batched one bit for bit. The six arrays travel through one pinned block in one H2D copy; no sync, except the one the
+ * quad feedback kernel needs to read its hand-on count (candidates it hands on, of whichever environments, are rolled out by the
+ * wavefront-per-candidate kernel afterwards, as in the plain call). The plain calls keep using the state of mjpcx_set_state.
+ * MJPCX_EINVAL: no preceding mjpcx_set_states with the same E, E < 1, n_per_env < 1, horizon < 1, nominal_horizon < 1, mode 0 with
+ * horizon > nominal_horizon, an unknown mode or representation. MJPCX_EUNSUPPORTED: a context sharded with mjpcx_comm_init (world > 1);
+ * xfrc noise; fp32 contexts of the wavefront-per-candidate family, as the plain call refuses them. */
+int mjpcx_rollout_feedback_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int mode, int representation,
+                                   int use_state, int nominal_horizon, const double* times, const double* states,
+                                   const double* actions, const double* gains, const double* improvement, const double* alpha);
 
 /* ---- measurement --------------------------------------------------------------
  * HIP-event timing of the rollout kernel on the context's own stream.

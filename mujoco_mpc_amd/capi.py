@@ -30,6 +30,7 @@ EXPORTS = [
     "mjpcx_elite_allreduce", "mjpcx_comm_barrier", "mjpcx_comm_destroy",
     "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
     "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched", "mjpcx_gradient_step_batched",
+    "mjpcx_rollout_feedback_batched",
 ]
 
 _LIB = None
@@ -86,6 +87,7 @@ def lib():
         L.mjpcx_fetch_trajectory.argtypes = [vp, C.c_int, C.POINTER(MjpcxTrajView)]
         L.mjpcx_fetch_spline.argtypes = [vp, C.c_int, c_f64p]
         L.mjpcx_rollout_feedback.argtypes = [vp] + [C.c_int] * 6 + [c_f64p] * 6
+        L.mjpcx_rollout_feedback_batched.argtypes = [vp] + [C.c_int] * 7 + [c_f64p] * 6
         L.mjpcx_transition_fd.argtypes = [vp, C.c_int, c_f64p, c_f64p, c_f64p, C.c_double, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_cost_derivatives.argtypes = [vp, C.c_int] + [c_f64p] * 8
         L.mjpcx_backward_pass.argtypes = ([vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [c_f64p] * 14 +
@@ -388,6 +390,29 @@ class Context:
         self._chk(lib().mjpcx_rollout_feedback(self.handle, N, int(horizon), int(mode), int(representation), int(use_state),
                                                Tn, *[as_f64p(a) for a in arrs]))
         self.N, self.H, self.P = N, int(horizon), 0
+
+    def rollout_feedback_batched(self, horizon, mode, representation, use_state, times, states, actions, gains, improvement, alpha,
+                                 num_envs=None, n_per_env=None):
+        """rollout_feedback for E environments in one launch (mjpcx_rollout_feedback_batched), from the states of set_states: times
+        E x Tn, states E x Tn x dim_state, actions E x Tn x nu, gains E x Tn x nu x ndx, improvement E x Tn x nu, alpha E x n_per_env
+        (any n_per_env >= 1). E and n_per_env come from alpha's shape; candidates are environment-major."""
+        al = _f(alpha)
+        if al.ndim != 2 and (num_envs is None or n_per_env is None):
+            raise ValueError("rollout_feedback_batched: alpha must be E x n_per_env")
+        E = int(num_envs) if num_envs is not None else al.shape[0]
+        n = int(n_per_env) if n_per_env is not None else al.shape[1]
+        tm = _f(times)
+        Tn = tm.size // max(E, 1)
+        ndx = 2 * self.nv
+        arrs = [_f(x).reshape(-1) for x in (tm, states, actions, gains, improvement, al)]
+        if E >= 1 and n >= 1 and Tn >= 1:
+            want = [E * Tn, E * Tn * self.dim_state, E * Tn * self.nu, E * Tn * self.nu * ndx, E * Tn * self.nu, E * n]
+            if [a.size for a in arrs] != want:
+                raise ValueError(f"rollout_feedback_batched: array sizes {[a.size for a in arrs]} for {E} environments x {Tn} steps x {n} "
+                                 f"candidates, expected {want}")
+        self._chk(lib().mjpcx_rollout_feedback_batched(self.handle, E, n, int(horizon), int(mode), int(representation), int(use_state),
+                                                       Tn, *[as_f64p(a) for a in arrs]))
+        self.N, self.H, self.P, self.n_per_env = E * n, int(horizon), 0, n
 
     def transition_fd(self, times, states, actions, eps=1e-6, centered=0):
         T, ndx, nu, nr = len(times), 2 * self.nv, self.nu, self.num_residual

@@ -3,6 +3,9 @@
 // environment (0: one environment), and env_stride, the bytes between the records [node_times | nominal | variance | blob] of consecutive
 // environments; node_times, nominal, the CE variance and the blob pointer are environment 0's. env_n is a multiple of 64: the environment is uniform over
 // a wavefront, and over a workgroup of the lane, quad and limb kernels, so it lives in SGPRs and selects with scalar arithmetic.
+// The feedback kernels of mjpcx_rollout_feedback_batched take ANY env_n >= 1: on rollout_feedback_quad_kernel and the wave / tree feedback
+// kernels a 64-thread workgroup is one candidate (cpw = 1), so its environment is blockIdx.x / env_n; rollout_feedback_kernel<ENVS> of the
+// lane family pads every environment to whole wavefronts instead (FeedbackArgs::env_waves).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

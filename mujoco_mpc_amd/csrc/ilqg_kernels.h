@@ -22,6 +22,13 @@ struct FeedbackArgs {
   int mode;            // 0: index policy (RolloutDiscrete), 1: continuous-time iLQGPolicy::Action
   int representation;  // mode 1: 0 zero-order, 1 linear, 2 cubic (ilqg_representation)
   int use_state;       // mode 1: settings.nominal_feedback_scaling
+  // several environments in one launch (mjpcx_rollout_feedback_batched): the five nominal arrays hold env_n-candidate environments' blocks
+  // of Tn steps, environment-major and contiguous; alpha is indexed by the global candidate c = e * env_n + i. Every environment is padded to
+  // env_waves = ceil(env_n / 64) wavefronts, so a wavefront serves one environment, whose initial-condition record is init moved by
+  // e * env_stride bytes (env_select.h). env_n = 0: one environment, the LaneTask of the kernel arguments.
+  int env_n, env_waves;
+  unsigned env_stride;
+  const LaneInit<T>* init;
 };
 
 // FindInterval (mjpc/utilities.h:124-144) on a wave-uniform query
@@ -70,10 +77,23 @@ __device__ __forceinline__ InterpWeights<T> interp_weights(const T* xs, T value,
   return r;
 }
 
-template <class TP, class TK, typename T, class MC>
-__global__ __launch_bounds__(64) void rollout_feedback_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk,
-                                                               const RolloutArgs<T> a, const FeedbackArgs<T> fb) {
+// ENVS: the instantiation mjpcx_rollout_feedback_batched launches (FeedbackArgs::env_n > 0): workgroup b serves environment
+// b / env_waves -- its LaneInit record, its block of the nominal arrays, its candidates; the plain one is the kernel of mjpcx_rollout_feedback
+template <class TP, class TK, typename T, class MC, bool ENVS = false>
+__global__ __launch_bounds__(64) void rollout_feedback_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk_karg,
+                                                               const RolloutArgs<T> a, const FeedbackArgs<T> fb_karg) {
   decltype(auto) m = MC::template get<T>(m_karg);
+  LaneTask<T> tk = tk_karg;
+  FeedbackArgs<T> fb = fb_karg;
+  int cand = blockIdx.x * 64 + threadIdx.x, end = a.N;  // this lane's candidate; one past the last candidate that shares the nominal and tk
+  if constexpr (ENVS) {  // (the environment is workgroup-uniform: scalar arithmetic, scalar loads of the record)
+    const int env = (int)blockIdx.x / fb.env_waves, first = env * fb.env_n;
+    lane_task_init(tk, env_ptr(fb.init, env, fb.env_stride));
+    const size_t t0 = (size_t)env * fb.Tn;
+    fb.times += t0; fb.states += t0 * 2 * TP::NV; fb.actions += t0 * TP::NU; fb.gains += t0 * TP::NU * 2 * TP::NV; fb.improvement += t0 * TP::NU;
+    cand = first + ((int)blockIdx.x - env * fb.env_waves) * 64 + (int)threadIdx.x;
+    end = first + fb.env_n;
+  }
   constexpr int NV = TP::NV, NU = TP::NU, NS = TP::NSITE, NR = TK::NR, DS = 2 * NV, NDX = 2 * NV;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   // the nominal trajectory is shared by all candidates: staged once into LDS, broadcast reads afterwards
@@ -88,10 +108,8 @@ __global__ __launch_bounds__(64) void rollout_feedback_kernel(const LaneModel<T>
   for (int i = threadIdx.x; i < fb.Tn * NU * NDX; i += 64) l_gains[i] = fb.gains[i];
   __syncthreads();
 
-  const int lane = threadIdx.x;
-  const int cand = blockIdx.x * 64 + lane;
-  const bool live = cand < a.N;
-  const int ci = live ? cand : a.N - 1;
+  const bool live = cand < end;
+  const int ci = live ? cand : end - 1;  // clamp: dead lanes compute a duplicate (of their own environment), never store
   const T alpha = fb.alpha[ci];
   const int H = a.H;
 

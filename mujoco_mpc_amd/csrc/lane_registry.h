@@ -57,6 +57,10 @@ hipError_t launch_feedback_impl(const LaneModel<T>& m, const LaneTask<T>& tk, co
   static_assert(sizeof(LaneModel<T>) + sizeof(LaneTask<T>) + sizeof(RolloutArgs<T>) + sizeof(FeedbackArgs<T>) <= 4096, "kernarg");
   const int blocks = (a.N + 63) / 64;
   const size_t shmem = (size_t)fb.Tn * (1 + 2 * TP::NV + 2 * TP::NU + TP::NU * 2 * TP::NV) * sizeof(T);
+  if (fb.env_n > 0) {  // several environments (mjpcx_rollout_feedback_batched): every environment's candidates padded to whole wavefronts
+    hipLaunchKernelGGL((rollout_feedback_kernel<TP, TK, T, MC, true>), dim3((unsigned)(a.N / fb.env_n) * fb.env_waves), dim3(64), shmem, s, m, tk, a, fb);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL((rollout_feedback_kernel<TP, TK, T, MC>), dim3(blocks), dim3(64), shmem, s, m, tk, a, fb);
   return hipGetLastError();
 }

@@ -499,6 +499,9 @@ struct mjpcx_ctx {
   DevBuf d_nodes, d_in_nodes, d_ilqg, d_ilqg_out, d_wblob;
   DevBuf d_grad;                                  // workspace of mjpcx_gradient_step_batched: inputs, every intermediate, the result block
   void* grad_host = nullptr; size_t grad_cap = 0; // its pinned [inputs | result block]
+  // pinned staging block of mjpcx_rollout_feedback_batched (the six policy arrays of every environment, one H2D copy; the call does not
+  // sync, so the block is rewritten only after the copy that read it has passed fb_done)
+  void* fb_host = nullptr; size_t fb_cap = 0; hipEvent_t fb_done = nullptr; bool fb_pending = false;
   DevBuf d_states, d_actions, d_times, d_residual, d_costs, d_trace, d_ret, d_fail, d_sort, d_stage;
   bool traj_candidate_major = false;
   int nsite_model = 0;
@@ -1496,6 +1499,8 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   if (c->best_host) (void)hipHostFree(c->best_host);
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
   if (c->grad_host) (void)hipHostFree(c->grad_host);
+  if (c->fb_host) (void)hipHostFree(c->fb_host);
+  if (c->fb_done) (void)hipEventDestroy(c->fb_done);
   (void)mjpcx_comm_destroy(c);
   c->wh.release();
   DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_wblob, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
@@ -2577,6 +2582,139 @@ int mjpcx_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int T, int ne, co
                                                                gradient, dV, A, B, cx, cu)
                             : do_gradient_step_batched<float>(c, E, cand, T, ne, evaluate, eps, centered, representation, P, node_times, nominal_return, k,
                                                               gradient, dV, A, B, cx, cu);
+}
+
+}  // extern "C"
+
+namespace {
+// mjpcx_rollout_feedback_batched after validation: the environments' plan records (stage_plan_inputs), the six policy arrays through ONE
+// pinned block and ONE H2D copy, then the launch of mjpcx_rollout_feedback's kernels with the environment selection switched on
+template <typename T>
+int do_feedback_batched(mjpcx_ctx* c, int E, int n, int H, int mode, int representation, int use_state, int Tn, const double* times,
+                        const double* states, const double* actions, const double* gains, const double* improvement, const double* alpha) {
+  int rc;
+  const int N = E * n;
+  if ((rc = reserve_rollout(c, N, H, 1)) != MJPCX_OK) return rc;
+  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, sET = (size_t)E * Tn;
+  // the environments' plan records, restaged: a preceding rollout's slot may have been recycled since
+  const T *d_rec_times, *d_rec_nominal;
+  const double* d_rec_var;
+  const void* d_blob = nullptr;
+  mjpcx_ctx::Slot* slot = nullptr;
+  unsigned stride = 0;
+  if ((rc = stage_plan_inputs<T>(c, 0, E, nullptr, nullptr, nullptr, false, &d_rec_times, &d_rec_nominal, &d_rec_var, &slot, &d_blob, &stride)) != MJPCX_OK)
+    return rc;
+  // [times | states | actions | gains | improvement | alpha] in the context's precision, each on a 16-byte boundary
+  const std::pair<const double*, size_t> arrays[6] = {{times, sET}, {states, sET * ds}, {actions, sET * nu}, {gains, sET * nu * ndx},
+                                                      {improvement, sET * nu}, {alpha, (size_t)N}};
+  size_t off[6], total = 0;
+  for (int k = 0; k < 6; k++) { off[k] = total; total += (arrays[k].second + 3) & ~(size_t)3; }
+  const size_t bytes = total * sizeof(T);
+  if (c->fb_pending) { HIPCHK(c, hipEventSynchronize(c->fb_done)); c->fb_pending = false; }
+  if (!c->fb_done) HIPCHK(c, hipEventCreateWithFlags(&c->fb_done, hipEventDisableTiming));
+  if (bytes > c->fb_cap) {
+    if (c->fb_host) (void)hipHostFree(c->fb_host);
+    c->fb_host = nullptr; c->fb_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->fb_host, bytes, hipHostMallocDefault));
+    c->fb_cap = bytes;
+  }
+  HIPCHK(c, c->d_ilqg.reserve(bytes));
+  T* host = (T*)c->fb_host;
+  for (int k = 0; k < 6; k++)
+    for (size_t i = 0; i < arrays[k].second; i++) host[off[k] + i] = (T)arrays[k].first[i];
+  HIPCHK(c, hipMemcpyAsync(c->d_ilqg.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->fb_done, c->stream));
+  c->fb_pending = true;
+  const T* d[6];
+  for (int k = 0; k < 6; k++) d[k] = (const T*)c->d_ilqg.p + off[k];
+  RolloutArgs<T> a{};
+  a.N = N; a.H = H; a.P = c->wave ? 1 : 0; a.interp = 0; a.nodes = (T*)c->d_nodes.p; a.noise.mode = -1;
+  a.states = (T*)c->d_states.p; a.actions = (T*)c->d_actions.p; a.times = (T*)c->d_times.p;
+  a.residual = (T*)c->d_residual.p; a.costs = (T*)c->d_costs.p; a.trace = (T*)c->d_trace.p;
+  a.total_return = (double*)c->d_ret.p; a.failure = (int*)c->d_fail.p;
+  auto finish = [&]() {
+    HIPCHK(c, hipEventRecord(slot->done, c->stream));
+    slot->pending = true;
+    c->N = N; c->H = H; c->P = a.P; c->env_n = n;
+    c->have_rollout = true;
+    c->traj_candidate_major = c->wave;
+    return (int)MJPCX_OK;
+  };
+  if (!c->wave) {
+    FeedbackArgs<T> fb{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
+    fb.env_n = n; fb.env_waves = (n + 63) / 64; fb.env_stride = stride; fb.init = (const LaneInit<T>*)d_blob;
+    hipError_t le;
+    if constexpr (sizeof(T) == 8) le = c->kernel->feedback64(c->hm64, c->ht64, a, fb, c->stream);
+    else { convert_task(c->ht32, c->ht64); le = c->kernel->feedback32(c->hm32, c->ht32, a, fb, c->stream); }
+    if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("feedback kernel launch: ") + hipGetErrorString(le));
+    return finish();
+  }
+  if constexpr (sizeof(T) == 8) {
+    WaveTask wt = c->wh.t;
+    wt.blob = (const double*)d_blob;
+    wt.stamps = nullptr;
+    wt.stamp_step = 0;
+    w64::FeedbackWaveArgs fb{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state, 0, n, stride};
+    const bool tree = c->wh.tree_ok && !c->no_tree;
+    // the quad form first, as in the plain call; the candidates it hands on -- of whichever environments -- go to the tree / wave kernel
+    if (c->quad_ok && !c->no_quad_feedback && c->wh.m.integrator == MJPCX_INT_EULER) {
+      quad::QArgs q{};
+      q.N = N; q.H = H; q.P = 1; q.noise_mode = -1; q.nodes = (double*)c->d_nodes.p;
+      q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
+      q.total_return = a.total_return; q.failure = a.failure; q.con_cap = c->quad_con_cap; q.cpw = 1;
+      q.env_n = n; q.env_stride = stride;
+      const quad::QBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
+      const quad::QFeedback qf{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
+      HIPCHK(c, hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream));
+      HIPCHK(c, quad::launch_feedback_quad(c->d_qmodel.p, c->d_qtab.p, wt.blob, bo, q, qf, (int*)c->d_qstats.p, c->stream));
+      if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 32, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
+      bool handed_on = true;
+      if (c->h_qstats) {  // (the one sync of the call: the hand-on count)
+        HIPCHK(c, hipMemcpyAsync(c->h_qstats, c->d_qstats.p, 32, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        handed_on = static_cast<const int*>(c->h_qstats)[0] != 0;
+      }
+      if (!handed_on) return finish();
+      fb.only_flagged = 1;
+    }
+    const int Ppolicy = tree ? (int)(ndx + 2 * ds) : (int)((ndx + 2 * ds + nu - 1) / nu + 1);
+    const size_t lds = wave_lds_bytes(c, Ppolicy, tree);
+    const bool rk4 = c->wh.m.integrator == MJPCX_INT_RK4;
+    HIPCHK(c, launch_feedback_wave(c->wh.m, wt, a, fb, N, lds, tree, rk4, c->wh.registered == 0 ? c->wh.dev_image : nullptr, c->wh.blob_bytes, c->stream));
+    return finish();
+  }
+  return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+}
+}  // namespace
+
+extern "C" {
+
+int mjpcx_rollout_feedback_batched(mjpcx_ctx* c, int E, int n, int H, int mode, int representation, int use_state, int Tn, const double* times,
+                                   const double* states, const double* actions, const double* gains, const double* improvement,
+                                   const double* alpha) {
+  const char* who = "mjpcx_rollout_feedback_batched: ";
+  if (!c || !times || !states || !actions || !gains || !improvement || !alpha) return fail(c, MJPCX_EINVAL, std::string(who) + "null argument");
+  if (E < 1) return fail(c, MJPCX_EINVAL, std::string(who) + "the number of environments must be >= 1");
+  if (n < 1 || H < 1 || Tn < 1) return fail(c, MJPCX_EINVAL, std::string(who) + "n_per_env, H and Tn must be >= 1");
+  if ((long long)E * n > 0x7fffffffLL / 64 || (long long)E * Tn * (1 + 2 * c->nv * c->nu) > 0x7fffffffLL / 64)
+    return fail(c, MJPCX_EINVAL, std::string(who) + "too many candidates or steps");
+  if (mode == 0 && H > Tn) return fail(c, MJPCX_EINVAL, std::string(who) + "index policy needs a nominal trajectory at least as long as the horizon");
+  if (mode != 0 && mode != 1) return fail(c, MJPCX_EINVAL, std::string(who) + "unknown feedback policy mode");
+  if (mode == 1 && (representation < 0 || representation > 2))
+    return fail(c, MJPCX_EINVAL, std::string(who) + "iLQG policy representation must be 0 (zero-order), 1 (linear) or 2 (cubic)");
+  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "not implemented on a context sharded with mjpcx_comm_init");
+  if (c->xfrc_std > 0) return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "xfrc noise (NoisyRollout) is not implemented for batched rollouts");
+  if (c->env_E != E)
+    return fail(c, MJPCX_EINVAL, c->env_E == 0 ? std::string(who) + "before mjpcx_set_states"
+                                               : std::string(who) + std::to_string(E) + " environments after mjpcx_set_states of " + std::to_string(c->env_E));
+  if (c->wave && c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->wave) {
+    const size_t shmem = (size_t)Tn * (1 + 2 * c->nv + 2 * c->nu + c->nu * 2 * c->nv) * esize(c);
+    if (shmem > 120 * 1024) return fail(c, MJPCX_EUNSUPPORTED, "nominal trajectory too large for the LDS stage");
+  }
+  return c->precision == 64 ? do_feedback_batched<double>(c, E, n, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha)
+                            : do_feedback_batched<float>(c, E, n, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha);
 }
 
 }  // extern "C"

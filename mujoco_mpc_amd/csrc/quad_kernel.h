@@ -263,7 +263,16 @@ __global__ __launch_bounds__(256) void rollout_quad_kernel(const QuadModel* __re
 // and rolled out by rollout_feedback_tree_kernel.
 __global__ __launch_bounds__(256) void rollout_feedback_quad_kernel(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob,
                                                                     const QBlob bo, const QArgs a, const QFeedback fb, int* __restrict__ stats) {
-  quad_kernel_body<true>(gm, tab, blob, bo, a, fb, stats);
+  // several environments (mjpcx_rollout_feedback_batched): quad_kernel_body picks the workgroup's blob from env_of; here its block of the
+  // nominal arrays (Tn steps each, environment-major; alpha is indexed by the global candidate). One candidate per 64-thread workgroup
+  // (cpw = 1), so the environment is blockIdx.x / env_n for ANY env_n >= 1 -- no multiple of 64 as the rollout kernels need (env_select.h)
+  QFeedback fe = fb;
+  if (a.env_n > 0) {
+    constexpr size_t nu = kQLegs * kQLinks, ds = 37, ndx = 36;
+    const size_t t0 = (size_t)((int)blockIdx.x / a.env_n) * fb.Tn;
+    fe.times += t0; fe.states += t0 * ds; fe.actions += t0 * nu; fe.gains += t0 * nu * ndx; fe.improvement += t0 * nu;
+  }
+  quad_kernel_body<true>(gm, tab, blob, bo, a, fe, stats);
 }
 
 } }  // namespace mjpcx::quad

@@ -328,36 +328,58 @@ __device__ __forceinline__ void feedback_rollout_body(const MODEL& m, const TASK
   }
 }
 
-template <int NMAX, bool TREE = false, bool RK4 = false>
+// the candidate's environment (0 of one unless fb.env_n is set): fb's nominal arrays moved to that environment's block (workgroup-uniform,
+// scalar arithmetic); the caller moves the blob with env_ptr as rollout_wave_kernel does
+__device__ __forceinline__ int feedback_env(FeedbackWaveArgs& fb, int cand, int ds, int nu, int ndx) {
+  if (fb.env_n <= 0) return 0;
+  const int env = cand / fb.env_n;
+  const size_t t0 = (size_t)env * fb.Tn;
+  fb.times += t0; fb.states += t0 * ds; fb.actions += t0 * nu; fb.gains += t0 * nu * ndx; fb.improvement += t0 * nu;
+  return env;
+}
+
+// ENVS: the instantiation mjpcx_rollout_feedback_batched launches (FeedbackWaveArgs::env_n > 0); the plain one is the kernel of
+// mjpcx_rollout_feedback
+template <int NMAX, bool TREE = false, bool RK4 = false, bool ENVS = false>
 __global__ __launch_bounds__(64) void rollout_feedback_wave_kernel(const WModel m, const WTask tk, const RolloutArgs<wreal> a,
                                                                     const FeedbackWaveArgs fb) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   if (fb.only_flagged && !(a.failure[blockIdx.x] & kQFallback)) return;  // (workgroup-uniform)
-  feedback_rollout_body<NMAX, TREE, RK4>(m, tk, a, fb, smem_raw, blockIdx.x, threadIdx.x);
+  if constexpr (ENVS) {
+    FeedbackWaveArgs fe = fb;
+    WTask tke = tk;
+    tke.blob = env_ptr(tk.blob, feedback_env(fe, blockIdx.x, m.nq + m.nv, m.nu, 2 * m.nv), fb.env_stride);
+    feedback_rollout_body<NMAX, TREE, RK4>(m, tke, a, fe, smem_raw, blockIdx.x, threadIdx.x);
+  } else {
+    feedback_rollout_body<NMAX, TREE, RK4>(m, tk, a, fb, smem_raw, blockIdx.x, threadIdx.x);
+  }
 }
 
 // the same for a REGISTERED model (tree_registry.h): its image and the per-plan blob staged into LDS as rollout_tree_kernel does
 // (tree_kernel.h). The iLQG phases are 1 and ~10 rollouts of pure per-step latency, and every model read on that chain is an LDS read
 // at a compile-time offset instead of a load through the caches: 0.20 against 0.26 ms per step (profiles/r03_latency_probe.log).
-template <class C>
+template <class C, bool ENVS = false>
 __global__ __launch_bounds__(64) void rollout_feedback_tree_kernel(const WModel m_in, const WTask tk_in, const RolloutArgs<wreal> a,
                                                                     const FeedbackWaveArgs fb, const unsigned char* __restrict__ image,
                                                                     unsigned blob_bytes) {
   typedef LdsLayout<C, wreal> L;
   const int lane = threadIdx.x;
   if (fb.only_flagged && !(a.failure[blockIdx.x] & kQFallback)) return;  // (workgroup-uniform)
+  FeedbackWaveArgs fe = fb;
+  int env = 0;
+  if constexpr (ENVS) env = feedback_env(fe, blockIdx.x, m_in.nq + m_in.nv, m_in.nu, 2 * m_in.nv);
   {
     const uint4* src = reinterpret_cast<const uint4*>(image);
     uint4* dst = reinterpret_cast<uint4*>(mjpcx_lds);
     for (unsigned i = lane; i < L::kBytes / 16; i += 64) dst[i] = src[i];
-    const uint4* bs = reinterpret_cast<const uint4*>(tk_in.blob);
+    const uint4* bs = reinterpret_cast<const uint4*>(ENVS ? env_ptr(tk_in.blob, env, fb.env_stride) : tk_in.blob);  // (the environment's blob)
     uint4* bd = reinterpret_cast<uint4*>(mjpcx_lds + L::kBytes);
     for (unsigned i = lane; i < blob_bytes / 16; i += 64) bd[i] = bs[i];
   }
   __syncthreads();
   const LdsModelT<C, wreal> m(m_in);
   const LdsTaskT<C, wreal> tk(tk_in, reinterpret_cast<const wreal*>(mjpcx_lds + L::kBytes));
-  feedback_rollout_body<C::NMAX, true, false>(m, tk, a, fb, mjpcx_lds + L::kBytes + blob_bytes, blockIdx.x, lane);
+  feedback_rollout_body<C::NMAX, true, false>(m, tk, a, fe, mjpcx_lds + L::kBytes + blob_bytes, blockIdx.x, lane);
 }
 
 } }  // namespace mjpcx::WAVE_NS

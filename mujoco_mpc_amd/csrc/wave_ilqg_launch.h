@@ -24,6 +24,11 @@ struct FeedbackWaveArgs {
   const double *times, *states, *actions, *gains, *improvement, *alpha;  // as FeedbackArgs (ilqg_kernels.h)
   int Tn, mode, representation, use_state;
   int only_flagged;  // roll out only the candidates whose failure[] carries kQFallback: the ones rollout_feedback_quad_kernel handed on
+  // several environments in one launch (mjpcx_rollout_feedback_batched): candidate c belongs to environment c / env_n (any env_n >= 1: a
+  // workgroup is one candidate), whose plan blob is the task's moved by that many env_stride bytes (env_select.h) and whose nominal is
+  // block c / env_n of the five arrays (Tn steps each, environment-major); alpha is indexed by c. env_n = 0: one environment.
+  int env_n;
+  unsigned env_stride;
 };
 }  // namespace w64
 

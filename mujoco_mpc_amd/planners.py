@@ -985,6 +985,7 @@ class GpuILQGPlanner:
         self._backend_factory = backend_factory
         self.settings = ILQGSettings()
         self.mtx_ = threading.RLock()
+        self.first_candidate = 0    # this planner's first candidate in the context's rollout (a member of GpuBatchILQGPlanner: env * n)
 
     def initialize(self, model, task: Task):
         self.model, self.task = model, task
@@ -1076,15 +1077,25 @@ class GpuILQGPlanner:
         if self.num_trajectory_ == 0:
             return
         t0 = _time.perf_counter()
-        self.policy.trajectory.horizon = horizon
-        steps = self._linesearch_steps()
-        tr = self.policy.trajectory
+        request = self._nominal_request(horizon)
         sync_task(self.ctx, self.task)
         self.ctx.set_state(self.state, self.time, self.mocap, self.userdata)
-        self.ctx.rollout_feedback(horizon, 1, self.policy.representation, self.settings.nominal_feedback_scaling,
-                                  tr.times[:horizon], tr.states[:horizon], tr.actions[:horizon],
-                                  self.policy.feedback_gain[:horizon], self.policy.action_improvement[:horizon], steps)
+        self.ctx.rollout_feedback(horizon, 1, self.policy.representation, self.settings.nominal_feedback_scaling, *request)
         ret, fail = self.ctx.returns()
+        self._nominal_select(horizon, ret, fail)
+        self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
+
+    # The two rollout phases of a plan step, each split at its launch, so that GpuBatchILQGPlanner can put the launches of a whole fleet
+    # into one batched call and run this planner's own code on either side: *_request gives the arrays of the feedback rollouts
+    # (times, states, actions, gains, improvement, alpha), the other half takes this planner's returns of them.
+    def _nominal_request(self, horizon):
+        self.policy.trajectory.horizon = horizon
+        tr = self.policy.trajectory
+        return (tr.times[:horizon], tr.states[:horizon], tr.actions[:horizon], self.policy.feedback_gain[:horizon],
+                self.policy.action_improvement[:horizon], self._linesearch_steps())
+
+    def _nominal_select(self, horizon, ret, fail):
+        steps = self._linesearch_steps()
         best = self.best_rollout(ret, fail)
         if best == -1:
             import copy
@@ -1096,11 +1107,10 @@ class GpuILQGPlanner:
         self.candidate0.feedback_gain[:horizon] = self.policy.feedback_gain[:horizon]
         self.candidate0.action_improvement[:horizon] = self.policy.action_improvement[:horizon]
         self.candidate0.representation = self.policy.representation
-        self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
 
     def _take_trajectory(self, policy, index, horizon):
         """candidate_policy[0].trajectory = trajectory[index] (buffers keep their allocated capacity)."""
-        got = self.ctx.fetch_trajectory(index)
+        got = self.ctx.fetch_trajectory(self.first_candidate + index)
         tr = policy.trajectory
         for name in ("states", "actions", "times", "residual", "costs", "trace"):
             getattr(tr, name)[:horizon] = getattr(got, name)
@@ -1111,13 +1121,27 @@ class GpuILQGPlanner:
 
     # ---- Iteration, planner.cc:377-627
     def iteration(self, horizon, pool=None):
+        request = self._iteration_before_rollouts(horizon)
+        if request is None:
+            return
+        # ---- ActionRollouts, planner.cc:630-692: line search over the improvement step
+        t0 = _time.perf_counter()
+        sync_task(self.ctx, self.task)
+        self.ctx.set_state(self.state, self.time, self.mocap, self.userdata)
+        self.ctx.rollout_feedback(horizon, 0, 0, 1, *request)
+        ret, fail = self.ctx.returns()
+        if self._iteration_after_rollouts(horizon, ret, fail):
+            self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
+
+    def _iteration_before_rollouts(self, horizon):
+        """derivatives and the backward pass on the context's current state; the line search's request, or None when the backward
+        pass failed every retry (the iteration ends there)"""
         st = self.settings
         c0 = self.candidate0
         tr = c0.trajectory
-        T, n, m = horizon, self.dim_state_derivative, self.dim_action
-        previous_return = tr.total_return
+        T = horizon
+        self._previous_return = tr.total_return
         self.iteration_completed = False
-        steps = self._linesearch_steps()
         t0 = _time.perf_counter()
         A, B, C, D = self._model_derivatives(tr, T)
         # the last step has no transition (model_derivatives.cc:88-92 computes only C there)
@@ -1141,21 +1165,24 @@ class GpuILQGPlanner:
                 break
         self.timers["backward_pass"] = (_time.perf_counter() - t0) * 1e6
         if not ok:
-            return
+            return None
         self.dV = out["dV"]
         c0.feedback_gain[:T] = out["K"]
         c0.action_improvement[:T] = out["du"]
-        # ---- ActionRollouts, planner.cc:630-692: line search over the improvement step
-        t0 = _time.perf_counter()
-        sync_task(self.ctx, self.task)
-        self.ctx.set_state(self.state, self.time, self.mocap, self.userdata)
-        self.ctx.rollout_feedback(T, 0, 0, 1, tr.times[:T], tr.states[:T], tr.actions[:T], c0.feedback_gain[:T],
-                                  c0.action_improvement[:T], steps)
-        ret, fail = self.ctx.returns()
+        return (tr.times[:T], tr.states[:T], tr.actions[:T], c0.feedback_gain[:T], c0.action_improvement[:T], self._linesearch_steps())
+
+    def _iteration_after_rollouts(self, horizon, ret, fail):
+        """selection, regularisation update and policy update from the line search's returns; False when every rollout failed"""
+        st = self.settings
+        c0 = self.candidate0
+        tr = c0.trajectory
+        T = horizon
+        steps = self._linesearch_steps()
+        previous_return = self._previous_return
         self.linesearch0_return = float(ret[0])
         best = self.best_rollout(ret, fail)
         if best == -1:
-            return
+            return False
         self.winner = best
         self.winner_return = float(ret[best])
         # candidate_policy[winner]: the nominal trajectory with actions += step * improvement (NOT re-rolled)
@@ -1172,13 +1199,13 @@ class GpuILQGPlanner:
         self.improvement = previous_return - float(ret[best])
         self.surprise = min(max(0.0, self.improvement / self.expected), 2.0)
         self.update_regularization(st.min_regularization, st.max_regularization, self.surprise, self.action_step)
-        self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
         with self.mtx_:
             self.previous_policy.copy_from(self.policy, T)
             self.previous_policy.feedback_scaling = self.policy.feedback_scaling
             self.policy.copy_from(winner_policy, T)
             self.policy.feedback_scaling = 1.0
         self.iteration_completed = True
+        return True
 
     def action_from_policy(self, action, state, time, use_previous=False):
         with self.mtx_:
@@ -1190,6 +1217,142 @@ class GpuILQGPlanner:
 
     def num_parameters(self):
         return self.dim_action * K_MAX_TRAJECTORY_HORIZON
+
+
+class GpuBatchILQGPlanner:
+    """iLQG for `num_envs` environments (robots) on ONE context. The two feedback-rollout phases of a plan step -- the nominal
+    under iLQGPolicy::Action and the line search under the index policy, three quarters of an iteration and pure per-step latency --
+    are one `rollout_feedback_batched` launch each for the whole fleet (any number of rollouts per environment: iLQG's ten). Between
+    them every environment runs the unchanged sequential chain on the shared context: plain `set_state` of that environment, model
+    derivatives, cost derivatives, the backward pass with its regularisation retries. An environment whose backward pass fails every
+    retry sits the line search out, exactly as GpuILQGPlanner.iteration returns early. The environments share the model, the task
+    and the settings; each has its own state, clock, mocap pose, policy and regularisation. The per-environment logic (BestRollout,
+    the regularisation schedule, the policy bookkeeping) IS GpuILQGPlanner's, one member per environment."""
+
+    def __init__(self, num_envs, device=0, precision=64, backend_factory=None):
+        if int(num_envs) < 1:
+            raise ValueError("GpuBatchILQGPlanner needs at least one environment")
+        self.num_envs, self.device, self.precision = int(num_envs), device, precision
+        self._backend_factory = backend_factory
+        self.model = self.task = self.ctx = None
+        self.timers = {}
+        # the members never create a context of their own: they are handed the shared one
+        self.envs = [GpuILQGPlanner(device, precision, backend_factory=lambda task: self.ctx) for _ in range(self.num_envs)]
+        for p in self.envs:
+            p.settings = self.envs[0].settings      # one ILQGSettings for the fleet
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        for p in self.envs:
+            p.initialize(model, task)
+
+    num_rollouts_gui_ = _fleet_setting("num_rollouts_gui_")
+    derivative_skip_ = _fleet_setting("derivative_skip_")
+    settings = _fleet_setting("settings")
+
+    def allocate(self):
+        if self._backend_factory is not None:
+            self.ctx = self._backend_factory(self.task)
+        else:
+            differentiable = bool(int(self.model.get_number("agent_differentiable", 1)))
+            self.ctx = capi.Context(self.task.packed_model(differentiable=differentiable), self.task.packed(), self.device, self.precision)
+        for p in self.envs:
+            p.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        for p in self.envs:
+            p.reset(horizon, initial_repeated_action)
+        self.timers = {}
+
+    def set_states(self, states):
+        """one State per environment (Planner::SetState for each)"""
+        if len(states) != self.num_envs:
+            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
+        for p, st in zip(self.envs, states):
+            p.set_state(st)
+
+    def _push_states(self):
+        sync_task(self.ctx, self.task)
+        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
+                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
+                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+
+    def _rollout(self, horizon, mode, representation, use_state, requests):
+        """one batched launch of every environment's request; each member's share of the returns"""
+        n = len(requests[0][5])
+        self._push_states()
+        self.ctx.rollout_feedback_batched(horizon, mode, representation, use_state, *[np.stack([r[k] for r in requests]) for k in range(6)])
+        ret, fail = self.ctx.returns()
+        for e, p in enumerate(self.envs):
+            p.first_candidate = e * n
+        return [(ret[e * n:(e + 1) * n], fail[e * n:(e + 1) * n]) for e in range(self.num_envs)]
+
+    def _prepare(self):
+        n = int(self.num_rollouts_gui_)
+        if n < 1:
+            raise ValueError("GpuBatchILQGPlanner: ilqg_num_rollouts / num_rollouts_gui_ must be >= 1")
+        if any(p.policy.representation != self.envs[0].policy.representation for p in self.envs):
+            raise ValueError("the environments' policies have different representations")
+        for p in self.envs:
+            p.num_trajectory_ = n
+
+    # ---- NominalTrajectory of every environment: one launch
+    def nominal_trajectory(self, horizon, pool=None):
+        self._prepare()
+        t0 = _time.perf_counter()
+        first = self.envs[0]
+        shares = self._rollout(horizon, 1, first.policy.representation, first.settings.nominal_feedback_scaling,
+                               [p._nominal_request(horizon) for p in self.envs])
+        for p, (ret, fail) in zip(self.envs, shares):
+            p._nominal_select(horizon, ret, fail)
+        self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
+
+    # ---- OptimizePolicy, ilqg/planner.cc:156-164, for every environment
+    def optimize_policy(self, horizon, pool=None):
+        self.nominal_trajectory(horizon)
+        # ---- derivatives and the backward pass, one environment after the other on that environment's plain state
+        t0 = _time.perf_counter()
+        requests = []
+        for p in self.envs:
+            self.ctx.set_state(p.state, p.time, p.mocap, p.userdata)
+            requests.append(p._iteration_before_rollouts(horizon))
+        self.timers["derivatives_backward"] = (_time.perf_counter() - t0) * 1e6
+        for key in ("model_derivative", "cost_derivative", "backward_pass"):
+            self.timers[key] = sum(p.timers[key] for p in self.envs)
+        # ---- ActionRollouts of the environments that got that far: one launch. The others ride along on their nominal with zero
+        # steps and are ignored.
+        self.sat_out = [r is None for r in requests]
+        if all(self.sat_out):
+            return
+        t0 = _time.perf_counter()
+        for e, p in enumerate(self.envs):
+            if requests[e] is None:
+                tr, c0 = p.candidate0.trajectory, p.candidate0
+                requests[e] = (tr.times[:horizon], tr.states[:horizon], tr.actions[:horizon], c0.feedback_gain[:horizon],
+                               c0.action_improvement[:horizon], np.zeros(p.num_trajectory_))
+        shares = self._rollout(horizon, 0, 0, 1, requests)
+        for p, out, (ret, fail) in zip(self.envs, self.sat_out, shares):
+            if not out:
+                p._iteration_after_rollouts(horizon, ret, fail)
+        self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
+
+    def action_from_policy(self, env, action, state, time, use_previous=False):
+        return self.envs[env].action_from_policy(action, state, time, use_previous)
+
+    def best_trajectory(self, env):
+        return self.envs[env].best_trajectory()
+
+    def num_parameters(self):
+        return self.envs[0].num_parameters()
+
+    winner = property(lambda self: [p.winner for p in self.envs])
+    action_step = property(lambda self: [p.action_step for p in self.envs])
+    feedback_scaling = property(lambda self: [p.feedback_scaling for p in self.envs])
+    dV = property(lambda self: [p.dV for p in self.envs])
+    improvement = property(lambda self: [p.improvement for p in self.envs])
+    expected = property(lambda self: [p.expected for p in self.envs])
+    surprise = property(lambda self: [p.surprise for p in self.envs])
+    regularization = property(lambda self: [p.regularization for p in self.envs])
 
 
 # ====================================================================================== Gradient

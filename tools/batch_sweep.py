@@ -17,6 +17,11 @@ GpuBatchGradientPlanner plan step (rollout_splines_batched, gradient_step_batche
 fleet), host logic included on both sides, 64 line-search candidates per environment. The record carries the batched planner's stage
 timers (medians). Default output profiles/batch_sweep_gradient.jsonl.
 
+--planner ilqg: the iLQG plan step on the A1 (T = 36, 10 rollouts). (a) E GpuILQGPlanner plan steps on one context, one after the other,
+against (b) one GpuBatchILQGPlanner plan step: the nominal and the line-search rollouts of the fleet in one rollout_feedback_batched
+launch each, the derivative chain and the Riccati pass still per environment. Host logic included on both sides. The record carries the
+batched planner's stage timers (medians) and one environment's sequential ones. Default output profiles/batch_sweep_ilqg.jsonl.
+
 Kernel thresholds are the library's defaults: the sequential side of 8 x 2048 runs eight launches of the kernel a 2048-candidate batch gets,
 the batched side one launch of the kernel a 16384-candidate batch gets -- that is the feature."""
 import argparse
@@ -124,6 +129,63 @@ def sweep_gradient(name, precision, H, shapes, steps, warmup, out):
     ctx.close()
 
 
+ILQG_SHAPES = [("QuadrupedFlat", 64, 36, [(1, 10), (2, 10), (4, 10), (8, 10), (16, 10)])]
+
+
+def sweep_ilqg(name, precision, H, shapes, steps, warmup, out):
+    from mujoco_mpc_amd.planners import GpuBatchILQGPlanner, GpuILQGPlanner, State
+    task = load_task(name)
+    m = task.model
+    rng = np.random.default_rng(1)
+    ctx = capi.Context(task.packed_model(differentiable=bool(int(m.get_number("agent_differentiable", 1)))), task.packed(), 0, precision)
+    for E, n in shapes:
+        raw, clocks, mocap = initial(task, name, E, rng)
+        states = []
+        for e in range(E):
+            st = State(m)
+            mp = None if mocap is None else mocap[e].reshape(-1, 7)
+            st.set(raw[e][:m.nq], raw[e][m.nq:], mocap_pos=None if mp is None else mp[:, :3], mocap_quat=None if mp is None else mp[:, 3:],
+                   time=float(clocks[e]))
+            states.append(st)
+        singles = [GpuILQGPlanner(precision=precision, backend_factory=lambda t: ctx) for _ in range(E)]
+        batch = GpuBatchILQGPlanner(E, precision=precision, backend_factory=lambda t: ctx)
+        for p in singles + [batch]:
+            p.initialize(m, task)
+            p.num_rollouts_gui_ = n
+            p.allocate()
+            p.reset(H)
+
+        def sequential():
+            for p, st in zip(singles, states):
+                p.set_state(st)
+                p.optimize_policy(H)
+
+        def batched():
+            batch.set_states(states)
+            batch.optimize_policy(H)
+
+        for _ in range(warmup):
+            sequential()
+            batched()
+        ts, tb, stages = [], [], {}
+        for _ in range(steps):   # alternating: both sides see the same clocks and the same neighbours on the machine
+            t0 = time.perf_counter(); sequential(); t1 = time.perf_counter(); batched(); t2 = time.perf_counter()
+            ts.append((t1 - t0) * 1e3)
+            tb.append((t2 - t1) * 1e3)
+            for k, v in batch.timers.items():
+                stages.setdefault(k, []).append(v * 1e-3)
+        rec = {"planner": "ilqg", "task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps,
+               "warmup": warmup, "kernel": ctx.kernel_name.split(" (")[0], "sequential_ms": stats(ts), "batched_ms": stats(tb),
+               "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)), "beyond_spread": bool(np.max(tb) < np.min(ts)),
+               "batched_stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
+               "sequential_stage_ms_per_env": {k: float(v) * 1e-3 for k, v in singles[0].timers.items()},
+               "sat_out": int(sum(batch.sat_out)) if hasattr(batch, "sat_out") else 0}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+        out.flush()
+    ctx.close()
+
+
 def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling"):
     task = load_task(name)
     m = task.model
@@ -215,20 +277,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient"], default="sampling")
+    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
+        a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
     keep = None if a.shapes is None else {tuple(int(x) for x in sh.split("x")) for sh in a.shapes.split(",")}
     if a.steps < 10:
         raise SystemExit("batch_sweep.py: at least 10 timed steps")
     with open(a.out, "w") as out:
-        for name, precision, H, shapes in (GRADIENT_SHAPES if a.planner == "gradient" else SHAPES):
+        for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
             if shapes and (a.only is None or a.only == name):
                 if a.planner == "gradient":
                     sweep_gradient(name, precision, H, shapes, a.steps, a.warmup, out)
+                elif a.planner == "ilqg":
+                    sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out)
                 else:
                     sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner)
 
