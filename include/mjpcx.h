@@ -497,6 +497,41 @@ int mjpcx_gradient_step_batched(mjpcx_ctx* ctx, int num_envs, int candidate, int
                                 int centered, int representation, int P, const double* node_times, double* nominal_return, double* k,
                                 double* gradient, double* dV, double* A, double* B, double* cx, double* cu);
 
+/* iLQG's derivative chain and backward pass for E environments (the middle of iLQGPlanner::Iteration, ilqg/planner.cc:377-520, with
+ * model_derivatives.cc:45-165, cost_derivatives.cc:112-230 and backward_pass.cc:65-356), chained on the device after a batched rollout of
+ * num_envs environments with horizon >= T -- in practice mjpcx_rollout_feedback_batched, the nominal phase. Environment e's nominal is
+ * local candidate candidate[e] of that rollout, read from the device Trajectory buffers; candidate[e] == -1: the environment takes no part.
+ * Enqueued on the context's stream, in order:
+ *   the gather of every environment's candidate (times, states, actions at the evaluated steps; residual and actions at all T steps);
+ *   ModelDerivatives::Compute (mjpcx_transition_fd: eps, centered) at the num_eval steps of `evaluate`, every environment's items with
+ *     that environment's record from mjpcx_set_states / mjpcx_set_residual_states, restaged by this call; the assembly; the
+ *     interpolation to all T steps with A, B, D of step T - 1 set to zero -- the stages of mjpcx_gradient_step_batched;
+ *   CostDerivatives::Compute in full (mjpcx_cost_derivatives: cx, cu, cxx, cxu, cuu) on the rollout's residual, E x T workgroups;
+ *   the backward pass (mjpcx_backward_pass: reg_type, use_limits, the model's control ranges) with its regularisation retries inside
+ *     the kernel, one workgroup per environment, from mu[e] and rate[e]:
+ *       retries = 0; while retries < max_iter and not ok: sweep at mu; if not ok and mu <= max_reg: rate = factor > 1 ?
+ *       max(rate factor, factor) : min(rate factor, factor), mu = min(max(mu rate, min_reg), max_reg), retries += 1; elif not ok: break
+ *     (ilqg/planner.cc:429-520 with ScaleRegularization, backward_pass.cc:327-340).
+ * Then ONE device-to-host block and ONE sync. Outputs: K (E x T x m x n), du (E x T x m), dV (E x 2) of the last sweep; status (E: 1 ok,
+ * 0 failed every retry, -1 took no part); mu_out, rate_out (E: the regularisation after the retries), retries (E: the number of
+ * scalings); nominal_return (E, may be NULL); optional (NULL: they never visit the host) A, B, cx, cu, cxx, cxu, cuu, Vx, Vxx, shaped as
+ * the plain calls' with a leading E; n = 2 nv, m = nu. With status 0, K, du, Vx and Vxx hold the steps the sweeps reached (zero where
+ * none did) and mean nothing. An environment that takes no part is computed on a copy of the first active environment's nominal and
+ * ignored -- the finite-difference launch keeps its shape -- and every output of it is zero, its status -1; with no active environment
+ * nothing is launched. With every step evaluated the results equal, bit for bit, those of mjpcx_transition_fd ->
+ * mjpcx_cost_derivatives -> the retry loop over mjpcx_backward_pass fed with mjpcx_fetch_trajectory of the same candidates; the
+ * interpolation is two products and a sum, not contracted. Deterministic. Both precisions of the lane family (fp32: the finite
+ * differences in fp32, the rest in fp64, as the plain calls).
+ * MJPCX_EINVAL: the last rollout was not a batched one of num_envs environments, a candidate outside [-1, n_per_env), T < 2 or beyond
+ * the rollout's horizon, a bad evaluate list, eps <= 0, reg_type outside 0..2, max_iter outside [1, 64], a non-finite or non-positive
+ * mu, rate or factor, min_reg / max_reg non-finite or min_reg > max_reg. MJPCX_EUNSUPPORTED: beyond n <= 48, m <= 16, T <= 512, 32 cost
+ * terms of 32 residuals; a context sharded with mjpcx_comm_init (world > 1); fp32 contexts of the wavefront-per-candidate family. */
+int mjpcx_ilqg_step_batched(mjpcx_ctx* ctx, int num_envs, const int32_t* candidate, int T, int num_eval, const int32_t* evaluate, double eps,
+                            int centered, int reg_type, int use_limits, const double* mu, const double* rate, double factor, double min_reg,
+                            double max_reg, int max_iter, double* K, double* du, double* dV, int32_t* status, double* mu_out, double* rate_out,
+                            int32_t* retries, double* nominal_return, double* A, double* B, double* cx, double* cu, double* cxx, double* cxu,
+                            double* cuu, double* Vx, double* Vxx);
+
 /* mjpcx_rollout_feedback for E environments in one launch: for every environment e exactly mjpcx_rollout_feedback(n_per_env, ...) with
  * row e of every array -- times E x Tn, states E x Tn x (nq+nv), actions E x Tn x nu, gains E x Tn x nu x ndx, improvement E x Tn x nu,
  * alpha E x n_per_env -- from the state, clock, mocap pose, userdata and frozen residual state mjpcx_set_states /

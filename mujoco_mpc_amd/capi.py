@@ -30,7 +30,7 @@ EXPORTS = [
     "mjpcx_elite_allreduce", "mjpcx_comm_barrier", "mjpcx_comm_destroy",
     "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
     "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched", "mjpcx_gradient_step_batched",
-    "mjpcx_rollout_feedback_batched",
+    "mjpcx_rollout_feedback_batched", "mjpcx_ilqg_step_batched",
 ]
 
 _LIB = None
@@ -78,6 +78,8 @@ def lib():
         L.mjpcx_rollout_noise_batched_ce.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_ce_update_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_gradient_step_batched.argtypes = ([vp] + [C.c_int] * 4 + [c_i32p, C.c_double] + [C.c_int] * 3 + [c_f64p] * 9)
+        L.mjpcx_ilqg_step_batched.argtypes = ([vp, C.c_int, c_i32p, C.c_int, C.c_int, c_i32p, C.c_double] + [C.c_int] * 3 + [c_f64p] * 2 +
+                                              [C.c_double] * 3 + [C.c_int] + [c_f64p] * 3 + [c_i32p] + [c_f64p] * 2 + [c_i32p] + [c_f64p] * 10)
         L.mjpcx_sync.argtypes = [vp]
         L.mjpcx_get_returns.argtypes = [vp, c_f64p, c_i32p]
         L.mjpcx_get_return_at.argtypes = [vp, C.c_int, C.POINTER(C.c_double), c_i32p]
@@ -413,6 +415,34 @@ class Context:
         self._chk(lib().mjpcx_rollout_feedback_batched(self.handle, E, n, int(horizon), int(mode), int(representation), int(use_state),
                                                        Tn, *[as_f64p(a) for a in arrs]))
         self.N, self.H, self.P, self.n_per_env = E * n, int(horizon), 0, n
+
+    def ilqg_step_batched(self, candidate, T, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg, max_reg, max_iter,
+                          with_matrices=False, num_envs=None):
+        """iLQG's derivative chain and backward pass, regularisation retries included, for every environment of the last batched
+        rollout, on the device, one sync (mjpcx_ilqg_step_batched). candidate: E local indices, -1 = the environment takes no part.
+        Dict of K (E x T x nu x ndx), du (E x T x nu), dV (E x 2), status (E: 1 ok, 0 failed every retry, -1 took no part), mu, rate,
+        retries (E), nominal_return (E) and, with with_matrices (tests), A, B, cx, cu, cxx, cxu, cuu, Vx, Vxx."""
+        cand = np.ascontiguousarray(candidate, dtype=np.int32).reshape(-1)
+        E, T = (cand.size if num_envs is None else int(num_envs)), int(T)
+        ev = np.ascontiguousarray(evaluate, dtype=np.int32).reshape(-1)
+        mu_in, rate_in = _f(mu).reshape(-1), _f(rate).reshape(-1)
+        if E >= 1 and (cand.size, mu_in.size, rate_in.size) != (E, E, E):
+            raise ValueError(f"ilqg_step_batched: {cand.size} candidates, {mu_in.size} mu, {rate_in.size} rate for {E} environments")
+        n, m, Ea, Ta = 2 * self.nv, self.nu, max(E, 1), max(T, 1)
+        out = dict(K=np.zeros((Ea, Ta, m, n)), du=np.zeros((Ea, Ta, m)), dV=np.zeros((Ea, 2)), status=np.zeros(Ea, np.int32), mu=np.zeros(Ea),
+                   rate=np.zeros(Ea), retries=np.zeros(Ea, np.int32), nominal_return=np.zeros(Ea))
+        names = ("A", "B", "cx", "cu", "cxx", "cxu", "cuu", "Vx", "Vxx")
+        if with_matrices:
+            shapes = ((n, n), (n, m), (n,), (m,), (n, n), (n, m), (m, m), (n,), (n, n))
+            out.update({k: np.zeros((Ea, Ta) + sh) for k, sh in zip(names, shapes)})
+        opt = [as_f64p(out[k]) if with_matrices else None for k in names]
+        self._chk(lib().mjpcx_ilqg_step_batched(self.handle, E, as_i32p(cand) if cand.size else as_i32p(np.zeros(1, np.int32)), T, ev.size,
+                                                as_i32p(ev) if ev.size else as_i32p(np.zeros(1, np.int32)), float(eps), int(centered),
+                                                int(reg_type), int(use_limits), as_f64p(mu_in), as_f64p(rate_in), float(factor), float(min_reg),
+                                                float(max_reg), int(max_iter), as_f64p(out["K"]), as_f64p(out["du"]), as_f64p(out["dV"]),
+                                                as_i32p(out["status"]), as_f64p(out["mu"]), as_f64p(out["rate"]), as_i32p(out["retries"]),
+                                                as_f64p(out["nominal_return"]), *opt))
+        return out
 
     def transition_fd(self, times, states, actions, eps=1e-6, centered=0):
         T, ndx, nu, nr = len(times), 2 * self.nv, self.nu, self.num_residual

@@ -1,0 +1,59 @@
+// ilqg_batched.h -- the glue kernel of mjpcx_ilqg_step_batched: iLQG's derivative chain and backward pass for E environments, every
+// stage on the device ("iLQG's derivative chain and backward pass for the fleet"):
+//   gather_candidates_kernel   local candidate cands[e] of environment e of the last batched rollout -- iLQG's nominal is the best of
+//                              each environment's own nominal rollouts -- out of the Trajectory buffers in whichever layout the rollout
+//                              kernel left them, into the environment-major arrays the stages below read; the actions of ALL T steps
+//                              (the box-QP of the backward pass needs them), not only those of the evaluated ones
+//   transition_fd_kernel<ENVS> / transition_fd_wave_kernel, fd_assemble_kernel, fd_interpolate_kernel as in gradient_batched.h
+//   cost_derivatives_kernel (ilqg_dense.h) on E x T workgroups: workgroup e * T + t forms step t of environment e
+//   backward_pass_batched_kernel (ilqg_dense.h) on E workgroups
+#pragma once
+#include "device_common.h"
+
+namespace mjpcx {
+
+template <typename T>
+struct GatherCandidatesArgs {
+  const T *states, *actions, *times, *residual;  // the rollout's Trajectory buffers
+  const double* total_return;                    // [N]
+  int N, H, n_per_env, candidate_major;          // environment e reads global candidate source[e] * n_per_env + cands[e]
+  const int* source;                             // [E] e itself; for an environment that takes no part, the first active one
+  const int* cands;                              // [E] local candidates of the source, every one within [0, n_per_env)
+  const int* active;                             // [E]: 0 = the environment takes no part (its nominal_return is 0)
+  int E, Tn, ne;                                 // environments, steps, evaluated steps
+  const int* evaluate;                           // [ne]
+  int ds_roll, ds, nu, nr;                       // state row of the rollout (nq + nv + na), its leading nq + nv, controls, residuals
+  T *fd_times, *fd_states, *fd_actions;          // [E][ne], [E][ne][ds], [E][ne][nu]: the finite-difference kernels' inputs
+  double *residual_out, *actions_out, *nominal_return;  // [E][Tn][nr], [E][Tn][nu], [E]
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void gather_candidates_kernel(const GatherCandidatesArgs<T> g) {
+  const int per_fd = 1 + g.ds + g.nu, per_t = g.nr + g.nu;
+  const size_t per_env = (size_t)g.ne * per_fd + (size_t)g.Tn * per_t + 1, total = per_env * g.E;
+  for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const int e = (int)(idx / per_env);
+    size_t r = idx - (size_t)e * per_env;
+    const size_t c = (size_t)g.source[e] * g.n_per_env + g.cands[e];
+    // [(cand * H + t) * width + k] (wavefront-per-candidate kernels) or [(t * width + k) * N + cand] (lane kernels): gather_traj_kernel
+    auto load = [&](const T* src, int width, int t, int k) {
+      return g.candidate_major ? src[(c * g.H + t) * width + k] : src[((size_t)t * width + k) * g.N + c];
+    };
+    if (r < (size_t)g.ne * per_fd) {
+      const int i = (int)(r / per_fd), j = (int)(r % per_fd), t = g.evaluate[i];
+      const size_t row = (size_t)e * g.ne + i;
+      if (j == 0) g.fd_times[row] = load(g.times, 1, t, 0);
+      else if (j <= g.ds) g.fd_states[row * g.ds + (j - 1)] = load(g.states, g.ds_roll, t, j - 1);
+      else g.fd_actions[row * g.nu + (j - 1 - g.ds)] = load(g.actions, g.nu, t, j - 1 - g.ds);
+    } else if ((r -= (size_t)g.ne * per_fd) < (size_t)g.Tn * per_t) {
+      const int t = (int)(r / per_t), j = (int)(r % per_t);
+      const size_t row = (size_t)e * g.Tn + t;
+      if (j < g.nr) g.residual_out[row * g.nr + j] = (double)load(g.residual, g.nr, t, j);
+      else g.actions_out[row * g.nu + (j - g.nr)] = (double)load(g.actions, g.nu, t, j - g.nr);
+    } else {
+      g.nominal_return[e] = g.active[e] ? g.total_return[c] : 0.0;
+    }
+  }
+}
+
+}  // namespace mjpcx

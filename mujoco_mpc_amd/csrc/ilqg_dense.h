@@ -718,10 +718,13 @@ __device__ __forceinline__ void flat_store(double* l, const double (&v)[K], int 
 // All LDS matrices are DENSE (leading dimension = their column count), which makes every staging copy flat:
 //   W[n*n] Wx[n] At[n*n] Bt[n*m] tmp[n*n] tmp2[m*n] Qxx[n*n] Qxu[n*m] Quu[m*m] Quur[m*m] Qx[n] Qu[m]
 //   Kt[m*n] KQ[m*n] dut[m] qsum[m] L[16*16] cxl[n] cul[m] actl[m] lim[2m]      (carved with NP = 16*ceil(n/16), 16)
+// backward_sweep is ONE sweep over the horizon at a.mu, called by every thread of the workgroup with the dynamic LDS block: the body of
+// backward_pass_kernel and, per regularisation retry, of backward_pass_batched_kernel. Everything a sweep starts from (dV, ok, the
+// box-QP warm start, the terminal V, the W / Qxx roles) is set up here, so a sweep does not see the one before it. The result is in
+// *a.status (global, written by thread 0).
 template <int M>
-__global__ __launch_bounds__(kBackwardThreads) void backward_pass_kernel(const BackwardArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int n = a.n, m = a.m, T = a.T, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__device__ __forceinline__ void backward_sweep(const BackwardArgs& a, unsigned char* smem_raw, const int tid) {
+  const int n = a.n, m = a.m, T = a.T, lane = tid & 63, wave = tid >> 6;
   constexpr int NW = kBackwardWaves, NT = kBackwardThreads;
   const int NP = (n + 15) & ~15, MP = 16;
   const int nn = n * n, nm = n * m, mm = m * m;
@@ -922,6 +925,79 @@ __global__ __launch_bounds__(kBackwardThreads) void backward_pass_kernel(const B
     for (int i = tid; i < m; i += NT) a.du[(size_t)(T - 1) * m + i] = a.du[(size_t)(T - 2) * m + i];
   }
   if (tid == 0) { a.dV[0] = dV0; a.dV[1] = dV1; *a.status = ok_s; }
+#undef MJPCX_STAMP
+}
+
+template <int M>
+__global__ __launch_bounds__(kBackwardThreads) void backward_pass_kernel(const BackwardArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  backward_sweep<M>(a, smem_raw, threadIdx.x);
+}
+
+// iLQG's backward pass with its regularisation retries (ilqg/planner.cc:429-520) for E trajectories in one launch: workgroup e walks
+// row e of the environment-major arrays of `base` (A, B, c* at [E][T]..., actions [E][T][m], outputs likewise, dV [E][2]; the limits are
+// shared) with backward_sweep, the body of backward_pass_kernel, so a sweep's results are that kernel's. Between sweeps thread 0
+// applies ScaleRegularization (backward_pass.cc:327-340) in plain fp64 and the workgroup takes the new mu from LDS:
+//   while retries < max_iter and not ok: sweep at mu; if not ok and mu <= max_reg: scale, retries += 1; elif not ok: break
+// An environment with active[e] == 0 writes status -1 and nothing else. max_iter is bounded by the host (1..64).
+struct BackwardBatchedArgs {
+  BackwardArgs base;              // n, m, T, reg_type, use_limits, limits; the array pointers of environment 0; mu, status, stamps unused
+  const int* active;              // [E]
+  const double *mu, *rate;        // [E]
+  double factor, min_reg, max_reg;
+  int max_iter;
+  int *status, *retries;          // [E]: 1 ok, 0 failed every retry, -1 inactive; the number of scalings
+  double *mu_out, *rate_out;      // [E]
+};
+
+template <int M>
+__global__ __launch_bounds__(kBackwardThreads) void backward_pass_batched_kernel(const BackwardBatchedArgs b) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ double reg_s[2];
+  __shared__ int ok_b;
+  const size_t e = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (!b.active[e]) {  // (uniform over the workgroup)
+    if (tid == 0) b.status[e] = -1;
+    return;
+  }
+  BackwardArgs a = b.base;
+  const size_t n = a.n, m = a.m, T = a.T;
+  a.A += e * T * n * n; a.B += e * T * n * m; a.cx += e * T * n; a.cu += e * T * m; a.cxx += e * T * n * n; a.cxu += e * T * n * m;
+  a.cuu += e * T * m * m; a.actions += e * T * m;
+  a.Vx += e * T * n; a.Vxx += e * T * n * n; a.K += e * T * m * n; a.du += e * T * m; a.dV += e * 2;
+  a.status = b.status + e;
+  a.stamps = nullptr;
+  double mu = b.mu[e], rate = b.rate[e];  // (the same in every thread)
+  int ok = 0, retries = 0;
+  while (retries < b.max_iter && !ok) {
+    a.mu = mu;
+    // the sweep gets the thread index as a value the compiler cannot see through, anew for every sweep: otherwise everything derived
+    // from it is hoisted out of this loop and stays live across the whole sweep, which already fills the register file (77 spilled
+    // registers at M = 12 where backward_pass_kernel has none)
+    int stid = tid;
+    asm volatile("" : "+v"(stid));
+    __builtin_assume(stid >= 0 && stid < kBackwardThreads);
+    backward_sweep<M>(a, smem_raw, stid);
+    // thread 0 reads the sweep's status back, applies ScaleRegularization and hands the decision to the workgroup through LDS; the
+    // barrier also keeps the next sweep's set-up behind every thread's last access of this one
+    if (tid == 0) {
+      const int done = *a.status;
+      double r = rate, u = mu;
+      if (!done && mu <= b.max_reg) {
+        const double f = b.factor;
+        r = f > 1 ? fmax(rate * f, f) : fmin(rate * f, f);
+        u = fmin(fmax(mu * r, b.min_reg), b.max_reg);
+      }
+      reg_s[0] = u; reg_s[1] = r; ok_b = done;
+    }
+    __syncthreads();
+    ok = __builtin_amdgcn_readfirstlane(ok_b);
+    if (ok || !(mu <= b.max_reg)) break;
+    mu = bcast_lane(reg_s[0], 0); rate = bcast_lane(reg_s[1], 0);
+    retries++;  // (reg_s and ok_b are rewritten only after the next sweep, whose own barriers lie in between)
+  }
+  if (tid == 0) { b.status[e] = ok; b.mu_out[e] = mu; b.rate_out[e] = rate; b.retries[e] = retries; }
 }
 
 }  // namespace mjpcx

@@ -20,6 +20,7 @@
 #include "ilqg_dense.h"
 #include "gradient_pass.h"
 #include "gradient_batched.h"
+#include "ilqg_batched.h"
 #include "rollout_wave.h"
 #include "quad_launch.h"
 #include "limb_launch.h"
@@ -497,7 +498,7 @@ struct mjpcx_ctx {
   void* best_host = nullptr; void* best_dev = nullptr; size_t best_cap = 0;
   // rollout buffers
   DevBuf d_nodes, d_in_nodes, d_ilqg, d_ilqg_out, d_wblob;
-  DevBuf d_grad;                                  // workspace of mjpcx_gradient_step_batched: inputs, every intermediate, the result block
+  DevBuf d_grad;                                  // workspace of mjpcx_gradient_step_batched / mjpcx_ilqg_step_batched: inputs, every intermediate, the result block
   void* grad_host = nullptr; size_t grad_cap = 0; // its pinned [inputs | result block]
   // pinned staging block of mjpcx_rollout_feedback_batched (the six policy arrays of every environment, one H2D copy; the call does not
   // sync, so the block is rewritten only after the copy that read it has passed fb_done)
@@ -2233,6 +2234,11 @@ int make_cost_spec(mjpcx_ctx* c, CostSpec* out) {
   }
   return MJPCX_OK;
 }
+// dynamic LDS of backward_pass_kernel / backward_pass_batched_kernel: the carve of backward_sweep (ilqg_dense.h), with slack
+size_t backward_pass_lds_bytes(int n) {
+  const int NP = (n + 15) & ~15;
+  return (size_t)(5 * NP * NP + 3 * NP + 6 * NP * 16 + 5 * 256 + 16 * 23 + 16 * 13) * 8;
+}
 }  // namespace
 
 extern "C" {
@@ -2339,8 +2345,7 @@ int mjpcx_backward_pass(mjpcx_ctx* c, int n, int m, int T, double mu, int reg_ty
   a.Vx = o; a.Vxx = a.Vx + sT * sn; a.K = a.Vxx + sT * sn * sn; a.du = a.K + sT * sm * sn; a.dV = a.du + sT * sm;
   a.status = (int*)(a.dV + 2);
   a.stamps = c->stamp_step >= 0 ? (long long*)(a.dV + 4) : nullptr;
-  const int NP = (n + 15) & ~15;
-  const size_t lds = (size_t)(5 * NP * NP + 3 * NP + 6 * NP * 16 + 5 * 256 + 16 * 23 + 16 * 13) * 8;  // (the carve of backward_pass_kernel, with slack)
+  const size_t lds = backward_pass_lds_bytes(n);
   hipEvent_t e0, e1;
   HIPCHK(c, hipEventCreate(&e0));
   HIPCHK(c, hipEventCreate(&e1));
@@ -2428,6 +2433,52 @@ int mjpcx_gradient_pass(mjpcx_ctx* c, int n, int m, int T, const double* A, cons
 }  // extern "C"
 
 namespace {
+// ModelDerivatives::Compute for E environments, enqueued on the context's stream (the shared front of mjpcx_gradient_step_batched and
+// mjpcx_ilqg_step_batched): the finite differences at the ne evaluated steps of every environment with that environment's record of the
+// staged blob, their assembly into A, B, C, D at those steps, and the interpolation to all Tn steps with A, B, D of the last one zeroed
+template <typename T>
+struct FdChain {
+  const T *fd_times, *fd_states, *fd_actions;  // [E][ne]...: the gathered nominal at the evaluated steps
+  const int* evaluate;                         // [ne]
+  const T* range; const int* limited;          // ctrlrange [2 nu], ctrllimited [nu]
+  T *next, *sens; double* tan;                 // finite-difference workspaces
+  double *Ae, *Be, *Ce, *De, *A, *B, *C, *D;   // at the evaluated steps / at all Tn steps
+};
+template <typename T>
+int enqueue_fd_chain(mjpcx_ctx* c, int E, int ne, int Tn, double eps, int centered, const void* d_blob, unsigned stride, const FdChain<T>& f) {
+  const size_t ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, nc = 1 + 2 * (ndx + nu), sE = E, sT = Tn, sne = ne, rows = sE * sne;
+  const T* fd_next = f.next;
+  if (c->wave) {
+    if constexpr (sizeof(T) == 8) {
+      WaveTask wt = c->wh.t;
+      wt.blob = (const double*)d_blob;
+      wt.stamps = nullptr;
+      wt.stamp_step = 0;
+      w64::FdWaveArgs fa{f.fd_times, f.fd_states, f.fd_actions, (int)rows, (int)nc, eps, f.next, f.sens, ne, stride};
+      const bool tree = c->wh.tree_ok && !c->no_tree;
+      HIPCHK(c, launch_transition_fd_wave(c->wh.m, wt, fa, (unsigned)(rows * nc), wave_lds_bytes(c, 1, tree), tree, c->wh.m.integrator == MJPCX_INT_RK4, c->stream));
+      HIPCHK(c, launch_fd_tangent(c->wh.m, (const double*)f.next, f.tan, (int)rows, (int)nc, c->stream));
+      fd_next = (const T*)f.tan;
+    }
+  } else {
+    FdArgs<T> fa{f.fd_times, f.fd_states, f.fd_actions, ne, (T)eps, f.next, f.sens};
+    fa.num_envs = E; fa.env_items = (int)((sne * nc + 63) / 64 * 64); fa.env_stride = stride; fa.init = (const LaneInit<T>*)d_blob;
+    hipError_t le;
+    if constexpr (sizeof(T) == 8) le = c->kernel->fd64(c->hm64, c->ht64, fa, c->stream);
+    else { convert_task(c->ht32, c->ht64); le = c->kernel->fd32(c->hm32, c->ht32, fa, c->stream); }
+    if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("fd kernel launch: ") + hipGetErrorString(le));
+  }
+  const size_t a_items = rows * (ndx + nr) * (ndx + nu);
+  hipLaunchKernelGGL((fd_assemble_kernel<T>), dim3((unsigned)std::min<size_t>((a_items + 255) / 256, 1024)), dim3(256), 0, c->stream, fd_next,
+                     (const T*)f.sens, f.fd_actions, f.range, f.limited, (int)rows, (int)ndx, (int)nu, (int)nr, (T)eps, centered, f.Ae, f.Be, f.Ce, f.De);
+  HIPCHK(c, hipGetLastError());
+  const size_t sA = ndx * ndx, sB = ndx * nu, sC = nr * ndx, sD = nr * nu, i_items = sE * sT * (sA + sB + sC + sD);
+  hipLaunchKernelGGL(fd_interpolate_kernel, dim3((unsigned)std::min<size_t>((i_items + 255) / 256, 4096)), dim3(256), 0, c->stream, f.Ae, f.Be, f.Ce, f.De,
+                     f.evaluate, E, ne, Tn, (int)sA, (int)sB, (int)sC, (int)sD, f.A, f.B, f.C, f.D);
+  HIPCHK(c, hipGetLastError());
+  return MJPCX_OK;
+}
+
 // mjpcx_gradient_step_batched after validation: stage, launch the chain, one sync, unpack
 template <typename T>
 int do_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int Tn, int ne, const int32_t* evaluate, double eps, int centered, int representation,
@@ -2487,39 +2538,12 @@ int do_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int Tn, int ne, cons
   const size_t g_items = sE * (sne * (1 + ds + nu) + sT * (1 + nr) + 1);
   hipLaunchKernelGGL((gather_nominal_kernel<T>), dim3((unsigned)std::min<size_t>((g_items + 255) / 256, 2048)), dim3(256), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
-  // ---- ModelDerivatives::Compute at the evaluated steps of every environment
-  const T* fd_next = (const T*)(base + o_next);
-  if (c->wave) {
-    if constexpr (sizeof(T) == 8) {
-      WaveTask wt = c->wh.t;
-      wt.blob = (const double*)d_blob;
-      wt.stamps = nullptr;
-      wt.stamp_step = 0;
-      w64::FdWaveArgs f{g.fd_times, g.fd_states, g.fd_actions, (int)rows, (int)nc, eps, (double*)(base + o_next), (double*)(base + o_sens), ne, stride};
-      const bool tree = c->wh.tree_ok && !c->no_tree;
-      HIPCHK(c, launch_transition_fd_wave(c->wh.m, wt, f, (unsigned)(rows * nc), wave_lds_bytes(c, 1, tree), tree, c->wh.m.integrator == MJPCX_INT_RK4, c->stream));
-      HIPCHK(c, launch_fd_tangent(c->wh.m, (const double*)(base + o_next), (double*)(base + o_tan), (int)rows, (int)nc, c->stream));
-      fd_next = (const T*)(base + o_tan);
-    }
-  } else {
-    FdArgs<T> f{g.fd_times, g.fd_states, g.fd_actions, ne, (T)eps, (T*)(base + o_next), (T*)(base + o_sens)};
-    f.num_envs = E; f.env_items = (int)((sne * nc + 63) / 64 * 64); f.env_stride = stride; f.init = (const LaneInit<T>*)d_blob;
-    hipError_t le;
-    if constexpr (sizeof(T) == 8) le = c->kernel->fd64(c->hm64, c->ht64, f, c->stream);
-    else { convert_task(c->ht32, c->ht64); le = c->kernel->fd32(c->hm32, c->ht32, f, c->stream); }
-    if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("fd kernel launch: ") + hipGetErrorString(le));
-  }
-  double *dAe = (double*)(base + o_Ae), *dBe = (double*)(base + o_Be), *dCe = (double*)(base + o_Ce), *dDe = (double*)(base + o_De);
+  // ---- ModelDerivatives::Compute at the evaluated steps of every environment, interpolated to all Tn steps
   double *dA = (double*)(base + o_A), *dB = (double*)(base + o_B), *dC = (double*)(base + o_C), *dD = (double*)(base + o_D);
-  const size_t a_items = rows * (ndx + nr) * (ndx + nu);
-  hipLaunchKernelGGL((fd_assemble_kernel<T>), dim3((unsigned)std::min<size_t>((a_items + 255) / 256, 1024)), dim3(256), 0, c->stream, fd_next,
-                     (const T*)(base + o_sens), (const T*)g.fd_actions, (const T*)(base + o_range), (const int*)(base + o_lim), (int)rows, (int)ndx,
-                     (int)nu, (int)nr, (T)eps, centered, dAe, dBe, dCe, dDe);
-  HIPCHK(c, hipGetLastError());
-  const size_t i_items = sE * sT * (sA + sB + sC + sD);
-  hipLaunchKernelGGL(fd_interpolate_kernel, dim3((unsigned)std::min<size_t>((i_items + 255) / 256, 4096)), dim3(256), 0, c->stream, dAe, dBe, dCe, dDe,
-                     d_eval, E, ne, Tn, (int)sA, (int)sB, (int)sC, (int)sD, dA, dB, dC, dD);
-  HIPCHK(c, hipGetLastError());
+  const FdChain<T> fc{g.fd_times, g.fd_states, g.fd_actions, d_eval, (const T*)(base + o_range), (const int*)(base + o_lim), (T*)(base + o_next),
+                      (T*)(base + o_sens), (double*)(base + o_tan), (double*)(base + o_Ae), (double*)(base + o_Be), (double*)(base + o_Ce),
+                      (double*)(base + o_De), dA, dB, dC, dD};
+  if ((rc = enqueue_fd_chain<T>(c, E, ne, Tn, eps, centered, d_blob, stride, fc)) != MJPCX_OK) return rc;
   // ---- CostDerivatives::Compute (first order) and Gradient::Compute with the projection, per environment
   double *dcx = (double*)(base + o_cx), *dcu = (double*)(base + o_cu);
   hipLaunchKernelGGL(cost_gradient_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32) * 8, c->stream, cs, (const double*)g.residual_out,
@@ -2582,6 +2606,190 @@ int mjpcx_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int T, int ne, co
                                                                gradient, dV, A, B, cx, cu)
                             : do_gradient_step_batched<float>(c, E, cand, T, ne, evaluate, eps, centered, representation, P, node_times, nominal_return, k,
                                                               gradient, dV, A, B, cx, cu);
+}
+
+}  // extern "C"
+
+namespace {
+// mjpcx_ilqg_step_batched after validation: stage, launch the chain, one sync, unpack
+template <typename T>
+int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, int ne, const int32_t* evaluate, double eps, int centered, int reg_type,
+                         int use_limits, const double* mu, const double* rate, double factor, double min_reg, double max_reg, int max_iter, double* K,
+                         double* du, double* dV, int32_t* status, double* mu_out, double* rate_out, int32_t* retries, double* nominal_return,
+                         double* const (&opt)[9]) {
+  int rc;
+  CostSpec cs{};
+  if ((rc = make_cost_spec(c, &cs)) != MJPCX_OK) return rc;
+  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, nc = 1 + 2 * (ndx + nu);
+  const size_t sE = E, sT = Tn, sne = ne, rows = sE * sne;
+  if (sE * std::max(sne * nc, sT) * (ndx + nr) * (ndx + nu) > 0x7fffffffULL) return fail(c, MJPCX_EUNSUPPORTED, "mjpcx_ilqg_step_batched: too many environments x steps");
+  const size_t sA = ndx * ndx, sB = ndx * nu, sC = nr * ndx, sD = nr * nu;
+  // an environment that takes no part rides along on the first active one's nominal (its finite differences need SOME valid trajectory)
+  int first = -1;
+  for (int e = 0; e < E && first < 0; e++) if (candidate[e] >= 0) first = e;
+  auto unpack_inactive = [&](int e) {
+    std::memset(K + (size_t)e * sT * sB, 0, sT * sB * 8); std::memset(du + (size_t)e * sT * nu, 0, sT * nu * 8); std::memset(dV + (size_t)e * 2, 0, 16);
+    status[e] = -1; mu_out[e] = 0; rate_out[e] = 0; retries[e] = 0;
+    if (nominal_return) nominal_return[e] = 0;
+    const size_t per[9] = {sT * sA, sT * sB, sT * ndx, sT * nu, sT * sA, sT * sB, sT * nu * nu, sT * ndx, sT * sA};
+    for (int k = 0; k < 9; k++) if (opt[k]) std::memset(opt[k] + (size_t)e * per[k], 0, per[k] * 8);
+  };
+  if (first < 0) {  // nobody takes part: nothing to launch
+    for (int e = 0; e < E; e++) unpack_inactive(e);
+    return MJPCX_OK;
+  }
+  // the environments' plan records, restaged: the preceding rollout's slot may have been recycled since
+  const T *d_rec_times, *d_rec_nominal;
+  const double* d_rec_var;
+  const void* d_blob = nullptr;
+  mjpcx_ctx::Slot* slot = nullptr;
+  unsigned stride = 0;
+  if ((rc = stage_plan_inputs<T>(c, 0, E, nullptr, nullptr, nullptr, false, &d_rec_times, &d_rec_nominal, &d_rec_var, &slot, &d_blob, &stride)) != MJPCX_OK)
+    return rc;
+  // ---- workspace carve: [evaluate | ctrllimited | ctrlrange | candidates | sources | active | mu | rate | limits] (one upload), the stages' arrays,
+  // [nominal_return | K | du | dV | mu_out | rate_out | status | retries] (one download)
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+  const size_t o_eval = carve(sne * 4), o_lim = carve(nu * 4), o_range = carve(2 * nu * sizeof(T)), o_cand = carve(sE * 4), o_src = carve(sE * 4), o_act = carve(sE * 4);
+  const size_t o_mu = carve(sE * 8), o_rate = carve(sE * 8), o_limits = carve(2 * nu * 8), in_bytes = off;
+  const size_t o_ft = carve(rows * sizeof(T)), o_fs = carve(rows * ds * sizeof(T)), o_fa = carve(rows * nu * sizeof(T));
+  const size_t o_res = carve(sE * sT * nr * 8), o_actions = carve(sE * sT * nu * 8);
+  const size_t o_next = carve(rows * nc * (c->wave ? ds : ndx) * sizeof(T)), o_tan = carve(c->wave ? rows * nc * ndx * 8 : 0), o_sens = carve(rows * nc * nr * sizeof(T));
+  const size_t o_Ae = carve(rows * sA * 8), o_Be = carve(rows * sB * 8), o_Ce = carve(rows * sC * 8), o_De = carve(rows * sD * 8);
+  const size_t o_A = carve(sE * sT * sA * 8), o_B = carve(sE * sT * sB * 8), o_C = carve(sE * sT * sC * 8), o_D = carve(sE * sT * sD * 8);
+  const size_t o_cx = carve(sE * sT * ndx * 8), o_cu = carve(sE * sT * nu * 8), o_cxx = carve(sE * sT * sA * 8), o_cxu = carve(sE * sT * sB * 8);
+  const size_t o_cuu = carve(sE * sT * nu * nu * 8), o_Vx = carve(sE * sT * ndx * 8), o_Vxx = carve(sE * sT * sA * 8);
+  const size_t o_out = off, o_ret = carve(sE * 8), o_K = carve(sE * sT * sB * 8), o_du = carve(sE * sT * nu * 8), o_dV = carve(sE * 2 * 8);
+  const size_t o_muo = carve(sE * 8), o_rateo = carve(sE * 8), o_status = carve(sE * 4), o_retries = carve(sE * 4), out_bytes = off - o_out;
+  HIPCHK(c, c->d_grad.reserve(off));
+  if (in_bytes + out_bytes > c->grad_cap) {
+    if (c->grad_host) (void)hipHostFree(c->grad_host);
+    c->grad_host = nullptr; c->grad_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->grad_host, in_bytes + out_bytes, hipHostMallocDefault));
+    c->grad_cap = in_bytes + out_bytes;
+  }
+  char* base = (char*)c->d_grad.p;
+  char* hin = (char*)c->grad_host;
+  char* hout = hin + in_bytes;
+  std::memcpy(hin + o_eval, evaluate, sne * 4);
+  std::memcpy(hin + o_lim, c->ctrllimited.data(), nu * 4);
+  for (size_t i = 0; i < 2 * nu; i++) { ((T*)(hin + o_range))[i] = (T)c->ctrlrange[i]; ((double*)(hin + o_limits))[i] = c->ctrlrange[i]; }
+  for (int e = 0; e < E; e++) {
+    const bool on = candidate[e] >= 0;
+    ((int*)(hin + o_cand))[e] = on ? candidate[e] : candidate[first];
+    ((int*)(hin + o_src))[e] = on ? e : first;
+    ((int*)(hin + o_act))[e] = on ? 1 : 0;
+    ((double*)(hin + o_mu))[e] = mu[e]; ((double*)(hin + o_rate))[e] = rate[e];
+  }
+  HIPCHK(c, hipMemcpyAsync(base, hin, in_bytes, hipMemcpyHostToDevice, c->stream));
+  // (Vx .. retries are contiguous: what a failed sweep or an environment that takes no part does not write reads as zero)
+  HIPCHK(c, hipMemsetAsync(base + o_Vx, 0, off - o_Vx, c->stream));
+  const int* d_eval = (const int*)(base + o_eval);
+  const int* d_active = (const int*)(base + o_act);
+  // ---- gather the nominal candidates; an inactive environment's rows are a copy of the first active one's
+  GatherCandidatesArgs<T> g{};
+  g.states = (const T*)c->d_states.p; g.actions = (const T*)c->d_actions.p; g.times = (const T*)c->d_times.p; g.residual = (const T*)c->d_residual.p;
+  g.total_return = (const double*)c->d_ret.p;
+  g.N = c->N; g.H = c->H; g.n_per_env = c->env_n; g.candidate_major = c->traj_candidate_major ? 1 : 0;
+  g.cands = (const int*)(base + o_cand); g.source = (const int*)(base + o_src); g.active = d_active;
+  g.E = E; g.Tn = Tn; g.ne = ne; g.evaluate = d_eval;
+  g.ds_roll = c->nq + c->nv + c->na; g.ds = (int)ds; g.nu = (int)nu; g.nr = (int)nr;
+  g.fd_times = (T*)(base + o_ft); g.fd_states = (T*)(base + o_fs); g.fd_actions = (T*)(base + o_fa);
+  g.residual_out = (double*)(base + o_res); g.actions_out = (double*)(base + o_actions); g.nominal_return = (double*)(base + o_ret);
+  const size_t g_items = sE * (sne * (1 + ds + nu) + sT * (nr + nu) + 1);
+  hipLaunchKernelGGL((gather_candidates_kernel<T>), dim3((unsigned)std::min<size_t>((g_items + 255) / 256, 2048)), dim3(256), 0, c->stream, g);
+  HIPCHK(c, hipGetLastError());
+  // ---- ModelDerivatives::Compute at the evaluated steps of every environment, interpolated to all Tn steps
+  double *dA = (double*)(base + o_A), *dB = (double*)(base + o_B), *dC = (double*)(base + o_C), *dD = (double*)(base + o_D);
+  const FdChain<T> fc{g.fd_times, g.fd_states, g.fd_actions, d_eval, (const T*)(base + o_range), (const int*)(base + o_lim), (T*)(base + o_next),
+                      (T*)(base + o_sens), (double*)(base + o_tan), (double*)(base + o_Ae), (double*)(base + o_Be), (double*)(base + o_Ce),
+                      (double*)(base + o_De), dA, dB, dC, dD};
+  if ((rc = enqueue_fd_chain<T>(c, E, ne, Tn, eps, centered, d_blob, stride, fc)) != MJPCX_OK) return rc;
+  // ---- CostDerivatives::Compute: workgroup e * Tn + t forms step t of environment e (every array is environment-major)
+  double *dcx = (double*)(base + o_cx), *dcu = (double*)(base + o_cu), *dcxx = (double*)(base + o_cxx), *dcxu = (double*)(base + o_cxu), *dcuu = (double*)(base + o_cuu);
+  hipLaunchKernelGGL(cost_derivatives_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32 + 32 * ndx + 32 * nu) * 8, c->stream, cs,
+                     (const double*)g.residual_out, (const double*)dC, (const double*)dD, Tn, (int)ndx, (int)nu, dcx, dcu, dcxx, dcxu, dcuu);
+  HIPCHK(c, hipGetLastError());
+  // ---- the backward pass with its regularisation retries, one workgroup per environment
+  BackwardBatchedArgs b{};
+  b.base.n = (int)ndx; b.base.m = (int)nu; b.base.T = Tn; b.base.reg_type = reg_type; b.base.use_limits = use_limits;
+  b.base.A = dA; b.base.B = dB; b.base.cx = dcx; b.base.cu = dcu; b.base.cxx = dcxx; b.base.cxu = dcxu; b.base.cuu = dcuu;
+  b.base.actions = g.actions_out; b.base.limits = (const double*)(base + o_limits);
+  b.base.Vx = (double*)(base + o_Vx); b.base.Vxx = (double*)(base + o_Vxx); b.base.K = (double*)(base + o_K); b.base.du = (double*)(base + o_du);
+  b.base.dV = (double*)(base + o_dV);
+  b.active = d_active; b.mu = (const double*)(base + o_mu); b.rate = (const double*)(base + o_rate);
+  b.factor = factor; b.min_reg = min_reg; b.max_reg = max_reg; b.max_iter = max_iter;
+  b.status = (int*)(base + o_status); b.retries = (int*)(base + o_retries); b.mu_out = (double*)(base + o_muo); b.rate_out = (double*)(base + o_rateo);
+  const size_t lds = backward_pass_lds_bytes((int)ndx);
+  if (nu <= 12) {  // as mjpcx_backward_pass: the m x m factorisation is unrolled to 12 or 16 columns
+    HIPCHK(c, hipFuncSetAttribute((const void*)backward_pass_batched_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(backward_pass_batched_kernel<12>, dim3(E), dim3(kBackwardThreads), lds, c->stream, b);
+  } else {
+    HIPCHK(c, hipFuncSetAttribute((const void*)backward_pass_batched_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(backward_pass_batched_kernel<16>, dim3(E), dim3(kBackwardThreads), lds, c->stream, b);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(slot->done, c->stream));
+  slot->pending = true;
+  // ---- results: one block into pinned memory; the optional matrices straight to the caller; ONE sync
+  HIPCHK(c, hipMemcpyAsync(hout, base + o_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  const std::pair<size_t, size_t> where[9] = {{o_A, sT * sA}, {o_B, sT * sB}, {o_cx, sT * ndx}, {o_cu, sT * nu}, {o_cxx, sT * sA}, {o_cxu, sT * sB},
+                                              {o_cuu, sT * nu * nu}, {o_Vx, sT * ndx}, {o_Vxx, sT * sA}};
+  for (int k = 0; k < 9; k++)
+    if (opt[k]) HIPCHK(c, hipMemcpyAsync(opt[k], base + where[k].first, sE * where[k].second * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (nominal_return) std::memcpy(nominal_return, hout + (o_ret - o_out), sE * 8);
+  std::memcpy(K, hout + (o_K - o_out), sE * sT * sB * 8);
+  std::memcpy(du, hout + (o_du - o_out), sE * sT * nu * 8);
+  std::memcpy(dV, hout + (o_dV - o_out), sE * 2 * 8);
+  std::memcpy(mu_out, hout + (o_muo - o_out), sE * 8);
+  std::memcpy(rate_out, hout + (o_rateo - o_out), sE * 8);
+  std::memcpy(status, hout + (o_status - o_out), sE * 4);
+  std::memcpy(retries, hout + (o_retries - o_out), sE * 4);
+  for (int e = 0; e < E; e++) if (candidate[e] < 0) unpack_inactive(e);
+  return MJPCX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mjpcx_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int T, int ne, const int32_t* evaluate, double eps, int centered, int reg_type,
+                            int use_limits, const double* mu, const double* rate, double factor, double min_reg, double max_reg, int max_iter, double* K,
+                            double* du, double* dV, int32_t* status, double* mu_out, double* rate_out, int32_t* retries, double* nominal_return, double* A,
+                            double* B, double* cx, double* cu, double* cxx, double* cxu, double* cuu, double* Vx, double* Vxx) {
+  const char* who = "mjpcx_ilqg_step_batched: ";
+  if (!c || !candidate || !evaluate || !mu || !rate || !K || !du || !dV || !status || !mu_out || !rate_out || !retries)
+    return fail(c, MJPCX_EINVAL, std::string(who) + "null argument");
+  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N || c->env_E != E)
+    return fail(c, MJPCX_EINVAL, std::string(who) + "the last rollout was not a batched one of " + std::to_string(E) + " environments");
+  for (int e = 0; e < E; e++)
+    if (candidate[e] < -1 || candidate[e] >= c->env_n)
+      return fail(c, MJPCX_EINVAL, std::string(who) + "candidate outside [-1, n_per_env) (environment " + std::to_string(e) + ")");
+  if (T < 2 || T > c->H) return fail(c, MJPCX_EINVAL, std::string(who) + "T must be >= 2 and within the rollout's horizon");
+  if (ne < 1 || ne > T) return fail(c, MJPCX_EINVAL, std::string(who) + "num_eval outside [1, T]");
+  for (int i = 0; i < ne; i++)
+    if (evaluate[i] < 0 || evaluate[i] >= T || (i > 0 && evaluate[i] <= evaluate[i - 1]))
+      return fail(c, MJPCX_EINVAL, std::string(who) + "the evaluate list must be strictly increasing and within [0, T)");
+  if (!(eps > 0)) return fail(c, MJPCX_EINVAL, std::string(who) + "epsilon must be > 0");
+  if (reg_type < 0 || reg_type > 2) return fail(c, MJPCX_EINVAL, std::string(who) + "unknown regularization type");
+  if (max_iter < 1 || max_iter > 64) return fail(c, MJPCX_EINVAL, std::string(who) + "max_iter outside [1, 64]");
+  for (int e = 0; e < E; e++)
+    if (!std::isfinite(mu[e]) || !(mu[e] > 0) || !std::isfinite(rate[e]) || !(rate[e] > 0))
+      return fail(c, MJPCX_EINVAL, std::string(who) + "mu and rate must be finite and > 0 (environment " + std::to_string(e) + ")");
+  if (!std::isfinite(factor) || !(factor > 0)) return fail(c, MJPCX_EINVAL, std::string(who) + "factor must be finite and > 0");
+  if (!std::isfinite(min_reg) || !std::isfinite(max_reg) || !(min_reg <= max_reg))
+    return fail(c, MJPCX_EINVAL, std::string(who) + "min_reg and max_reg must be finite, min_reg <= max_reg");
+  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "not implemented on a context sharded with mjpcx_comm_init");
+  if (c->wave && c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+  if (2 * c->nv > kGradMaxN || c->nu > kGradMaxM || T > kGradMaxT)
+    return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "covers n <= 48, m <= 16, T <= 512 (kMaxTrajectoryHorizon)");
+  HIPCHK(c, hipSetDevice(c->device));
+  double* const opt[9] = {A, B, cx, cu, cxx, cxu, cuu, Vx, Vxx};
+  return c->precision == 64 ? do_ilqg_step_batched<double>(c, E, candidate, T, ne, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg,
+                                                           max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt)
+                            : do_ilqg_step_batched<float>(c, E, candidate, T, ne, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg,
+                                                          max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt);
 }
 
 }  // extern "C"

@@ -1022,6 +1022,7 @@ class GpuILQGPlanner:
         self.action_step = self.feedback_scaling = self.improvement = self.expected = self.surprise = 0.0
         self.derivative_skip_ = int(self.model.get_number("derivative_skip", 0))
         self.winner = 0
+        self.nominal_index = -1
         # the last iteration's trajectory[winner] / trajectory[0] returns, and whether it reached the policy update
         self.winner_return = self.linesearch0_return = 0.0
         self.iteration_completed = False
@@ -1097,6 +1098,7 @@ class GpuILQGPlanner:
     def _nominal_select(self, horizon, ret, fail):
         steps = self._linesearch_steps()
         best = self.best_rollout(ret, fail)
+        self.nominal_index = best                           # this planner's winning nominal rollout; -1: every one failed
         if best == -1:
             import copy
             self.candidate0.trajectory = copy.deepcopy(self.policy.trajectory)
@@ -1223,11 +1225,18 @@ class GpuBatchILQGPlanner:
     """iLQG for `num_envs` environments (robots) on ONE context. The two feedback-rollout phases of a plan step -- the nominal
     under iLQGPolicy::Action and the line search under the index policy, three quarters of an iteration and pure per-step latency --
     are one `rollout_feedback_batched` launch each for the whole fleet (any number of rollouts per environment: iLQG's ten). Between
-    them every environment runs the unchanged sequential chain on the shared context: plain `set_state` of that environment, model
-    derivatives, cost derivatives, the backward pass with its regularisation retries. An environment whose backward pass fails every
-    retry sits the line search out, exactly as GpuILQGPlanner.iteration returns early. The environments share the model, the task
-    and the settings; each has its own state, clock, mocap pose, policy and regularisation. The per-environment logic (BestRollout,
-    the regularisation schedule, the policy bookkeeping) IS GpuILQGPlanner's, one member per environment."""
+    them the derivative chain and the backward pass with its regularisation retries run for the whole fleet in ONE call,
+    `ilqg_step_batched`, on the nominal rollouts still on the device (`device_chain`: None = whenever the context has that call, False
+    = never). Without it -- the oracle backends of the tests, or an environment whose nominal rollouts all failed, whose nominal is then
+    the host's policy trajectory and no device rollout -- an environment runs the unchanged sequential chain on the shared context:
+    plain `set_state` of that environment, model derivatives, cost derivatives, the backward pass with its retries. An environment
+    whose backward pass fails every retry sits the line search out, exactly as GpuILQGPlanner.iteration returns early. The environments
+    share the model, the task and the settings; each has its own state, clock, mocap pose, policy and regularisation. The
+    per-environment logic (BestRollout, the regularisation schedule, the policy bookkeeping) IS GpuILQGPlanner's, one member per
+    environment.
+    timers: `derivatives_backward` is the whole middle either way. On the sequential path `model_derivative`, `cost_derivative` and
+    `backward_pass` are the members' sums; with the device chain the stages are one call, whose total is under `model_derivative`, the
+    other two are 0 (plus whatever a member that fell back to the sequential chain spent)."""
 
     def __init__(self, num_envs, device=0, precision=64, backend_factory=None):
         if int(num_envs) < 1:
@@ -1236,6 +1245,8 @@ class GpuBatchILQGPlanner:
         self._backend_factory = backend_factory
         self.model = self.task = self.ctx = None
         self.timers = {}
+        self.device_chain = None    # None: ilqg_step_batched whenever the context has it; False: the sequential middle (the tests' comparison)
+        self.used_device_chain = False   # which middle the last optimize_policy ran
         # the members never create a context of their own: they are handed the shared one
         self.envs = [GpuILQGPlanner(device, precision, backend_factory=lambda task: self.ctx) for _ in range(self.num_envs)]
         for p in self.envs:
@@ -1307,18 +1318,71 @@ class GpuBatchILQGPlanner:
             p._nominal_select(horizon, ret, fail)
         self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
 
+    def _use_device_chain(self):
+        st = self.settings
+        if self.device_chain is not None and not self.device_chain:
+            return False
+        if not hasattr(self.ctx, "ilqg_step_batched"):
+            if self.device_chain:
+                raise ValueError("GpuBatchILQGPlanner: device_chain on a context without ilqg_step_batched")
+            return False
+        # what the call would refuse keeps the sequential middle: no retries at all (the iteration ends before the backward pass), members
+        # with different factors, a regularisation, rate or factor that is not a positive finite number
+        ok = lambda v: np.isfinite(v) and v > 0
+        return (1 <= st.max_regularization_iterations <= 64 and len({p.regularization_factor for p in self.envs}) == 1 and
+                all(ok(p.regularization) and ok(p.regularization_rate) and ok(p.regularization_factor) for p in self.envs) and
+                np.isfinite(st.min_regularization) and np.isfinite(st.max_regularization) and st.min_regularization <= st.max_regularization)
+
+    def _sequential_middle(self, p, horizon):
+        self.ctx.set_state(p.state, p.time, p.mocap, p.userdata)
+        return p._iteration_before_rollouts(horizon)
+
+    def _device_middle(self, horizon):
+        """GpuILQGPlanner._iteration_before_rollouts of every member from ONE ilqg_step_batched; the line search's requests"""
+        st, T = self.settings, horizon
+        t0 = _time.perf_counter()
+        out = self.ctx.ilqg_step_batched([p.nominal_index for p in self.envs], T, derivative_steps(T, self.derivative_skip_), st.fd_tolerance,
+                                         int(st.fd_mode), st.regularization_type, st.action_limits, [p.regularization for p in self.envs],
+                                         [p.regularization_rate for p in self.envs], self.envs[0].regularization_factor,
+                                         st.min_regularization, st.max_regularization, st.max_regularization_iterations)
+        requests = []
+        for e, p in enumerate(self.envs):
+            status = int(out["status"][e])
+            if status < 0:
+                requests.append(None)               # its nominal is not on the device: the sequential chain, below
+                continue
+            c0 = p.candidate0
+            tr = c0.trajectory
+            p._previous_return = tr.total_return
+            p.iteration_completed = False
+            p.regularization, p.regularization_rate = float(out["mu"][e]), float(out["rate"][e])
+            p.timers.update(model_derivative=0.0, cost_derivative=0.0, backward_pass=0.0)
+            if status == 0:
+                requests.append(None)
+                continue
+            p.dV = out["dV"][e].copy()
+            c0.feedback_gain[:T] = out["K"][e]
+            c0.action_improvement[:T] = out["du"][e]
+            requests.append((tr.times[:T], tr.states[:T], tr.actions[:T], c0.feedback_gain[:T], c0.action_improvement[:T], p._linesearch_steps()))
+        call_us = (_time.perf_counter() - t0) * 1e6
+        for e, p in enumerate(self.envs):
+            if out["status"][e] < 0:
+                requests[e] = self._sequential_middle(p, horizon)
+        return requests, call_us
+
     # ---- OptimizePolicy, ilqg/planner.cc:156-164, for every environment
     def optimize_policy(self, horizon, pool=None):
         self.nominal_trajectory(horizon)
-        # ---- derivatives and the backward pass, one environment after the other on that environment's plain state
+        # ---- derivatives and the backward pass: one call for the fleet, or one environment after the other on its plain state
         t0 = _time.perf_counter()
-        requests = []
-        for p in self.envs:
-            self.ctx.set_state(p.state, p.time, p.mocap, p.userdata)
-            requests.append(p._iteration_before_rollouts(horizon))
+        self.used_device_chain = self._use_device_chain()
+        if self.used_device_chain:
+            requests, call_us = self._device_middle(horizon)
+        else:
+            requests, call_us = [self._sequential_middle(p, horizon) for p in self.envs], 0.0
         self.timers["derivatives_backward"] = (_time.perf_counter() - t0) * 1e6
         for key in ("model_derivative", "cost_derivative", "backward_pass"):
-            self.timers[key] = sum(p.timers[key] for p in self.envs)
+            self.timers[key] = sum(p.timers[key] for p in self.envs) + (call_us if key == "model_derivative" else 0.0)
         # ---- ActionRollouts of the environments that got that far: one launch. The others ride along on their nominal with zero
         # steps and are ignored.
         self.sat_out = [r is None for r in requests]

@@ -19,8 +19,10 @@ timers (medians). Default output profiles/batch_sweep_gradient.jsonl.
 
 --planner ilqg: the iLQG plan step on the A1 (T = 36, 10 rollouts). (a) E GpuILQGPlanner plan steps on one context, one after the other,
 against (b) one GpuBatchILQGPlanner plan step: the nominal and the line-search rollouts of the fleet in one rollout_feedback_batched
-launch each, the derivative chain and the Riccati pass still per environment. Host logic included on both sides. The record carries the
-batched planner's stage timers (medians) and one environment's sequential ones. Default output profiles/batch_sweep_ilqg.jsonl.
+launch each, the derivative chain and the Riccati pass with its retries in one ilqg_step_batched between them (--no-device-chain: per
+environment on the plain calls, the planner's device_chain = False; `device_chain` in the record says which ran). Host logic included on
+both sides. The record carries the batched planner's stage timers (medians; median / min / max under batched_stage_spread_ms) and one
+environment's sequential ones. Default output profiles/batch_sweep_ilqg.jsonl.
 
 Kernel thresholds are the library's defaults: the sequential side of 8 x 2048 runs eight launches of the kernel a 2048-candidate batch gets,
 the batched side one launch of the kernel a 16384-candidate batch gets -- that is the feature."""
@@ -132,7 +134,7 @@ def sweep_gradient(name, precision, H, shapes, steps, warmup, out):
 ILQG_SHAPES = [("QuadrupedFlat", 64, 36, [(1, 10), (2, 10), (4, 10), (8, 10), (16, 10)])]
 
 
-def sweep_ilqg(name, precision, H, shapes, steps, warmup, out):
+def sweep_ilqg(name, precision, H, shapes, steps, warmup, out, device_chain=None):
     from mujoco_mpc_amd.planners import GpuBatchILQGPlanner, GpuILQGPlanner, State
     task = load_task(name)
     m = task.model
@@ -149,6 +151,7 @@ def sweep_ilqg(name, precision, H, shapes, steps, warmup, out):
             states.append(st)
         singles = [GpuILQGPlanner(precision=precision, backend_factory=lambda t: ctx) for _ in range(E)]
         batch = GpuBatchILQGPlanner(E, precision=precision, backend_factory=lambda t: ctx)
+        batch.device_chain = device_chain
         for p in singles + [batch]:
             p.initialize(m, task)
             p.num_rollouts_gui_ = n
@@ -177,7 +180,9 @@ def sweep_ilqg(name, precision, H, shapes, steps, warmup, out):
         rec = {"planner": "ilqg", "task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps,
                "warmup": warmup, "kernel": ctx.kernel_name.split(" (")[0], "sequential_ms": stats(ts), "batched_ms": stats(tb),
                "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)), "beyond_spread": bool(np.max(tb) < np.min(ts)),
+               "device_chain": bool(batch.used_device_chain),
                "batched_stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
+               "batched_stage_spread_ms": {k: stats(v) for k, v in stages.items()},
                "sequential_stage_ms_per_env": {k: float(v) * 1e-3 for k, v in singles[0].timers.items()},
                "sat_out": int(sum(batch.sat_out)) if hasattr(batch, "sat_out") else 0}
         print(json.dumps(rec), flush=True)
@@ -279,6 +284,7 @@ def main():
     ap.add_argument("--only", default=None)
     ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
+    ap.add_argument("--no-device-chain", action="store_true", help="--planner ilqg: the sequential middle (the A/B of ilqg_step_batched)")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
@@ -292,7 +298,7 @@ def main():
                 if a.planner == "gradient":
                     sweep_gradient(name, precision, H, shapes, a.steps, a.warmup, out)
                 elif a.planner == "ilqg":
-                    sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out)
+                    sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out, False if a.no_device_chain else None)
                 else:
                     sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner)
 
