@@ -1,7 +1,7 @@
-// gradient_batched.h -- the glue kernels of mjpcx_gradient_step_batched: the Gradient planner's derivative chain for E environments,
-// every stage on the device:
-//   gather_nominal_kernel   local candidate `cand` of every environment of the last batched rollout, out of the Trajectory buffers in
-//                           whichever layout the rollout kernel left them, into the environment-major arrays the stages below read
+// gradient_batched.h -- the interpolation kernel of the batched derivative chain (mjpcx_gradient_step_batched, mjpcx_ilqg_step_batched).
+// The Gradient planner's chain for E environments, every stage on the device:
+//   gather_candidates_kernel (ilqg_batched.h)   local candidate `cand` of every environment of the last batched rollout, out of the
+//                           Trajectory buffers, into the environment-major arrays the stages below read, with the step times
 //   transition_fd_kernel<ENVS> / transition_fd_wave_kernel (ilqg_kernels.h, wave_ilqg.h), fd_assemble_kernel over E x num_eval steps
 //   fd_interpolate_kernel   ModelDerivatives::Compute's skip interpolation (model_derivatives.cc:108-165) to all T steps, and the
 //                           zeroed last step of A, B, D (gradient/planner.cc:211-216)
@@ -10,47 +10,6 @@
 #include "device_common.h"
 
 namespace mjpcx {
-
-template <typename T>
-struct GatherNominalArgs {
-  const T *states, *actions, *times, *residual;  // the rollout's Trajectory buffers
-  const double* total_return;                    // [N]
-  int N, H, n_per_env, cand, candidate_major;    // global candidate of environment e: e * n_per_env + cand
-  int E, Tn, ne;                                 // environments, steps, evaluated steps
-  const int* evaluate;                           // [ne]
-  int ds_roll, ds, nu, nr;                       // state row of the rollout (nq + nv + na), its leading nq + nv, controls, residuals
-  T *fd_times, *fd_states, *fd_actions;          // [E][ne], [E][ne][ds], [E][ne][nu]: the finite-difference kernels' inputs
-  double *step_times, *residual_out, *nominal_return;  // [E][Tn], [E][Tn][nr], [E]
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void gather_nominal_kernel(const GatherNominalArgs<T> g) {
-  const int per_fd = 1 + g.ds + g.nu, per_t = 1 + g.nr;
-  const size_t per_env = (size_t)g.ne * per_fd + (size_t)g.Tn * per_t + 1, total = per_env * g.E;
-  for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const int e = (int)(idx / per_env);
-    size_t r = idx - (size_t)e * per_env;
-    const size_t c = (size_t)e * g.n_per_env + g.cand;
-    // [(cand * H + t) * width + k] (wavefront-per-candidate kernels) or [(t * width + k) * N + cand] (lane kernels): gather_traj_kernel
-    auto load = [&](const T* src, int width, int t, int k) {
-      return g.candidate_major ? src[(c * g.H + t) * width + k] : src[((size_t)t * width + k) * g.N + c];
-    };
-    if (r < (size_t)g.ne * per_fd) {
-      const int i = (int)(r / per_fd), j = (int)(r % per_fd), t = g.evaluate[i];
-      const size_t row = (size_t)e * g.ne + i;
-      if (j == 0) g.fd_times[row] = load(g.times, 1, t, 0);
-      else if (j <= g.ds) g.fd_states[row * g.ds + (j - 1)] = load(g.states, g.ds_roll, t, j - 1);
-      else g.fd_actions[row * g.nu + (j - 1 - g.ds)] = load(g.actions, g.nu, t, j - 1 - g.ds);
-    } else if ((r -= (size_t)g.ne * per_fd) < (size_t)g.Tn * per_t) {
-      const int t = (int)(r / per_t), j = (int)(r % per_t);
-      const size_t row = (size_t)e * g.Tn + t;
-      if (j == 0) g.step_times[row] = (double)load(g.times, 1, t, 0);
-      else g.residual_out[row * g.nr + (j - 1)] = (double)load(g.residual, g.nr, t, j - 1);
-    } else {
-      g.nominal_return[e] = g.total_return[c];
-    }
-  }
-}
 
 // X[e][t] = X_eval[e][i0] (1 - w) + X_eval[e][i1] w for X = A, B, C, D, with i0 the last evaluated step <= t, i1 the next one (the last:
 // itself) and w = (t - evaluate[i0]) / (evaluate[i1] - evaluate[i0]); an evaluated step is copied. Two products and a sum, not

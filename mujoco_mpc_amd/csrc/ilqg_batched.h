@@ -1,9 +1,12 @@
-// ilqg_batched.h -- the glue kernel of mjpcx_ilqg_step_batched: iLQG's derivative chain and backward pass for E environments, every
-// stage on the device ("iLQG's derivative chain and backward pass for the fleet"):
+// ilqg_batched.h -- the gather kernel of the batched derivative chains (mjpcx_ilqg_step_batched, mjpcx_gradient_step_batched). iLQG's
+// chain and backward pass for E environments, every stage on the device ("iLQG's derivative chain and backward pass for
+// the fleet"):
 //   gather_candidates_kernel   local candidate cands[e] of environment e of the last batched rollout -- iLQG's nominal is the best of
-//                              each environment's own nominal rollouts -- out of the Trajectory buffers in whichever layout the rollout
-//                              kernel left them, into the environment-major arrays the stages below read; the actions of ALL T steps
-//                              (the box-QP of the backward pass needs them), not only those of the evaluated ones
+//                              each environment's own nominal rollouts, the Gradient planner's the same candidate of every environment
+//                              -- out of the Trajectory buffers in whichever layout the rollout kernel left them, into the
+//                              environment-major arrays the stages below read. Per step, whichever the caller asks for: the actions of
+//                              ALL T steps (iLQG: the box-QP of the backward pass needs them), the step times (Gradient: the spline
+//                              projection needs them)
 //   transition_fd_kernel<ENVS> / transition_fd_wave_kernel, fd_assemble_kernel, fd_interpolate_kernel as in gradient_batched.h
 //   cost_derivatives_kernel (ilqg_dense.h) on E x T workgroups: workgroup e * T + t forms step t of environment e
 //   backward_pass_batched_kernel (ilqg_dense.h) on E workgroups
@@ -24,12 +27,13 @@ struct GatherCandidatesArgs {
   const int* evaluate;                           // [ne]
   int ds_roll, ds, nu, nr;                       // state row of the rollout (nq + nv + na), its leading nq + nv, controls, residuals
   T *fd_times, *fd_states, *fd_actions;          // [E][ne], [E][ne][ds], [E][ne][nu]: the finite-difference kernels' inputs
-  double *residual_out, *actions_out, *nominal_return;  // [E][Tn][nr], [E][Tn][nu], [E]
+  double *residual_out, *nominal_return;         // [E][Tn][nr], [E]
+  double *step_times, *actions_out;              // [E][Tn], [E][Tn][nu]; nullptr: the row is not written
 };
 
 template <typename T>
 __global__ __launch_bounds__(256) void gather_candidates_kernel(const GatherCandidatesArgs<T> g) {
-  const int per_fd = 1 + g.ds + g.nu, per_t = g.nr + g.nu;
+  const int nst = g.step_times ? 1 : 0, per_fd = 1 + g.ds + g.nu, per_t = g.nr + nst + (g.actions_out ? g.nu : 0);
   const size_t per_env = (size_t)g.ne * per_fd + (size_t)g.Tn * per_t + 1, total = per_env * g.E;
   for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int e = (int)(idx / per_env);
@@ -49,7 +53,8 @@ __global__ __launch_bounds__(256) void gather_candidates_kernel(const GatherCand
       const int t = (int)(r / per_t), j = (int)(r % per_t);
       const size_t row = (size_t)e * g.Tn + t;
       if (j < g.nr) g.residual_out[row * g.nr + j] = (double)load(g.residual, g.nr, t, j);
-      else g.actions_out[row * g.nu + (j - g.nr)] = (double)load(g.actions, g.nu, t, j - g.nr);
+      else if (j < g.nr + nst) g.step_times[row] = (double)load(g.times, 1, t, 0);
+      else g.actions_out[row * g.nu + (j - g.nr - nst)] = (double)load(g.actions, g.nu, t, j - g.nr - nst);
     } else {
       g.nominal_return[e] = g.active[e] ? g.total_return[c] : 0.0;
     }

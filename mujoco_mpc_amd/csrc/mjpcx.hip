@@ -473,6 +473,38 @@ struct DevBuf {
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+// Grow-only pinned host block that asynchronous copies read from (or write to). A call that ends in a stream sync may simply rewrite it;
+// a call that does not mark()s the block after enqueueing its last reader, and whoever rewrites the block wait()s first.
+struct PinnedBlock {
+  void* p = nullptr;
+  size_t cap = 0;
+  hipEvent_t last = nullptr;  // the last reader, while `pending`
+  bool pending = false;
+  hipError_t reserve(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+  hipError_t wait() {
+    if (!pending) return hipSuccess;
+    pending = false;
+    return hipEventSynchronize(last);
+  }
+  hipError_t mark(hipStream_t s) {
+    hipError_t e = last ? hipSuccess : hipEventCreateWithFlags(&last, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(last, s);
+    pending = e == hipSuccess;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    if (last) (void)hipEventDestroy(last);
+    p = nullptr; cap = 0; last = nullptr; pending = false;
+  }
+};
 
 struct mjpcx_ctx {
   int device = 0, precision = 64;
@@ -491,18 +523,16 @@ struct mjpcx_ctx {
   // plan inputs (node times, nominal spline, CE variances) go through a small ring of pinned
   // staging slots: one truly asynchronous H2D copy per rollout, no host sync
   static constexpr int kSlots = 4;
-  struct Slot { void* host = nullptr; DevBuf dev; size_t cap = 0; hipEvent_t done = nullptr; bool pending = false; };
+  struct Slot { PinnedBlock host; DevBuf dev; };  // host is marked behind the kernel that reads dev
   Slot slots[kSlots];
   int next_slot = 0;
   // pinned + device-mapped result record of mjpcx_best
   void* best_host = nullptr; void* best_dev = nullptr; size_t best_cap = 0;
   // rollout buffers
-  DevBuf d_nodes, d_in_nodes, d_ilqg, d_ilqg_out, d_wblob;
-  DevBuf d_grad;                                  // workspace of mjpcx_gradient_step_batched / mjpcx_ilqg_step_batched: inputs, every intermediate, the result block
-  void* grad_host = nullptr; size_t grad_cap = 0; // its pinned [inputs | result block]
-  // pinned staging block of mjpcx_rollout_feedback_batched (the six policy arrays of every environment, one H2D copy; the call does not
-  // sync, so the block is rewritten only after the copy that read it has passed fb_done)
-  void* fb_host = nullptr; size_t fb_cap = 0; hipEvent_t fb_done = nullptr; bool fb_pending = false;
+  DevBuf d_nodes, d_in_nodes, d_ilqg, d_ilqg_out;
+  PinnedBlock h_ilqg;  // host side of d_ilqg: the input arrays of the iLQG / Gradient entry points (upload_arrays; one H2D copy, marked: the feedback rollouts do not sync)
+  DevBuf d_grad;       // workspace of mjpcx_gradient_step_batched / mjpcx_ilqg_step_batched: inputs, every intermediate, the result block
+  PinnedBlock h_grad;  // its pinned [inputs | result block] (those calls end in a sync)
   DevBuf d_states, d_actions, d_times, d_residual, d_costs, d_trace, d_ret, d_fail, d_sort, d_stage;
   bool traj_candidate_major = false;
   int nsite_model = 0;
@@ -517,7 +547,6 @@ struct mjpcx_ctx {
   // wavefront-per-candidate family
   bool wave = false;
   WaveHost wh;
-  std::vector<unsigned char> blob_scratch;
   std::vector<double> h_stage;
   // tuning aids read from the environment ONCE, in mjpcx_create: MJPCX_STAMPS=<step> (phase cycle stamps of candidate 0)
   int stamp_step = -1;
@@ -704,18 +733,12 @@ int stage_plan_inputs(mjpcx_ctx* c, int P, int E, const double* node_times, cons
   const size_t bytes = rec * nrec;
   mjpcx_ctx::Slot& s = c->slots[c->next_slot];
   c->next_slot = (c->next_slot + 1) % mjpcx_ctx::kSlots;
-  if (s.pending) { HIPCHK(c, hipEventSynchronize(s.done)); s.pending = false; }
-  if (!s.done) HIPCHK(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-  if (bytes > s.cap) {
-    if (s.host) (void)hipHostFree(s.host);
-    s.host = nullptr; s.cap = 0;
-    HIPCHK(c, hipHostMalloc(&s.host, bytes, hipHostMallocDefault));
-    s.cap = bytes;
-  }
+  HIPCHK(c, s.host.wait());
+  HIPCHK(c, s.host.reserve(bytes));
   HIPCHK(c, s.dev.reserve(bytes));
   const int nst = c->nq + c->nv;
   for (int e = 0; e < nrec; e++) {
-    char* h = (char*)s.host + rec * e;
+    char* h = (char*)s.host.p + rec * e;
     T* ht = (T*)h;
     for (int p = 0; p < P; p++) ht[p] = (T)node_times[(size_t)e * P + p];
     T* hn = (T*)(h + off_nom);
@@ -749,7 +772,7 @@ int stage_plan_inputs(mjpcx_ctx* c, int P, int E, const double* node_times, cons
       }
     }
   }
-  HIPCHK(c, hipMemcpyAsync(s.dev.p, s.host, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(s.dev.p, s.host.p, bytes, hipMemcpyHostToDevice, c->stream));
   *d_times = (const T*)s.dev.p;
   *d_nominal = (const T*)((char*)s.dev.p + off_nom);
   *d_variance = (const double*)((char*)s.dev.p + off_var);
@@ -1195,8 +1218,7 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("rollout kernel launch: ") + hipGetErrorString(le));
   if (c->timing && c->cur_main) { HIPCHK(c, hipEventRecord(c->cur_main, c->stream)); c->cur_main = nullptr; }  // (paths with one kernel, or whose first pass is not singled out)
   if (c->timing) HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipEventRecord(slot->done, c->stream));
-  slot->pending = true;
+  HIPCHK(c, slot->host.mark(c->stream));
   c->N = N; c->H = H; c->P = P;
   c->env_n = E > 0 ? N / E : 0;
   c->have_rollout = true;
@@ -1492,19 +1514,14 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (auto& ev : c->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   for (auto& ev : c->events_main) (void)hipEventDestroy(ev);
-  for (auto& sl : c->slots) {
-    if (sl.host) (void)hipHostFree(sl.host);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-    sl.dev.release();
-  }
+  for (auto& sl : c->slots) { sl.host.release(); sl.dev.release(); }
+  c->h_ilqg.release();
+  c->h_grad.release();
   if (c->best_host) (void)hipHostFree(c->best_host);
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
-  if (c->grad_host) (void)hipHostFree(c->grad_host);
-  if (c->fb_host) (void)hipHostFree(c->fb_host);
-  if (c->fb_done) (void)hipEventDestroy(c->fb_done);
   (void)mjpcx_comm_destroy(c);
   c->wh.release();
-  DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_wblob, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
+  DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
                     &c->d_states, &c->d_actions, &c->d_times, &c->d_residual, &c->d_costs, &c->d_trace, &c->d_ret,
                     &c->d_fail, &c->d_sort, &c->d_stage};
   for (DevBuf* b : bufs) b->release();
@@ -2012,106 +2029,62 @@ int mjpcx_device_buffer(mjpcx_ctx* c, int which, void** ptr, size_t* bytes) {
 }  // extern "C"
 
 // ------------------------------------------------------------------ iLQG entry points
+// One host code path, as for the rollouts (do_rollout): every function below takes E, and E = 0 is the plain entry point -- one
+// environment, the state of mjpcx_set_state, the plain kernel instantiations; E >= 1 is the batched one -- the states of mjpcx_set_states,
+// the instantiations that select an environment.
 namespace {
-// uploads a list of host fp64 arrays into one device buffer, converting to T; returns device pointers
+// One upload for an iLQG / Gradient entry point: host arrays -- fp64 converted to T, int32 as they are -- into the pinned block h_ilqg,
+// each on a 16-byte boundary (whole groups of 4 elements), ONE asynchronous copy into d_ilqg, and the block marked. No sync: the block is
+// rewritten only after the copy out of it has completed. dev[k]: array k on the device.
+struct HostArray {
+  const void* src; size_t n; bool ints;
+  HostArray(const double* p, size_t n_) : src(p), n(n_), ints(false) {}
+  HostArray(const int32_t* p, size_t n_) : src(p), n(n_), ints(true) {}
+};
 template <typename T>
-int upload_arrays(mjpcx_ctx* c, DevBuf& buf, const std::vector<std::pair<const double*, size_t>>& arrays, std::vector<T*>* out) {
-  size_t total = 0;
-  for (auto& a : arrays) total += (a.second + 1) & ~(size_t)1;
-  HIPCHK(c, buf.reserve(total * sizeof(T)));
-  std::vector<T> host(total);
-  size_t off = 0;
-  out->clear();
+int upload_arrays(mjpcx_ctx* c, std::initializer_list<HostArray> arrays, const T** dev) {
+  auto room = [](const HostArray& a) { return ((a.n + 3) & ~(size_t)3) * (a.ints ? 4 : sizeof(T)); };
+  size_t bytes = 0, off = 0;
+  for (auto& a : arrays) bytes += room(a);
+  HIPCHK(c, c->h_ilqg.wait());
+  HIPCHK(c, c->h_ilqg.reserve(bytes));
+  HIPCHK(c, c->d_ilqg.reserve(bytes));
   for (auto& a : arrays) {
-    for (size_t i = 0; i < a.second; i++) host[off + i] = (T)a.first[i];
-    out->push_back((T*)buf.p + off);
-    off += (a.second + 1) & ~(size_t)1;
+    char* h = (char*)c->h_ilqg.p + off;
+    if (a.ints) std::memcpy(h, a.src, a.n * 4);
+    else for (size_t i = 0; i < a.n; i++) ((T*)h)[i] = (T)((const double*)a.src)[i];
+    *dev++ = (const T*)((char*)c->d_ilqg.p + off);
+    off += room(a);
   }
-  HIPCHK(c, hipMemcpyAsync(buf.p, host.data(), total * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_ilqg.p, c->h_ilqg.p, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->h_ilqg.mark(c->stream));
+  return MJPCX_OK;
+}
+// the tail of a call that returns arrays: the requested ones (dst != nullptr) copied to the host, then the call's ONE sync
+struct Download { void* dst; const void* src; size_t bytes; };
+int download(mjpcx_ctx* c, const Download* list, size_t n) {
+  for (size_t k = 0; k < n; k++)
+    if (list[k].dst) HIPCHK(c, hipMemcpyAsync(list[k].dst, list[k].src, list[k].bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return MJPCX_OK;
 }
+int download(mjpcx_ctx* c, std::initializer_list<Download> list) { return download(c, list.begin(), list.size()); }
 
+// The plan records alone, for the entry points that bring no spline: state, clock, mocap pose and task blob of the one environment
+// (E = 0) or of each of E, `stride` bytes apart (stage_plan_inputs). The caller marks slot->host behind the last kernel that reads them.
+struct PlanRecords { mjpcx_ctx::Slot* slot; const void* blob; unsigned stride; };
 template <typename T>
-int do_feedback(mjpcx_ctx* c, int N, int H, int mode, int representation, int use_state, int Tn, const double* times,
-                const double* states, const double* actions, const double* gains, const double* improvement,
-                const double* alpha) {
-  int rc;
-  if ((rc = reserve_rollout(c, N, H, 1)) != MJPCX_OK) return rc;
-  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu;
-  std::vector<T*> d;
-  if ((rc = upload_arrays<T>(c, c->d_ilqg, {{times, (size_t)Tn}, {states, Tn * ds}, {actions, Tn * nu},
-                                            {gains, Tn * nu * ndx}, {improvement, Tn * nu}, {alpha, (size_t)N}}, &d)) != MJPCX_OK)
-    return rc;
-  RolloutArgs<T> a{};
-  a.N = N; a.H = H; a.P = 0; a.interp = 0;
-  a.nodes = (T*)c->d_nodes.p; a.noise.mode = -1;
-  a.states = (T*)c->d_states.p; a.actions = (T*)c->d_actions.p; a.times = (T*)c->d_times.p;
-  a.residual = (T*)c->d_residual.p; a.costs = (T*)c->d_costs.p; a.trace = (T*)c->d_trace.p;
-  a.total_return = (double*)c->d_ret.p; a.failure = (int*)c->d_fail.p;
-  FeedbackArgs<T> fb{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
-  hipError_t le;
-  if constexpr (sizeof(T) == 8) le = c->kernel->feedback64(c->hm64, c->ht64, a, fb, c->stream);
-  else { convert_task(c->ht32, c->ht64); le = c->kernel->feedback32(c->hm32, c->ht32, a, fb, c->stream); }
-  if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("feedback kernel launch: ") + hipGetErrorString(le));
-  c->N = N; c->H = H; c->P = 0;
-  c->have_rollout = true;
-  c->traj_candidate_major = false;
-  return MJPCX_OK;
+int stage_records(mjpcx_ctx* c, int E, PlanRecords* r) {
+  const T *times, *nominal;
+  const double* variance;
+  return stage_plan_inputs<T>(c, 0, E, nullptr, nullptr, nullptr, false, &times, &nominal, &variance, &r->slot, &r->blob, &r->stride);
 }
-
-template <typename T>
-int do_transition_fd(mjpcx_ctx* c, int Tn, const double* times, const double* states, const double* actions, double eps,
-                     int centered, double* A, double* B, double* C, double* D) {
-  int rc;
-  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr;
-  const size_t nc = 1 + 2 * (ndx + nu);
-  std::vector<T*> d;
-  std::vector<double> cr(c->ctrlrange);
-  if ((rc = upload_arrays<T>(c, c->d_ilqg, {{times, (size_t)Tn}, {states, Tn * ds}, {actions, Tn * nu}, {cr.data(), 2 * nu}}, &d)) != MJPCX_OK)
-    return rc;
-  // outputs: next [Tn][nc][ndx] (T), sensor [Tn][nc][nr] (T), ctrllimited (int), then A,B,C,D (f64)
-  const size_t off_sensor = (Tn * nc * ndx * sizeof(T) + 15) & ~(size_t)15;
-  const size_t off_lim = (off_sensor + Tn * nc * nr * sizeof(T) + 15) & ~(size_t)15;
-  const size_t off_A = (off_lim + nu * sizeof(int) + 15) & ~(size_t)15;
-  const size_t nA = Tn * ndx * ndx, nB = Tn * ndx * nu, nC = Tn * nr * ndx, nD = Tn * nr * nu;
-  HIPCHK(c, c->d_ilqg_out.reserve(off_A + (nA + nB + nC + nD) * 8));
-  char* base = (char*)c->d_ilqg_out.p;
-  HIPCHK(c, hipMemcpyAsync(base + off_lim, c->ctrllimited.data(), nu * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  FdArgs<T> f{d[0], d[1], d[2], Tn, (T)eps, (T*)base, (T*)(base + off_sensor)};
-  hipError_t le;
-  if constexpr (sizeof(T) == 8) le = c->kernel->fd64(c->hm64, c->ht64, f, c->stream);
-  else { convert_task(c->ht32, c->ht64); le = c->kernel->fd32(c->hm32, c->ht32, f, c->stream); }
-  if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("fd kernel launch: ") + hipGetErrorString(le));
-  double* dA = (double*)(base + off_A);
-  double *dB = dA + nA, *dC = dB + nB, *dD = dC + nC;
-  const int total = (int)(Tn * (ndx + nr) * (ndx + nu));
-  hipLaunchKernelGGL((fd_assemble_kernel<T>), dim3(std::min((total + 255) / 256, 1024)), dim3(256), 0, c->stream,
-                     (const T*)base, (const T*)(base + off_sensor), (const T*)d[2], (const T*)d[3],
-                     (const int*)(base + off_lim), Tn, (int)ndx, (int)nu, (int)nr, (T)eps, centered, dA, dB, dC, dD);
-  HIPCHK(c, hipGetLastError());
-  if (A) HIPCHK(c, hipMemcpyAsync(A, dA, nA * 8, hipMemcpyDeviceToHost, c->stream));
-  if (B) HIPCHK(c, hipMemcpyAsync(B, dB, nB * 8, hipMemcpyDeviceToHost, c->stream));
-  if (C) HIPCHK(c, hipMemcpyAsync(C, dC, nC * 8, hipMemcpyDeviceToHost, c->stream));
-  if (D) HIPCHK(c, hipMemcpyAsync(D, dD, nD * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MJPCX_OK;
-}
-}  // namespace
-
-namespace {
-// per-plan task blob of a wave context on the device (not the Predictive-Sampling hot path: pageable copy)
-int wave_blob(mjpcx_ctx* c, WaveTask* wt) {
-  c->blob_scratch.resize(c->wh.blob_bytes);
-  c->wh.fill_blob(c->blob_scratch.data());
-  HIPCHK(c, c->d_wblob.reserve(c->wh.blob_bytes));
-  HIPCHK(c, hipMemcpyAsync(c->d_wblob.p, c->blob_scratch.data(), c->wh.blob_bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *wt = c->wh.t;
-  wt->blob = (const double*)c->d_wblob.p;
-  wt->stamps = nullptr;
-  wt->stamp_step = 0;
-  return MJPCX_OK;
+WaveTask wave_task(const mjpcx_ctx* c, const void* d_blob) {
+  WaveTask wt = c->wh.t;
+  wt.blob = (const double*)d_blob;
+  wt.stamps = nullptr;
+  wt.stamp_step = 0;
+  return wt;
 }
 // tree: the iLQG kernels of a model wave_tree.h covers run its forward pass (P = the scratch elements kept in the node-time slot)
 size_t wave_lds_bytes(const mjpcx_ctx* c, int P, bool tree = false) {
@@ -2122,105 +2095,135 @@ size_t wave_lds_bytes(const mjpcx_ctx* c, int P, bool tree = false) {
   return (8 * w64::wave_lds_elems(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, c->wh.t.nr, c->wh.t.nterm, P, wm.cone) + 15) & ~(size_t)15;
 }
 
-int do_feedback_wave(mjpcx_ctx* c, int N, int H, int mode, int representation, int use_state, int Tn, const double* times,
-                     const double* states, const double* actions, const double* gains, const double* improvement, const double* alpha) {
-  if (c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+// mjpcx_rollout_feedback (E = 0: n candidates) and mjpcx_rollout_feedback_batched (E >= 1: n per environment, the five nominal arrays
+// E x Tn steps) after validation: the plan records, the six policy arrays in one upload, the family's kernel. No sync on the lane family.
+template <typename T>
+int do_feedback(mjpcx_ctx* c, int E, int n, int H, int mode, int representation, int use_state, int Tn, const double* times,
+                const double* states, const double* actions, const double* gains, const double* improvement, const double* alpha) {
   int rc;
+  const int N = (E > 0 ? E : 1) * n, env_n = E > 0 ? n : 0;
   if ((rc = reserve_rollout(c, N, H, 1)) != MJPCX_OK) return rc;
-  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu;
-  std::vector<double*> d;
-  if ((rc = upload_arrays<double>(c, c->d_ilqg, {{times, (size_t)Tn}, {states, Tn * ds}, {actions, Tn * nu}, {gains, Tn * nu * ndx},
-                                                 {improvement, Tn * nu}, {alpha, (size_t)N}}, &d)) != MJPCX_OK) return rc;
-  WaveTask wt;
-  if ((rc = wave_blob(c, &wt)) != MJPCX_OK) return rc;
-  RolloutArgs<double> a{};
-  a.N = N; a.H = H; a.P = 1; a.interp = 0; a.nodes = (double*)c->d_nodes.p; a.noise.mode = -1;
-  a.states = (double*)c->d_states.p; a.actions = (double*)c->d_actions.p; a.times = (double*)c->d_times.p;
-  a.residual = (double*)c->d_residual.p; a.costs = (double*)c->d_costs.p; a.trace = (double*)c->d_trace.p;
+  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, sET = (size_t)(E > 0 ? E : 1) * Tn;
+  PlanRecords rec;
+  if ((rc = stage_records<T>(c, E, &rec)) != MJPCX_OK) return rc;
+  if (E == 0) rec.stride = 0;
+  const T* d[6];
+  if ((rc = upload_arrays<T>(c, {{times, sET}, {states, sET * ds}, {actions, sET * nu}, {gains, sET * nu * ndx}, {improvement, sET * nu},
+                                 {alpha, (size_t)N}}, d)) != MJPCX_OK) return rc;
+  RolloutArgs<T> a{};
+  a.N = N; a.H = H; a.P = c->wave ? 1 : 0; a.interp = 0; a.nodes = (T*)c->d_nodes.p; a.noise.mode = -1;
+  a.states = (T*)c->d_states.p; a.actions = (T*)c->d_actions.p; a.times = (T*)c->d_times.p;
+  a.residual = (T*)c->d_residual.p; a.costs = (T*)c->d_costs.p; a.trace = (T*)c->d_trace.p;
   a.total_return = (double*)c->d_ret.p; a.failure = (int*)c->d_fail.p;
-  w64::FeedbackWaveArgs fb{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state, 0};
-  const bool tree = c->wh.tree_ok && !c->no_tree;
-  // a model of the quad kernel's class: the iLQG rollouts are one or ten candidates of pure per-step latency, and the quad form's step is the
-  // shortest (one candidate per wavefront; MJPCX_NO_QUAD_FEEDBACK=1 keeps the wavefront-per-candidate kernel for A/B runs). Candidates it
-  // hands on are rolled out by that kernel afterwards, as for the sampling rollouts.
-  if (c->quad_ok && !c->no_quad_feedback && c->wh.m.integrator == MJPCX_INT_EULER) {
-    quad::QArgs q{};
-    q.N = N; q.H = H; q.P = 1; q.noise_mode = -1; q.nodes = (double*)c->d_nodes.p;
-    q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
-    q.total_return = a.total_return; q.failure = a.failure; q.con_cap = c->quad_con_cap; q.cpw = 1;
-    const quad::QBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
-    const quad::QFeedback qf{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
-    HIPCHK(c, hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream));
-    HIPCHK(c, quad::launch_feedback_quad(c->d_qmodel.p, c->d_qtab.p, wt.blob, bo, q, qf, (int*)c->d_qstats.p, c->stream));
-    if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 32, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
+  if (!c->wave) {
+    FeedbackArgs<T> fb{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
+    if (E > 0) { fb.env_n = n; fb.env_waves = (n + 63) / 64; fb.env_stride = rec.stride; fb.init = (const LaneInit<T>*)rec.blob; }
+    hipError_t le;
+    if constexpr (sizeof(T) == 8) le = c->kernel->feedback64(c->hm64, c->ht64, a, fb, c->stream);
+    else { convert_task(c->ht32, c->ht64); le = c->kernel->feedback32(c->hm32, c->ht32, a, fb, c->stream); }
+    if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("feedback kernel launch: ") + hipGetErrorString(le));
+  } else if constexpr (sizeof(T) == 8) {
+    const WaveTask wt = wave_task(c, rec.blob);
+    w64::FeedbackWaveArgs fb{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state, 0, env_n, rec.stride};
+    // a model of the quad kernel's class: the iLQG rollouts are one or ten candidates of pure per-step latency, and the quad form's step is the
+    // shortest (one candidate per wavefront; MJPCX_NO_QUAD_FEEDBACK=1 keeps the wavefront-per-candidate kernel for A/B runs). Candidates it
+    // hands on -- of whichever environments -- are rolled out by that kernel afterwards, as for the sampling rollouts.
     bool handed_on = true;
-    if (c->h_qstats) {
-      HIPCHK(c, hipMemcpyAsync(c->h_qstats, c->d_qstats.p, 32, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      handed_on = static_cast<const int*>(c->h_qstats)[0] != 0;
+    if (c->quad_ok && !c->no_quad_feedback && c->wh.m.integrator == MJPCX_INT_EULER) {
+      quad::QArgs q{};
+      q.N = N; q.H = H; q.P = 1; q.noise_mode = -1; q.nodes = (double*)c->d_nodes.p;
+      q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
+      q.total_return = a.total_return; q.failure = a.failure; q.con_cap = c->quad_con_cap; q.cpw = 1;
+      q.env_n = env_n; q.env_stride = rec.stride;
+      const quad::QBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
+      const quad::QFeedback qf{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
+      HIPCHK(c, hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream));
+      HIPCHK(c, quad::launch_feedback_quad(c->d_qmodel.p, c->d_qtab.p, wt.blob, bo, q, qf, (int*)c->d_qstats.p, c->stream));
+      if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 32, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
+      if (c->h_qstats) {  // (the one sync of the call: the hand-on count)
+        HIPCHK(c, hipMemcpyAsync(c->h_qstats, c->d_qstats.p, 32, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        handed_on = static_cast<const int*>(c->h_qstats)[0] != 0;
+      }
+      fb.only_flagged = 1;
     }
-    if (!handed_on) {
-      c->N = N; c->H = H; c->P = 1;
-      c->have_rollout = true;
-      c->traj_candidate_major = true;
-      return MJPCX_OK;
+    if (handed_on) {
+      const bool tree = c->wh.tree_ok && !c->no_tree;
+      const int Ppolicy = tree ? (int)(ndx + 2 * ds) : (int)((ndx + 2 * ds + nu - 1) / nu + 1);
+      HIPCHK(c, launch_feedback_wave(c->wh.m, wt, a, fb, N, wave_lds_bytes(c, Ppolicy, tree), tree, c->wh.m.integrator == MJPCX_INT_RK4,
+                                     c->wh.registered == 0 ? c->wh.dev_image : nullptr, c->wh.blob_bytes, c->stream));
     }
-    fb.only_flagged = 1;
+  } else {
+    return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
   }
-  const int Ppolicy = tree ? (int)(ndx + 2 * ds) : (int)((ndx + 2 * ds + nu - 1) / nu + 1);
-  const size_t lds = wave_lds_bytes(c, Ppolicy, tree);
-  const bool rk4 = c->wh.m.integrator == MJPCX_INT_RK4;
-  HIPCHK(c, launch_feedback_wave(c->wh.m, wt, a, fb, N, lds, tree, rk4, c->wh.registered == 0 ? c->wh.dev_image : nullptr, c->wh.blob_bytes, c->stream));
-  c->N = N; c->H = H; c->P = 1;
+  HIPCHK(c, rec.slot->host.mark(c->stream));
+  c->N = N; c->H = H; c->P = a.P;
+  c->env_n = env_n;
   c->have_rollout = true;
-  c->traj_candidate_major = true;
+  c->traj_candidate_major = c->wave;
+  return MJPCX_OK;
+}
+// the checks mjpcx_rollout_feedback and mjpcx_rollout_feedback_batched share (`who`: the prefix of the batched call's messages)
+int check_feedback_args(mjpcx_ctx* c, const std::string& who, int H, int Tn, int mode, int representation) {
+  if (mode == 0 && H > Tn) return fail(c, MJPCX_EINVAL, who + "index policy needs a nominal trajectory at least as long as the horizon");
+  if (mode != 0 && mode != 1) return fail(c, MJPCX_EINVAL, who + "unknown feedback policy mode");
+  if (mode == 1 && (representation < 0 || representation > 2))
+    return fail(c, MJPCX_EINVAL, who + "iLQG policy representation must be 0 (zero-order), 1 (linear) or 2 (cubic)");
+  if (c->wave && c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+  const size_t shmem = (size_t)Tn * (1 + 2 * c->nv + 2 * c->nu + c->nu * 2 * c->nv) * esize(c);
+  if (!c->wave && shmem > 120 * 1024) return fail(c, MJPCX_EUNSUPPORTED, "nominal trajectory too large for the LDS stage");
   return MJPCX_OK;
 }
 
-int do_transition_fd_wave(mjpcx_ctx* c, int Tn, const double* times, const double* states, const double* actions, double eps,
-                          int centered, double* A, double* B, double* C, double* D) {
-  if (c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
-  int rc;
-  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr;
-  const size_t nc = 1 + 2 * (ndx + nu);
-  std::vector<double*> d;
-  std::vector<double> cr(c->ctrlrange);
-  if ((rc = upload_arrays<double>(c, c->d_ilqg, {{times, (size_t)Tn}, {states, Tn * ds}, {actions, Tn * nu}, {cr.data(), 2 * nu}}, &d)) != MJPCX_OK)
-    return rc;
-  WaveTask wt;
-  if ((rc = wave_blob(c, &wt)) != MJPCX_OK) return rc;
-  // outputs: raw next [Tn][nc][ds], tangent next [Tn][nc][ndx], sensor [Tn][nc][nr], ctrllimited (int), then A,B,C,D
-  const size_t off_tan = (Tn * nc * ds * 8 + 15) & ~(size_t)15;
-  const size_t off_sensor = (off_tan + Tn * nc * ndx * 8 + 15) & ~(size_t)15;
-  const size_t off_lim = (off_sensor + Tn * nc * nr * 8 + 15) & ~(size_t)15;
-  const size_t off_A = (off_lim + nu * sizeof(int) + 15) & ~(size_t)15;
-  const size_t nA = Tn * ndx * ndx, nB = Tn * ndx * nu, nC = Tn * nr * ndx, nD = Tn * nr * nu;
-  HIPCHK(c, c->d_ilqg_out.reserve(off_A + (nA + nB + nC + nD) * 8));
-  char* base = (char*)c->d_ilqg_out.p;
-  HIPCHK(c, hipMemcpyAsync(base + off_lim, c->ctrllimited.data(), nu * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  w64::FdWaveArgs f{d[0], d[1], d[2], Tn, (int)nc, eps, (double*)base, (double*)(base + off_sensor)};
-  const bool tree = c->wh.tree_ok && !c->no_tree;
-  const size_t lds = wave_lds_bytes(c, 1, tree);
-  const bool rk4 = c->wh.m.integrator == MJPCX_INT_RK4;
-  HIPCHK(c, launch_transition_fd_wave(c->wh.m, wt, f, (unsigned)(Tn * nc), lds, tree, rk4, c->stream));
-  HIPCHK(c, launch_fd_tangent(c->wh.m, (const double*)base, (double*)(base + off_tan), Tn, (int)nc, c->stream));
-  double* dA = (double*)(base + off_A);
-  double *dB = dA + nA, *dC = dB + nB, *dD = dC + nC;
-  const int total = (int)(Tn * (ndx + nr) * (ndx + nu));
-  hipLaunchKernelGGL((fd_assemble_kernel<double>), dim3(std::min((total + 255) / 256, 1024)), dim3(256), 0, c->stream,
-                     (const double*)(base + off_tan), (const double*)(base + off_sensor), (const double*)d[2], (const double*)d[3],
-                     (const int*)(base + off_lim), Tn, (int)ndx, (int)nu, (int)nr, eps, centered, dA, dB, dC, dD);
+// ModelDerivatives::Compute at `ne` steps of the one environment (E = 0) or of each of E, enqueued on the context's stream: the finite
+// differences -- every environment's with its own plan record -- and their assembly into A, B, C, D at those steps. The workspace is
+// carved by carve_fd out of a buffer of the caller's: next | tangent (wave family) | sensor | A | B | C | D.
+struct FdCarve { size_t next, tan, sens, A, B, C, D; };
+template <typename T, class Carve>
+FdCarve carve_fd(const mjpcx_ctx* c, size_t rows, Carve&& carve) {
+  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, nc = 1 + 2 * (ndx + nu);
+  FdCarve w;
+  w.next = carve(rows * nc * (c->wave ? ds : ndx) * sizeof(T)); w.tan = carve(c->wave ? rows * nc * ndx * 8 : 0); w.sens = carve(rows * nc * nr * sizeof(T));
+  w.A = carve(rows * ndx * ndx * 8); w.B = carve(rows * ndx * nu * 8); w.C = carve(rows * nr * ndx * 8); w.D = carve(rows * nr * nu * 8);
+  return w;
+}
+template <typename T>
+struct FdIn {
+  const T *times, *states, *actions;   // [rows], [rows][nq + nv], [rows][nu], environment-major
+  const T* range; const int* limited;  // ctrlrange [2 nu], ctrllimited [nu]
+};
+template <typename T>
+int enqueue_fd(mjpcx_ctx* c, int E, int ne, double eps, int centered, const PlanRecords& rec, const FdIn<T>& in, char* base, const FdCarve& w) {
+  const size_t ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, nc = 1 + 2 * (ndx + nu), rows = (size_t)(E > 0 ? E : 1) * ne;
+  T *next = (T*)(base + w.next), *sens = (T*)(base + w.sens);
+  const T* fd_next = next;
+  if (c->wave) {
+    if constexpr (sizeof(T) == 8) {
+      w64::FdWaveArgs fa{in.times, in.states, in.actions, (int)rows, (int)nc, eps, next, sens, E > 0 ? ne : 0, E > 0 ? rec.stride : 0};
+      const bool tree = c->wh.tree_ok && !c->no_tree;
+      HIPCHK(c, launch_transition_fd_wave(c->wh.m, wave_task(c, rec.blob), fa, (unsigned)(rows * nc), wave_lds_bytes(c, 1, tree), tree,
+                                          c->wh.m.integrator == MJPCX_INT_RK4, c->stream));
+      HIPCHK(c, launch_fd_tangent(c->wh.m, next, (double*)(base + w.tan), (int)rows, (int)nc, c->stream));
+      fd_next = (const T*)(base + w.tan);
+    } else {
+      return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+    }
+  } else {
+    FdArgs<T> fa{in.times, in.states, in.actions, ne, (T)eps, next, sens};
+    if (E > 0) { fa.num_envs = E; fa.env_items = (int)(((size_t)ne * nc + 63) / 64 * 64); fa.env_stride = rec.stride; fa.init = (const LaneInit<T>*)rec.blob; }
+    hipError_t le;
+    if constexpr (sizeof(T) == 8) le = c->kernel->fd64(c->hm64, c->ht64, fa, c->stream);
+    else { convert_task(c->ht32, c->ht64); le = c->kernel->fd32(c->hm32, c->ht32, fa, c->stream); }
+    if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("fd kernel launch: ") + hipGetErrorString(le));
+  }
+  const size_t items = rows * (ndx + nr) * (ndx + nu);
+  hipLaunchKernelGGL((fd_assemble_kernel<T>), dim3((unsigned)std::min<size_t>((items + 255) / 256, 1024)), dim3(256), 0, c->stream, fd_next, (const T*)sens,
+                     in.actions, in.range, in.limited, (int)rows, (int)ndx, (int)nu, (int)nr, (T)eps, centered, (double*)(base + w.A),
+                     (double*)(base + w.B), (double*)(base + w.C), (double*)(base + w.D));
   HIPCHK(c, hipGetLastError());
-  if (A) HIPCHK(c, hipMemcpyAsync(A, dA, nA * 8, hipMemcpyDeviceToHost, c->stream));
-  if (B) HIPCHK(c, hipMemcpyAsync(B, dB, nB * 8, hipMemcpyDeviceToHost, c->stream));
-  if (C) HIPCHK(c, hipMemcpyAsync(C, dC, nC * 8, hipMemcpyDeviceToHost, c->stream));
-  if (D) HIPCHK(c, hipMemcpyAsync(D, dD, nD * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   return MJPCX_OK;
 }
-}  // namespace
 
-namespace {
 // the context's current cost specification as the cost-derivative kernel takes it
 int make_cost_spec(mjpcx_ctx* c, CostSpec* out) {
   if (c->nterm > 32) return fail(c, MJPCX_EUNSUPPORTED, "more than 32 cost terms");
@@ -2234,11 +2237,30 @@ int make_cost_spec(mjpcx_ctx* c, CostSpec* out) {
   }
   return MJPCX_OK;
 }
-// dynamic LDS of backward_pass_kernel / backward_pass_batched_kernel: the carve of backward_sweep (ilqg_dense.h), with slack
-size_t backward_pass_lds_bytes(int n) {
+// backward_pass_kernel / backward_pass_batched_kernel: the m x m factorisation / box-QP of a step is unrolled to 12 or 16 columns at
+// compile time (the A1 has 12 controls); dynamic LDS: the carve of backward_sweep (ilqg_dense.h), with slack
+template <class Kernel, class Args>
+int launch_backward(mjpcx_ctx* c, Kernel kernel12, Kernel kernel16, int n, int m, unsigned grid, const Args& args) {
   const int NP = (n + 15) & ~15;
-  return (size_t)(5 * NP * NP + 3 * NP + 6 * NP * 16 + 5 * 256 + 16 * 23 + 16 * 13) * 8;
+  const size_t lds = (size_t)(5 * NP * NP + 3 * NP + 6 * NP * 16 + 5 * 256 + 16 * 23 + 16 * 13) * 8;
+  Kernel kernel = m <= 12 ? kernel12 : kernel16;
+  HIPCHK(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBackwardThreads), lds, c->stream, args);
+  HIPCHK(c, hipGetLastError());
+  return MJPCX_OK;
 }
+// an event pair around one launch (kernel_ms of mjpcx_backward_pass / mjpcx_gradient_pass); destroyed on every way out of the call
+struct LaunchTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~LaunchTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  hipError_t start(hipStream_t s) {
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    return e == hipSuccess ? hipEventRecord(e0, s) : e;
+  }
+  hipError_t stop(hipStream_t s) { return hipEventRecord(e1, s); }
+  double ms() const { float t = 0; (void)hipEventElapsedTime(&t, e0, e1); return t; }  // (after the call's sync)
+};
 }  // namespace
 
 extern "C" {
@@ -2248,15 +2270,32 @@ int mjpcx_rollout_feedback(mjpcx_ctx* c, int N, int H, int mode, int representat
                            const double* improvement, const double* alpha) {
   if (!c || !times || !states || !actions || !gains || !improvement || !alpha) return fail(c, MJPCX_EINVAL, "null argument");
   if (N < 1 || H < 1 || Tn < 1) return fail(c, MJPCX_EINVAL, "N, H and Tn must be >= 1");
-  if (mode == 0 && H > Tn) return fail(c, MJPCX_EINVAL, "index policy needs a nominal trajectory at least as long as the horizon");
-  if (mode != 0 && mode != 1) return fail(c, MJPCX_EINVAL, "unknown feedback policy mode");
-  if (mode == 1 && (representation < 0 || representation > 2)) return fail(c, MJPCX_EINVAL, "iLQG policy representation must be 0 (zero-order), 1 (linear) or 2 (cubic)");
+  int rc;
+  if ((rc = check_feedback_args(c, "", H, Tn, mode, representation)) != MJPCX_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->wave) return do_feedback_wave(c, N, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha);
-  const size_t shmem = (size_t)Tn * (1 + 2 * c->nv + 2 * c->nu + c->nu * 2 * c->nv) * esize(c);
-  if (shmem > 120 * 1024) return fail(c, MJPCX_EUNSUPPORTED, "nominal trajectory too large for the LDS stage");
-  return c->precision == 64 ? do_feedback<double>(c, N, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha)
-                            : do_feedback<float>(c, N, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha);
+  return c->precision == 64 ? do_feedback<double>(c, 0, N, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha)
+                            : do_feedback<float>(c, 0, N, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha);
+}
+
+int mjpcx_rollout_feedback_batched(mjpcx_ctx* c, int E, int n, int H, int mode, int representation, int use_state, int Tn, const double* times,
+                                   const double* states, const double* actions, const double* gains, const double* improvement,
+                                   const double* alpha) {
+  const std::string who = "mjpcx_rollout_feedback_batched: ";
+  if (!c || !times || !states || !actions || !gains || !improvement || !alpha) return fail(c, MJPCX_EINVAL, who + "null argument");
+  if (E < 1) return fail(c, MJPCX_EINVAL, who + "the number of environments must be >= 1");
+  if (n < 1 || H < 1 || Tn < 1) return fail(c, MJPCX_EINVAL, who + "n_per_env, H and Tn must be >= 1");
+  if ((long long)E * n > 0x7fffffffLL / 64 || (long long)E * Tn * (1 + 2 * c->nv * c->nu) > 0x7fffffffLL / 64)
+    return fail(c, MJPCX_EINVAL, who + "too many candidates or steps");
+  int rc;
+  if ((rc = check_feedback_args(c, who, H, Tn, mode, representation)) != MJPCX_OK) return rc;
+  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, who + "not implemented on a context sharded with mjpcx_comm_init");
+  if (c->xfrc_std > 0) return fail(c, MJPCX_EUNSUPPORTED, who + "xfrc noise (NoisyRollout) is not implemented for batched rollouts");
+  if (c->env_E != E)
+    return fail(c, MJPCX_EINVAL, c->env_E == 0 ? who + "before mjpcx_set_states"
+                                               : who + std::to_string(E) + " environments after mjpcx_set_states of " + std::to_string(c->env_E));
+  HIPCHK(c, hipSetDevice(c->device));
+  return c->precision == 64 ? do_feedback<double>(c, E, n, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha)
+                            : do_feedback<float>(c, E, n, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha);
 }
 
 int mjpcx_transition_fd(mjpcx_ctx* c, int Tn, const double* times, const double* states, const double* actions, double eps,
@@ -2264,9 +2303,25 @@ int mjpcx_transition_fd(mjpcx_ctx* c, int Tn, const double* times, const double*
   if (!c || !times || !states || !actions) return fail(c, MJPCX_EINVAL, "null argument");
   if (Tn < 1 || !(eps > 0)) return fail(c, MJPCX_EINVAL, "bad horizon or epsilon");
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->wave) return do_transition_fd_wave(c, Tn, times, states, actions, eps, centered, A, B, C, D);
-  return c->precision == 64 ? do_transition_fd<double>(c, Tn, times, states, actions, eps, centered, A, B, C, D)
-                            : do_transition_fd<float>(c, Tn, times, states, actions, eps, centered, A, B, C, D);
+  if (c->wave && c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+  auto run = [&](auto precision) {
+    using T = decltype(precision);
+    int rc;
+    const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, sT = Tn;
+    PlanRecords rec;
+    if ((rc = stage_records<T>(c, 0, &rec)) != MJPCX_OK) return rc;
+    const T* d[5];
+    if ((rc = upload_arrays<T>(c, {{times, sT}, {states, sT * ds}, {actions, sT * nu}, {c->ctrlrange.data(), 2 * nu}, {c->ctrllimited.data(), nu}}, d)) != MJPCX_OK)
+      return rc;
+    size_t off = 0;
+    const FdCarve w = carve_fd<T>(c, sT, [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; });
+    HIPCHK(c, c->d_ilqg_out.reserve(off));
+    char* base = (char*)c->d_ilqg_out.p;
+    if ((rc = enqueue_fd<T>(c, 0, Tn, eps, centered, rec, FdIn<T>{d[0], d[1], d[2], d[3], (const int*)d[4]}, base, w)) != MJPCX_OK) return rc;
+    HIPCHK(c, rec.slot->host.mark(c->stream));
+    return download(c, {{A, base + w.A, sT * ndx * ndx * 8}, {B, base + w.B, sT * ndx * nu * 8}, {C, base + w.C, sT * nr * ndx * 8}, {D, base + w.D, sT * nr * nu * 8}});
+  };
+  return c->precision == 64 ? run(double{}) : run(float{});
 }
 
 int mjpcx_kinematics(mjpcx_ctx* c, double* xpos, double* xquat, double* xmat, double* xipos, double* site_xpos, double* subtree_com,
@@ -2275,17 +2330,17 @@ int mjpcx_kinematics(mjpcx_ctx* c, double* xpos, double* xquat, double* xmat, do
   if (!c->wave) return fail(c, MJPCX_EUNSUPPORTED, "mjpcx_kinematics is implemented for the wavefront-per-candidate models only");
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  WaveTask wt;
-  if ((rc = wave_blob(c, &wt)) != MJPCX_OK) return rc;
+  PlanRecords rec;
+  if ((rc = stage_records<double>(c, 0, &rec)) != MJPCX_OK) return rc;  // (the fp64 blob in either precision: the kernel is fp64)
   const size_t nb = (size_t)c->wh.m.nbody_model, ns = (size_t)c->nsite_model;
   const size_t total = 3 * nb + 4 * nb + 9 * nb + 3 * nb + 3 * ns + 3 * nb + 3 * nb;
   HIPCHK(c, c->d_ilqg_out.reserve(total * 8));
   HIPCHK(c, hipMemsetAsync(c->d_ilqg_out.p, 0, total * 8, c->stream));
   const size_t lds = wave_lds_bytes(c, 1);
-  HIPCHK(c, launch_kinematics_wave(c->wh.m, wt, (double*)c->d_ilqg_out.p, (int)nb, (int)ns, lds, c->stream));
+  HIPCHK(c, launch_kinematics_wave(c->wh.m, wave_task(c, rec.blob), (double*)c->d_ilqg_out.p, (int)nb, (int)ns, lds, c->stream));
+  HIPCHK(c, rec.slot->host.mark(c->stream));
   std::vector<double> h(total);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->d_ilqg_out.p, total * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = download(c, {{h.data(), c->d_ilqg_out.p, total * 8}})) != MJPCX_OK) return rc;
   const double* p = h.data();
   auto take = [&](double* dst, size_t n) { if (dst) std::memcpy(dst, p, n * 8); p += n; };
   take(xpos, 3 * nb); take(xquat, 4 * nb); take(xmat, 9 * nb); take(xipos, 3 * nb); take(site_xpos, 3 * ns); take(subtree_com, 3 * nb);
@@ -2302,23 +2357,16 @@ int mjpcx_cost_derivatives(mjpcx_ctx* c, int T, const double* residual, const do
   CostSpec cs{};
   int rc;
   if ((rc = make_cost_spec(c, &cs)) != MJPCX_OK) return rc;
-  std::vector<double*> d;
-  if ((rc = upload_arrays<double>(c, c->d_ilqg, {{residual, T * nr}, {C, T * nr * ndx}, {D, T * nr * nu}}, &d)) != MJPCX_OK) return rc;
+  const double* d[3];
+  if ((rc = upload_arrays<double>(c, {{residual, T * nr}, {C, T * nr * ndx}, {D, T * nr * nu}}, d)) != MJPCX_OK) return rc;
   const size_t n_out = T * (ndx + nu + ndx * ndx + ndx * nu + nu * nu);
   HIPCHK(c, c->d_ilqg_out.reserve(n_out * 8));
   double* o = (double*)c->d_ilqg_out.p;
   double *dcx = o, *dcu = dcx + T * ndx, *dcxx = dcu + T * nu, *dcxu = dcxx + T * ndx * ndx, *dcuu = dcxu + T * ndx * nu;
   const size_t shmem = (32 + 32 * 32 + 32 * ndx + 32 * nu) * 8;
-  hipLaunchKernelGGL(cost_derivatives_kernel, dim3(T), dim3(64), shmem, c->stream, cs, (const double*)d[0], (const double*)d[1],
-                     (const double*)d[2], T, (int)ndx, (int)nu, dcx, dcu, dcxx, dcxu, dcuu);
+  hipLaunchKernelGGL(cost_derivatives_kernel, dim3(T), dim3(64), shmem, c->stream, cs, d[0], d[1], d[2], T, (int)ndx, (int)nu, dcx, dcu, dcxx, dcxu, dcuu);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(cx, dcx, T * ndx * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cu, dcu, T * nu * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cxx, dcxx, T * ndx * ndx * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cxu, dcxu, T * ndx * nu * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cuu, dcuu, T * nu * nu * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MJPCX_OK;
+  return download(c, {{cx, dcx, T * ndx * 8}, {cu, dcu, T * nu * 8}, {cxx, dcxx, T * ndx * ndx * 8}, {cxu, dcxu, T * ndx * nu * 8}, {cuu, dcuu, T * nu * nu * 8}});
 }
 
 int mjpcx_backward_pass(mjpcx_ctx* c, int n, int m, int T, double mu, int reg_type, int use_limits, const double* A,
@@ -2330,11 +2378,11 @@ int mjpcx_backward_pass(mjpcx_ctx* c, int n, int m, int T, double mu, int reg_ty
   if (n < 1 || n > 48 || m < 1 || m > 16 || T < 2) return fail(c, MJPCX_EUNSUPPORTED, "backward pass kernel covers 1 <= n <= 48, 1 <= m <= 16, T >= 2");
   if (reg_type < 0 || reg_type > 2) return fail(c, MJPCX_EINVAL, "unknown regularization type");
   HIPCHK(c, hipSetDevice(c->device));
-  std::vector<double*> d;
+  const double* d[9];
   int rc;
   const size_t sn = n, sm = m, sT = T;
-  if ((rc = upload_arrays<double>(c, c->d_ilqg, {{A, sT * sn * sn}, {B, sT * sn * sm}, {cx, sT * sn}, {cu, sT * sm}, {cxx, sT * sn * sn},
-                                                 {cxu, sT * sn * sm}, {cuu, sT * sm * sm}, {actions, sT * sm}, {limits, 2 * sm}}, &d)) != MJPCX_OK)
+  if ((rc = upload_arrays<double>(c, {{A, sT * sn * sn}, {B, sT * sn * sm}, {cx, sT * sn}, {cu, sT * sm}, {cxx, sT * sn * sn},
+                                      {cxu, sT * sn * sm}, {cuu, sT * sm * sm}, {actions, sT * sm}, {limits, 2 * sm}}, d)) != MJPCX_OK)
     return rc;
   const size_t n_out = sT * (sn + sn * sn + sm * sn + sm) + 2 + 2 + 16;
   HIPCHK(c, c->d_ilqg_out.reserve(n_out * 8));
@@ -2345,42 +2393,20 @@ int mjpcx_backward_pass(mjpcx_ctx* c, int n, int m, int T, double mu, int reg_ty
   a.Vx = o; a.Vxx = a.Vx + sT * sn; a.K = a.Vxx + sT * sn * sn; a.du = a.K + sT * sm * sn; a.dV = a.du + sT * sm;
   a.status = (int*)(a.dV + 2);
   a.stamps = c->stamp_step >= 0 ? (long long*)(a.dV + 4) : nullptr;
-  const size_t lds = backward_pass_lds_bytes(n);
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0));
-  HIPCHK(c, hipEventCreate(&e1));
-  // the m x m factorisation / box-QP of a step is unrolled to 12 or 16 columns at compile time (the A1 has 12 controls)
-  if (m <= 12) {
-    HIPCHK(c, hipFuncSetAttribute((const void*)backward_pass_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-    hipLaunchKernelGGL(backward_pass_kernel<12>, dim3(1), dim3(64 * kBackwardWaves), lds, c->stream, a);
-  } else {
-    HIPCHK(c, hipFuncSetAttribute((const void*)backward_pass_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-    hipLaunchKernelGGL(backward_pass_kernel<16>, dim3(1), dim3(64 * kBackwardWaves), lds, c->stream, a);
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipMemcpyAsync(Vx, a.Vx, sT * sn * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(Vxx, a.Vxx, sT * sn * sn * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(K, a.K, sT * sm * sn * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(du, a.du, sT * sm * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dV, a.dV, 16, hipMemcpyDeviceToHost, c->stream));
-  int st = 0;
-  HIPCHK(c, hipMemcpyAsync(&st, a.status, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *status = st;
+  LaunchTimer timer;
+  HIPCHK(c, timer.start(c->stream));
+  if ((rc = launch_backward(c, backward_pass_kernel<12>, backward_pass_kernel<16>, n, m, 1, a)) != MJPCX_OK) return rc;
+  HIPCHK(c, timer.stop(c->stream));
+  if ((rc = download(c, {{Vx, a.Vx, sT * sn * 8}, {Vxx, a.Vxx, sT * sn * sn * 8}, {K, a.K, sT * sm * sn * 8}, {du, a.du, sT * sm * 8}, {dV, a.dV, 16},
+                         {status, a.status, 4}})) != MJPCX_OK)
+    return rc;
   if (a.stamps) {
     long long h[9];
     (void)hipMemcpy(h, a.stamps, sizeof h, hipMemcpyDeviceToHost);
     std::fprintf(stderr, "backward_pass phase cycles (second step): stage %lld gemm %lld reg %lld du/qp %lld Kcols %lld update %lld write %lld\n",
                  h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3], h[5] - h[4], h[6] - h[5], h[7] - h[6]);
   }
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  if (kernel_ms) *kernel_ms = ms;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  if (kernel_ms) *kernel_ms = timer.ms();
   return MJPCX_OK;
 }
 
@@ -2396,11 +2422,10 @@ int mjpcx_gradient_pass(mjpcx_ctx* c, int n, int m, int T, const double* A, cons
   for (int i = 1; i < P; i++)
     if (!(node_times[i] > node_times[i - 1])) return fail(c, MJPCX_EINVAL, "node times must be strictly increasing");
   HIPCHK(c, hipSetDevice(c->device));
-  std::vector<double*> d;
+  const double* d[6];
   int rc;
   const size_t sn = n, sm = m, sT = T, sP = P;
-  if ((rc = upload_arrays<double>(c, c->d_ilqg, {{A, sT * sn * sn}, {B, sT * sn * sm}, {cx, sT * sn}, {cu, sT * sm}, {node_times, sP},
-                                                 {step_times, sT}}, &d)) != MJPCX_OK)
+  if ((rc = upload_arrays<double>(c, {{A, sT * sn * sn}, {B, sT * sn * sm}, {cx, sT * sn}, {cu, sT * sm}, {node_times, sP}, {step_times, sT}}, d)) != MJPCX_OK)
     return rc;
   const size_t n_out = sT * (sn + sm) + 2 + sP * sm;
   HIPCHK(c, c->d_ilqg_out.reserve(n_out * 8));
@@ -2410,76 +2435,117 @@ int mjpcx_gradient_pass(mjpcx_ctx* c, int n, int m, int T, const double* A, cons
   a.Vx = (double*)c->d_ilqg_out.p; a.k = a.Vx + sT * sn; a.dV = a.k + sT * sm; a.gradient = a.dV + 2;
   const size_t lds = gradient_pass_lds_bytes(T, m, P);
   HIPCHK(c, hipFuncSetAttribute((const void*)gradient_pass_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0));
-  HIPCHK(c, hipEventCreate(&e1));
-  HIPCHK(c, hipEventRecord(e0, c->stream));
+  LaunchTimer timer;
+  HIPCHK(c, timer.start(c->stream));
   hipLaunchKernelGGL(gradient_pass_kernel, dim3(1), dim3(64), lds, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipMemcpyAsync(Vx, a.Vx, sT * sn * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(k, a.k, sT * sm * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dV, a.dV, 16, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(gradient, a.gradient, sP * sm * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  if (kernel_ms) *kernel_ms = ms;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  HIPCHK(c, timer.stop(c->stream));
+  if ((rc = download(c, {{Vx, a.Vx, sT * sn * 8}, {k, a.k, sT * sm * 8}, {dV, a.dV, 16}, {gradient, a.gradient, sP * sm * 8}})) != MJPCX_OK) return rc;
+  if (kernel_ms) *kernel_ms = timer.ms();
   return MJPCX_OK;
 }
 
 }  // extern "C"
 
 namespace {
-// ModelDerivatives::Compute for E environments, enqueued on the context's stream (the shared front of mjpcx_gradient_step_batched and
-// mjpcx_ilqg_step_batched): the finite differences at the ne evaluated steps of every environment with that environment's record of the
-// staged blob, their assembly into A, B, C, D at those steps, and the interpolation to all Tn steps with A, B, D of the last one zeroed
+// The shared front and tail of mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched: ModelDerivatives::Compute for E environments from
+// the last batched rollout, enqueued on the context's stream, and the one download. One device workspace (d_grad), carved in this order:
+//   [evaluate | ctrllimited | ctrlrange | candidates | sources | active | the caller's inputs]              one upload from h_grad
+//   [gathered nominal | finite-difference workspace | A, B, C, D at all T steps | the caller's arrays]
+//   [nominal_return | the caller's results]                                                                 one download into h_grad
+// The caller carves its own fields with carve() after the constructor, after carve_work() and after carve_results(); then stage(), its
+// inputs into hin, run(), its own kernels, finish().
+struct StepResult { size_t at, bytes_per_env; void* dst; };  // a field of the result block and where it goes (nullptr: nowhere)
 template <typename T>
-struct FdChain {
-  const T *fd_times, *fd_states, *fd_actions;  // [E][ne]...: the gathered nominal at the evaluated steps
-  const int* evaluate;                         // [ne]
-  const T* range; const int* limited;          // ctrlrange [2 nu], ctrllimited [nu]
-  T *next, *sens; double* tan;                 // finite-difference workspaces
-  double *Ae, *Be, *Ce, *De, *A, *B, *C, *D;   // at the evaluated steps / at all Tn steps
-};
-template <typename T>
-int enqueue_fd_chain(mjpcx_ctx* c, int E, int ne, int Tn, double eps, int centered, const void* d_blob, unsigned stride, const FdChain<T>& f) {
-  const size_t ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, nc = 1 + 2 * (ndx + nu), sE = E, sT = Tn, sne = ne, rows = sE * sne;
-  const T* fd_next = f.next;
-  if (c->wave) {
-    if constexpr (sizeof(T) == 8) {
-      WaveTask wt = c->wh.t;
-      wt.blob = (const double*)d_blob;
-      wt.stamps = nullptr;
-      wt.stamp_step = 0;
-      w64::FdWaveArgs fa{f.fd_times, f.fd_states, f.fd_actions, (int)rows, (int)nc, eps, f.next, f.sens, ne, stride};
-      const bool tree = c->wh.tree_ok && !c->no_tree;
-      HIPCHK(c, launch_transition_fd_wave(c->wh.m, wt, fa, (unsigned)(rows * nc), wave_lds_bytes(c, 1, tree), tree, c->wh.m.integrator == MJPCX_INT_RK4, c->stream));
-      HIPCHK(c, launch_fd_tangent(c->wh.m, (const double*)f.next, f.tan, (int)rows, (int)nc, c->stream));
-      fd_next = (const T*)f.tan;
-    }
-  } else {
-    FdArgs<T> fa{f.fd_times, f.fd_states, f.fd_actions, ne, (T)eps, f.next, f.sens};
-    fa.num_envs = E; fa.env_items = (int)((sne * nc + 63) / 64 * 64); fa.env_stride = stride; fa.init = (const LaneInit<T>*)d_blob;
-    hipError_t le;
-    if constexpr (sizeof(T) == 8) le = c->kernel->fd64(c->hm64, c->ht64, fa, c->stream);
-    else { convert_task(c->ht32, c->ht64); le = c->kernel->fd32(c->hm32, c->ht32, fa, c->stream); }
-    if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("fd kernel launch: ") + hipGetErrorString(le));
-  }
-  const size_t a_items = rows * (ndx + nr) * (ndx + nu);
-  hipLaunchKernelGGL((fd_assemble_kernel<T>), dim3((unsigned)std::min<size_t>((a_items + 255) / 256, 1024)), dim3(256), 0, c->stream, fd_next,
-                     (const T*)f.sens, f.fd_actions, f.range, f.limited, (int)rows, (int)ndx, (int)nu, (int)nr, (T)eps, centered, f.Ae, f.Be, f.Ce, f.De);
-  HIPCHK(c, hipGetLastError());
-  const size_t sA = ndx * ndx, sB = ndx * nu, sC = nr * ndx, sD = nr * nu, i_items = sE * sT * (sA + sB + sC + sD);
-  hipLaunchKernelGGL(fd_interpolate_kernel, dim3((unsigned)std::min<size_t>((i_items + 255) / 256, 4096)), dim3(256), 0, c->stream, f.Ae, f.Be, f.Ce, f.De,
-                     f.evaluate, E, ne, Tn, (int)sA, (int)sB, (int)sC, (int)sD, f.A, f.B, f.C, f.D);
-  HIPCHK(c, hipGetLastError());
-  return MJPCX_OK;
-}
+struct StepChain {
+  mjpcx_ctx* c;
+  int E, Tn, ne;
+  size_t ds, ndx, nu, nr, nc, sE, sT, rows, sA, sB, sC, sD;
+  size_t off = 0, in_bytes = 0, o_out = 0;
+  size_t o_eval, o_lim, o_range, o_cand, o_src, o_act, o_ft = 0, o_fs = 0, o_fa = 0, o_res = 0, o_A = 0, o_B = 0, o_C = 0, o_D = 0, o_ret = 0;
+  FdCarve fd{};
+  PlanRecords rec{};
+  char *base = nullptr, *hin = nullptr, *hout = nullptr;
 
-// mjpcx_gradient_step_batched after validation: stage, launch the chain, one sync, unpack
+  size_t carve(size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; }
+  double* f64(size_t o) const { return (double*)(base + o); }
+  int* i32(size_t o) const { return (int*)(base + o); }
+  T* real(size_t o) const { return (T*)(base + o); }
+  StepChain(mjpcx_ctx* c_, int E_, int Tn_, int ne_) : c(c_), E(E_), Tn(Tn_), ne(ne_) {
+    ds = c->nq + c->nv; ndx = 2 * (size_t)c->nv; nu = c->nu; nr = c->nr; nc = 1 + 2 * (ndx + nu);
+    sE = E; sT = Tn; rows = sE * ne; sA = ndx * ndx; sB = ndx * nu; sC = nr * ndx; sD = nr * nu;
+    o_eval = carve((size_t)ne * 4); o_lim = carve(nu * 4); o_range = carve(2 * nu * sizeof(T));
+    o_cand = carve(sE * 4); o_src = carve(sE * 4); o_act = carve(sE * 4);
+  }
+  bool too_large() const { return sE * std::max((size_t)ne * nc, sT) * (ndx + nr) * (ndx + nu) > 0x7fffffffULL; }  // (the kernels index with int)
+  void carve_work() {
+    in_bytes = off;
+    o_ft = carve(rows * sizeof(T)); o_fs = carve(rows * ds * sizeof(T)); o_fa = carve(rows * nu * sizeof(T)); o_res = carve(sE * sT * nr * 8);
+    fd = carve_fd<T>(c, rows, [this](size_t bytes) { return carve(bytes); });
+    o_A = carve(sE * sT * sA * 8); o_B = carve(sE * sT * sB * 8); o_C = carve(sE * sT * sC * 8); o_D = carve(sE * sT * sD * 8);
+  }
+  void carve_results() { o_out = off; o_ret = carve(sE * 8); }
+  // the buffers, the environments' plan records restaged (the preceding rollout's slot may have been recycled since) and the shared
+  // inputs. candidate[e] < 0: environment e takes no part and rides along on the first active one's nominal (its finite differences
+  // need SOME valid trajectory); at least one takes part.
+  int stage(const int32_t* candidate, const int32_t* evaluate) {
+    int rc;
+    if ((rc = stage_records<T>(c, E, &rec)) != MJPCX_OK) return rc;
+    HIPCHK(c, c->d_grad.reserve(off));
+    HIPCHK(c, c->h_grad.reserve(in_bytes + off - o_out));
+    base = (char*)c->d_grad.p; hin = (char*)c->h_grad.p; hout = hin + in_bytes;
+    std::memcpy(hin + o_eval, evaluate, (size_t)ne * 4);
+    std::memcpy(hin + o_lim, c->ctrllimited.data(), nu * 4);
+    for (size_t i = 0; i < 2 * nu; i++) ((T*)(hin + o_range))[i] = (T)c->ctrlrange[i];
+    int first = 0;
+    while (candidate[first] < 0) first++;
+    for (int e = 0; e < E; e++) {
+      const bool on = candidate[e] >= 0;
+      ((int*)(hin + o_cand))[e] = candidate[on ? e : first];
+      ((int*)(hin + o_src))[e] = on ? e : first;
+      ((int*)(hin + o_act))[e] = on ? 1 : 0;
+    }
+    return MJPCX_OK;
+  }
+  // the upload; the nominal candidates gathered (with the rows the caller asks for); the finite differences at the evaluated steps of
+  // every environment, interpolated to all Tn steps with A, B, D of the last one zeroed
+  int run(double eps, int centered, double* step_times, double* actions_out) {
+    HIPCHK(c, hipMemcpyAsync(base, hin, in_bytes, hipMemcpyHostToDevice, c->stream));
+    GatherCandidatesArgs<T> g{};
+    g.states = (const T*)c->d_states.p; g.actions = (const T*)c->d_actions.p; g.times = (const T*)c->d_times.p; g.residual = (const T*)c->d_residual.p;
+    g.total_return = (const double*)c->d_ret.p;
+    g.N = c->N; g.H = c->H; g.n_per_env = c->env_n; g.candidate_major = c->traj_candidate_major ? 1 : 0;
+    g.cands = i32(o_cand); g.source = i32(o_src); g.active = i32(o_act);
+    g.E = E; g.Tn = Tn; g.ne = ne; g.evaluate = i32(o_eval);
+    g.ds_roll = c->nq + c->nv + c->na; g.ds = (int)ds; g.nu = (int)nu; g.nr = (int)nr;
+    g.fd_times = real(o_ft); g.fd_states = real(o_fs); g.fd_actions = real(o_fa);
+    g.residual_out = f64(o_res); g.nominal_return = f64(o_ret); g.step_times = step_times; g.actions_out = actions_out;
+    const size_t g_items = sE * ((size_t)ne * (1 + ds + nu) + sT * (nr + (step_times ? 1 : 0) + (actions_out ? nu : 0)) + 1);
+    hipLaunchKernelGGL((gather_candidates_kernel<T>), dim3((unsigned)std::min<size_t>((g_items + 255) / 256, 2048)), dim3(256), 0, c->stream, g);
+    HIPCHK(c, hipGetLastError());
+    int rc;
+    const FdIn<T> in{g.fd_times, g.fd_states, g.fd_actions, real(o_range), i32(o_lim)};
+    if ((rc = enqueue_fd<T>(c, E, ne, eps, centered, rec, in, base, fd)) != MJPCX_OK) return rc;
+    const size_t i_items = sE * sT * (sA + sB + sC + sD);
+    hipLaunchKernelGGL(fd_interpolate_kernel, dim3((unsigned)std::min<size_t>((i_items + 255) / 256, 4096)), dim3(256), 0, c->stream, f64(fd.A),
+                       f64(fd.B), f64(fd.C), f64(fd.D), i32(o_eval), E, ne, Tn, (int)sA, (int)sB,
+                       (int)sC, (int)sD, f64(o_A), f64(o_B), f64(o_C), f64(o_D));
+    HIPCHK(c, hipGetLastError());
+    return MJPCX_OK;
+  }
+  // the result block into pinned memory, the optional arrays straight to the caller, ONE sync, and the block's fields to where they go
+  int finish(const Download* optional, size_t n_optional, std::initializer_list<StepResult> results) {
+    HIPCHK(c, rec.slot->host.mark(c->stream));
+    HIPCHK(c, hipMemcpyAsync(hout, base + o_out, off - o_out, hipMemcpyDeviceToHost, c->stream));
+    int rc;
+    if ((rc = download(c, optional, n_optional)) != MJPCX_OK) return rc;
+    for (auto& r : results)
+      if (r.dst) std::memcpy(r.dst, hout + (r.at - o_out), sE * r.bytes_per_env);
+    return MJPCX_OK;
+  }
+};
+
+// mjpcx_gradient_step_batched after validation
 template <typename T>
 int do_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int Tn, int ne, const int32_t* evaluate, double eps, int centered, int representation,
                              int P, const double* node_times, double* nominal_return, double* k, double* gradient, double* dV, double* A,
@@ -2487,89 +2553,99 @@ int do_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int Tn, int ne, cons
   int rc;
   CostSpec cs{};
   if ((rc = make_cost_spec(c, &cs)) != MJPCX_OK) return rc;
-  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, nc = 1 + 2 * (ndx + nu);
-  const size_t sE = E, sT = Tn, sne = ne, sP = P, rows = sE * sne;
-  if (sE * std::max(sne * nc, sT) * (ndx + nr) * (ndx + nu) > 0x7fffffffULL) return fail(c, MJPCX_EUNSUPPORTED, "mjpcx_gradient_step_batched: too many environments x steps");
-  // the environments' plan records, restaged: the preceding rollout's slot may have been recycled since
-  const T *d_rec_times, *d_rec_nominal;
-  const double* d_rec_var;
-  const void* d_blob = nullptr;
-  mjpcx_ctx::Slot* slot = nullptr;
-  unsigned stride = 0;
-  if ((rc = stage_plan_inputs<T>(c, P, E, node_times, nullptr, nullptr, false, &d_rec_times, &d_rec_nominal, &d_rec_var, &slot, &d_blob, &stride)) != MJPCX_OK)
-    return rc;
-  // ---- workspace carve: [evaluate | ctrllimited | ctrlrange | node_times] (one upload), the stages' arrays, [nominal_return | k | gradient | dV] (one download)
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
-  const size_t o_eval = carve(sne * 4), o_lim = carve(nu * 4), o_range = carve(2 * nu * sizeof(T)), o_nodes = carve(sE * sP * 8), in_bytes = off;
-  const size_t o_ft = carve(rows * sizeof(T)), o_fs = carve(rows * ds * sizeof(T)), o_fa = carve(rows * nu * sizeof(T));
-  const size_t o_st = carve(sE * sT * 8), o_res = carve(sE * sT * nr * 8);
-  const size_t o_next = carve(rows * nc * (c->wave ? ds : ndx) * sizeof(T)), o_tan = carve(c->wave ? rows * nc * ndx * 8 : 0), o_sens = carve(rows * nc * nr * sizeof(T));
-  const size_t sA = ndx * ndx, sB = ndx * nu, sC = nr * ndx, sD = nr * nu;
-  const size_t o_Ae = carve(rows * sA * 8), o_Be = carve(rows * sB * 8), o_Ce = carve(rows * sC * 8), o_De = carve(rows * sD * 8);
-  const size_t o_A = carve(sE * sT * sA * 8), o_B = carve(sE * sT * sB * 8), o_C = carve(sE * sT * sC * 8), o_D = carve(sE * sT * sD * 8);
-  const size_t o_cx = carve(sE * sT * ndx * 8), o_cu = carve(sE * sT * nu * 8), o_Vx = carve(sE * sT * ndx * 8);
-  const size_t o_out = off, o_ret = carve(sE * 8), o_k = carve(sE * sT * nu * 8), o_g = carve(sE * sP * nu * 8), o_dV = carve(sE * 2 * 8), out_bytes = off - o_out;
-  HIPCHK(c, c->d_grad.reserve(off));
-  if (in_bytes + out_bytes > c->grad_cap) {
-    if (c->grad_host) (void)hipHostFree(c->grad_host);
-    c->grad_host = nullptr; c->grad_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->grad_host, in_bytes + out_bytes, hipHostMallocDefault));
-    c->grad_cap = in_bytes + out_bytes;
-  }
-  char* base = (char*)c->d_grad.p;
-  char* hin = (char*)c->grad_host;
-  char* hout = hin + in_bytes;
-  std::memcpy(hin + o_eval, evaluate, sne * 4);
-  std::memcpy(hin + o_lim, c->ctrllimited.data(), nu * 4);
-  for (size_t i = 0; i < 2 * nu; i++) ((T*)(hin + o_range))[i] = (T)c->ctrlrange[i];
-  std::memcpy(hin + o_nodes, node_times, sE * sP * 8);
-  HIPCHK(c, hipMemcpyAsync(base, hin, in_bytes, hipMemcpyHostToDevice, c->stream));
-  const int* d_eval = (const int*)(base + o_eval);
-  // ---- gather the nominal candidates
-  GatherNominalArgs<T> g{};
-  g.states = (const T*)c->d_states.p; g.actions = (const T*)c->d_actions.p; g.times = (const T*)c->d_times.p; g.residual = (const T*)c->d_residual.p;
-  g.total_return = (const double*)c->d_ret.p;
-  g.N = c->N; g.H = c->H; g.n_per_env = c->env_n; g.cand = cand; g.candidate_major = c->traj_candidate_major ? 1 : 0;
-  g.E = E; g.Tn = Tn; g.ne = ne; g.evaluate = d_eval;
-  g.ds_roll = c->nq + c->nv + c->na; g.ds = (int)ds; g.nu = (int)nu; g.nr = (int)nr;
-  g.fd_times = (T*)(base + o_ft); g.fd_states = (T*)(base + o_fs); g.fd_actions = (T*)(base + o_fa);
-  g.step_times = (double*)(base + o_st); g.residual_out = (double*)(base + o_res); g.nominal_return = (double*)(base + o_ret);
-  const size_t g_items = sE * (sne * (1 + ds + nu) + sT * (1 + nr) + 1);
-  hipLaunchKernelGGL((gather_nominal_kernel<T>), dim3((unsigned)std::min<size_t>((g_items + 255) / 256, 2048)), dim3(256), 0, c->stream, g);
-  HIPCHK(c, hipGetLastError());
-  // ---- ModelDerivatives::Compute at the evaluated steps of every environment, interpolated to all Tn steps
-  double *dA = (double*)(base + o_A), *dB = (double*)(base + o_B), *dC = (double*)(base + o_C), *dD = (double*)(base + o_D);
-  const FdChain<T> fc{g.fd_times, g.fd_states, g.fd_actions, d_eval, (const T*)(base + o_range), (const int*)(base + o_lim), (T*)(base + o_next),
-                      (T*)(base + o_sens), (double*)(base + o_tan), (double*)(base + o_Ae), (double*)(base + o_Be), (double*)(base + o_Ce),
-                      (double*)(base + o_De), dA, dB, dC, dD};
-  if ((rc = enqueue_fd_chain<T>(c, E, ne, Tn, eps, centered, d_blob, stride, fc)) != MJPCX_OK) return rc;
+  StepChain<T> s(c, E, Tn, ne);
+  if (s.too_large()) return fail(c, MJPCX_EUNSUPPORTED, "mjpcx_gradient_step_batched: too many environments x steps");
+  const size_t sE = E, sT = Tn, sP = P, ndx = s.ndx, nu = s.nu;
+  const size_t o_nodes = s.carve(sE * sP * 8);
+  s.carve_work();
+  const size_t o_st = s.carve(sE * sT * 8), o_cx = s.carve(sE * sT * ndx * 8), o_cu = s.carve(sE * sT * nu * 8), o_Vx = s.carve(sE * sT * ndx * 8);
+  s.carve_results();
+  const size_t o_k = s.carve(sE * sT * nu * 8), o_g = s.carve(sE * sP * nu * 8), o_dV = s.carve(sE * 2 * 8);
+  const std::vector<int32_t> cands(E, cand);  // the same local candidate of every environment; every environment takes part
+  if ((rc = s.stage(cands.data(), evaluate)) != MJPCX_OK) return rc;
+  std::memcpy(s.hin + o_nodes, node_times, sE * sP * 8);
+  if ((rc = s.run(eps, centered, s.f64(o_st), nullptr)) != MJPCX_OK) return rc;
   // ---- CostDerivatives::Compute (first order) and Gradient::Compute with the projection, per environment
-  double *dcx = (double*)(base + o_cx), *dcu = (double*)(base + o_cu);
-  hipLaunchKernelGGL(cost_gradient_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32) * 8, c->stream, cs, (const double*)g.residual_out,
-                     (const double*)dC, (const double*)dD, Tn, (int)ndx, (int)nu, dcx, dcu);
+  double *dA = s.f64(s.o_A), *dB = s.f64(s.o_B), *dcx = s.f64(o_cx), *dcu = s.f64(o_cu);
+  hipLaunchKernelGGL(cost_gradient_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32) * 8, c->stream, cs, s.f64(s.o_res),
+                     s.f64(s.o_C), s.f64(s.o_D), Tn, (int)ndx, (int)nu, dcx, dcu);
   HIPCHK(c, hipGetLastError());
   GradientArgs ga{};
   ga.n = (int)ndx; ga.m = (int)nu; ga.T = Tn; ga.P = P; ga.representation = representation;
-  ga.A = dA; ga.B = dB; ga.cx = dcx; ga.cu = dcu; ga.node_times = (const double*)(base + o_nodes); ga.step_times = g.step_times;
-  ga.Vx = (double*)(base + o_Vx); ga.k = (double*)(base + o_k); ga.dV = (double*)(base + o_dV); ga.gradient = (double*)(base + o_g);
+  ga.A = dA; ga.B = dB; ga.cx = dcx; ga.cu = dcu; ga.node_times = s.f64(o_nodes); ga.step_times = s.f64(o_st);
+  ga.Vx = s.f64(o_Vx); ga.k = s.f64(o_k); ga.dV = s.f64(o_dV); ga.gradient = s.f64(o_g);
   const size_t lds = gradient_pass_lds_bytes(Tn, (int)nu, P);
   HIPCHK(c, hipFuncSetAttribute((const void*)gradient_pass_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(gradient_pass_batched_kernel, dim3(E), dim3(64), lds, c->stream, ga);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(slot->done, c->stream));
-  slot->pending = true;
-  // ---- results: one block into pinned memory; the optional matrices straight to the caller; ONE sync
-  HIPCHK(c, hipMemcpyAsync(hout, base + o_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (A) HIPCHK(c, hipMemcpyAsync(A, dA, sE * sT * sA * 8, hipMemcpyDeviceToHost, c->stream));
-  if (B) HIPCHK(c, hipMemcpyAsync(B, dB, sE * sT * sB * 8, hipMemcpyDeviceToHost, c->stream));
-  if (cx) HIPCHK(c, hipMemcpyAsync(cx, dcx, sE * sT * ndx * 8, hipMemcpyDeviceToHost, c->stream));
-  if (cu) HIPCHK(c, hipMemcpyAsync(cu, dcu, sE * sT * nu * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (nominal_return) std::memcpy(nominal_return, hout + (o_ret - o_out), sE * 8);
-  std::memcpy(k, hout + (o_k - o_out), sE * sT * nu * 8);
-  std::memcpy(gradient, hout + (o_g - o_out), sE * sP * nu * 8);
-  std::memcpy(dV, hout + (o_dV - o_out), sE * 2 * 8);
+  const Download optional[4] = {{A, dA, sE * sT * s.sA * 8}, {B, dB, sE * sT * s.sB * 8}, {cx, dcx, sE * sT * ndx * 8}, {cu, dcu, sE * sT * nu * 8}};
+  return s.finish(optional, 4, {{s.o_ret, 8, nominal_return}, {o_k, sT * nu * 8, k}, {o_g, sP * nu * 8, gradient}, {o_dV, 16, dV}});
+}
+
+// mjpcx_ilqg_step_batched after validation
+template <typename T>
+int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, int ne, const int32_t* evaluate, double eps, int centered, int reg_type,
+                         int use_limits, const double* mu, const double* rate, double factor, double min_reg, double max_reg, int max_iter, double* K,
+                         double* du, double* dV, int32_t* status, double* mu_out, double* rate_out, int32_t* retries, double* nominal_return,
+                         double* const (&opt)[9]) {
+  int rc;
+  CostSpec cs{};
+  if ((rc = make_cost_spec(c, &cs)) != MJPCX_OK) return rc;
+  StepChain<T> s(c, E, Tn, ne);
+  if (s.too_large()) return fail(c, MJPCX_EUNSUPPORTED, "mjpcx_ilqg_step_batched: too many environments x steps");
+  const size_t sE = E, sT = Tn, ndx = s.ndx, nu = s.nu, sA = s.sA, sB = s.sB;
+  // the optional outputs A, B, cx, cu, cxx, cxu, cuu, Vx, Vxx: elements per environment
+  const size_t per[9] = {sT * sA, sT * sB, sT * ndx, sT * nu, sT * sA, sT * sB, sT * nu * nu, sT * ndx, sT * sA};
+  // an environment that takes no part gets zeros and status -1
+  auto unpack_inactive = [&](int e) {
+    std::memset(K + (size_t)e * sT * sB, 0, sT * sB * 8); std::memset(du + (size_t)e * sT * nu, 0, sT * nu * 8); std::memset(dV + (size_t)e * 2, 0, 16);
+    status[e] = -1; mu_out[e] = 0; rate_out[e] = 0; retries[e] = 0;
+    if (nominal_return) nominal_return[e] = 0;
+    for (int k = 0; k < 9; k++) if (opt[k]) std::memset(opt[k] + (size_t)e * per[k], 0, per[k] * 8);
+  };
+  if (std::all_of(candidate, candidate + E, [](int32_t x) { return x < 0; })) {  // nobody takes part: nothing to launch
+    for (int e = 0; e < E; e++) unpack_inactive(e);
+    return MJPCX_OK;
+  }
+  const size_t o_mu = s.carve(sE * 8), o_rate = s.carve(sE * 8), o_limits = s.carve(2 * nu * 8);
+  s.carve_work();
+  const size_t o_actions = s.carve(sE * sT * nu * 8);
+  const size_t o_cx = s.carve(sE * per[2] * 8), o_cu = s.carve(sE * per[3] * 8), o_cxx = s.carve(sE * per[4] * 8), o_cxu = s.carve(sE * per[5] * 8);
+  const size_t o_cuu = s.carve(sE * per[6] * 8), o_Vx = s.carve(sE * per[7] * 8), o_Vxx = s.carve(sE * per[8] * 8);
+  s.carve_results();
+  const size_t o_K = s.carve(sE * sT * sB * 8), o_du = s.carve(sE * sT * nu * 8), o_dV = s.carve(sE * 2 * 8);
+  const size_t o_muo = s.carve(sE * 8), o_rateo = s.carve(sE * 8), o_status = s.carve(sE * 4), o_retries = s.carve(sE * 4);
+  if ((rc = s.stage(candidate, evaluate)) != MJPCX_OK) return rc;
+  std::memcpy(s.hin + o_mu, mu, sE * 8);
+  std::memcpy(s.hin + o_rate, rate, sE * 8);
+  std::memcpy(s.hin + o_limits, c->ctrlrange.data(), 2 * nu * 8);
+  // (Vx .. retries are contiguous: what a failed sweep or an environment that takes no part does not write reads as zero)
+  HIPCHK(c, hipMemsetAsync(s.base + o_Vx, 0, s.off - o_Vx, c->stream));
+  if ((rc = s.run(eps, centered, nullptr, s.f64(o_actions))) != MJPCX_OK) return rc;
+  // ---- CostDerivatives::Compute: workgroup e * Tn + t forms step t of environment e (every array is environment-major)
+  const size_t at[9] = {s.o_A, s.o_B, o_cx, o_cu, o_cxx, o_cxu, o_cuu, o_Vx, o_Vxx};
+  double* w[9];
+  for (int k = 0; k < 9; k++) w[k] = s.f64(at[k]);
+  hipLaunchKernelGGL(cost_derivatives_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32 + 32 * ndx + 32 * nu) * 8, c->stream, cs,
+                     s.f64(s.o_res), s.f64(s.o_C), s.f64(s.o_D), Tn, (int)ndx, (int)nu,
+                     w[2], w[3], w[4], w[5], w[6]);
+  HIPCHK(c, hipGetLastError());
+  // ---- the backward pass with its regularisation retries, one workgroup per environment
+  BackwardBatchedArgs b{};
+  b.base.n = (int)ndx; b.base.m = (int)nu; b.base.T = Tn; b.base.reg_type = reg_type; b.base.use_limits = use_limits;
+  b.base.A = w[0]; b.base.B = w[1]; b.base.cx = w[2]; b.base.cu = w[3]; b.base.cxx = w[4]; b.base.cxu = w[5]; b.base.cuu = w[6];
+  b.base.actions = s.f64(o_actions); b.base.limits = s.f64(o_limits);
+  b.base.Vx = w[7]; b.base.Vxx = w[8]; b.base.K = s.f64(o_K); b.base.du = s.f64(o_du); b.base.dV = s.f64(o_dV);
+  b.active = s.i32(s.o_act); b.mu = s.f64(o_mu); b.rate = s.f64(o_rate);
+  b.factor = factor; b.min_reg = min_reg; b.max_reg = max_reg; b.max_iter = max_iter;
+  b.status = s.i32(o_status); b.retries = s.i32(o_retries); b.mu_out = s.f64(o_muo); b.rate_out = s.f64(o_rateo);
+  if ((rc = launch_backward(c, backward_pass_batched_kernel<12>, backward_pass_batched_kernel<16>, (int)ndx, (int)nu, (unsigned)E, b)) != MJPCX_OK) return rc;
+  Download optional[9];
+  for (int k = 0; k < 9; k++) optional[k] = {opt[k], w[k], sE * per[k] * 8};
+  if ((rc = s.finish(optional, 9, {{s.o_ret, 8, nominal_return}, {o_K, sT * sB * 8, K}, {o_du, sT * nu * 8, du}, {o_dV, 16, dV}, {o_muo, 8, mu_out},
+                                   {o_rateo, 8, rate_out}, {o_status, 4, status}, {o_retries, 4, retries}})) != MJPCX_OK)
+    return rc;
+  for (int e = 0; e < E; e++) if (candidate[e] < 0) unpack_inactive(e);
   return MJPCX_OK;
 }
 }  // namespace
@@ -2608,151 +2684,6 @@ int mjpcx_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int T, int ne, co
                                                               gradient, dV, A, B, cx, cu);
 }
 
-}  // extern "C"
-
-namespace {
-// mjpcx_ilqg_step_batched after validation: stage, launch the chain, one sync, unpack
-template <typename T>
-int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, int ne, const int32_t* evaluate, double eps, int centered, int reg_type,
-                         int use_limits, const double* mu, const double* rate, double factor, double min_reg, double max_reg, int max_iter, double* K,
-                         double* du, double* dV, int32_t* status, double* mu_out, double* rate_out, int32_t* retries, double* nominal_return,
-                         double* const (&opt)[9]) {
-  int rc;
-  CostSpec cs{};
-  if ((rc = make_cost_spec(c, &cs)) != MJPCX_OK) return rc;
-  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, nr = c->nr, nc = 1 + 2 * (ndx + nu);
-  const size_t sE = E, sT = Tn, sne = ne, rows = sE * sne;
-  if (sE * std::max(sne * nc, sT) * (ndx + nr) * (ndx + nu) > 0x7fffffffULL) return fail(c, MJPCX_EUNSUPPORTED, "mjpcx_ilqg_step_batched: too many environments x steps");
-  const size_t sA = ndx * ndx, sB = ndx * nu, sC = nr * ndx, sD = nr * nu;
-  // an environment that takes no part rides along on the first active one's nominal (its finite differences need SOME valid trajectory)
-  int first = -1;
-  for (int e = 0; e < E && first < 0; e++) if (candidate[e] >= 0) first = e;
-  auto unpack_inactive = [&](int e) {
-    std::memset(K + (size_t)e * sT * sB, 0, sT * sB * 8); std::memset(du + (size_t)e * sT * nu, 0, sT * nu * 8); std::memset(dV + (size_t)e * 2, 0, 16);
-    status[e] = -1; mu_out[e] = 0; rate_out[e] = 0; retries[e] = 0;
-    if (nominal_return) nominal_return[e] = 0;
-    const size_t per[9] = {sT * sA, sT * sB, sT * ndx, sT * nu, sT * sA, sT * sB, sT * nu * nu, sT * ndx, sT * sA};
-    for (int k = 0; k < 9; k++) if (opt[k]) std::memset(opt[k] + (size_t)e * per[k], 0, per[k] * 8);
-  };
-  if (first < 0) {  // nobody takes part: nothing to launch
-    for (int e = 0; e < E; e++) unpack_inactive(e);
-    return MJPCX_OK;
-  }
-  // the environments' plan records, restaged: the preceding rollout's slot may have been recycled since
-  const T *d_rec_times, *d_rec_nominal;
-  const double* d_rec_var;
-  const void* d_blob = nullptr;
-  mjpcx_ctx::Slot* slot = nullptr;
-  unsigned stride = 0;
-  if ((rc = stage_plan_inputs<T>(c, 0, E, nullptr, nullptr, nullptr, false, &d_rec_times, &d_rec_nominal, &d_rec_var, &slot, &d_blob, &stride)) != MJPCX_OK)
-    return rc;
-  // ---- workspace carve: [evaluate | ctrllimited | ctrlrange | candidates | sources | active | mu | rate | limits] (one upload), the stages' arrays,
-  // [nominal_return | K | du | dV | mu_out | rate_out | status | retries] (one download)
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
-  const size_t o_eval = carve(sne * 4), o_lim = carve(nu * 4), o_range = carve(2 * nu * sizeof(T)), o_cand = carve(sE * 4), o_src = carve(sE * 4), o_act = carve(sE * 4);
-  const size_t o_mu = carve(sE * 8), o_rate = carve(sE * 8), o_limits = carve(2 * nu * 8), in_bytes = off;
-  const size_t o_ft = carve(rows * sizeof(T)), o_fs = carve(rows * ds * sizeof(T)), o_fa = carve(rows * nu * sizeof(T));
-  const size_t o_res = carve(sE * sT * nr * 8), o_actions = carve(sE * sT * nu * 8);
-  const size_t o_next = carve(rows * nc * (c->wave ? ds : ndx) * sizeof(T)), o_tan = carve(c->wave ? rows * nc * ndx * 8 : 0), o_sens = carve(rows * nc * nr * sizeof(T));
-  const size_t o_Ae = carve(rows * sA * 8), o_Be = carve(rows * sB * 8), o_Ce = carve(rows * sC * 8), o_De = carve(rows * sD * 8);
-  const size_t o_A = carve(sE * sT * sA * 8), o_B = carve(sE * sT * sB * 8), o_C = carve(sE * sT * sC * 8), o_D = carve(sE * sT * sD * 8);
-  const size_t o_cx = carve(sE * sT * ndx * 8), o_cu = carve(sE * sT * nu * 8), o_cxx = carve(sE * sT * sA * 8), o_cxu = carve(sE * sT * sB * 8);
-  const size_t o_cuu = carve(sE * sT * nu * nu * 8), o_Vx = carve(sE * sT * ndx * 8), o_Vxx = carve(sE * sT * sA * 8);
-  const size_t o_out = off, o_ret = carve(sE * 8), o_K = carve(sE * sT * sB * 8), o_du = carve(sE * sT * nu * 8), o_dV = carve(sE * 2 * 8);
-  const size_t o_muo = carve(sE * 8), o_rateo = carve(sE * 8), o_status = carve(sE * 4), o_retries = carve(sE * 4), out_bytes = off - o_out;
-  HIPCHK(c, c->d_grad.reserve(off));
-  if (in_bytes + out_bytes > c->grad_cap) {
-    if (c->grad_host) (void)hipHostFree(c->grad_host);
-    c->grad_host = nullptr; c->grad_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->grad_host, in_bytes + out_bytes, hipHostMallocDefault));
-    c->grad_cap = in_bytes + out_bytes;
-  }
-  char* base = (char*)c->d_grad.p;
-  char* hin = (char*)c->grad_host;
-  char* hout = hin + in_bytes;
-  std::memcpy(hin + o_eval, evaluate, sne * 4);
-  std::memcpy(hin + o_lim, c->ctrllimited.data(), nu * 4);
-  for (size_t i = 0; i < 2 * nu; i++) { ((T*)(hin + o_range))[i] = (T)c->ctrlrange[i]; ((double*)(hin + o_limits))[i] = c->ctrlrange[i]; }
-  for (int e = 0; e < E; e++) {
-    const bool on = candidate[e] >= 0;
-    ((int*)(hin + o_cand))[e] = on ? candidate[e] : candidate[first];
-    ((int*)(hin + o_src))[e] = on ? e : first;
-    ((int*)(hin + o_act))[e] = on ? 1 : 0;
-    ((double*)(hin + o_mu))[e] = mu[e]; ((double*)(hin + o_rate))[e] = rate[e];
-  }
-  HIPCHK(c, hipMemcpyAsync(base, hin, in_bytes, hipMemcpyHostToDevice, c->stream));
-  // (Vx .. retries are contiguous: what a failed sweep or an environment that takes no part does not write reads as zero)
-  HIPCHK(c, hipMemsetAsync(base + o_Vx, 0, off - o_Vx, c->stream));
-  const int* d_eval = (const int*)(base + o_eval);
-  const int* d_active = (const int*)(base + o_act);
-  // ---- gather the nominal candidates; an inactive environment's rows are a copy of the first active one's
-  GatherCandidatesArgs<T> g{};
-  g.states = (const T*)c->d_states.p; g.actions = (const T*)c->d_actions.p; g.times = (const T*)c->d_times.p; g.residual = (const T*)c->d_residual.p;
-  g.total_return = (const double*)c->d_ret.p;
-  g.N = c->N; g.H = c->H; g.n_per_env = c->env_n; g.candidate_major = c->traj_candidate_major ? 1 : 0;
-  g.cands = (const int*)(base + o_cand); g.source = (const int*)(base + o_src); g.active = d_active;
-  g.E = E; g.Tn = Tn; g.ne = ne; g.evaluate = d_eval;
-  g.ds_roll = c->nq + c->nv + c->na; g.ds = (int)ds; g.nu = (int)nu; g.nr = (int)nr;
-  g.fd_times = (T*)(base + o_ft); g.fd_states = (T*)(base + o_fs); g.fd_actions = (T*)(base + o_fa);
-  g.residual_out = (double*)(base + o_res); g.actions_out = (double*)(base + o_actions); g.nominal_return = (double*)(base + o_ret);
-  const size_t g_items = sE * (sne * (1 + ds + nu) + sT * (nr + nu) + 1);
-  hipLaunchKernelGGL((gather_candidates_kernel<T>), dim3((unsigned)std::min<size_t>((g_items + 255) / 256, 2048)), dim3(256), 0, c->stream, g);
-  HIPCHK(c, hipGetLastError());
-  // ---- ModelDerivatives::Compute at the evaluated steps of every environment, interpolated to all Tn steps
-  double *dA = (double*)(base + o_A), *dB = (double*)(base + o_B), *dC = (double*)(base + o_C), *dD = (double*)(base + o_D);
-  const FdChain<T> fc{g.fd_times, g.fd_states, g.fd_actions, d_eval, (const T*)(base + o_range), (const int*)(base + o_lim), (T*)(base + o_next),
-                      (T*)(base + o_sens), (double*)(base + o_tan), (double*)(base + o_Ae), (double*)(base + o_Be), (double*)(base + o_Ce),
-                      (double*)(base + o_De), dA, dB, dC, dD};
-  if ((rc = enqueue_fd_chain<T>(c, E, ne, Tn, eps, centered, d_blob, stride, fc)) != MJPCX_OK) return rc;
-  // ---- CostDerivatives::Compute: workgroup e * Tn + t forms step t of environment e (every array is environment-major)
-  double *dcx = (double*)(base + o_cx), *dcu = (double*)(base + o_cu), *dcxx = (double*)(base + o_cxx), *dcxu = (double*)(base + o_cxu), *dcuu = (double*)(base + o_cuu);
-  hipLaunchKernelGGL(cost_derivatives_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32 + 32 * ndx + 32 * nu) * 8, c->stream, cs,
-                     (const double*)g.residual_out, (const double*)dC, (const double*)dD, Tn, (int)ndx, (int)nu, dcx, dcu, dcxx, dcxu, dcuu);
-  HIPCHK(c, hipGetLastError());
-  // ---- the backward pass with its regularisation retries, one workgroup per environment
-  BackwardBatchedArgs b{};
-  b.base.n = (int)ndx; b.base.m = (int)nu; b.base.T = Tn; b.base.reg_type = reg_type; b.base.use_limits = use_limits;
-  b.base.A = dA; b.base.B = dB; b.base.cx = dcx; b.base.cu = dcu; b.base.cxx = dcxx; b.base.cxu = dcxu; b.base.cuu = dcuu;
-  b.base.actions = g.actions_out; b.base.limits = (const double*)(base + o_limits);
-  b.base.Vx = (double*)(base + o_Vx); b.base.Vxx = (double*)(base + o_Vxx); b.base.K = (double*)(base + o_K); b.base.du = (double*)(base + o_du);
-  b.base.dV = (double*)(base + o_dV);
-  b.active = d_active; b.mu = (const double*)(base + o_mu); b.rate = (const double*)(base + o_rate);
-  b.factor = factor; b.min_reg = min_reg; b.max_reg = max_reg; b.max_iter = max_iter;
-  b.status = (int*)(base + o_status); b.retries = (int*)(base + o_retries); b.mu_out = (double*)(base + o_muo); b.rate_out = (double*)(base + o_rateo);
-  const size_t lds = backward_pass_lds_bytes((int)ndx);
-  if (nu <= 12) {  // as mjpcx_backward_pass: the m x m factorisation is unrolled to 12 or 16 columns
-    HIPCHK(c, hipFuncSetAttribute((const void*)backward_pass_batched_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(backward_pass_batched_kernel<12>, dim3(E), dim3(kBackwardThreads), lds, c->stream, b);
-  } else {
-    HIPCHK(c, hipFuncSetAttribute((const void*)backward_pass_batched_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(backward_pass_batched_kernel<16>, dim3(E), dim3(kBackwardThreads), lds, c->stream, b);
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(slot->done, c->stream));
-  slot->pending = true;
-  // ---- results: one block into pinned memory; the optional matrices straight to the caller; ONE sync
-  HIPCHK(c, hipMemcpyAsync(hout, base + o_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  const std::pair<size_t, size_t> where[9] = {{o_A, sT * sA}, {o_B, sT * sB}, {o_cx, sT * ndx}, {o_cu, sT * nu}, {o_cxx, sT * sA}, {o_cxu, sT * sB},
-                                              {o_cuu, sT * nu * nu}, {o_Vx, sT * ndx}, {o_Vxx, sT * sA}};
-  for (int k = 0; k < 9; k++)
-    if (opt[k]) HIPCHK(c, hipMemcpyAsync(opt[k], base + where[k].first, sE * where[k].second * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (nominal_return) std::memcpy(nominal_return, hout + (o_ret - o_out), sE * 8);
-  std::memcpy(K, hout + (o_K - o_out), sE * sT * sB * 8);
-  std::memcpy(du, hout + (o_du - o_out), sE * sT * nu * 8);
-  std::memcpy(dV, hout + (o_dV - o_out), sE * 2 * 8);
-  std::memcpy(mu_out, hout + (o_muo - o_out), sE * 8);
-  std::memcpy(rate_out, hout + (o_rateo - o_out), sE * 8);
-  std::memcpy(status, hout + (o_status - o_out), sE * 4);
-  std::memcpy(retries, hout + (o_retries - o_out), sE * 4);
-  for (int e = 0; e < E; e++) if (candidate[e] < 0) unpack_inactive(e);
-  return MJPCX_OK;
-}
-}  // namespace
-
-extern "C" {
-
 int mjpcx_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int T, int ne, const int32_t* evaluate, double eps, int centered, int reg_type,
                             int use_limits, const double* mu, const double* rate, double factor, double min_reg, double max_reg, int max_iter, double* K,
                             double* du, double* dV, int32_t* status, double* mu_out, double* rate_out, int32_t* retries, double* nominal_return, double* A,
@@ -2790,139 +2721,6 @@ int mjpcx_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int T
                                                            max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt)
                             : do_ilqg_step_batched<float>(c, E, candidate, T, ne, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg,
                                                           max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt);
-}
-
-}  // extern "C"
-
-namespace {
-// mjpcx_rollout_feedback_batched after validation: the environments' plan records (stage_plan_inputs), the six policy arrays through ONE
-// pinned block and ONE H2D copy, then the launch of mjpcx_rollout_feedback's kernels with the environment selection switched on
-template <typename T>
-int do_feedback_batched(mjpcx_ctx* c, int E, int n, int H, int mode, int representation, int use_state, int Tn, const double* times,
-                        const double* states, const double* actions, const double* gains, const double* improvement, const double* alpha) {
-  int rc;
-  const int N = E * n;
-  if ((rc = reserve_rollout(c, N, H, 1)) != MJPCX_OK) return rc;
-  const size_t ds = c->nq + c->nv, ndx = 2 * (size_t)c->nv, nu = c->nu, sET = (size_t)E * Tn;
-  // the environments' plan records, restaged: a preceding rollout's slot may have been recycled since
-  const T *d_rec_times, *d_rec_nominal;
-  const double* d_rec_var;
-  const void* d_blob = nullptr;
-  mjpcx_ctx::Slot* slot = nullptr;
-  unsigned stride = 0;
-  if ((rc = stage_plan_inputs<T>(c, 0, E, nullptr, nullptr, nullptr, false, &d_rec_times, &d_rec_nominal, &d_rec_var, &slot, &d_blob, &stride)) != MJPCX_OK)
-    return rc;
-  // [times | states | actions | gains | improvement | alpha] in the context's precision, each on a 16-byte boundary
-  const std::pair<const double*, size_t> arrays[6] = {{times, sET}, {states, sET * ds}, {actions, sET * nu}, {gains, sET * nu * ndx},
-                                                      {improvement, sET * nu}, {alpha, (size_t)N}};
-  size_t off[6], total = 0;
-  for (int k = 0; k < 6; k++) { off[k] = total; total += (arrays[k].second + 3) & ~(size_t)3; }
-  const size_t bytes = total * sizeof(T);
-  if (c->fb_pending) { HIPCHK(c, hipEventSynchronize(c->fb_done)); c->fb_pending = false; }
-  if (!c->fb_done) HIPCHK(c, hipEventCreateWithFlags(&c->fb_done, hipEventDisableTiming));
-  if (bytes > c->fb_cap) {
-    if (c->fb_host) (void)hipHostFree(c->fb_host);
-    c->fb_host = nullptr; c->fb_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->fb_host, bytes, hipHostMallocDefault));
-    c->fb_cap = bytes;
-  }
-  HIPCHK(c, c->d_ilqg.reserve(bytes));
-  T* host = (T*)c->fb_host;
-  for (int k = 0; k < 6; k++)
-    for (size_t i = 0; i < arrays[k].second; i++) host[off[k] + i] = (T)arrays[k].first[i];
-  HIPCHK(c, hipMemcpyAsync(c->d_ilqg.p, host, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->fb_done, c->stream));
-  c->fb_pending = true;
-  const T* d[6];
-  for (int k = 0; k < 6; k++) d[k] = (const T*)c->d_ilqg.p + off[k];
-  RolloutArgs<T> a{};
-  a.N = N; a.H = H; a.P = c->wave ? 1 : 0; a.interp = 0; a.nodes = (T*)c->d_nodes.p; a.noise.mode = -1;
-  a.states = (T*)c->d_states.p; a.actions = (T*)c->d_actions.p; a.times = (T*)c->d_times.p;
-  a.residual = (T*)c->d_residual.p; a.costs = (T*)c->d_costs.p; a.trace = (T*)c->d_trace.p;
-  a.total_return = (double*)c->d_ret.p; a.failure = (int*)c->d_fail.p;
-  auto finish = [&]() {
-    HIPCHK(c, hipEventRecord(slot->done, c->stream));
-    slot->pending = true;
-    c->N = N; c->H = H; c->P = a.P; c->env_n = n;
-    c->have_rollout = true;
-    c->traj_candidate_major = c->wave;
-    return (int)MJPCX_OK;
-  };
-  if (!c->wave) {
-    FeedbackArgs<T> fb{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
-    fb.env_n = n; fb.env_waves = (n + 63) / 64; fb.env_stride = stride; fb.init = (const LaneInit<T>*)d_blob;
-    hipError_t le;
-    if constexpr (sizeof(T) == 8) le = c->kernel->feedback64(c->hm64, c->ht64, a, fb, c->stream);
-    else { convert_task(c->ht32, c->ht64); le = c->kernel->feedback32(c->hm32, c->ht32, a, fb, c->stream); }
-    if (le != hipSuccess) return fail(c, MJPCX_EDEVICE, std::string("feedback kernel launch: ") + hipGetErrorString(le));
-    return finish();
-  }
-  if constexpr (sizeof(T) == 8) {
-    WaveTask wt = c->wh.t;
-    wt.blob = (const double*)d_blob;
-    wt.stamps = nullptr;
-    wt.stamp_step = 0;
-    w64::FeedbackWaveArgs fb{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state, 0, n, stride};
-    const bool tree = c->wh.tree_ok && !c->no_tree;
-    // the quad form first, as in the plain call; the candidates it hands on -- of whichever environments -- go to the tree / wave kernel
-    if (c->quad_ok && !c->no_quad_feedback && c->wh.m.integrator == MJPCX_INT_EULER) {
-      quad::QArgs q{};
-      q.N = N; q.H = H; q.P = 1; q.noise_mode = -1; q.nodes = (double*)c->d_nodes.p;
-      q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
-      q.total_return = a.total_return; q.failure = a.failure; q.con_cap = c->quad_con_cap; q.cpw = 1;
-      q.env_n = n; q.env_stride = stride;
-      const quad::QBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
-      const quad::QFeedback qf{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
-      HIPCHK(c, hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream));
-      HIPCHK(c, quad::launch_feedback_quad(c->d_qmodel.p, c->d_qtab.p, wt.blob, bo, q, qf, (int*)c->d_qstats.p, c->stream));
-      if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 32, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
-      bool handed_on = true;
-      if (c->h_qstats) {  // (the one sync of the call: the hand-on count)
-        HIPCHK(c, hipMemcpyAsync(c->h_qstats, c->d_qstats.p, 32, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        handed_on = static_cast<const int*>(c->h_qstats)[0] != 0;
-      }
-      if (!handed_on) return finish();
-      fb.only_flagged = 1;
-    }
-    const int Ppolicy = tree ? (int)(ndx + 2 * ds) : (int)((ndx + 2 * ds + nu - 1) / nu + 1);
-    const size_t lds = wave_lds_bytes(c, Ppolicy, tree);
-    const bool rk4 = c->wh.m.integrator == MJPCX_INT_RK4;
-    HIPCHK(c, launch_feedback_wave(c->wh.m, wt, a, fb, N, lds, tree, rk4, c->wh.registered == 0 ? c->wh.dev_image : nullptr, c->wh.blob_bytes, c->stream));
-    return finish();
-  }
-  return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
-}
-}  // namespace
-
-extern "C" {
-
-int mjpcx_rollout_feedback_batched(mjpcx_ctx* c, int E, int n, int H, int mode, int representation, int use_state, int Tn, const double* times,
-                                   const double* states, const double* actions, const double* gains, const double* improvement,
-                                   const double* alpha) {
-  const char* who = "mjpcx_rollout_feedback_batched: ";
-  if (!c || !times || !states || !actions || !gains || !improvement || !alpha) return fail(c, MJPCX_EINVAL, std::string(who) + "null argument");
-  if (E < 1) return fail(c, MJPCX_EINVAL, std::string(who) + "the number of environments must be >= 1");
-  if (n < 1 || H < 1 || Tn < 1) return fail(c, MJPCX_EINVAL, std::string(who) + "n_per_env, H and Tn must be >= 1");
-  if ((long long)E * n > 0x7fffffffLL / 64 || (long long)E * Tn * (1 + 2 * c->nv * c->nu) > 0x7fffffffLL / 64)
-    return fail(c, MJPCX_EINVAL, std::string(who) + "too many candidates or steps");
-  if (mode == 0 && H > Tn) return fail(c, MJPCX_EINVAL, std::string(who) + "index policy needs a nominal trajectory at least as long as the horizon");
-  if (mode != 0 && mode != 1) return fail(c, MJPCX_EINVAL, std::string(who) + "unknown feedback policy mode");
-  if (mode == 1 && (representation < 0 || representation > 2))
-    return fail(c, MJPCX_EINVAL, std::string(who) + "iLQG policy representation must be 0 (zero-order), 1 (linear) or 2 (cubic)");
-  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "not implemented on a context sharded with mjpcx_comm_init");
-  if (c->xfrc_std > 0) return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "xfrc noise (NoisyRollout) is not implemented for batched rollouts");
-  if (c->env_E != E)
-    return fail(c, MJPCX_EINVAL, c->env_E == 0 ? std::string(who) + "before mjpcx_set_states"
-                                               : std::string(who) + std::to_string(E) + " environments after mjpcx_set_states of " + std::to_string(c->env_E));
-  if (c->wave && c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!c->wave) {
-    const size_t shmem = (size_t)Tn * (1 + 2 * c->nv + 2 * c->nu + c->nu * 2 * c->nv) * esize(c);
-    if (shmem > 120 * 1024) return fail(c, MJPCX_EUNSUPPORTED, "nominal trajectory too large for the LDS stage");
-  }
-  return c->precision == 64 ? do_feedback_batched<double>(c, E, n, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha)
-                            : do_feedback_batched<float>(c, E, n, H, mode, representation, use_state, Tn, times, states, actions, gains, improvement, alpha);
 }
 
 }  // extern "C"

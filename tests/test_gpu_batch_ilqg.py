@@ -84,7 +84,7 @@ class Case:
 
     def make_context(self):
         ctx = context(self.pm, step_bank.packed_task(self.task, self.states[0]), self.precision, self.env)
-        assert self.kernel in ctx.kernel_name, ctx.kernel_name   # (the context's family decides the feedback kernel: mjpcx.hip, do_feedback_wave)
+        assert self.kernel in ctx.kernel_name, ctx.kernel_name   # (the context's family decides the feedback kernel: mjpcx.hip, do_feedback)
         return ctx
 
     def mocap(self, e):
@@ -269,6 +269,43 @@ def test_plain_call_is_untouched_by_a_batched_one(name):
     for k in ("total_return", "failure") + FIELDS:
         assert np.array_equal(before[k], after[k]), k
     ctx.close()
+
+
+def test_a_plain_feedback_rollout_ends_the_batched_one():
+    """mjpcx_rollout_feedback resets the context's candidates-per-environment like every plain rollout. After a batched feedback
+    rollout of E x n candidates and then a plain one of N = E * n, mjpcx_ilqg_step_batched and mjpcx_gradient_step_batched refuse -- the
+    shape alone (E * n == N, E environments set) would let them gather "environment e's candidate" from a rollout that had no
+    environments -- and a batched rollout + iLQG step after that equal the same pair on a fresh context bit for bit.
+    Cartpole fp64, E = 2, n = 3, H = Tn = 6."""
+    case = make_case("cartpole64")
+    envs, n = [0, 1], 3
+    pol = case.policy(envs, n)
+    ev = np.arange(H, dtype=np.int32)
+    step = dict(T=H, evaluate=ev, eps=1e-6, centered=0, reg_type=0, use_limits=1, mu=np.full(2, 1e-3), rate=np.ones(2), factor=2.0,
+                min_reg=1e-6, max_reg=1e6, max_iter=5)
+
+    def batched_pair(ctx):
+        case.run_batched(ctx, envs, pol, H, 0, 0, 1)
+        return ctx.ilqg_step_batched([0, 0], **step)
+
+    ctx = case.make_context()
+    case.run_batched(ctx, envs, pol, H, 0, 0, 1)
+    flat = [np.concatenate([p[0], p[0]]) if k == 5 else p[0] for k, p in enumerate(pol)]    # one nominal, N = 6 step sizes
+    case.run_plain(ctx, 0, flat, H, 0, 0, 1)
+    assert ctx.N == len(envs) * n
+    with pytest.raises(capi.MjpcxError, match="the last rollout was not a batched one") as e:
+        ctx.ilqg_step_batched([0, 0], **step)
+    assert e.value.code == -1
+    with pytest.raises(capi.MjpcxError, match="the last rollout was not a batched one") as e:
+        ctx.gradient_step_batched(2, 0, H, ev, 1e-6, 0, 1, np.tile(np.linspace(0.0, 0.05, 3), (2, 1)))
+    assert e.value.code == -1
+    got = batched_pair(ctx)
+    ctx.close()
+    fresh = case.make_context()
+    ref = batched_pair(fresh)
+    fresh.close()
+    for k in ("K", "du", "dV"):
+        assert np.array_equal(got[k], ref[k]), k
 
 
 def test_refusals():
