@@ -87,7 +87,11 @@ struct LdsStore { qlds_f64* lds; double* ovf; };
 #define QOVF_STRIDE 64
 #endif
 struct LdsM { qlds_f64* ml; qlds_f64* mt; };
+#ifndef QEXP_SUBSTAMPS
 struct QProf { long long* buf; long long last; };
+#else
+struct QProf { long long* buf; long long last, sub; };  // (sub: the sub-stamps' clock)
+#endif
 } }
 __device__ __forceinline__ void qcs_load(const mjpcx::quad::LdsStore& cs, int slot, mjpcx::quad::QContact& c);
 __device__ __forceinline__ void qcs_store(mjpcx::quad::LdsStore& cs, int slot, const mjpcx::quad::QContact& c);
@@ -101,6 +105,18 @@ __device__ __forceinline__ void qms_set_t(mjpcx::quad::LdsM& m, int i, double v)
 // phase cycle stamps of wavefront 0 (pf.buf != nullptr only there): s_memtime deltas accumulated per phase
 #define QPROF(pf, idx) do { if ((pf).buf) { const long long now_ = __builtin_readcyclecounter(); (pf).buf[idx] += now_ - (pf).last; (pf).last = now_; } } while (0)
 #define QPROF_COUNT(pf, idx, n) do { if ((pf).buf) (pf).buf[idx] += (n); } while (0)
+// sub-stamps inside a phase (a QEXP_SUBSTAMPS build only -- they cost the forward pass registers; slots 46..63, named by tools/quad_prof.py
+// --stamps): QPROF_T0 starts their clock (pf.sub), QPROF_SUB adds the cycles since to buf[idx] and moves it on; the phase stamps keep their own
+// clock (pf.last), so a phase's total still holds what they split. QPROF_SUBCOUNT: a counter of such a build
+#ifdef QEXP_SUBSTAMPS
+#define QPROF_T0(pf) do { if ((pf).buf) (pf).sub = __builtin_readcyclecounter(); } while (0)
+#define QPROF_SUB(pf, idx) do { if ((pf).buf) { const long long now_ = __builtin_readcyclecounter(); (pf).buf[idx] += now_ - (pf).sub; (pf).sub = now_; } } while (0)
+#define QPROF_SUBCOUNT(pf, idx, n) QPROF_COUNT(pf, idx, n)
+#else
+#define QPROF_T0(pf)
+#define QPROF_SUB(pf, idx)
+#define QPROF_SUBCOUNT(pf, idx, n)
+#endif
 // buf[idx + k] += 1 if any lane of the wavefront has v > bound_k (bounds 0 1 2 3 4 6 8 12), buf[idx + 8] += the sum of v over the lanes, buf[idx + 9] += the largest
 #define QPROF_WAVE_HIST(pf, idx, v) do { if ((pf).buf) { const int b_[8] = {0, 1, 2, 3, 4, 6, 8, 12}; \
     for (int k_ = 0; k_ < 8; k_++) if (__ballot((v) > b_[k_])) (pf).buf[(idx) + k_] += 1; \

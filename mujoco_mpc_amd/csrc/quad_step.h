@@ -31,6 +31,9 @@
 #define QPROF(pf, idx)
 #define QPROF_COUNT(pf, idx, n)
 #define QPROF_WAVE_HIST(pf, idx, v)
+#define QPROF_T0(pf)
+#define QPROF_SUB(pf, idx)
+#define QPROF_SUBCOUNT(pf, idx, n)
 #define QWAVE_TIMES(a, iters, general, ncon)
 #endif
 #ifndef QCLASS_NOW
@@ -147,6 +150,11 @@ QD void cross_force(double* res, const double* vel, const double* f) {
 QD double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // solimp (digested: quad_model.h) -> impedance at violation `dist` (oracle impedance())
+// (a power other than 1 or 2: out of line -- inlined, the expansions of pow sat in the contact-creation loops of the floor and
+// self-collision stages and in the joint-limit rows, and the A1 never takes them: 48.79 -> 48.54 ms on the bench's launches, same box)
+QNOINLINE double impedance_power(double x, double mid, double power) {
+  return x <= mid ? pow(x, power) / pow(mid, power - 1) : 1 - pow(1 - x, power) / pow(1 - mid, power - 1);
+}
 QD double impedance(const double* d, double dist) {
   const double dmin = d[0], dmax = d[1], width = d[2], mid = d[3], power = d[4];
   if (dmin == dmax || width <= kQMinVal) return 0.5 * (dmin + dmax);
@@ -156,7 +164,7 @@ QD double impedance(const double* d, double dist) {
   double y;
   if (power == 1) y = x;
   else if (power == 2) y = x <= mid ? x * x / mid : 1 - (1 - x) * (1 - x) / (1 - mid);
-  else y = x <= mid ? pow(x, power) / pow(mid, power - 1) : 1 - pow(1 - x, power) / pow(1 - mid, power - 1);
+  else y = impedance_power(x, mid, power);
   return dmin + y * (dmax - dmin);
 }
 QD void make_frame(double* frame) {
@@ -1293,8 +1301,32 @@ QD int static_near_mask(const QuadModel& m, const QStaticPose* sp, const double*
   }
   return near;
 }
-template <class CS>
-QD void collide_geom(const QuadModel& m, const QStaticPose* sp, const QuadGeom& g, int near, const QuadPair* pairs /* [kQStatic] stride: QEXP_SPAIR_GLOBAL only */, int pair_stride, const double* com, const double* cvel, int depth, const double* gp, const double* gR, CS& cs, int& ncon, int& flags) {
+// Whether collide_geom can find anything for this geom (centre gp, axis ga = the third column of its world orientation): its own bounding
+// tests, taken BEFORE the geom's orientation is formed, and against a plane with the geom's lowest point instead of its bounding sphere --
+// centre height minus the extent along the normal (sphere: the radius; capsule, cylinder: half length x |axis . normal| + radius; box: the
+// bounding radius). That is a lower bound of the distance of every candidate point collide_geom forms, and contact margins are below 9 mm
+// (quad_build), so a geom cleared here creates no contact: skipping it leaves the contact list as it was, bit for bit.
+QD bool static_pretest(const QuadModel& m, const QStaticPose* sp, const QuadGeom& g, int near, const double* gp, const double* ga) {
+  bool hit = false;
+  QNOUNROLL for (int s = 0; s < m.nstatic; s++) {
+    if (((near >> s) & 1) == 0) continue;
+    const QuadStatic& S = m.stat[s];
+    if (S.type < 0 || !((g.static_mask >> s) & 1)) continue;
+    const double* p1 = sp[s].pos; const double* R1 = sp[s].mat;
+    const double rel[3] = {gp[0] - p1[0], gp[1] - p1[1], gp[2] - p1[2]};
+    if (S.type == MJPCX_GEOM_PLANE) {
+      const double cdist = rel[0] * R1[2] + rel[1] * R1[5] + rel[2] * R1[8], an = ga[0] * R1[2] + ga[1] * R1[5] + ga[2] * R1[8];
+      const double ext = g.type == MJPCX_GEOM_SPHERE ? g.size[0] : (g.type == MJPCX_GEOM_CAPSULE || g.type == MJPCX_GEOM_CYLINDER) ? g.size[1] * fabs(an) + g.size[0] : g.bound;
+      hit = hit || cdist - ext < 0.01;
+    } else if (g.type == MJPCX_GEOM_SPHERE) {  // (static spheres and boxes collide with moving spheres only: collide_geom's own reach tests)
+      const double reach = (S.type == MJPCX_GEOM_SPHERE ? S.size[0] : S.bound) + g.size[0] + 0.01;
+      hit = hit || rel[0] * rel[0] + rel[1] * rel[1] + rel[2] * rel[2] < reach * reach;
+    }
+  }
+  return hit;
+}
+template <class CS, class QProfT>
+QD void collide_geom(const QuadModel& m, const QStaticPose* sp, const QuadGeom& g, int near, const QuadPair* pairs /* [kQStatic] stride: QEXP_SPAIR_GLOBAL only */, int pair_stride, const double* com, const double* cvel, int depth, const double* gp, const double* gR, CS& cs, int& ncon, int& flags, QProfT& pf) {
   QNOUNROLL for (int s = 0; s < m.nstatic; s++) {
     if (((near >> s) & 1) == 0) continue;
     const QuadStatic& S = m.stat[s];
@@ -1409,10 +1441,13 @@ QD void collide_geom(const QuadModel& m, const QStaticPose* sp, const QuadGeom& 
     if (nc == 0) continue;
     // the pair's contacts, in the candidates' order: one instance of the contact's creation, the candidates shifted through slot 0
     const QSPAIR_T& p = QSPAIR(m, g, s);
+    QPROF_SUB(pf, 47);
     QNOUNROLL for (int k = 0; k < nc; k++) {
+      QPROF_SUBCOUNT(pf, 49, 1);
       add_contact(p, com, cvel, depth, cd[0], cp[0], cn, cs, ncon, flags);
       QUNROLL for (int j = 0; j < 3; j++) { cd[j] = cd[j + 1]; QUNROLL for (int c = 0; c < 3; c++) cp[j][c] = cp[j + 1][c]; }
     }
+    QPROF_SUB(pf, 48);
   }
 }
 
@@ -1468,6 +1503,7 @@ QNOINLINE void pair_contacts_tests(const QuadModel& m_in, const QuadTables& tab,
   const QuadModel& m = QREBIND_LDS(QuadModel, m_in);
   auto* args = QREBIND_PRIVATE(QPairArgs, args_in);
   QProfT pf = pf_in;
+  QPROF_SUB(pf, 51);
 #ifdef QEXP_NEED_MASK
   const int need = args->need & (QEXP_NEED_MASK);  // (tuning: which of the sources below the time goes to)
 #else
@@ -1497,11 +1533,13 @@ QNOINLINE void pair_contacts_tests(const QuadModel& m_in, const QuadTables& tab,
   }
   const double bmg = mg + 1e-9;
   double oc[kQPairGeom][3], oa[kQPairGeom][3], ov[3][6];
+  QPROF_SUB(pf, 52);
   for (int src = 0; src < 5; src++) {  // 0: the trunk's pair geoms, 1: the own leg (its cylinders), 2..4: the leg d = src - 1 lanes on
     const bool mine = ((need >> src) & 1) != 0;
     if (qd_or(mine ? 1 : 0) == 0) continue;  // (quad-uniform; the bits of the other legs are quad-uniform themselves)
     const int d = src - 1, o = src == 0 ? kQLegs : (src == 1 ? leg : ((leg + d) & 3));
     const int on = !mine ? 0 : (src == 0 ? m.ntpg : m.leg[o & 3].npg);
+    QPROF_SUBCOUNT(pf, 54, 1);
     // the pretest: a ROLLED loop over the other side's geoms (centre and half extents of geom j arrive -- through the quad rotation for
     // another leg -- and meet the eight own geoms in registers): a hundred instructions instead of the 8 x 8 grid unrolled
     unsigned long long mask = 0;
@@ -1529,6 +1567,7 @@ QNOINLINE void pair_contacts_tests(const QuadModel& m_in, const QuadTables& tab,
       }
     }
     mask &= L.pg_active[o];
+    QPROF_SUB(pf, 53);
     if (src >= 2) {
       if (qd_or(mask != 0 ? 1 : 0) == 0) continue;  // (quad-uniform: the axes and velocities are only fetched for a partner that is near)
       for (int j = 0; j < kQPairGeom; j++) for (int k = 0; k < 3; k++) { oc[j][k] = qd_rotv(args->pg.c[j][k], d); oa[j][k] = qd_rotv(args->pg.a[j][k], d); }
@@ -1549,6 +1588,7 @@ QNOINLINE void pair_contacts_tests(const QuadModel& m_in, const QuadTables& tab,
         for (int j = 0; j < 3; j++) for (int k = 0; k < 6; k++) ov[j][k] = args->cvel[j][k];
       }
     }
+    QPROF_SUB(pf, 55);
     while (mask) {  // (ascending bits: own geom first, then the other's -- the order contacts are created in)
       const int bit = __builtin_ctzll(mask);
       mask &= mask - 1;
@@ -1655,6 +1695,7 @@ QNOINLINE void pair_contacts_tests(const QuadModel& m_in, const QuadTables& tab,
         }
       }
     }
+    QPROF_SUB(pf, 56);
   }
   args->ncon = ncon; args->flags = flags; args->pmask = pmask; args->nrel = nrel;
   pf_in = pf;
@@ -1692,6 +1733,7 @@ QD void pair_contacts(const QuadModel& m, const QuadTables& tab, int leg, QPairA
 #endif
   const double* blo = bx.blo; const double* bhi = bx.bhi; const double* tlo = bx.tlo; const double* thi = bx.thi;
   const double bmg = mg + 1e-9;
+  QPROF_T0(pf);  // (sub-stamps 50..57: cull, hand-over + call, own boxes, pretests, fetch, exact tests, return)
   bool trunk_near = L.pg_active[kQLegs] != 0;
   QUNROLL for (int k = 0; k < 3; k++) trunk_near = trunk_near && !(tlo[k] > m.tpg_box[1][k] + bmg) && !(m.tpg_box[0][k] > thi[k] + bmg);
   int need = (trunk_near ? 1 : 0) | ((L.pg_active[leg] != 0 && self_walk) ? 2 : 0);
@@ -1703,6 +1745,7 @@ QD void pair_contacts(const QuadModel& m, const QuadTables& tab, int leg, QPairA
     }
     need |= qd_or(apart ? 0 : 1) << (1 + d);  // (quad-uniform: clear only if all four (leg, leg + d) pairs are)
   }
+  QPROF_SUB(pf, 50);
   if (qd_or(need) == 0) return;
 #ifdef QEXP_PAIRS_SKIP2
   if (mg > -1.0) return;  // (tuning: the leg-level cull runs, the tests never do)
@@ -1712,8 +1755,10 @@ QD void pair_contacts(const QuadModel& m, const QuadTables& tab, int leg, QPairA
   QUNROLL for (int j = 0; j < 3; j++) QUNROLL for (int k = 0; k < 6; k++) args.cvel[j][k] = cvel[j][k];
   QUNROLL for (int k = 0; k < 6; k++) args.cvelT[k] = cvelT[k];
   args.need = need; args.ncon = ncon; args.flags = flags; args.pmask = pmask; args.nrel = nrel;
+  QPROF_SUBCOUNT(pf, 58, 1);
   pair_contacts_tests(m, tab, leg, &args, cs, pf);
   ncon = args.ncon; flags = args.flags; pmask = args.pmask; nrel = args.nrel;
+  QPROF_SUB(pf, 57);
 }
 
 // ---------------------------------------------------------------- mj_forward (oracle o_forward) for the lane's share of one candidate
@@ -1913,33 +1958,62 @@ QD int forward_smooth(const QuadModel& m, const QuadTables& tab, const QStaticPo
     QPairArgs pargs;  // (the self-collision tests' argument block: in memory -- they are out of line; the loop below writes the pair geoms' poses into it)
     QPairBoxes pbox;
     pair_boxes_init(pbox);
+    QPROF_T0(pf);  // (sub-stamps 46..48: pose + boxes, bounding test + candidate points, contact creation)
     for (int i = 0; i < kQPairGeom; i++) for (int k = 0; k < 3; k++) { pargs.pg.c[i][k] = 0; pargs.pg.a[i][k] = 0; }
-    for (int gi = 0; gi < L.ngeom; gi++) {
-      const QuadGeom& g = L.geom[gi];
-      double gp[3], gR[9];
+    // A geom goes on to its orientation and to collide_geom only if static_pretest leaves something to find for SOME lane of the wavefront
+    // -- in a gait that is the feet and the calves; hips, thighs and the trunk's geoms cost their centre and axis. (The ballot only decides
+    // whether the wavefront walks the code: a lane's own contacts do not depend on the other lanes. Trip counts are the wavefront's -- the
+    // legs' largest geom count, the largest share of the trunk's geoms: a lane without a geom at some trip only takes part in the ballot.)
+    int nleg = m.leg[0].ngeom;
+    QUNROLL for (int k = 1; k < kQLegs; k++) nleg = m.leg[k].ngeom > nleg ? m.leg[k].ngeom : nleg;
+    for (int gi = 0; gi < nleg; gi++) {
+      const bool have = gi < L.ngeom;
+      const QuadGeom& g = L.geom[have ? gi : 0];
+      double gp[3], ga[3];
       const int lk = g.link;
-      double bm[9], bp[3], bv[6];
+      double bm[9], bp[3];
       QUNROLL for (int k = 0; k < 9; k++) bm[k] = lk == 0 ? xmat[0][k] : (lk == 1 ? xmat[1][k] : xmat[2][k]);
       QUNROLL for (int k = 0; k < 3; k++) bp[k] = lk == 0 ? xpos[0][k] : (lk == 1 ? xpos[1][k] : xpos[2][k]);
-      QUNROLL for (int k = 0; k < 6; k++) bv[k] = lk == 0 ? cvel[0][k] : (lk == 1 ? cvel[1][k] : cvel[2][k]);
       mv3(gp, bm, g.pos);
       QUNROLL for (int k = 0; k < 3; k++) gp[k] += bp[k];
-      QUNROLL for (int r = 0; r < 3; r++) QUNROLL for (int c = 0; c < 3; c++) gR[3 * r + c] = bm[3 * r] * g.rot[c] + bm[3 * r + 1] * g.rot[3 + c] + bm[3 * r + 2] * g.rot[6 + c];
-      if (gi == L.foot_slot) { QUNROLL for (int k = 0; k < 3; k++) out.foot[k] = gp[k]; }
-      if (g.pgi >= 0) {  // a pair geom: its pose to the tests' argument block (memory, run-time slot), its box into the cull's
-        const double ga[3] = {gR[2], gR[5], gR[8]};
+      QUNROLL for (int r = 0; r < 3; r++) ga[r] = bm[3 * r] * g.rot[2] + bm[3 * r + 1] * g.rot[3 + 2] + bm[3 * r + 2] * g.rot[6 + 2];
+      if (have && g.pgi >= 0) {  // a pair geom: its pose to the tests' argument block (memory, run-time slot), its box into the cull's
         for (int k = 0; k < 3; k++) { pargs.pg.c[g.pgi][k] = gp[k]; pargs.pg.a[g.pgi][k] = ga[k]; }
         pair_boxes_add(L, g.pgi, gp, ga, txpos, txm, pbox);
       }
-      collide_geom(m, sp, g, near_leg, &tab.leg[leg][0][gi], kQLegGeom, com, bv, lk + 1, gp, gR, cs, ncon, flags);
+      QPROF_SUB(pf, 46);
+      const bool hit = have && static_pretest(m, sp, g, near_leg, gp, ga);
+      if (!qw_any(hit)) { QPROF_SUB(pf, 47); QPROF_SUBCOUNT(pf, 59, 1); continue; }
+      double gR[9], bv[6];
+      QUNROLL for (int r = 0; r < 3; r++) QUNROLL for (int c = 0; c < 3; c++) gR[3 * r + c] = bm[3 * r] * g.rot[c] + bm[3 * r + 1] * g.rot[3 + c] + bm[3 * r + 2] * g.rot[6 + c];
+      QUNROLL for (int k = 0; k < 6; k++) bv[k] = lk == 0 ? cvel[0][k] : (lk == 1 ? cvel[1][k] : cvel[2][k]);
+      QPROF_SUB(pf, 46);
+      if (hit) collide_geom(m, sp, g, near_leg, &tab.leg[leg][0][gi], kQLegGeom, com, bv, lk + 1, gp, gR, cs, ncon, flags, pf);
+      QPROF_SUB(pf, 47);
     }
-    for (int gi = leg; gi < m.ntrunk_geom; gi += kQLegs) {
-      const QuadGeom& g = m.trunk_geom[gi];
-      double gp[3], gR[9];
+    {  // the foot the residual reads: its centre as the loop above formed it (once, not a select per geom that keeps QSense alive in the loop)
+      const QuadGeom& g = L.geom[L.foot_slot];
+      const int lk = g.link;
+      double gp[3], bm[9];
+      QUNROLL for (int k = 0; k < 9; k++) bm[k] = lk == 0 ? xmat[0][k] : (lk == 1 ? xmat[1][k] : xmat[2][k]);
+      mv3(gp, bm, g.pos);
+      QUNROLL for (int k = 0; k < 3; k++) out.foot[k] = gp[k] + (lk == 0 ? xpos[0][k] : (lk == 1 ? xpos[1][k] : xpos[2][k]));
+    }
+    for (int gi = leg; gi - leg < m.ntrunk_geom; gi += kQLegs) {  // (the trips of the lane with the largest share)
+      const bool have = gi < m.ntrunk_geom;
+      const QuadGeom& g = m.trunk_geom[have ? gi : 0];
+      double gp[3], ga[3];
       mv3(gp, txm, g.pos);
       QUNROLL for (int k = 0; k < 3; k++) gp[k] += txpos[k];
+      QUNROLL for (int r = 0; r < 3; r++) ga[r] = txm[3 * r] * g.rot[2] + txm[3 * r + 1] * g.rot[3 + 2] + txm[3 * r + 2] * g.rot[6 + 2];
+      QPROF_SUB(pf, 46);
+      const bool hit = have && static_pretest(m, sp, g, near_trunk, gp, ga);
+      if (!qw_any(hit)) { QPROF_SUB(pf, 47); QPROF_SUBCOUNT(pf, 59, 1); continue; }
+      double gR[9];
       QUNROLL for (int r = 0; r < 3; r++) QUNROLL for (int c = 0; c < 3; c++) gR[3 * r + c] = txm[3 * r] * g.rot[c] + txm[3 * r + 1] * g.rot[3 + c] + txm[3 * r + 2] * g.rot[6 + c];
-      collide_geom(m, sp, g, near_trunk, &tab.trunk[0][gi], kQTrunkGeom, com, cvelT, 0, gp, gR, cs, ncon, flags);
+      QPROF_SUB(pf, 46);
+      if (hit) collide_geom(m, sp, g, near_trunk, &tab.trunk[0][gi], kQTrunkGeom, com, cvelT, 0, gp, gR, cs, ncon, flags, pf);
+      QPROF_SUB(pf, 47);
     }
     QPROF(pf, 2);
     int pmask = 0, nrel = 0;

@@ -3,6 +3,17 @@
 for the quad kernel (kernel trace, PMC passes)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+# python tools/quad_prof.py --stamps LOG: the sub-stamps of a QEXP_SUBSTAMPS build (quad_kernel.h; slots 46..63 of the "raw counters 40..63"
+# lines an MJPCX_QUAD_STAMPS=1 run prints) with their names, per launch: cycles of wavefront 0 over the launch's steps, counts per launch
+SUB = {46: "floor: centre + axis + pair boxes, orientation", 47: "floor: bounding tests + candidate points", 48: "floor: contact creation",
+       49: "#floor: contact-creation trips", 50: "pairs: leg-level cull", 51: "pairs: hand-over + call", 52: "pairs: own geoms' boxes",
+       53: "pairs: pretests", 54: "#pairs: sources walked", 55: "pairs: partner fetch", 56: "pairs: exact tests", 57: "pairs: return",
+       58: "#pairs: calls of the tests", 59: "#floor: geoms the wavefront skipped"}
+if len(sys.argv) > 2 and sys.argv[1] == "--stamps":
+    rows = [[int(x) for x in l.split(":")[1].split()] for l in open(sys.argv[2]) if "raw counters 40..63" in l]
+    for k, name in sorted(SUB.items()):
+        print(f"{k:3d} {name:52s}" + "".join(f"{r[k - 40]:>10d}" for r in rows))
+    sys.exit(0)
 import numpy as np
 from mujoco_mpc_amd import capi
 from mujoco_mpc_amd.task import load_task
