@@ -325,7 +325,8 @@ int mjpcx_set_residual_state(mjpcx_ctx* ctx, const int32_t* residual_int, const 
 
 /* ---- several environments in one launch ---------------------------------------
  * An environment is one robot: its own state, clock, mocap pose, userdata and nominal spline. All environments of a context
- * share the model, the task weights and parameters, the horizon and the spline shape (P nodes, interpolation); the frozen
+ * share the model, the norm kinds and term dimensions, the horizon and the spline shape (P nodes, interpolation); the task weights,
+ * norm parameters, parameters and risk are shared unless mjpcx_set_task_params_batched gives each environment its own, and the frozen
  * residual state is shared unless mjpcx_set_residual_states gives one per environment. Candidates are environment-major: global
  * candidate c = e * n_per_env + i, and every getter (mjpcx_get_returns, mjpcx_get_return_at, mjpcx_fetch_trajectory,
  * mjpcx_fetch_spline, mjpcx_device_buffer) takes the global index. The rollout kernel is chosen from the TOTAL E * n_per_env, by the
@@ -346,6 +347,21 @@ int mjpcx_set_states(mjpcx_ctx* ctx, int num_envs, const double* states, const d
  * robots are not in the same mode or gait phase. After mjpcx_set_states with the same E. A later plain
  * mjpcx_set_residual_state applies to all environments again. */
 int mjpcx_set_residual_states(mjpcx_ctx* ctx, int num_envs, const int32_t* residual_int, const double* residual_real);
+
+/* mjpcx_set_task_params per environment: weight E x num_term, norm_parameter E x (sum of num_norm_parameter), parameters
+ * E x num_parameter, risk E. Any pointer may be NULL: that field is the context's (mjpcx_set_task_params) for every environment.
+ * All four NULL: everything shared again. After mjpcx_set_states with the same E (MJPCX_EINVAL otherwise).
+ *   - Every batched entry point reads the rows: mjpcx_rollout_splines_batched, mjpcx_rollout_noise_batched,
+ *     mjpcx_rollout_noise_batched_ce, mjpcx_rollout_feedback_batched, mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched.
+ *     Environment e of such a call behaves exactly like the plain call after mjpcx_set_task_params(row e): equal bits.
+ *   - mjpcx_set_task_params and the plain entry points neither read nor clear the rows: plain and batched values live side by
+ *     side, as the states of mjpcx_set_state and mjpcx_set_states do (NOT the rule of mjpcx_set_residual_state above: a plain
+ *     chain run for one robot between two batched launches leaves the fleet's rows alone).
+ *   - Every call replaces all four fields. The rows persist across plan steps until replaced; mjpcx_set_states with a different
+ *     E drops them, as it drops the per-environment residual state.
+ *   - The norm kinds, the term dimensions and the model stay shared. */
+int mjpcx_set_task_params_batched(mjpcx_ctx* ctx, int num_envs, const double* weight, const double* norm_parameter,
+                                  const double* parameters, const double* risk);
 
 /* mjpcx_rollout_splines for E environments: node_times E x P, node_values E x n_per_env x P x nu. */
 int mjpcx_rollout_splines_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,

@@ -28,7 +28,7 @@ EXPORTS = [
     "mjpcx_backward_pass", "mjpcx_gradient_pass", "mjpcx_timing_reset", "mjpcx_timing_read", "mjpcx_timing_read_main", "mjpcx_quad_stats", "mjpcx_algorithmic_bytes",
     "mjpcx_device_buffer", "mjpcx_comm_unique_id", "mjpcx_comm_init", "mjpcx_comm_info", "mjpcx_exchange_best", "mjpcx_merge_topk",
     "mjpcx_elite_allreduce", "mjpcx_comm_barrier", "mjpcx_comm_destroy",
-    "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
+    "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_set_task_params_batched", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
     "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched", "mjpcx_gradient_step_batched",
     "mjpcx_rollout_feedback_batched", "mjpcx_ilqg_step_batched",
 ]
@@ -72,6 +72,7 @@ def lib():
         L.mjpcx_kinematics.argtypes = [vp] + [c_f64p] * 7
         L.mjpcx_set_states.argtypes = [vp, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_set_residual_states.argtypes = [vp, C.c_int, c_i32p, c_f64p]
+        L.mjpcx_set_task_params_batched.argtypes = [vp, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_rollout_splines_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p]
         L.mjpcx_rollout_noise_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
@@ -253,6 +254,27 @@ class Context:
         E = (ri if ri is not None else rr).shape[0] if (ri is not None or rr is not None) else getattr(self, "E", 0)
         self._chk(lib().mjpcx_set_residual_states(self.handle, int(E), None if ri is None else ri.ctypes.data_as(c_i32p),
                                                   None if rr is None else as_f64p(rr)))
+
+    def set_task_params_batched(self, weight=None, norm_parameter=None, parameters=None, risk=None):
+        """set_task_params per environment of the last set_states: weight E x num_term, norm_parameter E x (sum of num_norm_parameter),
+        parameters E x num_parameter, risk E. None: that field is the context's (set_task_params) for every environment; all four
+        None: everything shared again. Only the batched calls read the rows; they persist until replaced."""
+        E = int(getattr(self, "E", 0))
+        arrs = []
+        for name, a, ndim in (("weight", weight, 2), ("norm_parameter", norm_parameter, 2), ("parameters", parameters, 2), ("risk", risk, 1)):
+            if a is not None:
+                a = _f(a)
+                if a.ndim != ndim or a.shape[0] != E:
+                    raise ValueError(f"set_task_params_batched: {name} has shape {a.shape} for the {E} environments of set_states")
+                if a.size == 0:
+                    a = None
+            arrs.append(a)
+        t = self._pt.struct
+        want = (t.num_term, int(sum(t.num_norm_parameter[k] for k in range(t.num_term))), t.num_parameter)
+        for name, a, n in zip(("weight", "norm_parameter", "parameters"), arrs, want):
+            if a is not None and a.shape[1] != n:
+                raise ValueError(f"set_task_params_batched: {name} has {a.shape[1]} columns, the task has {n}")
+        self._chk(lib().mjpcx_set_task_params_batched(self.handle, E, *[None if a is None else as_f64p(a) for a in arrs]))
 
     def rollout_splines_batched(self, horizon, interp, node_times, node_values, num_envs=None, n_per_env=None):
         """node_times E x P, node_values E x n_per_env x P x nu."""

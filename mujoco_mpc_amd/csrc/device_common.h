@@ -60,15 +60,19 @@ struct LaneTask {
   T mocap_pos[kLaneMaxMocap][3], mocap_quat[kLaneMaxMocap][4];
 };
 
-// The initial condition as the rollout kernels of the lane family read it: one LaneInit per environment, staged behind the plan's
-// node times and nominal spline (mjpcx.hip, stage_plan_inputs) -- E of them do not fit the kernel-argument segment. The environment is
-// wave-uniform, so these are scalar loads like the kernel arguments they replace. (LaneTask keeps its copy for the feedback and
-// finite-difference kernels, which serve one environment.)
+// The initial condition and the task parameters as the rollout kernels of the lane family read them: one LaneInit per environment,
+// staged behind the plan's node times and nominal spline (mjpcx.hip, stage_plan_inputs) -- E of them do not fit the kernel-argument
+// segment. The environment is wave-uniform, so these are scalar loads like the kernel arguments they replace. Weights, norm parameters,
+// parameters and risk are the environment's own (mjpcx_set_task_params_batched) or the context's; the norm kinds stay in LaneTask.
+// (LaneTask keeps its copy of all of it for the plain feedback and finite-difference kernels, which serve one environment.)
 template <typename T>
 struct LaneInit {
   T qpos[kLaneMaxDof], qvel[kLaneMaxDof];
   T time;
   T mocap_pos[kLaneMaxMocap][3], mocap_quat[kLaneMaxMocap][4];
+  T weight[kLaneMaxTerm], norm_p[kLaneMaxTerm], norm_q[kLaneMaxTerm];
+  T parameters[kLaneMaxParam];
+  T risk;
 };
 // wave-uniform read-only data behind a global pointer, read through the constant address space: s_load, whatever the kernel stores elsewhere
 template <typename T> using const_as_ptr = const __attribute__((address_space(4))) T*;
@@ -85,6 +89,11 @@ __device__ __forceinline__ void lane_task_init(LaneTask<T>& tk, const LaneInit<T
 #pragma unroll
     for (int k = 0; k < 4; k++) tk.mocap_quat[i][k] = p->mocap_quat[i][k];
   }
+#pragma unroll
+  for (int k = 0; k < kLaneMaxTerm; k++) { tk.weight[k] = p->weight[k]; tk.norm_p[k] = p->norm_p[k]; tk.norm_q[k] = p->norm_q[k]; }
+#pragma unroll
+  for (int k = 0; k < kLaneMaxParam; k++) tk.parameters[k] = p->parameters[k];
+  tk.risk = p->risk;
 }
 
 // ---- small fixed-size math; all indices are compile-time after unrolling ----

@@ -99,12 +99,28 @@ struct CostSpec {  // Task cost specification, by value in the kernarg segment
   double weight[32], p[32], q[32];
   double risk;
 };
+// One environment's weights, norm parameters and risk (mjpcx_set_task_params_batched), in device memory: the batched chains pass E of
+// them, and workgroup e * env_T + t then takes these four fields from row e instead of the CostSpec. The workgroup's environment is
+// uniform, so the reads are scalar loads through the constant address space, like the kernel-argument loads they replace.
+struct CostRow { double weight[32], p[32], q[32], risk; };
+struct CostParams {
+  const CostSpec& cs;
+  const_as_ptr<CostRow> row;  // nullptr: the CostSpec's
+  __device__ __forceinline__ CostParams(const CostSpec& cs_, const CostRow* rows, int env_T)
+      : cs(cs_), row(rows ? (const_as_ptr<CostRow>)(rows + blockIdx.x / (unsigned)env_T) : nullptr) {}
+  __device__ __forceinline__ double weight(int k) const { return row ? row->weight[k] : cs.weight[k]; }
+  __device__ __forceinline__ double p(int k) const { return row ? row->p[k] : cs.p[k]; }
+  __device__ __forceinline__ double q(int k) const { return row ? row->q[k] : cs.q[k]; }
+  __device__ __forceinline__ double risk() const { return row ? row->risk : cs.risk; }
+};
 
-// one workgroup (64 lanes) per timestep
+// one workgroup (64 lanes) per timestep; rows: nullptr, or per-environment task parameters for env_T consecutive workgroups each
 __global__ __launch_bounds__(64) void cost_derivatives_kernel(const CostSpec cs, const double* __restrict__ r,
                                                                const double* __restrict__ C, const double* __restrict__ D,
                                                                int T, int ndx, int nu, double* cx, double* cu,
-                                                               double* cxx, double* cxu, double* cuu) {
+                                                               double* cxx, double* cxu, double* cuu, const CostRow* rows, int env_T) {
+  const CostParams par(cs, rows, env_T);
+  const double risk = par.risk();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* g = reinterpret_cast<double*>(smem_raw);  // [32]
   double* Hn = g + 32;                              // [32*32]
@@ -125,11 +141,11 @@ __global__ __launch_bounds__(64) void cost_derivatives_kernel(const CostSpec cs,
   int shift = 0;
   for (int k = 0; k < cs.num_term; k++) {
     const int nk = cs.dim[k];
-    const double w = cs.weight[k] / T;  // weights[i] / T, cost_derivatives.cc:151
+    const double w = par.weight(k) / T;  // weights[i] / T, cost_derivatives.cc:151
     const double* rk = r + (size_t)t * nr + shift;
     const double* rx = C + ((size_t)t * nr + shift) * ndx;  // nk x ndx
     const double* ru = D + ((size_t)t * nr + shift) * nu;   // nk x nu
-    if (lane == 0) cval += w * norm_grad_hess(g, Hn, rk, cs.p[k], cs.q[k], nk, cs.norm[k]);
+    if (lane == 0) cval += w * norm_grad_hess(g, Hn, rk, par.p(k), par.q(k), nk, cs.norm[k]);
     __syncthreads();
     for (int e = lane; e < nk * ndx; e += 64) {  // Hrx = H rx
       const int a = e / ndx, j = e % ndx;
@@ -169,24 +185,27 @@ __global__ __launch_bounds__(64) void cost_derivatives_kernel(const CostSpec cs,
   }
   // exponential risk transformation, cost_derivatives.cc:156-226 (including its use of the ALREADY scaled
   // cx / cu in the rank-one terms)
-  if (fabs(cs.risk) >= 1.0e-6) {
-    const double s = exp(cs.risk * cval);
+  if (fabs(risk) >= 1.0e-6) {
+    const double s = exp(risk * cval);
     __syncthreads();
     for (int i = lane; i < ndx; i += 64) cx_t[i] *= s;
     for (int i = lane; i < nu; i += 64) cu_t[i] *= s;
     __syncthreads();
-    for (int e = lane; e < ndx * ndx; e += 64) cxx_t[e] = cxx_t[e] * s + cs.risk * s * cx_t[e / ndx] * cx_t[e % ndx];
-    for (int e = lane; e < ndx * nu; e += 64) cxu_t[e] = cxu_t[e] * s + cs.risk * s * cx_t[e / nu] * cu_t[e % nu];
-    for (int e = lane; e < nu * nu; e += 64) cuu_t[e] = cuu_t[e] * s + cs.risk * s * cu_t[e / nu] * cu_t[e % nu];
+    for (int e = lane; e < ndx * ndx; e += 64) cxx_t[e] = cxx_t[e] * s + risk * s * cx_t[e / ndx] * cx_t[e % ndx];
+    for (int e = lane; e < ndx * nu; e += 64) cxu_t[e] = cxu_t[e] * s + risk * s * cx_t[e / nu] * cu_t[e % nu];
+    for (int e = lane; e < nu * nu; e += 64) cuu_t[e] = cuu_t[e] * s + risk * s * cu_t[e / nu] * cu_t[e % nu];
   }
 }
 
 // The first-order half of cost_derivatives_kernel for E trajectories in one launch (mjpcx_gradient_step_batched): workgroup e * T + t
 // forms cx and cu of step t of environment e over environment-major arrays, by the operations of the kernel above in its order, so
 // the results equal its cx / cu bit for bit; cxx, cxu, cuu and the H rx / H ru products they need are not formed. T is the horizon
-// the weights are divided by.
+// the weights are divided by; rows: nullptr, or E CostRows -- environment e's weights, norm parameters and risk.
 __global__ __launch_bounds__(64) void cost_gradient_kernel(const CostSpec cs, const double* __restrict__ r, const double* __restrict__ C,
-                                                            const double* __restrict__ D, int T, int ndx, int nu, double* cx, double* cu) {
+                                                            const double* __restrict__ D, int T, int ndx, int nu, double* cx, double* cu,
+                                                            const CostRow* rows) {
+  const CostParams par(cs, rows, T);
+  const double risk = par.risk();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* g = reinterpret_cast<double*>(smem_raw);  // [32]
   double* Hn = g + 32;                              // [32*32]
@@ -202,19 +221,19 @@ __global__ __launch_bounds__(64) void cost_gradient_kernel(const CostSpec cs, co
   int shift = 0;
   for (int k = 0; k < cs.num_term; k++) {
     const int nk = cs.dim[k];
-    const double w = cs.weight[k] / T;  // weights[i] / T, cost_derivatives.cc:151
+    const double w = par.weight(k) / T;  // weights[i] / T, cost_derivatives.cc:151
     const double* rk = r + t * nr + shift;
     const double* rx = C + (t * nr + shift) * ndx;  // nk x ndx
     const double* ru = D + (t * nr + shift) * nu;   // nk x nu
-    if (lane == 0) cval += w * norm_grad_hess(g, Hn, rk, cs.p[k], cs.q[k], nk, cs.norm[k]);
+    if (lane == 0) cval += w * norm_grad_hess(g, Hn, rk, par.p(k), par.q(k), nk, cs.norm[k]);
     __syncthreads();
     for (int i = lane; i < ndx; i += 64) { double s = 0; for (int a = 0; a < nk; a++) s += rx[a * ndx + i] * g[a]; cx_t[i] += w * s; }
     for (int i = lane; i < nu; i += 64) { double s = 0; for (int a = 0; a < nk; a++) s += ru[a * nu + i] * g[a]; cu_t[i] += w * s; }
     __syncthreads();
     shift += nk;
   }
-  if (fabs(cs.risk) >= 1.0e-6) {  // exponential risk transformation of the gradient, cost_derivatives.cc:156-226
-    const double s = exp(cs.risk * cval);
+  if (fabs(risk) >= 1.0e-6) {  // exponential risk transformation of the gradient, cost_derivatives.cc:156-226
+    const double s = exp(risk * cval);
     __syncthreads();
     for (int i = lane; i < ndx; i += 64) cx_t[i] *= s;
     for (int i = lane; i < nu; i += 64) cu_t[i] *= s;

@@ -24,8 +24,8 @@ struct FeedbackArgs {
   int use_state;       // mode 1: settings.nominal_feedback_scaling
   // several environments in one launch (mjpcx_rollout_feedback_batched): the five nominal arrays hold env_n-candidate environments' blocks
   // of Tn steps, environment-major and contiguous; alpha is indexed by the global candidate c = e * env_n + i. Every environment is padded to
-  // env_waves = ceil(env_n / 64) wavefronts, so a wavefront serves one environment, whose initial-condition record is init moved by
-  // e * env_stride bytes (env_select.h). env_n = 0: one environment, the LaneTask of the kernel arguments.
+  // env_waves = ceil(env_n / 64) wavefronts, so a wavefront serves one environment, whose LaneInit record (initial condition and task
+  // parameters) is init moved by e * env_stride bytes (env_select.h). env_n = 0: one environment, the LaneTask of the kernel arguments.
   int env_n, env_waves;
   unsigned env_stride;
   const LaneInit<T>* init;
@@ -220,7 +220,7 @@ struct FdArgs {
   T* sensor;    // [Tn][NC][NR]   residual (the leading user sensors) of each perturbed step
   // several environments in one launch (mjpcx_gradient_step_batched): the arrays above hold num_envs x Tn steps, environment-major, and
   // environment e's items are [e * env_items, e * env_items + Tn * NC). env_items is a multiple of 64, so a wavefront serves one
-  // environment, whose initial-condition record (the mocap pose the residual reads) is init moved by e * env_stride bytes
+  // environment, whose LaneInit record (the mocap pose and the task parameters the residual reads) is init moved by e * env_stride bytes
   // (env_select.h). num_envs = 0: one environment, the LaneTask of the kernel arguments.
   int num_envs, env_items;
   unsigned env_stride;

@@ -542,6 +542,9 @@ struct mjpcx_ctx {
   int env_E = 0;
   std::vector<double> env_state, env_time, env_mocap, env_rreal;
   std::vector<int32_t> env_rint;
+  // and, when given, E x the task parameters (mjpcx_set_task_params_batched; an empty vector: that field is the context's for every environment).
+  // Only the batched entry points read them; mjpcx_set_task_params neither reads nor clears them.
+  std::vector<double> env_weight, env_normp, env_normq, env_param, env_risk;  // E x nterm (three), E x nparam, E
   int env_n = 0;  // candidates per environment of the last rollout (0: not a batched one)
   bool have_rollout = false;
   // wavefront-per-candidate family
@@ -698,6 +701,12 @@ void set_norm_params(mjpcx_ctx* c, const double* norm_parameter) {
     shift += np;
   }
 }
+void clear_env_task_params(mjpcx_ctx* c) {
+  c->env_weight.clear(); c->env_normp.clear(); c->env_normq.clear(); c->env_param.clear(); c->env_risk.clear();
+}
+bool has_env_task_params(const mjpcx_ctx* c) {
+  return !(c->env_weight.empty() && c->env_normp.empty() && c->env_normq.empty() && c->env_param.empty() && c->env_risk.empty());
+}
 }  // namespace
 
 namespace {
@@ -756,6 +765,13 @@ int stage_plan_inputs(mjpcx_ctx* c, int P, int E, const double* node_times, cons
         if (mo) for (int i = 0; i < 7 * c->nmocap; i++) hb[t.off_mocap + i] = (T)mo[i];
         if (!c->env_rreal.empty()) for (int i = 0; i < t.nrr; i++) hb[t.off_rreal + i] = (T)c->env_rreal[(size_t)e * t.nrr + i];
         if (!c->env_rint.empty()) std::memcpy(hb + t.off_rint, c->env_rint.data() + (size_t)e * t.nri, sizeof(int32_t) * t.nri);
+        // and its own task parameters (mjpcx_set_task_params_batched), field by field, over the context's
+        const size_t nt = c->nterm, npar = c->nparam;
+        if (!c->env_weight.empty()) for (size_t i = 0; i < nt; i++) hb[t.off_weight + i] = (T)c->env_weight[e * nt + i];
+        if (!c->env_normp.empty()) for (size_t i = 0; i < nt; i++) hb[t.off_normp + i] = (T)c->env_normp[e * nt + i];
+        if (!c->env_normq.empty()) for (size_t i = 0; i < nt; i++) hb[t.off_normq + i] = (T)c->env_normq[e * nt + i];
+        if (!c->env_param.empty()) for (size_t i = 0; i < npar; i++) hb[t.off_param + i] = (T)c->env_param[e * npar + i];
+        if (!c->env_risk.empty()) hb[t.off_risk] = (T)c->env_risk[e];
       }
     } else {
       LaneInit<T>& li = *reinterpret_cast<LaneInit<T>*>(hb);
@@ -770,6 +786,17 @@ int stage_plan_inputs(mjpcx_ctx* c, int P, int E, const double* node_times, cons
         for (int q = 0; q < 3; q++) li.mocap_pos[i][q] = (T)(own ? mo[7 * i + q] : k.mocap_pos[i][q]);
         for (int q = 0; q < 4; q++) li.mocap_quat[i][q] = (T)(own ? mo[7 * i + 3 + q] : k.mocap_quat[i][q]);
       }
+      // the task parameters: the context's (the casts of convert_task), or with several environments the environment's own where given
+      const size_t nt = c->nterm, npar = c->nparam;
+      for (size_t i = 0; i < (size_t)kLaneMaxTerm; i++) {
+        const bool own = E > 0 && i < nt;
+        li.weight[i] = (T)(own && !c->env_weight.empty() ? c->env_weight[e * nt + i] : k.weight[i]);
+        li.norm_p[i] = (T)(own && !c->env_normp.empty() ? c->env_normp[e * nt + i] : k.norm_p[i]);
+        li.norm_q[i] = (T)(own && !c->env_normq.empty() ? c->env_normq[e * nt + i] : k.norm_q[i]);
+      }
+      for (size_t i = 0; i < (size_t)kLaneMaxParam; i++)
+        li.parameters[i] = (T)(E > 0 && i < npar && !c->env_param.empty() ? c->env_param[e * npar + i] : k.parameters[i]);
+      li.risk = (T)(E > 0 && !c->env_risk.empty() ? c->env_risk[e] : k.risk);
     }
   }
   HIPCHK(c, hipMemcpyAsync(s.dev.p, s.host.p, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1621,7 +1648,7 @@ int mjpcx_set_states(mjpcx_ctx* c, int E, const double* states, const double* ti
   c->env_time.assign(times, times + E);
   if (mocap) c->env_mocap.assign(mocap, mocap + (size_t)7 * c->nmocap * E);  // (NULL: every environment keeps the context's pose)
   else c->env_mocap.clear();
-  if (c->env_E != E) { c->env_rint.clear(); c->env_rreal.clear(); }  // (per-environment residual state of another fleet size)
+  if (c->env_E != E) { c->env_rint.clear(); c->env_rreal.clear(); clear_env_task_params(c); }  // (per-environment residual state and task parameters of another fleet size)
   c->env_E = E;
   return MJPCX_OK;
 }
@@ -1642,6 +1669,30 @@ int mjpcx_set_residual_states(mjpcx_ctx* c, int E, const int32_t* residual_int, 
     }
   }
   if (residual_real) c->env_rreal.assign(residual_real, residual_real + (size_t)nrr * E);
+  return MJPCX_OK;
+}
+
+int mjpcx_set_task_params_batched(mjpcx_ctx* c, int E, const double* weight, const double* norm_parameter, const double* parameters,
+                                  const double* risk) {
+  if (!c) return MJPCX_EINVAL;
+  if (E < 1) return fail(c, MJPCX_EINVAL, "mjpcx_set_task_params_batched: the number of environments must be >= 1");
+  if (E != c->env_E)
+    return fail(c, MJPCX_EINVAL, "mjpcx_set_task_params_batched: " + std::to_string(E) + " environments, but mjpcx_set_states gave " + std::to_string(c->env_E));
+  const size_t nt = c->nterm, npar = c->nparam;
+  if (weight) c->env_weight.assign(weight, weight + nt * E); else c->env_weight.clear();
+  if (norm_parameter) {  // split into p and q per term, as set_norm_params does
+    c->env_normp.assign(nt * E, 0.0); c->env_normq.assign(nt * E, 0.0);
+    size_t shift = 0;
+    for (int e = 0; e < E; e++)
+      for (size_t k = 0; k < nt; k++) {
+        const int np = c->num_norm_parameter[k];
+        if (np > 0) c->env_normp[e * nt + k] = norm_parameter[shift];
+        if (np > 1) c->env_normq[e * nt + k] = norm_parameter[shift + 1];
+        shift += np;
+      }
+  } else { c->env_normp.clear(); c->env_normq.clear(); }
+  if (parameters && npar > 0) c->env_param.assign(parameters, parameters + npar * E); else c->env_param.clear();
+  if (risk) c->env_risk.assign(risk, risk + E); else c->env_risk.clear();
   return MJPCX_OK;
 }
 
@@ -2364,7 +2415,7 @@ int mjpcx_cost_derivatives(mjpcx_ctx* c, int T, const double* residual, const do
   double* o = (double*)c->d_ilqg_out.p;
   double *dcx = o, *dcu = dcx + T * ndx, *dcxx = dcu + T * nu, *dcxu = dcxx + T * ndx * ndx, *dcuu = dcxu + T * ndx * nu;
   const size_t shmem = (32 + 32 * 32 + 32 * ndx + 32 * nu) * 8;
-  hipLaunchKernelGGL(cost_derivatives_kernel, dim3(T), dim3(64), shmem, c->stream, cs, d[0], d[1], d[2], T, (int)ndx, (int)nu, dcx, dcu, dcxx, dcxu, dcuu);
+  hipLaunchKernelGGL(cost_derivatives_kernel, dim3(T), dim3(64), shmem, c->stream, cs, d[0], d[1], d[2], T, (int)ndx, (int)nu, dcx, dcu, dcxx, dcxu, dcuu, (const CostRow*)nullptr, 1);
   HIPCHK(c, hipGetLastError());
   return download(c, {{cx, dcx, T * ndx * 8}, {cu, dcu, T * nu * 8}, {cxx, dcxx, T * ndx * ndx * 8}, {cxu, dcxu, T * ndx * nu * 8}, {cuu, dcuu, T * nu * nu * 8}});
 }
@@ -2450,7 +2501,7 @@ int mjpcx_gradient_pass(mjpcx_ctx* c, int n, int m, int T, const double* A, cons
 namespace {
 // The shared front and tail of mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched: ModelDerivatives::Compute for E environments from
 // the last batched rollout, enqueued on the context's stream, and the one download. One device workspace (d_grad), carved in this order:
-//   [evaluate | ctrllimited | ctrlrange | candidates | sources | active | the caller's inputs]              one upload from h_grad
+//   [evaluate | ctrllimited | ctrlrange | candidates | sources | active | cost rows | the caller's inputs]  one upload from h_grad
 //   [gathered nominal | finite-difference workspace | A, B, C, D at all T steps | the caller's arrays]
 //   [nominal_return | the caller's results]                                                                 one download into h_grad
 // The caller carves its own fields with carve() after the constructor, after carve_work() and after carve_results(); then stage(), its
@@ -2462,7 +2513,7 @@ struct StepChain {
   int E, Tn, ne;
   size_t ds, ndx, nu, nr, nc, sE, sT, rows, sA, sB, sC, sD;
   size_t off = 0, in_bytes = 0, o_out = 0;
-  size_t o_eval, o_lim, o_range, o_cand, o_src, o_act, o_ft = 0, o_fs = 0, o_fa = 0, o_res = 0, o_A = 0, o_B = 0, o_C = 0, o_D = 0, o_ret = 0;
+  size_t o_eval, o_lim, o_range, o_cand, o_src, o_act, o_rows, o_ft = 0, o_fs = 0, o_fa = 0, o_res = 0, o_A = 0, o_B = 0, o_C = 0, o_D = 0, o_ret = 0;
   FdCarve fd{};
   PlanRecords rec{};
   char *base = nullptr, *hin = nullptr, *hout = nullptr;
@@ -2476,7 +2527,10 @@ struct StepChain {
     sE = E; sT = Tn; rows = sE * ne; sA = ndx * ndx; sB = ndx * nu; sC = nr * ndx; sD = nr * nu;
     o_eval = carve((size_t)ne * 4); o_lim = carve(nu * 4); o_range = carve(2 * nu * sizeof(T));
     o_cand = carve(sE * 4); o_src = carve(sE * 4); o_act = carve(sE * 4);
+    o_rows = carve(has_env_task_params(c) ? sE * sizeof(CostRow) : 0);  // (mjpcx_set_task_params_batched: each environment's cost parameters)
   }
+  // what the cost kernels take as their rows: nullptr while every environment shares the context's task parameters
+  const CostRow* cost_rows() const { return has_env_task_params(c) ? (const CostRow*)(base + o_rows) : nullptr; }
   bool too_large() const { return sE * std::max((size_t)ne * nc, sT) * (ndx + nr) * (ndx + nu) > 0x7fffffffULL; }  // (the kernels index with int)
   void carve_work() {
     in_bytes = off;
@@ -2488,7 +2542,7 @@ struct StepChain {
   // the buffers, the environments' plan records restaged (the preceding rollout's slot may have been recycled since) and the shared
   // inputs. candidate[e] < 0: environment e takes no part and rides along on the first active one's nominal (its finite differences
   // need SOME valid trajectory); at least one takes part.
-  int stage(const int32_t* candidate, const int32_t* evaluate) {
+  int stage(const int32_t* candidate, const int32_t* evaluate, const CostSpec& cs) {
     int rc;
     if ((rc = stage_records<T>(c, E, &rec)) != MJPCX_OK) return rc;
     HIPCHK(c, c->d_grad.reserve(off));
@@ -2504,6 +2558,18 @@ struct StepChain {
       ((int*)(hin + o_cand))[e] = candidate[on ? e : first];
       ((int*)(hin + o_src))[e] = on ? e : first;
       ((int*)(hin + o_act))[e] = on ? 1 : 0;
+    }
+    if (has_env_task_params(c)) {  // the environment's own fields where given, the context's (cs) elsewhere
+      const size_t nt = c->nterm;
+      for (int e = 0; e < E; e++) {
+        CostRow& row = ((CostRow*)(hin + o_rows))[e];
+        std::memcpy(row.weight, cs.weight, sizeof row.weight); std::memcpy(row.p, cs.p, sizeof row.p); std::memcpy(row.q, cs.q, sizeof row.q);
+        row.risk = c->env_risk.empty() ? cs.risk : c->env_risk[e];
+        for (size_t k = 0; k < nt; k++) {
+          if (!c->env_weight.empty()) row.weight[k] = c->env_weight[e * nt + k];
+          if (!c->env_normp.empty()) { row.p[k] = c->env_normp[e * nt + k]; row.q[k] = c->env_normq[e * nt + k]; }
+        }
+      }
     }
     return MJPCX_OK;
   }
@@ -2562,13 +2628,13 @@ int do_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int Tn, int ne, cons
   s.carve_results();
   const size_t o_k = s.carve(sE * sT * nu * 8), o_g = s.carve(sE * sP * nu * 8), o_dV = s.carve(sE * 2 * 8);
   const std::vector<int32_t> cands(E, cand);  // the same local candidate of every environment; every environment takes part
-  if ((rc = s.stage(cands.data(), evaluate)) != MJPCX_OK) return rc;
+  if ((rc = s.stage(cands.data(), evaluate, cs)) != MJPCX_OK) return rc;
   std::memcpy(s.hin + o_nodes, node_times, sE * sP * 8);
   if ((rc = s.run(eps, centered, s.f64(o_st), nullptr)) != MJPCX_OK) return rc;
   // ---- CostDerivatives::Compute (first order) and Gradient::Compute with the projection, per environment
   double *dA = s.f64(s.o_A), *dB = s.f64(s.o_B), *dcx = s.f64(o_cx), *dcu = s.f64(o_cu);
   hipLaunchKernelGGL(cost_gradient_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32) * 8, c->stream, cs, s.f64(s.o_res),
-                     s.f64(s.o_C), s.f64(s.o_D), Tn, (int)ndx, (int)nu, dcx, dcu);
+                     s.f64(s.o_C), s.f64(s.o_D), Tn, (int)ndx, (int)nu, dcx, dcu, s.cost_rows());
   HIPCHK(c, hipGetLastError());
   GradientArgs ga{};
   ga.n = (int)ndx; ga.m = (int)nu; ga.T = Tn; ga.P = P; ga.representation = representation;
@@ -2615,7 +2681,7 @@ int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, 
   s.carve_results();
   const size_t o_K = s.carve(sE * sT * sB * 8), o_du = s.carve(sE * sT * nu * 8), o_dV = s.carve(sE * 2 * 8);
   const size_t o_muo = s.carve(sE * 8), o_rateo = s.carve(sE * 8), o_status = s.carve(sE * 4), o_retries = s.carve(sE * 4);
-  if ((rc = s.stage(candidate, evaluate)) != MJPCX_OK) return rc;
+  if ((rc = s.stage(candidate, evaluate, cs)) != MJPCX_OK) return rc;
   std::memcpy(s.hin + o_mu, mu, sE * 8);
   std::memcpy(s.hin + o_rate, rate, sE * 8);
   std::memcpy(s.hin + o_limits, c->ctrlrange.data(), 2 * nu * 8);
@@ -2628,7 +2694,7 @@ int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, 
   for (int k = 0; k < 9; k++) w[k] = s.f64(at[k]);
   hipLaunchKernelGGL(cost_derivatives_kernel, dim3((unsigned)(sE * sT)), dim3(64), (32 + 32 * 32 + 32 * ndx + 32 * nu) * 8, c->stream, cs,
                      s.f64(s.o_res), s.f64(s.o_C), s.f64(s.o_D), Tn, (int)ndx, (int)nu,
-                     w[2], w[3], w[4], w[5], w[6]);
+                     w[2], w[3], w[4], w[5], w[6], s.cost_rows(), Tn);
   HIPCHK(c, hipGetLastError());
   // ---- the backward pass with its regularisation retries, one workgroup per environment
   BackwardBatchedArgs b{};

@@ -137,7 +137,7 @@ struct RolloutArgs {
   // is uniform over a wavefront and over a workgroup of the lane, quad and limb kernels.
   int env_n;
   unsigned env_stride;
-  const LaneInit<T>* init;  // lane family: the initial condition (in the record)
+  const LaneInit<T>* init;  // lane family: the initial condition and the task parameters (in the record)
 };
 
 // NOISE = false: a pass that draws no noise (noise.mode < 0) and so has no use for the variance pointer
@@ -742,7 +742,7 @@ template <class TP, class TK, typename T, class MC, bool SPLIT = false, bool NOI
 __global__ __launch_bounds__(64) void rollout_lane_kernel(const LaneModel<T> m_karg, const LaneTask<T> tk_karg,
                                                            const RolloutArgs<T> a_karg) {
   decltype(auto) m = MC::template get<T>(m_karg);
-  // the workgroup's environment (one wavefront, 64 consecutive candidates): its plan record and initial condition
+  // the workgroup's environment (one wavefront, 64 consecutive candidates): its plan record, initial condition and task parameters
   const RolloutArgs<T> a = env_view(a_karg, env_of(a_karg, blockIdx.x * 64));
   LaneTask<T> tk = tk_karg;
   lane_task_init(tk, a.init);
@@ -980,8 +980,8 @@ __global__ __launch_bounds__(256) void cost_lane_kernel(const LaneModel<T> m_kar
   const size_t item = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (item >= N * (size_t)a.H) return;
   const int t = (int)(item / N), cand = (int)(item - (size_t)t * N);
-  // the mocap pose the residual reads is the environment's (with several environments N is a multiple of 64: a wavefront's 64 items are
-  // one step of 64 consecutive candidates, all of one environment)
+  // the mocap pose, weights, norm and residual parameters and risk are the environment's (with several environments N is a multiple of
+  // 64: a wavefront's 64 items are one step of 64 consecutive candidates, all of one environment)
   LaneTask<T> tk = tk_karg;
   lane_task_init(tk, env_ptr(a.init, env_of(a, cand), a.env_stride));
   const int fb = a.failure[cand];

@@ -354,11 +354,59 @@ class GpuSamplingPlanner:
         self._set_winner(self.trajectory_order[candidate], p.plan.values())
 
 
-class GpuBatchSamplingPlanner:
+class _FleetTasks:
+    """`set_tasks` of the fleet planners: one Task per environment instead of the one the fleet was initialised with."""
+    _tasks = None
+    _rows_pushed = False
+
+    def set_tasks(self, tasks):
+        """One Task per environment -- the same model and residual, norm kinds and term dimensions; weights, norm parameters,
+        parameters, risk and the frozen residual state (mode, gait phase) are each environment's own. Member e then plans with tasks[e]:
+        every batched launch carries the tasks' current values as per-environment rows (`set_task_params_batched`,
+        `set_residual_states`), so a task may be edited or `transition`ed between plan steps. After `initialize`. None: the fleet's one
+        task for every environment again."""
+        if tasks is None:
+            self._tasks = None
+            for p in self.envs:
+                p.task = self.task
+            return
+        tasks = list(tasks)
+        if len(tasks) != self.num_envs:
+            raise ValueError(f"{len(tasks)} tasks for {self.num_envs} environments")
+        if self.task is None:
+            raise ValueError("set_tasks before initialize")
+        ref = self.task
+        for e, t in enumerate(tasks):
+            same = (t.residual_id == ref.residual_id and t.model.source == ref.model.source and list(t.norm) == list(ref.norm) and
+                    list(t.dim_norm_residual) == list(ref.dim_norm_residual) and len(t.parameters) == len(ref.parameters) and
+                    len(t.residual_int) == len(ref.residual_int) and len(t.residual_real) == len(ref.residual_real))
+            if not same:
+                raise ValueError(f"set_tasks: the task of environment {e} differs from the fleet's in model, residual, norm kinds or dimensions")
+        self._tasks = tasks
+        for p, t in zip(self.envs, tasks):
+            p.task = t
+
+    def _push_task_rows(self):
+        """after ctx.set_states: the environments' own task parameters and frozen residual state, or nothing without set_tasks"""
+        ts = self._tasks
+        if ts is None:
+            if self._rows_pushed:     # set_tasks(None) after a fleet of unlike tasks: everything shared again
+                self.ctx.set_task_params_batched()
+                self._rows_pushed = False
+            return
+        rows = lambda name: np.array([getattr(t, name) for t in ts], dtype=np.float64).reshape(len(ts), -1)
+        self.ctx.set_task_params_batched(rows("weight"), rows("norm_parameter"), rows("parameters"), np.array([float(t.risk) for t in ts]))
+        self._rows_pushed = True
+        if hasattr(self.ctx, "set_residual_states") and (ts[0].residual_int or ts[0].residual_real):
+            self.ctx.set_residual_states(np.array([t.residual_int for t in ts], dtype=np.int32).reshape(len(ts), -1) if ts[0].residual_int else None,
+                                         rows("residual_real") if ts[0].residual_real else None)
+
+
+class GpuBatchSamplingPlanner(_FleetTasks):
     """Predictive Sampling for `num_envs` environments (robots) on ONE context: every plan step is one `set_states`, one
     `rollout_noise_batched` over all E x n candidates, one `best_batched` and one sync, instead of E plan steps one after the
-    other. The environments share the model and the task (weights, parameters); each has its own state, clock, mocap pose
-    and policy. Environment e with seed s behaves exactly like a GpuSamplingPlanner with seed s + e: the per-environment
+    other. The environments share the model and the task (weights, parameters) unless `set_tasks` gives each its own; each has its own
+    state, clock, mocap pose and policy. Environment e with seed s behaves exactly like a GpuSamplingPlanner with seed s + e: the per-environment
     logic (nominal resampling, policy copy, ActionFromPolicy) IS that planner's, one member per environment."""
 
     def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
@@ -417,6 +465,7 @@ class GpuBatchSamplingPlanner:
         self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
                             np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
                             np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+        self._push_task_rows()
 
     def optimize_policy(self, horizon, pool=None):
         n = self.num_trajectory_
@@ -666,12 +715,12 @@ def _fleet_setting(name):
     return property(fget, fset)
 
 
-class GpuBatchCrossEntropyPlanner:
+class GpuBatchCrossEntropyPlanner(_FleetTasks):
     """Cross-Entropy for `num_envs` environments (robots) on ONE context: every plan step is one `set_states`, one
     `rollout_noise_batched_ce` over all E x (n + 1) candidates with a variance row per environment, one `ce_update_batched`
     (selection of the elites, their mean, variance and mean return, on the device) and one sync -- instead of E plan steps of
-    four host round trips each. The environments share the model, the task and n_elite_, std_initial_, std_min_,
-    explore_fraction_; each has its own state, clock, mocap pose, policy and variance. Environment e with seed s behaves exactly
+    four host round trips each. The environments share the model, the task (unless `set_tasks` gives each its own) and n_elite_,
+    std_initial_, std_min_, explore_fraction_; each has its own state, clock, mocap pose, policy and variance. Environment e with seed s behaves exactly
     like a GpuCrossEntropyPlanner with seed s + e: the per-environment logic (ResamplePolicy, policy copy, ActionFromPolicy) IS
     that planner's, one member per environment. The nominal rollout rides along as each environment's last candidate, so
     num_trajectory_ + 1 must be a positive multiple of 64."""
@@ -730,6 +779,7 @@ class GpuBatchCrossEntropyPlanner:
         self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
                             np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
                             np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+        self._push_task_rows()
 
     # ---- OptimizePolicy, cross_entropy/planner.cc:168-291, for every environment
     def optimize_policy(self, horizon, pool=None):
@@ -1221,7 +1271,7 @@ class GpuILQGPlanner:
         return self.dim_action * K_MAX_TRAJECTORY_HORIZON
 
 
-class GpuBatchILQGPlanner:
+class GpuBatchILQGPlanner(_FleetTasks):
     """iLQG for `num_envs` environments (robots) on ONE context. The two feedback-rollout phases of a plan step -- the nominal
     under iLQGPolicy::Action and the line search under the index policy, three quarters of an iteration and pure per-step latency --
     are one `rollout_feedback_batched` launch each for the whole fleet (any number of rollouts per environment: iLQG's ten). Between
@@ -1231,7 +1281,8 @@ class GpuBatchILQGPlanner:
     the host's policy trajectory and no device rollout -- an environment runs the unchanged sequential chain on the shared context:
     plain `set_state` of that environment, model derivatives, cost derivatives, the backward pass with its retries. An environment
     whose backward pass fails every retry sits the line search out, exactly as GpuILQGPlanner.iteration returns early. The environments
-    share the model, the task and the settings; each has its own state, clock, mocap pose, policy and regularisation. The
+    share the model, the task (unless `set_tasks` gives each its own; a member's sequential chain then runs on its own task) and the
+    settings; each has its own state, clock, mocap pose, policy and regularisation. The
     per-environment logic (BestRollout, the regularisation schedule, the policy bookkeeping) IS GpuILQGPlanner's, one member per
     environment.
     timers: `derivatives_backward` is the whole middle either way. On the sequential path `model_derivative`, `cost_derivative` and
@@ -1287,6 +1338,7 @@ class GpuBatchILQGPlanner:
         self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
                             np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
                             np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+        self._push_task_rows()
 
     def _rollout(self, horizon, mode, representation, use_state, requests):
         """one batched launch of every environment's request; each member's share of the returns"""
@@ -1334,6 +1386,8 @@ class GpuBatchILQGPlanner:
                 np.isfinite(st.min_regularization) and np.isfinite(st.max_regularization) and st.min_regularization <= st.max_regularization)
 
     def _sequential_middle(self, p, horizon):
+        if self._tasks is not None:     # the plain calls of this chain read the context's plain values: the member's own task. (The plain
+            sync_task(self.ctx, p.task)  # residual state replaces the fleet's per-environment one; the next _push_states brings it back.)
         self.ctx.set_state(p.state, p.time, p.mocap, p.userdata)
         return p._iteration_before_rollouts(horizon)
 
@@ -1657,13 +1711,13 @@ def derivative_steps(T, derivative_skip):
     return sorted(set(e for e in evaluate if 0 <= e < T))
 
 
-class GpuBatchGradientPlanner:
+class GpuBatchGradientPlanner(_FleetTasks):
     """The Gradient planner for `num_envs` environments (robots) on ONE context: a plan step is one `set_states`, one
     `rollout_splines_batched` of the resampled policies (64 candidates per environment, candidate 0 the nominal), one
     `gradient_step_batched` -- model derivatives, cost derivatives and the adjoint sweep of every environment chained on the device,
     the first sync --, one `rollout_splines_batched` of theta + s_i * parameter_update for all environments and `returns()`, the
-    second sync: two host round trips for the fleet instead of six per robot. The environments share the model, the task and the
-    settings; each has its own state, clock, mocap pose and policy. The per-environment logic (ResamplePolicy, the line-search
+    second sync: two host round trips for the fleet instead of six per robot. The environments share the model, the task (unless `set_tasks` gives each its own)
+    and the settings; each has its own state, clock, mocap pose and policy. The per-environment logic (ResamplePolicy, the line-search
     steps, the selection rule with its ties toward the higher index, the policy bookkeeping) IS GpuGradientPlanner's, one member
     per environment. gradient_num_trajectory must be a positive multiple of 64."""
 
@@ -1721,6 +1775,7 @@ class GpuBatchGradientPlanner:
         self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
                             np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
                             np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+        self._push_task_rows()
 
     def _rollout_nominal(self, horizon):
         """candidate0 of every environment in one launch: 64 candidates per environment, candidate 0 carrying the policy"""

@@ -24,6 +24,11 @@ environment on the plain calls, the planner's device_chain = False; `device_chai
 both sides. The record carries the batched planner's stage timers (medians; median / min / max under batched_stage_spread_ms) and one
 environment's sequential ones. Default output profiles/batch_sweep_ilqg.jsonl.
 
+--mixed-params: every environment plans with task weights, norm parameters, residual parameters and risk of its own (sampling and
+cross_entropy: set_task_params_batched after set_states, and the plain set_task_params of the same row before every sequential plan
+step; gradient and ilqg: the fleet planner's set_tasks, and every sequential planner on its own task). The kernels do the same work
+either way; the record carries "mixed_params". Compare with the same run without the switch.
+
 Kernel thresholds are the library's defaults: the sequential side of 8 x 2048 runs eight launches of the kernel a 2048-candidate batch gets,
 the batched side one launch of the kernel a 16384-candidate batch gets -- that is the feature."""
 import argparse
@@ -70,6 +75,29 @@ def initial(task, name, E, rng):
     return np.stack(states), np.zeros(E), None if mocap is None else np.stack([mocap] * E)
 
 
+def mixed_tasks(task, E):
+    """E copies of the task (sharing its model) with their own weights (x 0.5 .. 2), norm parameters (x 0.7 .. 1.5), residual parameters
+    that are not selections (x 0.8 .. 1.2, + 0.01 .. 0.1) and risk (0 and 0.2 in turn)"""
+    import copy
+    rng = np.random.default_rng(5)
+    names = [k for k in task.model.numeric if k.startswith("residual_")]
+    out = []
+    for e in range(E):
+        t = copy.copy(task)
+        t.weight = [float(w * f) for w, f in zip(task.weight, rng.uniform(0.5, 2.0, len(task.weight)))]
+        t.norm_parameter = [float(p * f) for p, f in zip(task.norm_parameter, rng.uniform(0.7, 1.5, len(task.norm_parameter)))]
+        t.parameters = [float(v) if k.startswith("residual_select_") else float(v * rng.uniform(0.8, 1.2) + rng.uniform(0.01, 0.1))
+                        for k, v in zip(names, task.parameters)]
+        t.risk = 0.2 * (e % 2)
+        out.append(t)
+    return out
+
+
+def task_rows(tasks):
+    arr = lambda k: np.array([getattr(t, k) for t in tasks], float).reshape(len(tasks), -1)
+    return dict(weight=arr("weight"), norm_parameter=arr("norm_parameter"), parameters=arr("parameters"), risk=np.array([float(t.risk) for t in tasks]))
+
+
 GRADIENT_SHAPES = [("QuadrupedFlat", 64, 36, [(1, 64), (4, 64), (8, 64), (16, 64)]),
                    ("Cartpole", 64, 128, [(64, 64), (1, 64)])]
 
@@ -78,7 +106,7 @@ def stats(x):
     return {"median": float(np.median(x)), "min": float(np.min(x)), "max": float(np.max(x))}
 
 
-def sweep_gradient(name, precision, H, shapes, steps, warmup, out):
+def sweep_gradient(name, precision, H, shapes, steps, warmup, out, mixed=False):
     from mujoco_mpc_amd.planners import GpuBatchGradientPlanner, GpuGradientPlanner, State
     task = load_task(name)
     m = task.model
@@ -95,11 +123,14 @@ def sweep_gradient(name, precision, H, shapes, steps, warmup, out):
             states.append(st)
         singles = [GpuGradientPlanner(precision=precision, backend_factory=lambda t: ctx) for _ in range(E)]
         batch = GpuBatchGradientPlanner(E, precision=precision, backend_factory=lambda t: ctx)
-        for p in singles + [batch]:
-            p.initialize(m, task)
+        tasks = mixed_tasks(task, E) if mixed else [task] * E
+        for p, t in zip(singles + [batch], tasks + [task]):
+            p.initialize(m, t)
             p.num_trajectory = n
             p.allocate()
             p.reset(H)
+        if mixed:
+            batch.set_tasks(tasks)
 
         def sequential():
             for p, st in zip(singles, states):
@@ -121,7 +152,7 @@ def sweep_gradient(name, precision, H, shapes, steps, warmup, out):
             for k, v in batch.timers.items():
                 stages.setdefault(k, []).append(v * 1e-3)
         rec = {"planner": "gradient", "task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps,
-               "warmup": warmup, "kernel": ctx.kernel_name.split(" (")[0], "sequential_ms": stats(ts), "batched_ms": stats(tb),
+               "warmup": warmup, "mixed_params": bool(mixed), "kernel": ctx.kernel_name.split(" (")[0], "sequential_ms": stats(ts), "batched_ms": stats(tb),
                "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)), "beyond_spread": bool(np.max(tb) < np.min(ts)),
                "batched_stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
                "sequential_stage_ms_per_env": {k: float(v) * 1e-3 for k, v in singles[0].timers.items()}}
@@ -134,7 +165,7 @@ def sweep_gradient(name, precision, H, shapes, steps, warmup, out):
 ILQG_SHAPES = [("QuadrupedFlat", 64, 36, [(1, 10), (2, 10), (4, 10), (8, 10), (16, 10)])]
 
 
-def sweep_ilqg(name, precision, H, shapes, steps, warmup, out, device_chain=None):
+def sweep_ilqg(name, precision, H, shapes, steps, warmup, out, device_chain=None, mixed=False):
     from mujoco_mpc_amd.planners import GpuBatchILQGPlanner, GpuILQGPlanner, State
     task = load_task(name)
     m = task.model
@@ -152,11 +183,14 @@ def sweep_ilqg(name, precision, H, shapes, steps, warmup, out, device_chain=None
         singles = [GpuILQGPlanner(precision=precision, backend_factory=lambda t: ctx) for _ in range(E)]
         batch = GpuBatchILQGPlanner(E, precision=precision, backend_factory=lambda t: ctx)
         batch.device_chain = device_chain
-        for p in singles + [batch]:
-            p.initialize(m, task)
+        tasks = mixed_tasks(task, E) if mixed else [task] * E
+        for p, t in zip(singles + [batch], tasks + [task]):
+            p.initialize(m, t)
             p.num_rollouts_gui_ = n
             p.allocate()
             p.reset(H)
+        if mixed:
+            batch.set_tasks(tasks)
 
         def sequential():
             for p, st in zip(singles, states):
@@ -178,7 +212,7 @@ def sweep_ilqg(name, precision, H, shapes, steps, warmup, out, device_chain=None
             for k, v in batch.timers.items():
                 stages.setdefault(k, []).append(v * 1e-3)
         rec = {"planner": "ilqg", "task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps,
-               "warmup": warmup, "kernel": ctx.kernel_name.split(" (")[0], "sequential_ms": stats(ts), "batched_ms": stats(tb),
+               "warmup": warmup, "mixed_params": bool(mixed), "kernel": ctx.kernel_name.split(" (")[0], "sequential_ms": stats(ts), "batched_ms": stats(tb),
                "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)), "beyond_spread": bool(np.max(tb) < np.min(ts)),
                "device_chain": bool(batch.used_device_chain),
                "batched_stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
@@ -191,7 +225,7 @@ def sweep_ilqg(name, precision, H, shapes, steps, warmup, out, device_chain=None
     ctx.close()
 
 
-def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling"):
+def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mixed=False):
     task = load_task(name)
     m = task.model
     rng = np.random.default_rng(1)
@@ -205,16 +239,28 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling"):
         states, clocks, mocap = initial(task, name, E, rng)
         times, nominal = np.stack([times1] * E), np.zeros((E, P, m.nu))
         it = [0]
+        tasks = mixed_tasks(task, E) if mixed else None
+        rows = task_rows(tasks) if mixed else None
+
+        def plain_params(e):
+            if mixed:
+                ctx.set_task_params(tasks[e].weight, tasks[e].norm_parameter, tasks[e].parameters or None, tasks[e].risk)
+
+        def fleet_states():
+            ctx.set_states(states, clocks, mocap)
+            if mixed:
+                ctx.set_task_params_batched(**rows)
 
         def sequential():
             it[0] += 1
             for e in range(E):
+                plain_params(e)
                 ctx.set_state(states[e], clocks[e], None if mocap is None else mocap[e])
                 ctx.rollout_noise(n, H, interp, times[e], nominal[e], capi.make_noise_spec(seed=7 + e, iteration=it[0], std0=std))
                 ctx.best(0)
 
         def batched():
-            ctx.set_states(states, clocks, mocap)
+            fleet_states()
             ctx.rollout_noise_batched(n, H, interp, times, nominal, capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_envs=E)
             ctx.best_batched(E, 0)
 
@@ -229,6 +275,7 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling"):
         def ce_sequential():   # GpuCrossEntropyPlanner.optimize_policy's calls
             it[0] += 1
             for e in range(E):
+                plain_params(e)
                 ctx.set_state(states[e], clocks[e], None if mocap is None else mocap[e])
                 ctx.rollout_noise(n, H, interp, times[e], nominal[e], ce_spec(e, variance[e]))
                 idx, _ = ctx.topk(n_elite + 1)
@@ -237,7 +284,7 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling"):
                 ctx.elite_moments(idx, s / n_elite)
 
         def ce_rollout():
-            ctx.set_states(states, clocks, mocap)
+            fleet_states()
             ctx.rollout_noise_batched_ce(n, H, interp, times, nominal, variance, ce_spec(0, None), num_envs=E)
 
         def ce_batched():      # GpuBatchCrossEntropyPlanner.optimize_policy's calls
@@ -255,7 +302,7 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling"):
             ts.append((t1 - t0) * 1e3)
             tb.append((t2 - t1) * 1e3)
         rec = {"task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps, "warmup": warmup,
-               "kernel": ctx.kernel_name.split(" (")[0],
+               "mixed_params": bool(mixed), "kernel": ctx.kernel_name.split(" (")[0],
                "sequential_ms": {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))},
                "batched_ms": {"median": float(np.median(tb)), "min": float(np.min(tb)), "max": float(np.max(tb))},
                "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)),
@@ -284,6 +331,7 @@ def main():
     ap.add_argument("--only", default=None)
     ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
+    ap.add_argument("--mixed-params", action="store_true", help="every environment its own task weights, parameters and risk")
     ap.add_argument("--no-device-chain", action="store_true", help="--planner ilqg: the sequential middle (the A/B of ilqg_step_batched)")
     a = ap.parse_args()
     if a.out is None:
@@ -296,11 +344,11 @@ def main():
             shapes = [sh for sh in shapes if keep is None or sh in keep]
             if shapes and (a.only is None or a.only == name):
                 if a.planner == "gradient":
-                    sweep_gradient(name, precision, H, shapes, a.steps, a.warmup, out)
+                    sweep_gradient(name, precision, H, shapes, a.steps, a.warmup, out, a.mixed_params)
                 elif a.planner == "ilqg":
-                    sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out, False if a.no_device_chain else None)
+                    sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out, False if a.no_device_chain else None, a.mixed_params)
                 else:
-                    sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner)
+                    sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner, a.mixed_params)
 
 
 if __name__ == "__main__":
