@@ -10,6 +10,7 @@ import pytest
 
 from mujoco_mpc_amd import capi
 from oracle import pyoracle
+from riccati_cases import census, coupled as random_lq, free_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -90,21 +91,6 @@ def test_cost_derivatives_all_norms(particle):
         ctx.close()
 
 
-def random_lq(n, m, T, seed):
-    rng = np.random.default_rng(seed)
-    A = np.eye(n)[None] + 0.1 * rng.normal(size=(T, n, n))
-    B = 0.3 * rng.normal(size=(T, n, m))
-    def spd(k, scale):
-        M = rng.normal(size=(T, k, k))
-        return scale * (M @ np.transpose(M, (0, 2, 1)) / k + 0.5 * np.eye(k))
-    cxx, cuu = spd(n, 1.0), spd(m, 0.5)
-    cxu = 0.05 * rng.normal(size=(T, n, m))
-    cx, cu = rng.normal(size=(T, n)), rng.normal(size=(T, m))
-    actions = rng.uniform(-0.9, 0.9, size=(T, m))
-    limits = np.tile([-1.0, 1.0], (m, 1))
-    return A, B, cx, cu, cxx, cxu, cuu, actions, limits
-
-
 def test_backward_pass_golden_lqr(cartpole):
     """the reference's golden vectors (backward_pass_test.cc:101-138) through the MFMA kernel"""
     from test_oracle_riccati import lqr_problem
@@ -118,15 +104,21 @@ def test_backward_pass_golden_lqr(cartpole):
     assert np.allclose(out["du"][:2], [[-0.5], [-0.75]], atol=1e-5)
 
 
+LIMIT_SCALE = {(17, 5, 8): 0.5}
+
+
 @pytest.mark.parametrize("n,m,T", [(4, 1, 20), (4, 2, 11), (17, 5, 8), (36, 12, 36), (48, 16, 5)])
 @pytest.mark.parametrize("reg_type,limits", [(0, 1), (0, 0), (1, 1), (2, 1)])
 def test_backward_pass_vs_oracle(cartpole, n, m, T, reg_type, limits):
-    """(36, 12, 36) is the Quadruped iLQG shape of BASELINE configs[4]"""
-    prob = random_lq(n, m, T, seed=n * 100 + m)
+    """(36, 12, 36) is the Quadruped iLQG shape of BASELINE configs[4]. (17, 5, 8) has its control range halved: at the full range its
+    box binds nowhere. Every limited case with more than one control has a step with some controls clamped and some free."""
+    prob = random_lq(n, m, T, seed=n * 100 + m, limit_scale=LIMIT_SCALE.get((n, m, T), 1.0))
     ctx = capi.Context(cartpole.packed_model(), cartpole.packed(), 0, 64)
     out = ctx.backward_pass(0.3, reg_type, limits, *prob)
     ref = pyoracle.riccati(n, m, T, 0.3, reg_type, limits, *prob)
     assert out["ok"] == ref["ok"] == True
+    if limits and m >= 2:
+        assert census(free_rows(ref["K"]))[2] >= 1
     for k in ("Vx", "Vxx", "K", "du", "dV"):
         assert close(out[k], ref[k], 1e-9), (k, np.abs(out[k] - ref[k]).max())
 
