@@ -334,7 +334,10 @@ int mjpcx_set_residual_state(mjpcx_ctx* ctx, const int32_t* residual_int, const 
  *   - n_per_env must be a positive multiple of 64 (every wavefront then serves one environment) and E >= 1: MJPCX_EINVAL otherwise
  *     (mjpcx_rollout_feedback_batched alone takes any n_per_env >= 1);
  *   - a batched rollout needs a preceding mjpcx_set_states with the same E: MJPCX_EINVAL otherwise;
- *   - on a context sharded with mjpcx_comm_init (world > 1), or with xfrc noise: MJPCX_EUNSUPPORTED.
+ *   - on a context sharded with mjpcx_comm_init (world > 1): MJPCX_EUNSUPPORTED.
+ * Force noise (Trajectory::NoisyRollout) is batched too: mjpcx_rollout_splines_noisy_batched on the lane (NOISY), wave and tree kernels.
+ * The quad and limb kernels draw no force noise, so a noisy batch of any size runs on the wavefront-per-candidate kernels, as the
+ * plain noisy call does.
  * The plain entry points are the one-environment case of the same launch code and kernels; they keep using the state of
  * mjpcx_set_state, which mjpcx_set_states does not touch. */
 
@@ -351,8 +354,8 @@ int mjpcx_set_residual_states(mjpcx_ctx* ctx, int num_envs, const int32_t* resid
 /* mjpcx_set_task_params per environment: weight E x num_term, norm_parameter E x (sum of num_norm_parameter), parameters
  * E x num_parameter, risk E. Any pointer may be NULL: that field is the context's (mjpcx_set_task_params) for every environment.
  * All four NULL: everything shared again. After mjpcx_set_states with the same E (MJPCX_EINVAL otherwise).
- *   - Every batched entry point reads the rows: mjpcx_rollout_splines_batched, mjpcx_rollout_noise_batched,
- *     mjpcx_rollout_noise_batched_ce, mjpcx_rollout_feedback_batched, mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched.
+ *   - Every batched entry point reads the rows: mjpcx_rollout_splines_batched, mjpcx_rollout_splines_noisy_batched,
+ *     mjpcx_rollout_noise_batched, mjpcx_rollout_noise_batched_ce, mjpcx_robust_step_batched, mjpcx_rollout_feedback_batched, mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched.
  *     Environment e of such a call behaves exactly like the plain call after mjpcx_set_task_params(row e): equal bits.
  *   - mjpcx_set_task_params and the plain entry points neither read nor clear the rows: plain and batched values live side by
  *     side, as the states of mjpcx_set_state and mjpcx_set_states do (NOT the rule of mjpcx_set_residual_state above: a plain
@@ -366,6 +369,14 @@ int mjpcx_set_task_params_batched(mjpcx_ctx* ctx, int num_envs, const double* we
 /* mjpcx_rollout_splines for E environments: node_times E x P, node_values E x n_per_env x P x nu. */
 int mjpcx_rollout_splines_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,
                                   const double* node_times, const double* node_values);
+
+/* mjpcx_rollout_splines_noisy for E environments: node_times E x P, node_values E x n_per_env x P x nu. Environment e behaves exactly
+ * like mjpcx_rollout_splines_noisy after mjpcx_set_state(state e) with seed + e and the same candidate_offset, which is local to the
+ * environment (local candidate i draws the stream of candidate_offset + i) -- so E plain calls reproduce a batched one bit for bit.
+ * Validation as mjpcx_rollout_splines_batched, plus xfrc_std >= 0 and xfrc_rate > 0 (MJPCX_EINVAL). */
+int mjpcx_rollout_splines_noisy_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,
+                                        const double* node_times, const double* node_values, double xfrc_std, double xfrc_rate,
+                                        uint64_t seed, int candidate_offset);
 
 /* mjpcx_rollout_noise for E environments: node_times E x P, nominal_values E x P x nu. Environment e draws exactly the noise
  * that mjpcx_rollout_noise draws with noise->seed + e and the same remaining fields; candidate_offset and nominal_candidate
@@ -402,6 +413,31 @@ int mjpcx_ce_update_batched(mjpcx_ctx* ctx, int num_envs, int n_elite, int skip_
  * the winner's spline values -> spline_values (E x P x nu). Any output but index may be NULL. */
 int mjpcx_best_batched(mjpcx_ctx* ctx, int num_envs, int ref_candidate, int32_t* index, double* best_return,
                        double* ref_return, double* spline_values);
+
+/* The Robust planner's plan step (RobustPlanner::OptimizePolicy after the delegate's rollout) for E environments: select, replicate,
+ * roll out under force noise and score, enqueued on ctx's stream behind source's (an event; nothing goes through the host), ONE sync.
+ * `source` is the context of the delegate's rollout -- the same model, device and precision; its last rollout a batched one of num_envs
+ * environments, of either kind -- and is left unchanged, so the winner's unperturbed trajectory stays fetchable there. ctx has had
+ * mjpcx_set_states(num_envs, ...) (its own task rows are optional). Per environment:
+ *   1. the k = num_candidates best of source's n_per_env returns, in the order of mjpcx_ce_update_batched(skip_candidate = -1)
+ *      (ascending, ties to the lower index, NaN last) -> candidate (E x k, LOCAL index in source's rollout), candidate_return (E x k);
+ *   2. every chosen spline R = repetitions times under force noise, as mjpcx_rollout_splines_noisy_batched of the replicated splines:
+ *      local rollout j = rank * R + rep draws the stream (seed + e, candidate_offset + j). The share is padded to
+ *      n_pad = 64 * ceil(k R / 64) rollouts with the last rank's spline; the padding is rolled out and never scored.
+ *      P is source's, node_times E x P;
+ *   3. per rank, from the candidate's unperturbed return, mean = (valid * mean + return) / (valid + 1) over the repetitions that
+ *      did not fail, in that order of fp64 operations -> perturbed_score (E x k), valid (E x k: how many counted); the argmin with
+ *      strict < from rank 0 up (the lowest rank wins a tie, a NaN never beats an earlier rank) -> best (E: rank in 0..k-1), and the
+ *      winner's spline -> spline_values (E x P x nu).
+ * Any output but best may be NULL. Afterwards ctx's last rollout is the batched noisy one with n_per_env = n_pad: every getter works
+ * on it. A failed perturbed rollout is the planner's ordinary failure flag, not an error.
+ * MJPCX_EINVAL: source == ctx; different device, precision, nq / nv / nu; source's last rollout not batched with num_envs;
+ * k < 1, k > source's n_per_env or R < 1; ctx without mjpcx_set_states(num_envs); a row of node_times not strictly increasing;
+ * xfrc_std < 0 or xfrc_rate <= 0. Either context sharded: MJPCX_EUNSUPPORTED. */
+int mjpcx_robust_step_batched(mjpcx_ctx* ctx, mjpcx_ctx* source, int num_envs, int num_candidates, int repetitions, int horizon,
+                              int interpolation, const double* node_times, double xfrc_std, double xfrc_rate, uint64_t seed,
+                              int candidate_offset, int32_t* best, int32_t* candidate, double* candidate_return,
+                              double* perturbed_score, int32_t* valid, double* spline_values);
 
 /* Block until everything queued on the context's stream has finished. */
 int mjpcx_sync(mjpcx_ctx* ctx);
@@ -559,7 +595,7 @@ int mjpcx_ilqg_step_batched(mjpcx_ctx* ctx, int num_envs, const int32_t* candida
  * wavefront-per-candidate kernel afterwards, as in the plain call). The plain calls keep using the state of mjpcx_set_state.
  * MJPCX_EINVAL: no preceding mjpcx_set_states with the same E, E < 1, n_per_env < 1, horizon < 1, nominal_horizon < 1, mode 0 with
  * horizon > nominal_horizon, an unknown mode or representation. MJPCX_EUNSUPPORTED: a context sharded with mjpcx_comm_init (world > 1);
- * xfrc noise; fp32 contexts of the wavefront-per-candidate family, as the plain call refuses them. */
+ * fp32 contexts of the wavefront-per-candidate family, as the plain call refuses them. */
 int mjpcx_rollout_feedback_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int mode, int representation,
                                    int use_state, int nominal_horizon, const double* times, const double* states,
                                    const double* actions, const double* gains, const double* improvement, const double* alpha);

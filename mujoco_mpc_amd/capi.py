@@ -31,6 +31,7 @@ EXPORTS = [
     "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_set_task_params_batched", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
     "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched", "mjpcx_gradient_step_batched",
     "mjpcx_rollout_feedback_batched", "mjpcx_ilqg_step_batched",
+    "mjpcx_rollout_splines_noisy_batched", "mjpcx_robust_step_batched",
 ]
 
 _LIB = None
@@ -74,6 +75,9 @@ def lib():
         L.mjpcx_set_residual_states.argtypes = [vp, C.c_int, c_i32p, c_f64p]
         L.mjpcx_set_task_params_batched.argtypes = [vp, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_rollout_splines_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p]
+        L.mjpcx_rollout_splines_noisy_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.c_double, C.c_double, C.c_uint64, C.c_int]
+        L.mjpcx_robust_step_batched.argtypes = ([vp, vp] + [C.c_int] * 5 + [c_f64p, C.c_double, C.c_double, C.c_uint64, C.c_int] +
+                                                [c_i32p, c_i32p, c_f64p, c_f64p, c_i32p, c_f64p])
         L.mjpcx_rollout_noise_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_rollout_noise_batched_ce.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
@@ -286,6 +290,43 @@ class Context:
         assert nv.size == E * n * P * self.nu
         self._chk(lib().mjpcx_rollout_splines_batched(self.handle, E, n, int(horizon), P, int(interp), as_f64p(nt), as_f64p(nv)))
         self.N, self.H, self.P, self.n_per_env = E * n, int(horizon), P, n
+
+    def rollout_splines_noisy_batched(self, horizon, interp, node_times, node_values, xfrc_std, xfrc_rate, seed=0, candidate_offset=0,
+                                      num_envs=None, n_per_env=None):
+        """rollout_splines_noisy for E environments: node_times E x P, node_values E x n_per_env x P x nu; environment e draws the
+        force noise of a plain call with seed + e, candidate_offset local to the environment."""
+        nt = _f(node_times)
+        nv = _f(node_values)
+        E = int(num_envs) if num_envs is not None else (nt.shape[0] if nt.ndim == 2 else 1)
+        P = nt.size // E if E > 0 else nt.size
+        n = int(n_per_env) if n_per_env is not None else nv.size // max(E * P * self.nu, 1)
+        assert nv.size == E * n * P * self.nu
+        self._chk(lib().mjpcx_rollout_splines_noisy_batched(self.handle, E, n, int(horizon), P, int(interp), as_f64p(nt), as_f64p(nv),
+                                                            float(xfrc_std), float(xfrc_rate), int(seed), int(candidate_offset)))
+        self.N, self.H, self.P, self.n_per_env = E * n, int(horizon), P, n
+
+    def robust_step_batched(self, source, num_envs, num_candidates, repetitions, horizon, interp, node_times, xfrc_std, xfrc_rate, seed=0,
+                            candidate_offset=0):
+        """the Robust planner's plan step for every environment, behind `source`'s last batched rollout, one sync
+        (mjpcx_robust_step_batched): the k best candidates of each environment of `source`, each rolled out R times under force
+        noise on this context, scored by the planner's running mean. Dict of best (E: rank), candidate (E x k, local index in
+        source's rollout), candidate_return, perturbed_score (E x k), valid (E x k) and spline (E x P x nu: the winner's). This
+        context's last rollout is then the noisy one, 64 * ceil(k R / 64) per environment."""
+        E, k, R = int(num_envs), int(num_candidates), int(repetitions)
+        nt = _f(node_times)
+        P = int(source.P)
+        Ea, ka = max(E, 1), max(k, 1)
+        out = dict(best=np.zeros(Ea, np.int32), candidate=np.zeros((Ea, ka), np.int32), candidate_return=np.zeros((Ea, ka)),
+                   perturbed_score=np.zeros((Ea, ka)), valid=np.zeros((Ea, ka), np.int32), spline=np.zeros((Ea, max(P, 1), self.nu)))
+        if E >= 1 and nt.size != E * P:
+            raise ValueError(f"robust_step_batched: node_times has {nt.size} entries for {E} environments x {P} nodes of the source's rollout")
+        self._chk(lib().mjpcx_robust_step_batched(self.handle, source.handle, E, k, R, int(horizon), int(interp), as_f64p(nt), float(xfrc_std),
+                                                  float(xfrc_rate), int(seed), int(candidate_offset), as_i32p(out["best"]),
+                                                  as_i32p(out["candidate"]), as_f64p(out["candidate_return"]),
+                                                  as_f64p(out["perturbed_score"]), as_i32p(out["valid"]), as_f64p(out["spline"])))
+        n_pad = 64 * ((k * R + 63) // 64)
+        self.N, self.H, self.P, self.n_per_env = E * n_pad, int(horizon), P, n_pad
+        return out
 
     def rollout_noise_batched(self, n_per_env, horizon, interp, node_times, nominal, noise_spec, num_envs=None):
         """node_times E x P, nominal E x P x nu; environment e draws the noise of a plain call with seed + e."""

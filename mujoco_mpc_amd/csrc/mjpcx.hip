@@ -340,17 +340,9 @@ __device__ __forceinline__ void lane_merge(RetIdx& v, int i, int k) {  // the st
 }
 constexpr int kCeLdsKeys = 8192;  // 12 bytes a key: 96 KiB of a CU's 160 KiB of LDS
 struct CeRecord { size_t bytes, off_index, off_ret, off_mean, off_var; };  // avg_return at 0
-template <typename T, bool IN_LDS>
-__global__ __launch_bounds__(1024) void ce_update_kernel(const double* __restrict__ ret, const T* __restrict__ nodes, int N, int n_env, int n2, int np,
-                                                          int n_elite, int skip, double* scratch, unsigned char* out, CeRecord rec) {
-  extern __shared__ __attribute__((aligned(16))) double ce_lds[];
-  __shared__ double sm[4][256];
-  __shared__ double sm_mean[4];
-  const int env = blockIdx.x, first = env * n_env, tid = threadIdx.x;
-  double* keys;
-  int* idx;
-  if constexpr (IN_LDS) { keys = ce_lds; idx = reinterpret_cast<int*>(ce_lds + n2); }
-  else { keys = scratch + (size_t)env * (n2 + n2 / 2); idx = reinterpret_cast<int*>(keys + n2); }
+// The selection (step 1 above), shared by ce_update_kernel and robust_select_kernel: every thread of a workgroup of 1024 calls it; on
+// return keys[0..n2) / idx[0..n2) hold the environment's returns and local indices in less_ri order, visible to the whole workgroup.
+__device__ __forceinline__ void env_sort_keys(const double* __restrict__ ret, int first, int n_env, int n2, int skip, double* keys, int* idx, int tid) {
   // n2 is a multiple of 1024: every lane is active in every round of the loops over i
   for (int i = tid; i < n2; i += 1024) {
     RetIdx v = i < n_env && i != skip ? RetIdx{ret[first + i], i} : RetIdx{NAN, 0x7fffffff};
@@ -377,6 +369,19 @@ __global__ __launch_bounds__(1024) void ce_update_kernel(const double* __restric
     }
     __syncthreads();
   }
+}
+template <typename T, bool IN_LDS>
+__global__ __launch_bounds__(1024) void ce_update_kernel(const double* __restrict__ ret, const T* __restrict__ nodes, int N, int n_env, int n2, int np,
+                                                          int n_elite, int skip, double* scratch, unsigned char* out, CeRecord rec) {
+  extern __shared__ __attribute__((aligned(16))) double ce_lds[];
+  __shared__ double sm[4][256];
+  __shared__ double sm_mean[4];
+  const int env = blockIdx.x, first = env * n_env, tid = threadIdx.x;
+  double* keys;
+  int* idx;
+  if constexpr (IN_LDS) { keys = ce_lds; idx = reinterpret_cast<int*>(ce_lds + n2); }
+  else { keys = scratch + (size_t)env * (n2 + n2 / 2); idx = reinterpret_cast<int*>(keys + n2); }
+  env_sort_keys(ret, first, n_env, n2, skip, keys, idx, tid);
   unsigned char* r = out + (size_t)env * rec.bytes;
   int* o_index = reinterpret_cast<int*>(r + rec.off_index);
   double* o_ret = reinterpret_cast<double*>(r + rec.off_ret);
@@ -398,6 +403,79 @@ __global__ __launch_bounds__(1024) void ce_update_kernel(const double* __restric
     }
     __syncthreads();
   }
+}
+
+// The Robust planner's plan step for E environments (mjpcx_robust_step_batched), two kernels around the batched noisy rollout; one
+// workgroup per environment each. The environment's record, pinned and device-mapped:
+// [best (i32) | candidate (k i32) | candidate_return (k f64) | perturbed_score (k f64) | valid (k i32) | spline (np f64)].
+struct RobustRecord { size_t bytes, off_index, off_ret, off_score, off_valid, off_spline; };
+//  1. Select and expand: the k best of the environment's n_src returns of the SOURCE context, in the order of ce_update_kernel without
+//     a skip (env_sort_keys), -> the record; every chosen spline R times into this context's node buffer ([node * nu][candidate], what
+//     scatter_nodes_kernel writes; both contexts hold one precision: a copy). Local rollout j = rank * R + rep; the share is padded to
+//     n_pad, a multiple of 64, with the last rank's spline.
+template <typename T, bool IN_LDS>
+__global__ __launch_bounds__(1024) void robust_select_kernel(const double* __restrict__ src_ret, const T* __restrict__ src_nodes, int N_src, int n_src,
+                                                              int n2, int np, int k, int R, int n_pad, double* scratch, T* nodes, unsigned char* out,
+                                                              RobustRecord rec) {
+  extern __shared__ __attribute__((aligned(16))) double ce_lds[];
+  const int env = blockIdx.x, first = env * n_src, tid = threadIdx.x;
+  double* keys;
+  int* idx;
+  if constexpr (IN_LDS) { keys = ce_lds; idx = reinterpret_cast<int*>(ce_lds + n2); }
+  else { keys = scratch + (size_t)env * (n2 + n2 / 2); idx = reinterpret_cast<int*>(keys + n2); }
+  env_sort_keys(src_ret, first, n_src, n2, -1, keys, idx, tid);
+  unsigned char* r = out + (size_t)env * rec.bytes;
+  int* o_index = reinterpret_cast<int*>(r + rec.off_index);
+  double* o_ret = reinterpret_cast<double*>(r + rec.off_ret);
+  for (int i = tid; i < k; i += 1024) { o_index[i] = idx[i]; o_ret[i] = keys[i]; }
+  const size_t N = (size_t)gridDim.x * n_pad, to = (size_t)env * n_pad;
+  for (int i = tid; i < np * n_pad; i += 1024) {  // consecutive threads write consecutive rollouts of one node row
+    const int j = i / n_pad, slot = i - j * n_pad;
+    const int rank = min(slot / R, k - 1);
+    nodes[(size_t)j * N + to + slot] = src_nodes[(size_t)j * N_src + first + idx[rank]];
+  }
+}
+//  2. Score: per rank the running mean of RobustPlanner::OptimizePolicy in its order of operations -- from the candidate's unperturbed
+//     return, mean = (valid * mean + ret) / (valid + 1) over the repetitions that did not fail, plain fp64, nothing contracted --, then
+//     the planner's argmin: strict < from rank 0 up, so the lowest rank wins a tie and a NaN never beats an earlier rank (rank 0 stays
+//     when its own score is NaN; otherwise that is less_ri's minimum). The winner's spline is gathered in the same launch.
+template <typename T>
+__global__ __launch_bounds__(256) void robust_score_kernel(const double* __restrict__ ret, const int* __restrict__ fail, const T* __restrict__ nodes,
+                                                            int np, int k, int R, int n_pad, unsigned char* out, RobustRecord rec) {
+#pragma clang fp contract(off)
+  __shared__ RetIdx sm[4];
+  __shared__ double score0;
+  const int env = blockIdx.x, tid = threadIdx.x;
+  const size_t N = (size_t)gridDim.x * n_pad, first = (size_t)env * n_pad;
+  unsigned char* r = out + (size_t)env * rec.bytes;
+  const double* o_ret = reinterpret_cast<const double*>(r + rec.off_ret);
+  double* o_score = reinterpret_cast<double*>(r + rec.off_score);
+  int* o_valid = reinterpret_cast<int*>(r + rec.off_valid);
+  RetIdx best{NAN, 0x7fffffff};  // (sorts behind every rank)
+  for (int c = tid; c < k; c += 256) {
+    double mean = o_ret[c];
+    int valid = 0;
+    for (int j = 0; j < R; j++) {
+      if (fail[first + (size_t)c * R + j]) continue;
+      const double total = ret[first + (size_t)c * R + j];
+      mean = (valid * mean + total) / (valid + 1);
+      valid++;
+    }
+    o_score[c] = mean;
+    o_valid[c] = valid;
+    if (c == 0) score0 = mean;
+    const RetIdx v{mean, c};
+    if (less_ri(v, best)) best = v;
+  }
+  best = wave_argmin(best);
+  const int wave = tid >> 6, lane = tid & 63;
+  if (lane == 0) sm[wave] = best;
+  __syncthreads();
+  best = wave_argmin(lane < 4 ? sm[lane] : RetIdx{NAN, 0x7fffffff});
+  const int w = score0 != score0 ? 0 : best.i;
+  if (tid == 0) reinterpret_cast<int*>(r)[0] = w;
+  double* o_spline = reinterpret_cast<double*>(r + rec.off_spline);
+  for (int j = tid; j < np; j += 256) o_spline[j] = (double)nodes[(size_t)j * N + first + (size_t)w * R];
 }
 
 // single-workgroup bitonic sort of (return, index) pairs in global memory (n2 = pow2 >= n)
@@ -528,6 +606,7 @@ struct mjpcx_ctx {
   int next_slot = 0;
   // pinned + device-mapped result record of mjpcx_best
   void* best_host = nullptr; void* best_dev = nullptr; size_t best_cap = 0;
+  hipEvent_t source_done = nullptr;  // mjpcx_robust_step_batched: orders this stream behind the source context's
   // rollout buffers
   DevBuf d_nodes, d_in_nodes, d_ilqg, d_ilqg_out;
   PinnedBlock h_ilqg;  // host side of d_ilqg: the input arrays of the iLQG / Gradient entry points (upload_arrays; one H2D copy, marked: the feedback rollouts do not sync)
@@ -1062,10 +1141,13 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
 
 template <typename T>
 int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node_times,
-               const double* node_values, const double* nominal, const mjpcx_noise_spec* ns, int E = 0, const double* variance_rows = nullptr) {
+               const double* node_values, const double* nominal, const mjpcx_noise_spec* ns, int E = 0, const double* variance_rows = nullptr,
+               bool nodes_on_device = false) {
   // E = 0: the plain entry points (one environment, the state of mjpcx_set_state). E >= 1: N = E x n_per_env candidates, environment-major,
   // from the states of mjpcx_set_states; node_times is E x P and nominal E x P*nu. Same launch code, same kernels. variance_rows
   // (mjpcx_rollout_noise_batched_ce): E x P*nu cross-entropy variances, one row per environment, instead of ns->param_variance for all.
+  // nodes_on_device (mjpcx_robust_step_batched): a kernel enqueued on this stream has already written the N splines into d_nodes, which
+  // the caller reserved for this shape -- no host splines, no scatter, no sync.
   int rc;
   if ((rc = reserve_rollout(c, N, H, P)) != MJPCX_OK) return rc;
   const int np = P * c->nu;
@@ -1093,7 +1175,7 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
                        (const double*)c->d_in_nodes.p, (T*)c->d_nodes.p, N, np);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));  // pageable source buffer: make caller reuse safe
-  } else {
+  } else if (!nodes_on_device) {
     a.noise.mode = ns->mode;
     a.noise.seed = ns->seed; a.noise.iteration = ns->iteration;
     a.noise.candidate_offset = ns->candidate_offset; a.noise.nominal_candidate = ns->nominal_candidate;
@@ -1546,6 +1628,7 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   c->h_grad.release();
   if (c->best_host) (void)hipHostFree(c->best_host);
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
+  if (c->source_done) (void)hipEventDestroy(c->source_done);
   (void)mjpcx_comm_destroy(c);
   c->wh.release();
   DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
@@ -1704,7 +1787,6 @@ int check_batched_args(mjpcx_ctx* c, int E, int n, int H, int P, int interp, con
     return fail(c, MJPCX_EINVAL, "batched rollout: n_per_env = " + std::to_string(n) + " must be a positive multiple of 64 (a wavefront serves one environment)");
   if ((long long)E * n > 0x7fffffffLL / 64) return fail(c, MJPCX_EINVAL, "batched rollout: too many candidates");
   if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, "batched rollouts on a context sharded with mjpcx_comm_init are not implemented");
-  if (c->xfrc_std > 0) return fail(c, MJPCX_EUNSUPPORTED, "batched rollouts with xfrc noise (NoisyRollout) are not implemented");
   if (c->env_E != E)
     return fail(c, MJPCX_EINVAL, c->env_E == 0 ? std::string("batched rollout before mjpcx_set_states")
                                                : "batched rollout of " + std::to_string(E) + " environments after mjpcx_set_states of " + std::to_string(c->env_E));
@@ -1722,6 +1804,19 @@ int mjpcx_rollout_splines_batched(mjpcx_ctx* c, int E, int n, int H, int P, int 
   if (!node_values) return fail(c, MJPCX_EINVAL, "null node_values");
   return c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E)
                             : do_rollout<float>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E);
+}
+
+int mjpcx_rollout_splines_noisy_batched(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* node_values,
+                                        double xfrc_std, double xfrc_rate, uint64_t seed, int candidate_offset) {
+  int rc = check_batched_args(c, E, n, H, P, interp, node_times);
+  if (rc != MJPCX_OK) return rc;
+  if (!node_values) return fail(c, MJPCX_EINVAL, "null node_values");
+  if (!(xfrc_std >= 0) || !(xfrc_rate > 0)) return fail(c, MJPCX_EINVAL, "xfrc_std must be >= 0 and xfrc_rate > 0");
+  c->xfrc_std = xfrc_std; c->xfrc_rate = xfrc_rate; c->xfrc_seed = seed; c->xfrc_offset = candidate_offset;
+  rc = c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E)
+                          : do_rollout<float>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E);
+  c->xfrc_std = 0;
+  return rc;
 }
 
 int mjpcx_rollout_noise_batched(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* nominal,
@@ -1827,6 +1922,92 @@ int mjpcx_best_batched(mjpcx_ctx* c, int E, int ref_candidate, int32_t* index, d
     if (best_return) best_return[e] = r->best_return;
     if (ref_return) ref_return[e] = r->ref_return;
     if (spline_values) std::memcpy(spline_values + (size_t)e * np, r->spline, (size_t)np * 8);
+  }
+  return MJPCX_OK;
+}
+
+int mjpcx_robust_step_batched(mjpcx_ctx* c, mjpcx_ctx* src, int E, int k, int R, int H, int interp, const double* node_times, double xfrc_std,
+                              double xfrc_rate, uint64_t seed, int candidate_offset, int32_t* best, int32_t* candidate, double* candidate_return,
+                              double* perturbed_score, int32_t* valid, double* spline_values) {
+  const std::string who = "mjpcx_robust_step_batched: ";
+  if (!c || !src || !node_times || !best) return fail(c, MJPCX_EINVAL, who + "null argument");
+  if (src == c) return fail(c, MJPCX_EINVAL, who + "the source of the candidates must be another context (its rollout stays fetchable)");
+  if (c->comm_world > 1 || src->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, who + "not implemented on a context sharded with mjpcx_comm_init");
+  if (src->device != c->device || src->precision != c->precision || src->nq != c->nq || src->nv != c->nv || src->nu != c->nu)
+    return fail(c, MJPCX_EINVAL, who + "the two contexts differ in device, precision or model dimensions");
+  if (E < 1 || !src->have_rollout || src->env_n < 1 || (long long)E * src->env_n != src->N)
+    return fail(c, MJPCX_EINVAL, who + "the source's last rollout was not a batched one of " + std::to_string(E) + " environments");
+  if (k < 1 || k > src->env_n || R < 1)
+    return fail(c, MJPCX_EINVAL, who + "num_candidates = " + std::to_string(k) + " outside 1.." + std::to_string(src->env_n) + " or repetitions = " + std::to_string(R) + " < 1");
+  if (!(xfrc_std >= 0) || !(xfrc_rate > 0)) return fail(c, MJPCX_EINVAL, who + "xfrc_std must be >= 0 and xfrc_rate > 0");
+  const long long share = (long long)k * R;
+  if (share > 0x7fffffffLL / 64) return fail(c, MJPCX_EINVAL, who + "too many perturbed rollouts");
+  const int n_pad = (int)((share + 63) / 64 * 64), P = src->P, np = P * c->nu, n_src = src->env_n;
+  int rc = check_batched_args(c, E, n_pad, H, P, interp, node_times);  // (set_states(E) on this context, the rows of node_times, the batch size)
+  if (rc != MJPCX_OK) return rc;
+  if ((long long)np * n_pad > 0x7fffffffLL) return fail(c, MJPCX_EINVAL, who + "too many perturbed rollouts");
+  const int N = E * n_pad;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = reserve_rollout(c, N, H, P)) != MJPCX_OK) return rc;  // (before the first kernel writes d_nodes: do_rollout's own call then moves nothing)
+  RobustRecord rec;
+  rec.off_index = 8;
+  rec.off_ret = (rec.off_index + (size_t)k * 4 + 7) & ~(size_t)7;
+  rec.off_score = rec.off_ret + (size_t)k * 8;
+  rec.off_valid = rec.off_score + (size_t)k * 8;
+  rec.off_spline = (rec.off_valid + (size_t)k * 4 + 7) & ~(size_t)7;
+  rec.bytes = rec.off_spline + (size_t)np * 8;
+  const size_t bytes = rec.bytes * E;
+  if (bytes > c->best_cap) {
+    if (c->best_host) (void)hipHostFree(c->best_host);
+    c->best_host = nullptr; c->best_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
+    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
+    c->best_cap = bytes;
+  }
+  int n2 = 1024;  // (a multiple of the workgroup: env_sort_keys)
+  while (n2 < n_src) n2 <<= 1;
+  const bool in_lds = n2 <= kCeLdsKeys;
+  const size_t lds = in_lds ? (size_t)n2 * 12 : 0;
+  if (!in_lds) HIPCHK(c, c->d_sort.reserve((size_t)E * n2 * 12));
+  // everything below is enqueued on this context's stream, behind what the source's stream holds now
+  if (!c->source_done) HIPCHK(c, hipEventCreateWithFlags(&c->source_done, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(c->source_done, src->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->source_done, 0));
+  auto select = [&](auto kern, const auto* src_nodes, auto* nodes) {
+    hipError_t e = in_lds ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(E), dim3(1024), lds, c->stream, (const double*)src->d_ret.p, src_nodes, src->N, n_src, n2, np, k, R, n_pad,
+                       in_lds ? nullptr : (double*)c->d_sort.p, nodes, (unsigned char*)c->best_dev, rec);
+    return hipGetLastError();
+  };
+  hipError_t le;
+  if (c->precision == 64) le = in_lds ? select(robust_select_kernel<double, true>, (const double*)src->d_nodes.p, (double*)c->d_nodes.p)
+                                      : select(robust_select_kernel<double, false>, (const double*)src->d_nodes.p, (double*)c->d_nodes.p);
+  else le = in_lds ? select(robust_select_kernel<float, true>, (const float*)src->d_nodes.p, (float*)c->d_nodes.p)
+                   : select(robust_select_kernel<float, false>, (const float*)src->d_nodes.p, (float*)c->d_nodes.p);
+  HIPCHK(c, le);
+  // local rollout j of environment e draws the stream (seed + e, candidate_offset + j): one launch of k x R rollouts per environment
+  c->xfrc_std = xfrc_std; c->xfrc_rate = xfrc_rate; c->xfrc_seed = seed; c->xfrc_offset = candidate_offset;
+  rc = c->precision == 64 ? do_rollout<double>(c, N, H, P, interp, node_times, nullptr, nullptr, nullptr, E, nullptr, /*nodes_on_device=*/true)
+                          : do_rollout<float>(c, N, H, P, interp, node_times, nullptr, nullptr, nullptr, E, nullptr, /*nodes_on_device=*/true);
+  c->xfrc_std = 0;
+  if (rc != MJPCX_OK) return rc;
+  if (c->precision == 64)
+    hipLaunchKernelGGL((robust_score_kernel<double>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
+                       (const double*)c->d_nodes.p, np, k, R, n_pad, (unsigned char*)c->best_dev, rec);
+  else
+    hipLaunchKernelGGL((robust_score_kernel<float>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
+                       (const float*)c->d_nodes.p, np, k, R, n_pad, (unsigned char*)c->best_dev, rec);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int e = 0; e < E; e++) {
+    const char* r = (const char*)c->best_host + rec.bytes * e;
+    std::memcpy(best + e, r, 4);
+    if (candidate) std::memcpy(candidate + (size_t)e * k, r + rec.off_index, (size_t)k * 4);
+    if (candidate_return) std::memcpy(candidate_return + (size_t)e * k, r + rec.off_ret, (size_t)k * 8);
+    if (perturbed_score) std::memcpy(perturbed_score + (size_t)e * k, r + rec.off_score, (size_t)k * 8);
+    if (valid) std::memcpy(valid + (size_t)e * k, r + rec.off_valid, (size_t)k * 4);
+    if (spline_values) std::memcpy(spline_values + (size_t)e * np, r + rec.off_spline, (size_t)np * 8);
   }
   return MJPCX_OK;
 }
@@ -2340,7 +2521,6 @@ int mjpcx_rollout_feedback_batched(mjpcx_ctx* c, int E, int n, int H, int mode, 
   int rc;
   if ((rc = check_feedback_args(c, who, H, Tn, mode, representation)) != MJPCX_OK) return rc;
   if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, who + "not implemented on a context sharded with mjpcx_comm_init");
-  if (c->xfrc_std > 0) return fail(c, MJPCX_EUNSUPPORTED, who + "xfrc noise (NoisyRollout) is not implemented for batched rollouts");
   if (c->env_E != E)
     return fail(c, MJPCX_EINVAL, c->env_E == 0 ? who + "before mjpcx_set_states"
                                                : who + std::to_string(E) + " environments after mjpcx_set_states of " + std::to_string(c->env_E));

@@ -148,6 +148,7 @@ template <bool NOISE = true, typename T> __device__ __forceinline__ RolloutArgs<
   if constexpr (NOISE) r.noise.param_variance = env_ptr(a.noise.param_variance, env, a.env_stride);  // (CE: the environment's own variance row)
   r.noise.seed = a.noise.seed + (uint64_t)env;
   r.noise.candidate_offset = a.noise.candidate_offset - env * a.env_n;
+  r.xfrc_seed = a.xfrc_seed + (uint64_t)env;  // (NoisyRollout: the environment's own force-noise stream, as a plain call with seed + env)
   return r;
 }
 

@@ -467,7 +467,9 @@ class GpuBatchSamplingPlanner(_FleetTasks):
                             np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
         self._push_task_rows()
 
-    def optimize_policy(self, horizon, pool=None):
+    def _launch(self, horizon):
+        """First half of a plan step: every environment's nominal resampled, states and task rows pushed, the E x n candidates
+        enqueued in one launch -- nothing read back, no sync. Returns when the rollouts' clock started (rollouts_compute_time)."""
         n = self.num_trajectory_
         self._check_n(n)
         for p in self.envs:
@@ -481,20 +483,30 @@ class GpuBatchSamplingPlanner(_FleetTasks):
         self._push_states()
         self.ctx.rollout_noise_batched(n, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
                                        np.stack([pl.values() for pl in plans]), ns, num_envs=self.num_envs)
-        idx, best_ret, nominal_ret, values = self.ctx.best_batched(self.num_envs, 0)
         self._last = "plan"
         self._n = n
+        return t0
+
+    def _finish(self, t0, ranked):
+        """Second half: `ranked` yields, per environment, (trajectory_order, scores, winner's place in them, winner's spline values) of
+        the rollout _launch enqueued; the members take them as their own planner's."""
         self.rollouts_compute_time = (_time.perf_counter() - t0) * 1e6
         self.iteration += 1
         t0 = _time.perf_counter()
-        for e, p in enumerate(self.envs):
-            p._offset, p._n_local = 0, n
-            p.trajectory_order, p._scores = [int(idx[e])], [float(best_ret[e])]
+        for p, (order, scores, place, values) in zip(self.envs, ranked):
+            p._offset, p._n_local = 0, self._n
+            p.trajectory_order, p._scores = [int(i) for i in order], [float(r) for r in scores]
             p.iteration = self.iteration
-            p._set_winner(int(idx[e]), values[e])
+            p._set_winner(p.trajectory_order[place], values)
+        self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
+
+    def optimize_policy(self, horizon, pool=None):
+        t0 = self._launch(horizon)
+        idx, best_ret, nominal_ret, values = self.ctx.best_batched(self.num_envs, 0)
+        self._finish(t0, [([idx[e]], [best_ret[e]], 0, values[e]) for e in range(self.num_envs)])
+        for e, p in enumerate(self.envs):
             p.best_return, p.nominal_return = float(best_ret[e]), float(nominal_ret[e])
             p.improvement = max(float(nominal_ret[e] - best_ret[e]), 0.0)
-        self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
 
     @property
     def winners(self):
@@ -530,6 +542,222 @@ class GpuBatchSamplingPlanner(_FleetTasks):
 
     def num_parameters(self):
         return self.envs[0].num_parameters()
+
+
+def _fleet_setting(name):
+    """a planner setting that all environments of a batch planner share: read from the first member, written to every member"""
+    def fget(self):
+        return getattr(self.envs[0], name)
+
+    def fset(self, value):
+        for p in self.envs:
+            setattr(p, name, value)
+    return property(fget, fset)
+
+
+def robust_scores(scores, returns, failure, repetitions):
+    """RobustPlanner::OptimizePolicy's choice (robust_planner.cc:141-163), in its order of operations: per ranked candidate, from its
+    unperturbed score, the running mean over the perturbed rollouts [candidate * repetitions, +repetitions) that did not fail; the
+    lowest mean wins, strict < from candidate 0 up. -> (perturbed_score, valid rollouts per candidate, best_candidate)"""
+    perturbed, valid, best, best_score = [], [], -1, 0.0
+    for candidate, mean_return in enumerate(float(x) for x in scores):
+        valid_rollouts = 0
+        for j in range(repetitions * candidate, repetitions * (candidate + 1)):
+            if failure[j]:
+                continue
+            mean_return = (valid_rollouts * mean_return + float(returns[j])) / (valid_rollouts + 1)
+            valid_rollouts += 1
+        perturbed.append(mean_return)
+        valid.append(valid_rollouts)
+        if best == -1 or mean_return < best_score:
+            best, best_score = candidate, mean_return
+    return perturbed, valid, best
+
+
+class GpuRobustPlanner:
+    """mjpc::RobustPlanner (mjpc/planners/robust/robust_planner.{h,cc}) with both fan-outs on the device, the mirror of the C++
+    GpuRobustPlanner for one rank: the delegate (a GpuSamplingPlanner) ranks its candidates, the `robust_candidates` best are rolled
+    out `robust_repetitions` times each under Ornstein-Uhlenbeck force noise in ONE launch on a second context (the delegate's
+    rollout stays fetchable), and the candidate with the best mean perturbed return becomes the policy."""
+
+    def __init__(self, delegate, device=0, precision=64, seed=0, backend_factory=None):
+        if delegate.group is not None and delegate.group.world > 1:
+            raise ValueError("GpuRobustPlanner plans on one rank; the sharded Robust planner is HostPlanner(kind='robust')")
+        self.delegate = delegate
+        self.device, self.precision, self.seed = device, precision, seed
+        self._backend_factory = backend_factory
+        self.model = self.task = self.ctx = None
+        self.iteration = 0          # of the perturbed launches: the force noise of launch i is keyed on rollouts [i k R, (i + 1) k R)
+        self.best_candidate = -1
+        self.perturbed_score = []
+
+    # ---- Initialize, robust_planner.cc:30-50
+    def initialize(self, model, task: Task):
+        self.delegate.initialize(model, task)
+        self.model, self.task = model, task
+        self.nrepetitions_ = int(model.get_number("robust_repetitions", 5))
+        self.ncandidates_ = int(model.get_number("robust_candidates", -1))
+        if self.ncandidates_ == -1:   # derived from the number of rollouts in the sampling config
+            self.ncandidates_ = int(model.get_number("sampling_trajectories", 10)) // max(self.nrepetitions_, 1)
+        self.xfrc_std_ = model.get_number("robust_xfrc", 0.1)
+        self.xfrc_rate_ = model.get_number("robust_xfrc_rate", 0.1)
+
+    def allocate(self):
+        self.delegate.allocate()
+        if self._backend_factory is not None:
+            self.ctx = self._backend_factory(self.task)
+        else:
+            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.delegate.reset(horizon, initial_repeated_action)
+        self.best_candidate = -1
+
+    def set_state(self, state: State):
+        self.delegate.set_state(state)
+
+    # ---- OptimizePolicy, robust_planner.cc:90-170
+    def optimize_policy(self, horizon, pool=None):
+        d = self.delegate
+        k = d.optimize_policy_candidates(self.ncandidates_, horizon, pool)
+        if not k:
+            return
+        if k == 1:   # a single candidate: nothing to compare
+            self.best_candidate = 0
+            d.copy_candidate_to_policy(0)
+            return
+        R = max(self.nrepetitions_, 1)
+        plans = []
+        for i in range(k):
+            p = SamplingPolicy()
+            d._load_candidate_plan(p, d.trajectory_order[i])
+            plans.append(p.plan)
+        values = np.stack([np.broadcast_to(pl.values()[None], (R,) + pl.values().shape) for pl in plans])   # rollout j = candidate * R + repetition
+        sync_task(self.ctx, self.task)
+        self.ctx.set_state(d.state, d.time, d.mocap, d.userdata)
+        self.ctx.rollout_splines_noisy(horizon, plans[0].interpolation(), plans[0].times(), values, self.xfrc_std_, self.xfrc_rate_,
+                                       seed=self.seed, candidate_offset=self.iteration * k * R)
+        self.iteration += 1
+        ret, fail = self.ctx.returns()
+        self.perturbed_score, self.valid_rollouts, self.best_candidate = robust_scores(d._scores[:k], ret, fail, R)
+        d.copy_candidate_to_policy(self.best_candidate)
+
+    def nominal_trajectory(self, horizon, pool=None):
+        return self.delegate.nominal_trajectory(horizon, pool)
+
+    def action_from_policy(self, action, state, time, use_previous=False):
+        return self.delegate.action_from_policy(action, state, time, use_previous)
+
+    def best_trajectory(self):
+        """the chosen candidate's UNPERTURBED trajectory, from the delegate's context"""
+        return self.delegate.best_trajectory()
+
+    def num_parameters(self):
+        return self.delegate.num_parameters()
+
+
+class GpuBatchRobustPlanner(_FleetTasks):
+    """The Robust planner for `num_envs` robots on two contexts of one model: a plan step is the delegate fleet's launch
+    (GpuBatchSamplingPlanner: states and task rows pushed, E x n candidates rolled out, nothing read back) and one
+    `robust_step_batched` on the second context -- per environment the k best candidates selected, replicated R times, rolled out
+    under force noise and scored on the device -- two launch sequences and ONE sync. Member e plans exactly like
+    GpuRobustPlanner(GpuSamplingPlanner(seed = s + e), seed = s + e): the per-robot logic IS that planner's, one member per
+    environment over the delegate fleet's member."""
+    ncandidates_ = _fleet_setting("ncandidates_")
+    nrepetitions_ = _fleet_setting("nrepetitions_")
+    xfrc_std_ = _fleet_setting("xfrc_std_")
+    xfrc_rate_ = _fleet_setting("xfrc_rate_")
+
+    def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
+        self.delegate = GpuBatchSamplingPlanner(num_envs, device, precision, seed, backend_factory)
+        self.num_envs, self.device, self.precision, self.seed = self.delegate.num_envs, device, precision, seed
+        self._backend_factory = backend_factory
+        self.model = self.task = self.ctx = None
+        self.iteration = 0
+        # the members never roll out themselves: each sits on the delegate fleet's member and is handed the second context
+        self.envs = [GpuRobustPlanner(p, device, precision, seed + e, backend_factory=lambda task: self.ctx) for e, p in enumerate(self.delegate.envs)]
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        self.delegate.initialize(model, task)
+        for p in self.envs:
+            p.initialize(model, task)   # (its delegate, the delegate fleet's member, once more: the same values)
+
+    @property
+    def num_trajectory_(self):
+        return self.delegate.num_trajectory_
+
+    @num_trajectory_.setter
+    def num_trajectory_(self, n):
+        self.delegate.num_trajectory_ = n
+
+    def set_tasks(self, tasks):
+        super().set_tasks(tasks)
+        self.delegate.set_tasks(tasks)
+
+    def allocate(self):
+        self.delegate.allocate()
+        if self._backend_factory is not None:
+            self.ctx = self._backend_factory(self.task)
+        else:
+            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+        for p in self.envs:
+            p.ctx = self.ctx
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.delegate.reset(horizon, initial_repeated_action)
+        for p in self.envs:
+            p.best_candidate = -1
+
+    def set_states(self, states):
+        self.delegate.set_states(states)
+
+    def _push_states(self):
+        """the delegate fleet's states and task rows, to the second context"""
+        d = self.delegate.envs
+        sync_task(self.ctx, self.task)
+        self.ctx.set_states(np.stack([p.state for p in d]), np.array([p.time for p in d]),
+                            np.stack([p.mocap for p in d]) if self.model.nmocap else None,
+                            np.stack([p.userdata for p in d]) if self.model.nuserdata else None)
+        self._push_task_rows()
+
+    def optimize_policy(self, horizon, pool=None):
+        d = self.delegate
+        k, R = min(self.ncandidates_, d.num_trajectory_), max(self.nrepetitions_, 1)
+        if k == 1:   # nothing to compare: the delegate fleet's ordinary step (OptimizePolicyCandidates(1) + CopyCandidateToPolicy(0))
+            d.optimize_policy(horizon, pool)
+            for p in self.envs:
+                p.best_candidate = 0
+            return
+        t0 = d._launch(horizon)
+        self._push_states()
+        plans = [p.policy.plan for p in d.envs]
+        out = self.ctx.robust_step_batched(d.ctx, self.num_envs, k, R, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
+                                           self.xfrc_std_, self.xfrc_rate_, seed=self.seed, candidate_offset=self.iteration * k * R)
+        self.iteration += 1
+        d._finish(t0, [(out["candidate"][e], out["candidate_return"][e], int(out["best"][e]), out["spline"][e]) for e in range(self.num_envs)])
+        for e, p in enumerate(self.envs):
+            p.iteration = self.iteration
+            p.best_candidate = int(out["best"][e])
+            p.perturbed_score = [float(x) for x in out["perturbed_score"][e]]
+            p.valid_rollouts = [int(x) for x in out["valid"][e]]
+
+    @property
+    def winners(self):
+        return self.delegate.winners
+
+    def nominal_trajectory(self, horizon, pool=None):
+        return self.delegate.nominal_trajectory(horizon, pool)
+
+    def action_from_policy(self, env, action, state, time, use_previous=False):
+        return self.delegate.action_from_policy(env, action, state, time, use_previous)
+
+    def best_trajectory(self, env):
+        """the chosen candidate's unperturbed trajectory, fetched lazily from the delegate's context (global candidate env * n + winner)"""
+        return self.delegate.best_trajectory(env)
+
+    def num_parameters(self):
+        return self.delegate.num_parameters()
 
 
 class GpuCrossEntropyPlanner:
@@ -702,17 +930,6 @@ class GpuCrossEntropyPlanner:
 
     def num_parameters(self):
         return self.policy.num_spline_points * self.model.nu
-
-
-def _fleet_setting(name):
-    """a planner setting that all environments of a batch planner share: read from the first member, written to every member"""
-    def fget(self):
-        return getattr(self.envs[0], name)
-
-    def fset(self, value):
-        for p in self.envs:
-            setattr(p, name, value)
-    return property(fget, fset)
 
 
 class GpuBatchCrossEntropyPlanner(_FleetTasks):

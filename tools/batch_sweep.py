@@ -24,6 +24,11 @@ environment on the plain calls, the planner's device_chain = False; `device_chai
 both sides. The record carries the batched planner's stage timers (medians; median / min / max under batched_stage_spread_ms) and one
 environment's sequential ones. Default output profiles/batch_sweep_ilqg.jsonl.
 
+--planner robust: the Robust planner's plan step, k = 16 candidates x R = 4 repetitions (--robust 16x4). (a) E GpuRobustPlanner plan steps,
+one after the other, on two contexts (the delegate's rollout, topk, k spline fetches, the noisy rollout of k x R replicated splines,
+returns, the host loop: per robot) against (b) one GpuBatchRobustPlanner plan step on the same two contexts (rollout_noise_batched and
+robust_step_batched: two launch sequences, one sync). Host logic included on both sides. Default output profiles/batch_sweep_robust.jsonl.
+
 --mixed-params: every environment plans with task weights, norm parameters, residual parameters and risk of its own (sampling and
 cross_entropy: set_task_params_batched after set_states, and the plain set_task_params of the same row before every sequential plan
 step; gradient and ilqg: the fleet planner's set_tasks, and every sequential planner on its own task). The kernels do the same work
@@ -159,6 +164,73 @@ def sweep_gradient(name, precision, H, shapes, steps, warmup, out, mixed=False):
         print(json.dumps(rec), flush=True)
         out.write(json.dumps(rec) + "\n")
         out.flush()
+    ctx.close()
+
+
+ROBUST_SHAPES = [("QuadrupedFlat", 64, 100, [(1, 2048), (4, 2048), (8, 2048)]),
+                 ("Cartpole", 64, 128, [(64, 64)])]
+
+
+def sweep_robust(name, precision, H, shapes, steps, warmup, out, k, R, mixed=False):
+    from mujoco_mpc_amd.planners import GpuBatchRobustPlanner, GpuRobustPlanner, GpuSamplingPlanner, State
+    task = load_task(name)
+    m = task.model
+    rng = np.random.default_rng(1)
+    source = capi.Context(task.packed_model(), task.packed(), 0, precision)     # the delegates' rollouts
+    ctx = capi.Context(task.packed_model(), task.packed(), 0, precision)        # the perturbed ones
+    for E, n in shapes:
+        raw, clocks, mocap = initial(task, name, E, rng)
+        states = []
+        for e in range(E):
+            st = State(m)
+            mp = None if mocap is None else mocap[e].reshape(-1, 7)
+            st.set(raw[e][:m.nq], raw[e][m.nq:], mocap_pos=None if mp is None else mp[:, :3], mocap_quat=None if mp is None else mp[:, 3:],
+                   time=float(clocks[e]))
+            states.append(st)
+        singles = [GpuRobustPlanner(GpuSamplingPlanner(precision=precision, seed=7 + e, backend_factory=lambda t: source), precision=precision,
+                                    seed=7 + e, backend_factory=lambda t: ctx) for e in range(E)]
+        both = iter([source, ctx])                                               # the fleet allocates its delegate's context first
+        batch = GpuBatchRobustPlanner(E, precision=precision, seed=7, backend_factory=lambda t: next(both))
+        tasks = mixed_tasks(task, E) if mixed else [task] * E
+        for p, t in zip(singles + [batch], tasks + [task]):
+            p.initialize(m, t)
+            p.ncandidates_, p.nrepetitions_ = k, R
+            p.delegate.num_trajectory_ = n
+            p.allocate()
+            p.reset(H)
+        if mixed:
+            batch.set_tasks(tasks)
+
+        def sequential():
+            for p, st in zip(singles, states):
+                p.set_state(st)
+                p.optimize_policy(H)
+
+        def batched():
+            batch.set_states(states)
+            batch.optimize_policy(H)
+
+        for _ in range(warmup):
+            sequential()
+            batched()
+        ts, tb = [], []
+        for _ in range(steps):   # alternating: both sides see the same clocks and the same neighbours on the machine
+            t0 = time.perf_counter(); sequential(); t1 = time.perf_counter(); batched(); t2 = time.perf_counter()
+            ts.append((t1 - t0) * 1e3)
+            tb.append((t2 - t1) * 1e3)
+        rec = {"planner": "robust", "task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "num_candidates": k,
+               "repetitions": R, "steps": steps, "warmup": warmup, "mixed_params": bool(mixed), "context_kernel": source.kernel_name.split(" (")[0],
+               "note": "context_kernel is the kernel the two contexts were created for: the delegates' rollouts run on it in a launch that reaches "
+                       "its threshold (the A1's quad kernel: MJPCX_QUAD_MIN_N candidates in the launch, 2048 by default -- one robot's 2048 "
+                       "and a fleet's E x 2048 alike), on the wavefront-per-candidate kernel below it; the perturbed rollouts carry force noise and "
+                       "always run on the wavefront-per-candidate kernel (the lane kernels have a NOISY form of their own)",
+               "sequential_ms": stats(ts), "batched_ms": stats(tb), "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)),
+               "beyond_spread": bool(np.max(tb) < np.min(ts)), "batched_inside_sequential_range": bool(np.min(ts) <= np.median(tb) <= np.max(ts)),
+               "same_choice": bool(all(b.best_candidate == p.best_candidate for b, p in zip(batch.envs, singles)))}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+        out.flush()
+    source.close()
     ctx.close()
 
 
@@ -329,22 +401,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg"], default="sampling")
+    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "robust"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
     ap.add_argument("--mixed-params", action="store_true", help="every environment its own task weights, parameters and risk")
+    ap.add_argument("--robust", default="16x4", help="--planner robust: candidates x repetitions")
     ap.add_argument("--no-device-chain", action="store_true", help="--planner ilqg: the sequential middle (the A/B of ilqg_step_batched)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
+        a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl", "robust": "batch_sweep_robust.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
     keep = None if a.shapes is None else {tuple(int(x) for x in sh.split("x")) for sh in a.shapes.split(",")}
     if a.steps < 10:
         raise SystemExit("batch_sweep.py: at least 10 timed steps")
     with open(a.out, "w") as out:
-        for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES}.get(a.planner, SHAPES):
+        for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES, "robust": ROBUST_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
             if shapes and (a.only is None or a.only == name):
                 if a.planner == "gradient":
                     sweep_gradient(name, precision, H, shapes, a.steps, a.warmup, out, a.mixed_params)
+                elif a.planner == "robust":
+                    k, R = (int(x) for x in a.robust.split("x"))
+                    sweep_robust(name, precision, H, shapes, a.steps, a.warmup, out, k, R, a.mixed_params)
                 elif a.planner == "ilqg":
                     sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out, False if a.no_device_chain else None, a.mixed_params)
                 else:

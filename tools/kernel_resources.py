@@ -30,7 +30,8 @@ for obj in sorted(os.listdir(os.path.join(ROOT, "mujoco_mpc_amd", "build"))):
     def emit(rec):
         if rec and "name" in rec:
             name = subprocess.run(["c++filt", rec["name"]], capture_output=True, text=True).stdout.strip()
-            out.setdefault(obj, {})[re.sub(r"\(.*", "", name)[:120]] = {k: rec[k] for k in KEYS if k in rec}
+            name = name.replace("(anonymous namespace)::", "")   # (or every kernel of an unnamed namespace would share one key)
+            out.setdefault(obj, {})[re.sub(r"\(.*", "", name)] = {k: rec[k] for k in KEYS if k in rec}
 
     cur = None
     for line in notes.splitlines():
