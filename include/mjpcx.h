@@ -408,8 +408,8 @@ int mjpcx_rollout_noise_batched_ce(mjpcx_ctx* ctx, int num_envs, int n_per_env, 
 int mjpcx_ce_update_batched(mjpcx_ctx* ctx, int num_envs, int n_elite, int skip_candidate, int32_t* index, double* total_return,
                             double* mean, double* variance, double* avg_return);
 
-/* mjpcx_best, segmented: one launch and one sync give, per environment, the argmin over its n_per_env returns (ties by
- * index) as a LOCAL index -> index[E], best_return[E]; the return of local candidate ref_candidate (-1: skip) -> ref_return[E];
+/* mjpcx_best, segmented: one launch and one sync give, per environment, the argmin over its n_per_env returns (mjpcx_topk's
+ * order: ties to the lower index, NaN last) as a LOCAL index -> index[E], best_return[E]; the return of local candidate ref_candidate (-1: skip) -> ref_return[E];
  * the winner's spline values -> spline_values (E x P x nu). Any output but index may be NULL. */
 int mjpcx_best_batched(mjpcx_ctx* ctx, int num_envs, int ref_candidate, int32_t* index, double* best_return,
                        double* ref_return, double* spline_values);
@@ -452,11 +452,15 @@ int mjpcx_get_returns(mjpcx_ctx* ctx, double* total_return, int32_t* failure);
 int mjpcx_get_return_at(mjpcx_ctx* ctx, int candidate, double* total_return, int32_t* failure);
 
 /* Device-side selection replacing std::partial_sort (sampling/planner.cc:184):
- * indices and returns of the k best candidates, ascending, ties by index. */
+ * indices and returns of the k best candidates, ascending, ties to the lower index, NaN (of either sign) last and among
+ * themselves by index; -0.0 and +0.0 are equal and tie by index. This is the order of every selection below (mjpcx_best,
+ * mjpcx_best_batched, mjpcx_ce_update_batched, the select step of mjpcx_robust_step_batched). Returns come back with the
+ * bits the rollout wrote. All NaN: index 0 first. */
 int mjpcx_topk(mjpcx_ctx* ctx, int k, int32_t* index, double* total_return);
 
 /* The reads one Predictive-Sampling policy update needs, fused into one launch and one sync:
- * argmin over total_return (ties by index) -> *index, *best_return; the winner's spline values
+ * argmin over total_return (the first of mjpcx_topk's order: ties to the lower index, a NaN only when every return is
+ * one) -> *index, *best_return; the winner's spline values
  * (P x nu, may be NULL); and the return of `ref_candidate` (the nominal, candidate 0; -1: skip)
  * for `improvement` (sampling/planner.cc:197-212, 534-543). */
 int mjpcx_best(mjpcx_ctx* ctx, int ref_candidate, int32_t* index, double* best_return, double* ref_return,
