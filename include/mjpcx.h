@@ -355,7 +355,8 @@ int mjpcx_set_residual_states(mjpcx_ctx* ctx, int num_envs, const int32_t* resid
  * E x num_parameter, risk E. Any pointer may be NULL: that field is the context's (mjpcx_set_task_params) for every environment.
  * All four NULL: everything shared again. After mjpcx_set_states with the same E (MJPCX_EINVAL otherwise).
  *   - Every batched entry point reads the rows: mjpcx_rollout_splines_batched, mjpcx_rollout_splines_noisy_batched,
- *     mjpcx_rollout_noise_batched, mjpcx_rollout_noise_batched_ce, mjpcx_robust_step_batched, mjpcx_rollout_feedback_batched, mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched.
+ *     mjpcx_rollout_noise_batched, mjpcx_rollout_noise_batched_ce, mjpcx_robust_step_batched, mjpcx_rollout_sample_gradient_batched,
+ *     mjpcx_sample_gradient_update_batched, mjpcx_rollout_feedback_batched, mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched.
  *     Environment e of such a call behaves exactly like the plain call after mjpcx_set_task_params(row e): equal bits.
  *   - mjpcx_set_task_params and the plain entry points neither read nor clear the rows: plain and batched values live side by
  *     side, as the states of mjpcx_set_state and mjpcx_set_states do (NOT the rule of mjpcx_set_residual_state above: a plain
@@ -438,6 +439,50 @@ int mjpcx_robust_step_batched(mjpcx_ctx* ctx, mjpcx_ctx* source, int num_envs, i
                               int interpolation, const double* node_times, double xfrc_std, double xfrc_rate, uint64_t seed,
                               int candidate_offset, int32_t* best, int32_t* candidate, double* candidate_return,
                               double* perturbed_score, int32_t* valid, double* spline_values);
+
+/* The Sample-Gradient planner (mjpc/planners/sample_gradient/planner.cc:168-493) for E environments: two entry points per plan step, the
+ * second ends in the step's ONE sync. n = n_per_env, G = num_gradient in 0..n-1, num_noisy = n - G.
+ *
+ * mjpcx_rollout_sample_gradient_batched replaces planner.cc:290-400 (ResamplePolicy of the gradient candidates, AddNoiseToPolicy, Rollouts):
+ * a kernel writes every candidate's spline nodes on the device, then the batched rollout runs from them; nothing is read back, no sync.
+ * Local candidate 0 is the nominal (nominal_values E x P x nu, as given); candidates 1..num_noisy-1 are
+ * clamp(nominal + noise_exploration * z, ctrlrange), z = gaussian_pair(seed + e, local candidate, j >> 1, iteration)[j & 1] for parameter
+ * j = node * nu + actuator (standard normals, not scaled by the control range); candidates num_noisy..n-1 are the gradient candidates the
+ * previous mjpcx_sample_gradient_update_batched left on the device, each its own spline over that step's node times, sampled at
+ * node_times by TimeSpline::Sample (zero / linear / cubic) and clamped. gradient_values (E x G x P x nu) with gradient_times (E x P)
+ * uploads them instead -- after a reset, on the first step -- ; both NULL takes the device's. Environment e of a call equals a
+ * one-environment call with seed + e, bit for bit. Validation and error codes as mjpcx_rollout_noise_batched, plus MJPCX_EINVAL for G
+ * outside 0..n-1, noise_exploration <= 0, one of the two gradient arrays without the other, gradient_times not strictly increasing, and
+ * NULL gradient arrays with G >= 1 when no update with the same E, G, P has run on this context. */
+int mjpcx_rollout_sample_gradient_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int num_gradient, int horizon, int num_nodes,
+                                          int interpolation, const double* node_times, const double* nominal_values, double noise_exploration,
+                                          uint64_t seed, int iteration, const double* gradient_values, const double* gradient_times);
+
+#define MJPCX_SG_COMPUTE_WEIGHTS 1 /* recompute the shaping weights (planner.cc: return_weight_.size() != num_noisy) */
+#define MJPCX_SG_ZERO_GRADIENT 2   /* the gradient of the step before is zero (after Planner::Reset) */
+/* mjpcx_sample_gradient_update_batched replaces planner.cc:168-264 and 401-493 after that rollout, per environment, in one launch:
+ *   - the order is ascending returns, ties to the lower index, NaN last; winner = order[0] if its return is < the nominal's, else 0
+ *     -> index (E, LOCAL); winner_type 0 nominal / 1 perturbed / 2 gradient; best_return = return[winner]; nominal_return = return[0];
+ *     improvement = max(nominal_return - best_return, 0); spline_values (E x P x nu) the winner's nodes as mjpcx_best_batched gives them;
+ *   - for G >= 1 the gradient estimate, kept exactly as the reference has it: gradient_previous <- gradient; with
+ *     MJPCX_SG_COMPUTE_WEIGHTS the weights w[i] = max(0, f0 - log(order_noisy[i] + 1)) / den - 1 / num_noisy, f0 = log(num_noisy / 2 + 1),
+ *     den the sum of the numerators, from the order of the first num_noisy returns ALONE -- the logarithm takes the candidate index at
+ *     sorted position i, not i -- and that step pairs them with that order; otherwise the cached weights pair with the first num_noisy
+ *     entries of the order over all n candidates. gradient[j] = sum_i (w[i] / num_noisy) z[order[i]][j], fp64 in every context, z
+ *     re-drawn from the counter; the nominal and the gradient candidates carry zero noise (the reference's stale noise rows after a
+ *     change of G are not reproduced). Summation: partial sum t of 256 takes positions t, t + 256, ... in order; then
+ *     sum[t] += sum[t + s] for s = 128, 64, ..., 1;
+ *   - the next gradient candidates g < G: per parameter nominal + (-s filter) gradient + (-s (1 - filter)) gradient_previous, two
+ *     rounded additions in that order, clamped, with s = LogScale(max_step, min_step, G)[g] / noise_exploration; they stay on the
+ *     device with this step's node times.
+ * The weights, both gradients and the candidates live in the context. gradient (E x P*nu) and every other output but index may be
+ * NULL. Deterministic: two calls on the same rollout with MJPCX_SG_ZERO_GRADIENT give the same bits. MJPCX_EINVAL when the last
+ * rollout was not a mjpcx_rollout_sample_gradient_batched of num_envs environments with this num_gradient, for unknown flags,
+ * max_step / min_step / noise_exploration <= 0, and without MJPCX_SG_COMPUTE_WEIGHTS when no weights for this E and num_noisy exist. */
+int mjpcx_sample_gradient_update_batched(mjpcx_ctx* ctx, int num_envs, int num_gradient, int flags, double filter, double max_step,
+                                         double min_step, double noise_exploration, int32_t* index, int32_t* winner_type,
+                                         double* best_return, double* nominal_return, double* improvement, double* spline_values,
+                                         double* gradient);
 
 /* Block until everything queued on the context's stream has finished. */
 int mjpcx_sync(mjpcx_ctx* ctx);

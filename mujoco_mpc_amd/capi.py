@@ -32,7 +32,10 @@ EXPORTS = [
     "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched", "mjpcx_gradient_step_batched",
     "mjpcx_rollout_feedback_batched", "mjpcx_ilqg_step_batched",
     "mjpcx_rollout_splines_noisy_batched", "mjpcx_robust_step_batched",
+    "mjpcx_rollout_sample_gradient_batched", "mjpcx_sample_gradient_update_batched",
 ]
+
+SG_COMPUTE_WEIGHTS, SG_ZERO_GRADIENT = 1, 2   # MJPCX_SG_* flags of mjpcx_sample_gradient_update_batched
 
 _LIB = None
 
@@ -79,6 +82,8 @@ def lib():
         L.mjpcx_robust_step_batched.argtypes = ([vp, vp] + [C.c_int] * 5 + [c_f64p, C.c_double, C.c_double, C.c_uint64, C.c_int] +
                                                 [c_i32p, c_i32p, c_f64p, c_f64p, c_i32p, c_f64p])
         L.mjpcx_rollout_noise_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
+        L.mjpcx_rollout_sample_gradient_batched.argtypes = [vp] + [C.c_int] * 6 + [c_f64p, c_f64p, C.c_double, C.c_uint64, C.c_int, c_f64p, c_f64p]
+        L.mjpcx_sample_gradient_update_batched.argtypes = ([vp] + [C.c_int] * 3 + [C.c_double] * 4 + [c_i32p, c_i32p] + [c_f64p] * 5)
         L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_rollout_noise_batched_ce.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_ce_update_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p]
@@ -379,6 +384,46 @@ class Context:
                                                     float(eps), int(centered), int(representation), P, as_f64p(nt),
                                                     as_f64p(out["nominal_return"]), as_f64p(out["k"]), as_f64p(out["gradient"]),
                                                     as_f64p(out["dV"]), *opt))
+        return out
+
+    def rollout_sample_gradient_batched(self, n_per_env, num_gradient, horizon, interp, node_times, nominal, noise_exploration, seed=0, iteration=0,
+                                        gradient_values=None, gradient_times=None, num_envs=None):
+        """the Sample-Gradient planner's candidates, generated on the device, and their rollout (mjpcx_rollout_sample_gradient_batched):
+        node_times E x P, nominal E x P x nu; local candidate 0 the nominal, 1..n-G-1 clamp(nominal + noise_exploration z) with the normals
+        of (seed + e, candidate, pair, iteration), the last G the gradient candidates -- gradient_values E x G x P x nu over
+        gradient_times E x P, or (both None) those the last sample_gradient_update_batched left on the device -- sampled at node_times."""
+        nt, nom = _f(node_times), _f(nominal)
+        E = int(num_envs) if num_envs is not None else (nt.shape[0] if nt.ndim == 2 else 1)
+        P = nt.size // E if E > 0 else nt.size
+        n, G = int(n_per_env), int(num_gradient)
+        assert E < 1 or nom.size == E * P * self.nu
+        gv = gt = None
+        if gradient_values is not None or gradient_times is not None:
+            gv, gt = _f(gradient_values), _f(gradient_times)
+            if gv.size != max(E, 0) * max(G, 0) * P * self.nu or gt.size != max(E, 0) * P:
+                raise ValueError(f"rollout_sample_gradient_batched: gradient_values of {gv.size} and gradient_times of {gt.size} entries for "
+                                 f"{E} environments x {G} gradient candidates x {P} nodes")
+            if gv.size == 0:
+                gv = np.zeros(1)   # (G = 0: a pointer the library never reads)
+        self._chk(lib().mjpcx_rollout_sample_gradient_batched(self.handle, E, n, G, int(horizon), P, int(interp), as_f64p(nt), as_f64p(nom),
+                                                              float(noise_exploration), int(seed), int(iteration),
+                                                              as_f64p(gv) if gv is not None else None, as_f64p(gt) if gt is not None else None))
+        self.N, self.H, self.P, self.n_per_env = E * n, int(horizon), P, n
+
+    def sample_gradient_update_batched(self, num_envs, num_gradient, flags, gradient_filter, max_step, min_step, noise_exploration):
+        """the Sample-Gradient update of every environment after rollout_sample_gradient_batched, one launch / one sync
+        (mjpcx_sample_gradient_update_batched): dict of index (E: the winner, local), winner_type (E: 0 nominal, 1 perturbed, 2 gradient),
+        best_return, nominal_return, improvement (E), spline (E x P x nu: the winner's) and gradient (E x P*nu). The weights, the gradient
+        and the next gradient candidates stay in the context."""
+        E = int(num_envs)
+        Ea, P = max(E, 1), max(self.P, 1)
+        out = dict(index=np.zeros(Ea, np.int32), winner_type=np.zeros(Ea, np.int32), best_return=np.zeros(Ea), nominal_return=np.zeros(Ea),
+                   improvement=np.zeros(Ea), spline=np.zeros((Ea, P, self.nu)), gradient=np.zeros((Ea, P * self.nu)))
+        self._chk(lib().mjpcx_sample_gradient_update_batched(self.handle, E, int(num_gradient), int(flags), float(gradient_filter), float(max_step),
+                                                             float(min_step), float(noise_exploration), as_i32p(out["index"]),
+                                                             as_i32p(out["winner_type"]), as_f64p(out["best_return"]),
+                                                             as_f64p(out["nominal_return"]), as_f64p(out["improvement"]),
+                                                             as_f64p(out["spline"]), as_f64p(out["gradient"])))
         return out
 
     def best_batched(self, num_envs, ref_candidate=0, with_spline=True):

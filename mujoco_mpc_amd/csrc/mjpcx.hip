@@ -478,6 +478,216 @@ __global__ __launch_bounds__(256) void robust_score_kernel(const double* __restr
   for (int j = tid; j < np; j += 256) o_spline[j] = (double)nodes[(size_t)j * N + first + (size_t)w * R];
 }
 
+// The Sample-Gradient planner's plan step for E environments (mjpcx_rollout_sample_gradient_batched, mjpcx_sample_gradient_update_batched):
+// two kernels around the batched rollout. Everything is fp64 with nothing contracted, whatever the context's precision: the same
+// additions, multiplications and divisions in numpy (planners.sample_gradient_update) give the same bits from the same normals.
+struct SgCandArgs {
+  int n, num_noisy, P, nu, interp, num_envs, blocks_per_env;
+  const double *times, *nominal, *range;   // this step's node times E x P, nominals E x P*nu, ctrlrange 2 nu
+  const double *grad_times, *grad_values;  // the gradient candidates: their node times E x P, values E x G x P*nu
+  double noise_exploration;
+  uint64_t seed;
+  uint32_t iteration;
+};
+// TimeSpline::Sample (spline.cc:103-156) of actuator k of one spline at `time`: std::upper_bound, the end nodes held outside the grid,
+// zero / linear / cubic Hermite with the finite-difference slopes of spline.cc:269-287, in the order of operations of spline.py.
+__device__ __forceinline__ double sg_spline_sample(const double* __restrict__ ts, const double* __restrict__ vs, int P, int nu, int k, int interp, double time) {
+#pragma clang fp contract(off)
+  int up = 0;
+  while (up < P && !(time < ts[up])) up++;
+  if (up == P) return vs[(size_t)(P - 1) * nu + k];
+  if (up == 0) return vs[k];
+  const int lo = up - 1;
+  const double tl = ts[lo], tu = ts[up], t = (time - tl) / (tu - tl);
+  const double vl = vs[(size_t)lo * nu + k], vu = vs[(size_t)up * nu + k];
+  if (interp == 0) return vl;
+  if (interp == 1) return vl * (1 - t) + vu * t;
+  auto slope = [&](int node) {
+    const double v = vs[(size_t)node * nu + k];
+    if (node == 0) return (vs[(size_t)nu + k] - v) / (ts[1] - ts[0]);
+    if (node == P - 1) return (v - vs[(size_t)(node - 1) * nu + k]) / (ts[node] - ts[node - 1]);
+    return 0.5 * (vs[(size_t)(node + 1) * nu + k] - v) / (ts[node + 1] - ts[node]) + 0.5 * (v - vs[(size_t)(node - 1) * nu + k]) / (ts[node] - ts[node - 1]);
+  };
+  const double c0 = 2.0 * t * t * t - 3.0 * t * t + 1.0;
+  const double c1 = (t * t * t - 2.0 * t * t + t) * (tu - tl);
+  const double c2 = -2.0 * t * t * t + 3 * t * t;
+  const double c3 = (t * t * t - t * t) * (tu - tl);
+  return c0 * vl + c1 * slope(lo) + c2 * vu + c3 * slope(up);
+}
+//  1. Candidates (sample_gradient/planner.cc:355-400, 290-352): one thread per (local candidate c, parameter pair q) of an environment
+//     (blocks_per_env workgroups each), consecutive threads consecutive candidates, so the stores into the [parameter][candidate] node rows are coalesced.
+//     c = 0 the nominal as it came; 0 < c < num_noisy clamp(nominal + noise_exploration z), z = gaussian_pair(seed + e, c, q, iteration)
+//     -- ONE Philox + Box-Muller for the two parameters of the pair, not scaled by the control range --; c >= num_noisy the gradient
+//     candidate c - num_noisy, its own spline over grad_times, sampled at this step's node times and clamped (ResamplePolicy).
+template <typename T>
+__global__ __launch_bounds__(256) void sg_candidates_kernel(const SgCandArgs a, T* __restrict__ nodes) {
+#pragma clang fp contract(off)
+  const int env = blockIdx.x / a.blocks_per_env, n = a.n, np = a.P * a.nu, G = n - a.num_noisy;
+  const int work = (blockIdx.x - env * a.blocks_per_env) * 256 + threadIdx.x;
+  const int q = work / n, c = work - q * n;
+  if (2 * q >= np) return;
+  const size_t N = (size_t)a.num_envs * n, at = (size_t)env * n + c;
+  const double* nominal = a.nominal + (size_t)env * np;
+  double z[2] = {0.0, 0.0};
+  if (c > 0 && c < a.num_noisy) gaussian_pair(a.seed + (uint64_t)env, (uint32_t)c, (uint32_t)q, a.iteration, z);
+  for (int e = 0; e < 2; e++) {
+    const int j = 2 * q + e;
+    if (j >= np) break;
+    const int p = j / a.nu, k = j - p * a.nu;
+    const double lo = a.range[2 * k], hi = a.range[2 * k + 1];
+    double v = nominal[j];
+    if (c >= a.num_noisy)
+      v = clampv(sg_spline_sample(a.grad_times + (size_t)env * a.P, a.grad_values + ((size_t)env * G + (c - a.num_noisy)) * np, a.P, a.nu, k, a.interp,
+                                  a.times[(size_t)env * a.P + p]), lo, hi);
+    else if (c > 0)
+      v = clampv(v + a.noise_exploration * z[e], lo, hi);
+    nodes[(size_t)j * N + at] = (T)v;
+  }
+}
+//  2. Update (planner.cc:168-264, 401-493): workgroups (environment, chunk of four parameter pairs) of 1024 threads. Every workgroup
+//     sorts its environment's returns with env_sort_keys -- all n of them, or with MJPCX_SG_COMPUTE_WEIGHTS the first num_noisy only,
+//     as the reference does in that step; chunk 0 then finds the winner as the less_ri minimum of the sorted head and the rest.
+//     The reference's behaviour is kept exactly, not repaired: the shaping weight of sorted position i takes the logarithm of the
+//     CANDIDATE INDEX at that position, log(order[i] + 1), not of the rank; the weights are cached and on later steps pair with the
+//     first num_noisy entries of the order over ALL candidates, where the nominal and the gradient candidates carry zero noise.
+//     Summation order (den and every gradient entry alike): thread t of a quarter of the workgroup adds the terms of the sorted
+//     positions t, t + 256, t + 512, ... in that order, starting from 0; the 256 partial sums meet in a halving tree,
+//     s = 128, 64, ..., 1: sum[t] += sum[t + s]. The quarters take one pair each; z is re-drawn from the counter, never stored.
+//     log(k + 1) comes from a table the host computed (`logs`), so the device adds, multiplies and divides only.
+struct SgRecord { size_t bytes, off_spline, off_grad; };  // [index (i32) | winner_type (i32) | best | nominal | improvement | spline (np) | gradient (np)]
+struct SgUpdateArgs {
+  int n, n2, P, nu, G, num_noisy, flags;
+  double filter, noise_exploration, f0;
+  uint64_t seed;
+  uint32_t iteration;
+  const double *times, *nominal, *range, *logs, *steps;  // E x P, E x P*nu, 2 nu, log(k + 1) for k < num_noisy, LogScale step sizes G
+  double *gradient, *gradient_previous, *weights, *grad_times, *grad_values;  // the context's: E x P*nu (two), E x num_noisy, E x P, E x G x P*nu
+};
+__device__ __forceinline__ double sg_tree256(double v, int t, double* sm) {  // every thread of the workgroup calls it
+#pragma clang fp contract(off)
+  sm[t] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) sm[t] += sm[t + s];
+    __syncthreads();
+  }
+  const double r = sm[0];
+  __syncthreads();
+  return r;
+}
+template <typename T, bool IN_LDS>
+__global__ __launch_bounds__(1024) void sg_update_kernel(const double* __restrict__ ret, const T* __restrict__ nodes, const SgUpdateArgs a, double* scratch,
+                                                          unsigned char* out, SgRecord rec) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) double ce_lds[];
+  __shared__ double sm[2][4][256];
+  __shared__ RetIdx smin[16];
+  const int env = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x, n = a.n, nn = a.num_noisy, np = a.P * a.nu, first = env * n;
+  const size_t N = (size_t)gridDim.x * n;
+  double* keys;
+  int* idx;
+  if constexpr (IN_LDS) { keys = ce_lds; idx = reinterpret_cast<int*>(ce_lds + a.n2); }
+  else { keys = scratch + ((size_t)env * gridDim.y + chunk) * (a.n2 + a.n2 / 2); idx = reinterpret_cast<int*>(keys + a.n2); }
+  const bool compute = a.G > 0 && (a.flags & MJPCX_SG_COMPUTE_WEIGHTS), zero = (a.flags & MJPCX_SG_ZERO_GRADIENT) != 0;
+  const int sorted = compute ? nn : n;
+  env_sort_keys(ret, first, sorted, a.n2, -1, keys, idx, tid);
+  unsigned char* r = out + (size_t)env * rec.bytes;
+  double* o_grad = reinterpret_cast<double*>(r + rec.off_grad);
+  if (chunk == 0) {
+    RetIdx rest{NAN, 0x7fffffff};  // (sorts behind every candidate)
+    for (int c = sorted + tid; c < n; c += 1024) {
+      const RetIdx v{ret[first + c], c};
+      if (less_ri(v, rest)) rest = v;
+    }
+    rest = wave_argmin(rest);
+    const int wave = tid >> 6, lane = tid & 63;
+    if (lane == 0) smin[wave] = rest;
+    __syncthreads();
+    rest = wave_argmin(lane < 16 ? smin[lane] : RetIdx{NAN, 0x7fffffff});
+    RetIdx best{keys[0], idx[0]};
+    if (less_ri(rest, best)) best = rest;
+    const double r0 = ret[first];
+    const int w = best.r < r0 ? best.i : 0;  // a strict improvement on the nominal, or the nominal
+    if (tid == 0) {
+      const double rw = ret[first + w], d = r0 - rw;
+      reinterpret_cast<int*>(r)[0] = w;
+      reinterpret_cast<int*>(r)[1] = w == 0 ? 0 : (w < nn ? 1 : 2);
+      reinterpret_cast<double*>(r)[1] = rw;
+      reinterpret_cast<double*>(r)[2] = r0;
+      reinterpret_cast<double*>(r)[3] = d > 0 ? d : 0.0;
+    }
+    double* o_spline = reinterpret_cast<double*>(r + rec.off_spline);
+    for (int j = tid; j < np; j += 1024) o_spline[j] = (double)nodes[(size_t)j * N + first + w];
+    if (a.G < 1) {  // GradientCandidates returns at once: the gradient stays as it is (or as Reset left it)
+      for (int j = tid; j < np; j += 1024) {
+        const double g = zero ? 0.0 : a.gradient[(size_t)env * np + j];
+        if (zero) a.gradient[(size_t)env * np + j] = 0.0;
+        o_grad[j] = g;
+      }
+    } else {
+      for (int p = tid; p < a.P; p += 1024) a.grad_times[(size_t)env * a.P + p] = a.times[(size_t)env * a.P + p];
+    }
+  }
+  if (a.G < 1) return;
+  const int quarter = tid >> 8, t = tid & 255;
+  double den = 0.0;
+  if (compute) {
+    double acc = 0.0;
+    for (int i = t; i < nn; i += 256) {
+      const double f = a.f0 - a.logs[idx[i]];
+      acc += f > 0 ? f : 0.0;
+    }
+    den = sg_tree256(acc, t, sm[0][quarter]);
+  }
+  double* weights = a.weights + (size_t)env * nn;
+  auto weight = [&](int i) {
+    if (!compute) return weights[i];
+    const double f = a.f0 - a.logs[idx[i]];
+    return (f > 0 ? f : 0.0) / den - 1.0 / nn;
+  };
+  if (compute && chunk == 0)
+    for (int i = tid; i < nn; i += 1024) weights[i] = weight(i);
+  const int q = chunk * 4 + quarter;
+  const bool live = 2 * q < np;
+  double acc0 = 0.0, acc1 = 0.0;
+  if (live)
+    for (int i = t; i < nn; i += 256) {
+      const int c = idx[i];
+      if (c < 1 || c >= nn) continue;  // the nominal and the gradient candidates carry no noise: a zero term
+      const double wi = weight(i) / nn;
+      double z[2];
+      gaussian_pair(a.seed + (uint64_t)env, (uint32_t)c, (uint32_t)q, a.iteration, z);
+      acc0 += z[0] * wi;
+      acc1 += z[1] * wi;
+    }
+  const double sum[2] = {sg_tree256(acc0, t, sm[0][quarter]), sg_tree256(acc1, t, sm[1][quarter])};
+  double old[2] = {0.0, 0.0};
+  for (int e = 0; e < 2; e++) {
+    const int j = 2 * q + e;
+    if (live && j < np && !zero) old[e] = a.gradient[(size_t)env * np + j];
+  }
+  __syncthreads();  // every thread has the gradient of the step before
+  for (int e = 0; e < 2; e++) {
+    const int j = 2 * q + e;
+    if (!live || j >= np) continue;
+    if (t == 0) {
+      a.gradient_previous[(size_t)env * np + j] = old[e];
+      a.gradient[(size_t)env * np + j] = sum[e];
+      o_grad[j] = sum[e];
+    }
+    // the next gradient candidates (planner.cc:463-480): two rounded additions per node, then the clamp
+    const int k = j % a.nu;
+    const double lo = a.range[2 * k], hi = a.range[2 * k + 1], nominal = a.nominal[(size_t)env * np + j];
+    for (int g = t; g < a.G; g += 256) {
+      const double scaling = a.steps[g] / a.noise_exploration;
+      double v = nominal;
+      v += -scaling * a.filter * sum[e];
+      v += -scaling * (1.0 - a.filter) * old[e];
+      a.grad_values[((size_t)env * a.G + g) * np + j] = clampv(v, lo, hi);
+    }
+  }
+}
+
 // single-workgroup bitonic sort of (return, index) pairs in global memory (n2 = pow2 >= n)
 __global__ __launch_bounds__(1024) void sort_kernel(const double* __restrict__ ret, int n, int n2, RetIdx* buf) {
   for (int i = threadIdx.x; i < n2; i += blockDim.x) buf[i] = i < n ? RetIdx{ret[i], i} : RetIdx{NAN, 0x7fffffff};
@@ -607,6 +817,23 @@ struct mjpcx_ctx {
   // pinned + device-mapped result record of mjpcx_best
   void* best_host = nullptr; void* best_dev = nullptr; size_t best_cap = 0;
   hipEvent_t source_done = nullptr;  // mjpcx_robust_step_batched: orders this stream behind the source context's
+  // the Sample-Gradient planner's state between plan steps (mjpcx_rollout_sample_gradient_batched / mjpcx_sample_gradient_update_batched)
+  struct SampleGradient {
+    PinnedBlock h_in, h_up;       // pinned sides of d_in (marked: the rollout call does not sync) and d_up (the update ends in a sync)
+    DevBuf d_in;                  // the rollout's [node_times E x P | nominal E x np | ctrlrange 2 nu | uploaded gradient times E x P, values E x G x np]
+    DevBuf d_state;               // [gradient E x np | gradient_previous E x np | gradient candidates' times E x P | values E x G x np]
+    DevBuf d_weights;             // the cached shaping weights, E x num_noisy
+    DevBuf d_up;                  // [log(k + 1), k < n | LogScale step sizes G]
+    int E = 0, G = -1, P = 0;     // shape of d_state
+    int n = 0;                    // of the last rollout
+    bool candidates = false;      // d_state holds the gradient candidates an update of this shape left
+    int weights_E = 0, weights_n = 0;  // shape the cached weights were computed for (0: none)
+    unsigned long long serial = 0;     // rollout_serial of the last Sample-Gradient rollout
+    uint64_t seed = 0; uint32_t iteration = 0;
+    int logs_n = 0, steps_G = -1; double steps_max = 0, steps_min = 0;  // what d_up holds
+    void release() { h_in.release(); h_up.release(); d_in.release(); d_state.release(); d_weights.release(); d_up.release(); }
+  } sg;
+  unsigned long long rollout_serial = 0;  // counts the rollouts of every kind
   // rollout buffers
   DevBuf d_nodes, d_in_nodes, d_ilqg, d_ilqg_out;
   PinnedBlock h_ilqg;  // host side of d_ilqg: the input arrays of the iLQG / Gradient entry points (upload_arrays; one H2D copy, marked: the feedback rollouts do not sync)
@@ -1331,6 +1558,7 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   c->N = N; c->H = H; c->P = P;
   c->env_n = E > 0 ? N / E : 0;
   c->have_rollout = true;
+  c->rollout_serial++;
   c->traj_candidate_major = c->wave;
   return MJPCX_OK;
 }
@@ -1629,6 +1857,7 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   if (c->best_host) (void)hipHostFree(c->best_host);
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
   if (c->source_done) (void)hipEventDestroy(c->source_done);
+  c->sg.release();
   (void)mjpcx_comm_destroy(c);
   c->wh.release();
   DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
@@ -2008,6 +2237,159 @@ int mjpcx_robust_step_batched(mjpcx_ctx* c, mjpcx_ctx* src, int E, int k, int R,
     if (perturbed_score) std::memcpy(perturbed_score + (size_t)e * k, r + rec.off_score, (size_t)k * 8);
     if (valid) std::memcpy(valid + (size_t)e * k, r + rec.off_valid, (size_t)k * 4);
     if (spline_values) std::memcpy(spline_values + (size_t)e * np, r + rec.off_spline, (size_t)np * 8);
+  }
+  return MJPCX_OK;
+}
+
+// sample_gradient/planner.cc:290-400 (ResamplePolicy of the gradient candidates, AddNoiseToPolicy, Rollouts) for E environments
+int mjpcx_rollout_sample_gradient_batched(mjpcx_ctx* c, int E, int n, int G, int H, int P, int interp, const double* node_times, const double* nominal,
+                                          double noise_exploration, uint64_t seed, int iteration, const double* gradient_values,
+                                          const double* gradient_times) {
+  const std::string who = "mjpcx_rollout_sample_gradient_batched: ";
+  int rc = check_batched_args(c, E, n, H, P, interp, node_times);
+  if (rc != MJPCX_OK) return rc;
+  if (!nominal) return fail(c, MJPCX_EINVAL, who + "null nominal_values");
+  if (G < 0 || G > n - 1) return fail(c, MJPCX_EINVAL, who + "num_gradient = " + std::to_string(G) + " outside 0.." + std::to_string(n - 1));
+  if (!(noise_exploration > 0)) return fail(c, MJPCX_EINVAL, who + "noise_exploration must be > 0");
+  if ((gradient_values == nullptr) != (gradient_times == nullptr)) return fail(c, MJPCX_EINVAL, who + "gradient_values and gradient_times come together");
+  auto& s = c->sg;
+  const bool same = s.E == E && s.G == G && s.P == P, upload = G > 0 && gradient_values;
+  if (G > 0 && !upload && !(same && s.candidates))
+    return fail(c, MJPCX_EINVAL, who + "no gradient candidates on the device: no update with this num_envs, num_gradient and num_nodes has run");
+  if (upload)
+    for (int e = 0; e < E; e++)
+      for (int p = 1; p < P; p++)
+        if (!(gradient_times[(size_t)e * P + p] > gradient_times[(size_t)e * P + p - 1])) return fail(c, MJPCX_EINVAL, who + "gradient_times must be strictly increasing");
+  const int nu = c->nu, np = P * nu, npairs = (np + 1) / 2;
+  const long long per_env = ((long long)npairs * n + 255) / 256;
+  if (per_env * E > 0x7fffffffLL || (long long)npairs * n > 0x7fffffffLL - 256) return fail(c, MJPCX_EINVAL, who + "too many candidates");  // (the kernel's int indices)
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = reserve_rollout(c, E * n, H, P)) != MJPCX_OK) return rc;  // (before the kernel writes d_nodes: do_rollout's own call then moves nothing)
+  const size_t sE = E, o_gt = 2 * sE * np, o_gv = o_gt + sE * P;
+  if (!same) {  // another shape: nothing of the old state carries over; the gradient starts from zero as after Planner::Reset
+    HIPCHK(c, s.d_state.reserve((o_gv + sE * G * np) * 8));
+    HIPCHK(c, hipMemsetAsync(s.d_state.p, 0, o_gt * 8, c->stream));
+    s.E = E; s.G = G; s.P = P; s.candidates = false;
+  }
+  const size_t i_nom = sE * P, i_range = i_nom + sE * np, i_gt = i_range + 2 * (size_t)nu, i_gv = i_gt + sE * P;
+  const size_t bytes = (upload ? i_gv + sE * G * np : i_gt) * 8;
+  HIPCHK(c, s.h_in.wait());
+  HIPCHK(c, s.h_in.reserve(bytes));
+  HIPCHK(c, s.d_in.reserve(bytes));
+  double* h = (double*)s.h_in.p;
+  std::memcpy(h, node_times, sE * P * 8);
+  std::memcpy(h + i_nom, nominal, sE * np * 8);
+  std::memcpy(h + i_range, c->ctrlrange.data(), 2 * (size_t)nu * 8);
+  if (upload) {
+    std::memcpy(h + i_gt, gradient_times, sE * P * 8);
+    std::memcpy(h + i_gv, gradient_values, sE * G * np * 8);
+  }
+  HIPCHK(c, hipMemcpyAsync(s.d_in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
+  const double* din = (const double*)s.d_in.p;
+  const double* dst = (const double*)s.d_state.p;
+  SgCandArgs a{};
+  a.n = n; a.num_noisy = n - G; a.P = P; a.nu = nu; a.interp = interp; a.num_envs = E; a.blocks_per_env = (int)per_env;
+  a.times = din; a.nominal = din + i_nom; a.range = din + i_range;
+  a.grad_times = upload ? din + i_gt : dst + o_gt;
+  a.grad_values = upload ? din + i_gv : dst + o_gv;
+  a.noise_exploration = noise_exploration; a.seed = seed; a.iteration = (uint32_t)iteration;
+  if (c->precision == 64) hipLaunchKernelGGL((sg_candidates_kernel<double>), dim3((unsigned)(per_env * E)), dim3(256), 0, c->stream, a, (double*)c->d_nodes.p);
+  else hipLaunchKernelGGL((sg_candidates_kernel<float>), dim3((unsigned)(per_env * E)), dim3(256), 0, c->stream, a, (float*)c->d_nodes.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, s.h_in.mark(c->stream));
+  rc = c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, nullptr, nullptr, nullptr, E, nullptr, /*nodes_on_device=*/true)
+                          : do_rollout<float>(c, E * n, H, P, interp, node_times, nullptr, nullptr, nullptr, E, nullptr, /*nodes_on_device=*/true);
+  if (rc != MJPCX_OK) return rc;
+  s.serial = c->rollout_serial; s.n = n; s.seed = seed; s.iteration = (uint32_t)iteration;
+  return MJPCX_OK;
+}
+
+// sample_gradient/planner.cc:168-264 (the sort, the winner, the improvement) and 401-493 (GradientCandidates) for E environments
+int mjpcx_sample_gradient_update_batched(mjpcx_ctx* c, int E, int G, int flags, double filter, double max_step, double min_step, double noise_exploration,
+                                         int32_t* index, int32_t* winner_type, double* best_return, double* nominal_return, double* improvement,
+                                         double* spline_values, double* gradient) {
+  const std::string who = "mjpcx_sample_gradient_update_batched: ";
+  if (!c || !index) return fail(c, MJPCX_EINVAL, who + "null argument");
+  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  auto& s = c->sg;
+  if (E < 1 || s.serial == 0 || s.serial != c->rollout_serial || c->env_n < 1 || (long long)E * c->env_n != c->N || s.E != E || s.G != G)
+    return fail(c, MJPCX_EINVAL, who + "the last rollout was not a mjpcx_rollout_sample_gradient_batched of " + std::to_string(E) + " environments with num_gradient = " + std::to_string(G));
+  if (flags & ~(MJPCX_SG_COMPUTE_WEIGHTS | MJPCX_SG_ZERO_GRADIENT)) return fail(c, MJPCX_EINVAL, who + "unknown flags");
+  if (G > 0 && (!(max_step > 0) || !(min_step > 0) || !(noise_exploration > 0) || !std::isfinite(filter)))
+    return fail(c, MJPCX_EINVAL, who + "max_step, min_step and noise_exploration must be > 0 and filter finite");
+  const int n = c->env_n, nn = n - G, P = c->P, nu = c->nu, np = P * nu, npairs = (np + 1) / 2;
+  const bool compute = G > 0 && (flags & MJPCX_SG_COMPUTE_WEIGHTS);
+  if (G > 0 && !compute && !(s.weights_E == E && s.weights_n == nn))
+    return fail(c, MJPCX_EINVAL, who + "no shaping weights for " + std::to_string(E) + " environments of " + std::to_string(nn) + " noisy candidates: pass MJPCX_SG_COMPUTE_WEIGHTS");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sE = E;
+  if (G > 0) {
+    HIPCHK(c, s.d_weights.reserve(sE * nn * 8));
+    if (s.steps_G != G || s.steps_max != max_step || s.steps_min != min_step || s.logs_n != nn) {  // LogScale (utilities.cc:819-826) and log(k + 1), on the host
+      const size_t bytes = ((size_t)G + nn) * 8;
+      HIPCHK(c, s.h_up.reserve(bytes));
+      HIPCHK(c, s.d_up.reserve(bytes));
+      double* h = (double*)s.h_up.p;
+      const double step = (std::log(max_step) - std::log(min_step)) / (G > 1 ? G - 1 : 1);
+      for (int i = 0; i < G; i++) h[i] = std::exp(std::log(min_step) + i * step);
+      for (int k = 0; k < nn; k++) h[G + k] = std::log(k + 1);
+      HIPCHK(c, hipMemcpyAsync(s.d_up.p, h, bytes, hipMemcpyHostToDevice, c->stream));
+      s.steps_G = G; s.steps_max = max_step; s.steps_min = min_step; s.logs_n = nn;
+    }
+  }
+  SgRecord rec;
+  rec.off_spline = 32;
+  rec.off_grad = rec.off_spline + (size_t)np * 8;
+  rec.bytes = rec.off_grad + (size_t)np * 8;
+  const size_t bytes = rec.bytes * E;
+  if (bytes > c->best_cap) {
+    if (c->best_host) (void)hipHostFree(c->best_host);
+    c->best_host = nullptr; c->best_cap = 0;
+    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
+    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
+    c->best_cap = bytes;
+  }
+  int n2 = 1024;  // (a multiple of the workgroup: env_sort_keys)
+  while (n2 < n) n2 <<= 1;
+  const bool in_lds = n2 <= kCeLdsKeys;
+  const size_t lds = in_lds ? (size_t)n2 * 12 : 0;
+  const int chunks = G > 0 ? (npairs + 3) / 4 : 1;
+  if (!in_lds) HIPCHK(c, c->d_sort.reserve(sE * chunks * n2 * 12));
+  const double* din = (const double*)s.d_in.p;
+  double* dst = (double*)s.d_state.p;
+  SgUpdateArgs a{};
+  a.n = n; a.n2 = n2; a.P = P; a.nu = nu; a.G = G; a.num_noisy = nn; a.flags = flags;
+  a.filter = filter; a.noise_exploration = noise_exploration; a.f0 = std::log(0.5 * nn + 1.0);
+  a.seed = s.seed; a.iteration = s.iteration;
+  a.times = din; a.nominal = din + sE * P; a.range = din + sE * P + sE * np;
+  a.steps = (const double*)s.d_up.p; a.logs = a.steps + G;
+  a.gradient = dst; a.gradient_previous = dst + sE * np; a.weights = (double*)s.d_weights.p;
+  a.grad_times = dst + 2 * sE * np; a.grad_values = a.grad_times + sE * P;
+  auto launch = [&](auto kern, const auto* nodes) {
+    hipError_t e = in_lds ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(E, chunks), dim3(1024), lds, c->stream, (const double*)c->d_ret.p, nodes, a, in_lds ? nullptr : (double*)c->d_sort.p,
+                       (unsigned char*)c->best_dev, rec);
+    return hipGetLastError();
+  };
+  hipError_t le;
+  if (c->precision == 64) le = in_lds ? launch(sg_update_kernel<double, true>, (const double*)c->d_nodes.p) : launch(sg_update_kernel<double, false>, (const double*)c->d_nodes.p);
+  else le = in_lds ? launch(sg_update_kernel<float, true>, (const float*)c->d_nodes.p) : launch(sg_update_kernel<float, false>, (const float*)c->d_nodes.p);
+  HIPCHK(c, le);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (G > 0) {
+    s.candidates = true;
+    if (compute) { s.weights_E = E; s.weights_n = nn; }
+  }
+  for (int e = 0; e < E; e++) {
+    const char* r = (const char*)c->best_host + rec.bytes * e;
+    std::memcpy(index + e, r, 4);
+    if (winner_type) std::memcpy(winner_type + e, r + 4, 4);
+    if (best_return) std::memcpy(best_return + e, r + 8, 8);
+    if (nominal_return) std::memcpy(nominal_return + e, r + 16, 8);
+    if (improvement) std::memcpy(improvement + e, r + 24, 8);
+    if (spline_values) std::memcpy(spline_values + (size_t)e * np, r + rec.off_spline, (size_t)np * 8);
+    if (gradient) std::memcpy(gradient + (size_t)e * np, r + rec.off_grad, (size_t)np * 8);
   }
   return MJPCX_OK;
 }
@@ -2392,6 +2774,7 @@ int do_feedback(mjpcx_ctx* c, int E, int n, int H, int mode, int representation,
   c->N = N; c->H = H; c->P = a.P;
   c->env_n = env_n;
   c->have_rollout = true;
+  c->rollout_serial++;
   c->traj_candidate_major = c->wave;
   return MJPCX_OK;
 }

@@ -10,6 +10,7 @@ noise comes from a seedable counter-based generator (F4).
 """
 from __future__ import annotations
 
+import math
 import threading
 import time as _time
 
@@ -758,6 +759,314 @@ class GpuBatchRobustPlanner(_FleetTasks):
 
     def num_parameters(self):
         return self.delegate.num_parameters()
+
+
+def log_scale(max_value, min_value, steps):
+    """LogScale, mjpc/utilities.cc:819-826: log-spaced values from min_value up to max_value"""
+    step = (math.log(max_value) - math.log(min_value)) / (steps - 1 if steps > 1 else 1)
+    return np.array([math.exp(math.log(min_value) + i * step) for i in range(steps)])
+
+
+def strided_tree_sum(terms):
+    """The summation order of the device's Sample-Gradient update (sg_update_kernel), over the first axis of `terms`: partial sum t of
+    256 adds the terms t, t + 256, t + 512, ... in that order from 0; then sum[t] += sum[t + s] for s = 128, 64, ..., 1."""
+    terms = np.asarray(terms, dtype=np.float64)
+    acc = np.zeros((256,) + terms.shape[1:])
+    for k in range(0, terms.shape[0], 256):
+        chunk = terms[k:k + 256]
+        acc[:chunk.shape[0]] += chunk
+    s = 128
+    while s:
+        acc[:s] += acc[s:2 * s]
+        s >>= 1
+    return acc[0]
+
+
+def sample_gradient_update(returns, nominal, noise, num_gradient, ctrlrange, weights=None, gradient=None, compute_weights=True,
+                           gradient_filter=1.0, max_step=2.0, min_step=1.0e-3, noise_exploration=0.1):
+    """The Sample-Gradient planner's update after its rollouts (sample_gradient/planner.cc:168-264 and 401-493) for one robot, in the
+    device's order of operations -- the single statement of the arithmetic of mjpcx_sample_gradient_update_batched.
+    `returns` n, `nominal` the nominal's P*nu parameters, `noise` the standard normals n x P*nu of the candidates (the rows of the
+    nominal and of the gradient candidates are taken as zero, whatever they hold), `weights` the cached shaping weights (needed without
+    compute_weights), `gradient` the estimate of the step before (None: zero). The reference's behaviour is kept, not repaired: the
+    shaping weight of sorted position i takes log(candidate index at that position + 1), not log(i + 1); weights computed in this step
+    pair with the order of the first num_noisy returns alone, cached ones with the first num_noisy entries of the order over all n.
+    -> dict of order (ascending returns, ties to the lower index, NaN last), winner, winner_type (0 nominal, 1 perturbed, 2 gradient),
+    improvement, weights, gradient, gradient_previous, candidates (num_gradient x P*nu: the next gradient candidates)."""
+    ret = np.asarray(returns, dtype=np.float64).reshape(-1)
+    n, G = ret.size, int(num_gradient)
+    nn = n - G
+    if not 0 <= G <= n - 1:
+        raise ValueError(f"num_gradient = {G} outside 0..{n - 1}")
+    order = np.lexsort((np.arange(n), ret))
+    winner = int(order[0]) if ret[order[0]] < ret[0] else 0
+    d = ret[0] - ret[winner]
+    out = dict(order=order, winner=winner, winner_type=0 if winner == 0 else (1 if winner < nn else 2),
+               improvement=float(d) if d > 0 else 0.0, weights=weights, gradient=gradient, gradient_previous=None, candidates=None)
+    if G < 1:
+        return out
+    nominal = np.asarray(nominal, dtype=np.float64).reshape(-1)
+    previous = np.zeros(nominal.size) if gradient is None else np.asarray(gradient, dtype=np.float64).reshape(-1).copy()
+    if compute_weights:
+        used = np.lexsort((np.arange(nn), ret[:nn]))
+        f0 = math.log(0.5 * nn + 1.0)
+        f = np.array([max(0.0, f0 - math.log(int(c) + 1)) for c in used])
+        weights = f / strided_tree_sum(f) - 1.0 / nn
+    else:
+        weights = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if weights.size != nn:
+            raise ValueError(f"{weights.size} cached weights for {nn} noisy candidates")
+        used = order[:nn]
+    z = np.asarray(noise, dtype=np.float64).reshape(n, nominal.size)[used]
+    z = np.where(((used > 0) & (used < nn))[:, None], z, 0.0)
+    g = strided_tree_sum(z * (weights / nn)[:, None])
+    b = np.asarray(ctrlrange, dtype=np.float64).reshape(-1, 2)
+    lo, hi = np.resize(b[:, 0], nominal.size), np.resize(b[:, 1], nominal.size)   # parameter j belongs to actuator j % nu
+    candidates = np.zeros((G, nominal.size))
+    for i, step in enumerate(log_scale(max_step, min_step, G)):
+        scaling = step / noise_exploration
+        v = nominal.copy()
+        v += -scaling * gradient_filter * g
+        v += -scaling * (1.0 - gradient_filter) * previous
+        candidates[i] = np.maximum(lo, np.minimum(hi, v))
+    out.update(weights=weights, gradient=g, gradient_previous=previous, candidates=candidates)
+    return out
+
+
+class _SampleGradientMember:
+    """what mjpc::SampleGradientPlanner keeps per robot: state, policies, winner, gradient"""
+
+    def __init__(self, seed):
+        self.seed = seed
+        self.task = None
+        self.mtx_ = threading.RLock()
+        self.winner, self.winner_type_, self.improvement, self.iteration = 0, 0, 0.0, 0
+        self.best_return = self.nominal_return = 0.0
+        self.gradient = np.zeros(0)
+        self._best = None
+
+
+class GpuBatchSampleGradientPlanner(_FleetTasks):
+    """mjpc::SampleGradientPlanner (mjpc/planners/sample_gradient/planner.{h,cc}) for `num_envs` robots on ONE context, the candidates,
+    the sort, the fitness-shaped gradient estimate and the gradient-step candidates on the device: a plan step is the host resample of
+    every nominal, one `set_states`, one `rollout_sample_gradient_batched`, one `sample_gradient_update_batched` and ONE sync. The
+    shaping weights, the gradient and the next gradient candidates never leave the context. Member e plans exactly like
+    GpuSampleGradientPlanner(seed = s + e), which is this class with one environment.
+    Deviations from the reference, beside the seedable counter-based normals and the lifted candidate cap (F5): the noise rows
+    of the nominal and of the gradient candidates are zero (the reference leaves stale rows behind a change of num_gradient_); a change
+    of num_gradient_ or of the number of spline points starts the gradient candidates again from the zero spline, as a reset does."""
+
+    def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
+        if int(num_envs) < 1:
+            raise ValueError("GpuBatchSampleGradientPlanner needs at least one environment")
+        self.num_envs, self.device, self.precision, self.seed = int(num_envs), device, precision, seed
+        self._backend_factory = backend_factory
+        self.model = self.task = self.ctx = None
+        self.iteration = 0
+        self.rollouts_compute_time = self.policy_update_compute_time = 0.0
+        self.gradient_max_step_size, self.gradient_min_step_size = 2.0, 1.0e-3   # planner.h
+        self.envs = [_SampleGradientMember(seed + e) for e in range(self.num_envs)]
+        self._n = 0
+        self._weights_for = None      # num_noisy the context's shaping weights were computed for (return_weight_.size())
+        self._zero_gradient = True    # the context's gradient is to be taken as zero (Allocate / Reset)
+        self._candidates_for = None   # (num_gradient, spline points) of the gradient candidates on the device; None: upload the zero spline
+
+    # ---- Initialize, planner.cc:41-70
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        self.noise_exploration = model.get_number("sampling_exploration", 0.1)
+        self.num_trajectory_ = int(model.get_number("sampling_trajectories", 10))
+        self.interpolation_ = int(model.get_number("sampling_representation", CUBIC))
+        self.num_gradient_ = int(model.get_number("sample_gradient_trajectories", 0))
+        self.gradient_filter_ = model.get_number("sample_gradient_filter", 1.0)
+        for p in self.envs:
+            p.task = task
+
+    # ---- Allocate, planner.cc:73-112
+    def allocate(self):
+        m = self.model
+        if self._backend_factory is not None:
+            self.ctx = self._backend_factory(self.task)
+        else:
+            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+        for p in self.envs:
+            p.state, p.mocap, p.userdata, p.time = np.zeros(m.nq + m.nv + m.na), np.zeros(7 * m.nmocap), np.zeros(m.nuserdata), 0.0
+            p.policy, p.previous_policy = SamplingPolicy(), SamplingPolicy()
+            p.policy.allocate(m, self.task, K_MAX_TRAJECTORY_HORIZON)
+            p.previous_policy.allocate(m, self.task, K_MAX_TRAJECTORY_HORIZON)
+            p.gradient = np.zeros(p.policy.num_spline_points * m.nu)
+        self._zero_gradient, self._candidates_for = True, None
+
+    # ---- Reset, planner.cc:115-163: the gradient is zeroed, the shaping weights are kept
+    def reset(self, horizon, initial_repeated_action=None):
+        for p in self.envs:
+            p.state[:] = 0
+            p.mocap[:] = 0
+            p.userdata[:] = 0
+            p.time = 0.0
+            with p.mtx_:
+                p.policy.reset(horizon, initial_repeated_action)
+                p.previous_policy.reset(horizon, initial_repeated_action)
+            p.improvement, p.winner, p._best = 0.0, 0, None
+            p.gradient = np.zeros_like(p.gradient)
+        self._zero_gradient, self._candidates_for = True, None
+
+    def set_states(self, states):
+        """one State per environment (Planner::SetState for each)"""
+        if len(states) != self.num_envs:
+            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
+        for p, st in zip(self.envs, states):
+            p.state, p.mocap, p.userdata, p.time = st.copy_to()
+
+    def _push_states(self):
+        sync_task(self.ctx, self.task)
+        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
+                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
+                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
+        self._push_task_rows()
+
+    # ---- ResamplePolicy, planner.cc:290-318
+    def _resample(self, p, horizon):
+        num_spline_points = p.policy.num_spline_points
+        # model->opt.timestep as the C++ GpuSampleGradientPlanner reads it: the model's own timestep, where the sibling planners read
+        # agent_timestep first. In the reference the planner's model is the Agent's planning copy, whose opt.timestep IS agent_timestep;
+        # here a model that defines agent_timestep (Cartpole, Particle, the Humanoid) gets its nodes spaced by the model's own. Kept, so
+        # that this class and the C++ planner stay one specification (DESIGN.md 4.9, deviations); to be changed in both together.
+        timestep = self.model.timestep
+        time_shift = max((horizon - 1) * timestep / (num_spline_points - 1), 1.0e-5) if num_spline_points > 1 else 1.0e-5
+        plan = TimeSpline(self.model.nu, self.interpolation_)
+        nominal_time = p.time
+        with p.mtx_:
+            for _ in range(num_spline_points):
+                node = plan.add_node(nominal_time)
+                p.policy.action(node, None, nominal_time)
+                nominal_time += time_shift
+        return plan
+
+    # ---- OptimizePolicy, planner.cc:166-264
+    def optimize_policy(self, horizon, pool=None):
+        n = int(self.num_trajectory_)
+        if n < 64 or n % 64 != 0:
+            raise ValueError(f"{type(self).__name__}: {n} candidates per environment; a batched launch needs a positive multiple of 64 "
+                             "(every wavefront serves one environment) -- set sampling_trajectories / num_trajectory_ accordingly")
+        self.num_gradient_ = G = min(int(self.num_gradient_), n - 1)
+        E, nu = self.num_envs, self.model.nu
+        for p in self.envs:
+            p.policy.plan.set_interpolation(self.interpolation_)
+        plans = [self._resample(p, horizon) for p in self.envs]     # the nominal at the environment's clock: candidate 0
+        times = np.stack([pl.times() for pl in plans])
+        P = times.shape[1]
+        t0 = _time.perf_counter()
+        self._push_states()
+        upload = G > 0 and self._candidates_for != (G, P)
+        # the gradient candidates' splines before the first update are empty (candidate_policy[i].Reset): zero actions, clamped
+        zero_spline = clamp(np.zeros((E, G, P, nu)), self.model.actuator_ctrlrange) if upload else None
+        self.ctx.rollout_sample_gradient_batched(n, G, horizon, self.interpolation_, times, np.stack([pl.values() for pl in plans]),
+                                                 self.noise_exploration, seed=self.seed, iteration=self.iteration,
+                                                 gradient_values=zero_spline, gradient_times=times if upload else None, num_envs=E)
+        flags = 0
+        if G > 0 and self._weights_for != n - G:      # return_weight_.size() != num_noisy
+            flags |= capi.SG_COMPUTE_WEIGHTS
+        if self._zero_gradient:
+            flags |= capi.SG_ZERO_GRADIENT
+        out = self.ctx.sample_gradient_update_batched(E, G, flags, self.gradient_filter_, self.gradient_max_step_size,
+                                                      self.gradient_min_step_size, self.noise_exploration)
+        self.rollouts_compute_time = (_time.perf_counter() - t0) * 1e6
+        t0 = _time.perf_counter()
+        if G > 0:
+            self._weights_for, self._candidates_for = n - G, (G, P)
+        self._zero_gradient = False
+        self._n = n
+        self.iteration += 1
+        for e, p in enumerate(self.envs):
+            p.winner, p.winner_type_ = int(out["index"][e]), int(out["winner_type"][e])
+            p.best_return, p.nominal_return = float(out["best_return"][e]), float(out["nominal_return"][e])
+            p.improvement = float(out["improvement"][e])
+            p.gradient = np.array(out["gradient"][e], dtype=np.float64).reshape(-1)
+            p.iteration = self.iteration
+            plan = TimeSpline(nu, self.interpolation_)
+            for t, v in zip(times[e], np.asarray(out["spline"][e]).reshape(P, nu)):
+                plan.add_node(t, v)
+            with p.mtx_:
+                p.previous_policy.copy_from(p.policy)
+                p.policy.plan = plan                    # policy.SetPlan(candidate_policy[winner].plan)
+            p._best = None
+        self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
+
+    @property
+    def winners(self):
+        return [p.winner for p in self.envs]
+
+    def action_from_policy(self, env, action, state, time, use_previous=False):
+        p = self.envs[env]
+        with p.mtx_:
+            return (p.previous_policy if use_previous else p.policy).action(action, state, time)
+
+    def best_trajectory(self, env):
+        """the winner's trajectory, fetched lazily from the context (global candidate env * n + winner)"""
+        p = self.envs[env]
+        if p._best is None and self._n:
+            p._best = self.ctx.fetch_trajectory(env * self._n + p.winner)
+        return p._best
+
+    def num_parameters(self):
+        return self.envs[0].policy.num_spline_points * self.model.nu
+
+
+def _member_attr(name):
+    def fget(self):
+        return getattr(self.fleet.envs[0], name)
+    return property(fget)
+
+
+def _fleet_attr(name):
+    def fget(self):
+        return getattr(self.fleet, name)
+
+    def fset(self, value):
+        setattr(self.fleet, name, value)
+    return property(fget, fset)
+
+
+class GpuSampleGradientPlanner:
+    """mjpc::SampleGradientPlanner with everything but the nominal's resampling on the device: the Python mirror of the C++
+    GpuSampleGradientPlanner (host/mjpc/planners/gpu_sample_gradient), and GpuBatchSampleGradientPlanner with ONE environment -- the
+    same code, so a fleet's member e IS this planner with seed s + e. The candidate count must be a multiple of 64."""
+    winner, winner_type_, improvement, gradient = (_member_attr(k) for k in ("winner", "winner_type_", "improvement", "gradient"))
+    best_return, nominal_return = _member_attr("best_return"), _member_attr("nominal_return")
+    policy, previous_policy = _member_attr("policy"), _member_attr("previous_policy")
+    iteration, ctx, model, task = (_fleet_attr(k) for k in ("iteration", "ctx", "model", "task"))
+    num_trajectory_, num_gradient_, gradient_filter_ = (_fleet_attr(k) for k in ("num_trajectory_", "num_gradient_", "gradient_filter_"))
+    noise_exploration, interpolation_ = _fleet_attr("noise_exploration"), _fleet_attr("interpolation_")
+    gradient_max_step_size, gradient_min_step_size = _fleet_attr("gradient_max_step_size"), _fleet_attr("gradient_min_step_size")
+
+    def __init__(self, device=0, precision=64, seed=0, backend_factory=None):
+        self.fleet = GpuBatchSampleGradientPlanner(1, device, precision, seed, backend_factory)
+        self.seed = seed
+
+    def initialize(self, model, task: Task):
+        self.fleet.initialize(model, task)
+
+    def allocate(self):
+        self.fleet.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.fleet.reset(horizon, initial_repeated_action)
+
+    def set_state(self, state: State):
+        self.fleet.set_states([state])
+
+    def optimize_policy(self, horizon, pool=None):
+        self.fleet.optimize_policy(horizon, pool)
+
+    def action_from_policy(self, action, state, time, use_previous=False):
+        return self.fleet.action_from_policy(0, action, state, time, use_previous)
+
+    def best_trajectory(self):
+        return self.fleet.best_trajectory(0)
+
+    def num_parameters(self):
+        return self.fleet.num_parameters()
 
 
 class GpuCrossEntropyPlanner:

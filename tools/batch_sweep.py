@@ -29,6 +29,13 @@ one after the other, on two contexts (the delegate's rollout, topk, k spline fet
 returns, the host loop: per robot) against (b) one GpuBatchRobustPlanner plan step on the same two contexts (rollout_noise_batched and
 robust_step_batched: two launch sequences, one sync). Host logic included on both sides. Default output profiles/batch_sweep_robust.jsonl.
 
+--planner sample_gradient: the Sample-Gradient planner's plan step, G = 32 gradient candidates (--gradient-candidates 32). (a) E
+GpuSampleGradientPlanner plan steps, one after the other, each on a context of its own (the gradient candidates and the shaping weights
+live in the context: one per robot) against (b) one GpuBatchSampleGradientPlanner plan step on one context
+(rollout_sample_gradient_batched and sample_gradient_update_batched: one sync for the fleet). Host logic included on both sides. The
+record also splits the batched step, in a loop of its own: the rollout call up to its sync (candidate kernel + rollout), and the update
+call alone (launch + sync) after it. Default output profiles/batch_sweep_sample_gradient.jsonl.
+
 --mixed-params: every environment plans with task weights, norm parameters, residual parameters and risk of its own (sampling and
 cross_entropy: set_task_params_batched after set_states, and the plain set_task_params of the same row before every sequential plan
 step; gradient and ilqg: the fleet planner's set_tasks, and every sequential planner on its own task). The kernels do the same work
@@ -234,6 +241,79 @@ def sweep_robust(name, precision, H, shapes, steps, warmup, out, k, R, mixed=Fal
     ctx.close()
 
 
+SAMPLE_GRADIENT_SHAPES = [("QuadrupedFlat", 64, 100, [(1, 2048), (8, 2048), (16, 2048)])]
+
+
+def sweep_sample_gradient(name, precision, H, shapes, steps, warmup, out, G, mixed=False):
+    from mujoco_mpc_amd.planners import GpuBatchSampleGradientPlanner, GpuSampleGradientPlanner, State
+    task = load_task(name)
+    m = task.model
+    rng = np.random.default_rng(1)
+    for E, n in shapes:
+        raw, clocks, mocap = initial(task, name, E, rng)
+        states = []
+        for e in range(E):
+            st = State(m)
+            mp = None if mocap is None else mocap[e].reshape(-1, 7)
+            st.set(raw[e][:m.nq], raw[e][m.nq:], mocap_pos=None if mp is None else mp[:, :3], mocap_quat=None if mp is None else mp[:, 3:],
+                   time=float(clocks[e]))
+            states.append(st)
+        singles = [GpuSampleGradientPlanner(precision=precision, seed=7 + e) for e in range(E)]
+        batch = GpuBatchSampleGradientPlanner(E, precision=precision, seed=7)
+        tasks = mixed_tasks(task, E) if mixed else [task] * E
+        for p, t in zip(singles + [batch], tasks + [task]):
+            p.initialize(m, t)
+            p.num_trajectory_, p.num_gradient_ = n, G
+            p.allocate()
+            p.reset(H)
+        if mixed:
+            batch.set_tasks(tasks)
+
+        def sequential():
+            for p, st in zip(singles, states):
+                p.set_state(st)
+                p.optimize_policy(H)
+
+        def batched():
+            batch.set_states(states)
+            batch.optimize_policy(H)
+
+        for _ in range(warmup):
+            sequential()
+            batched()
+        ts, tb = [], []
+        for _ in range(steps):   # alternating: both sides see the same clocks and the same neighbours on the machine
+            t0 = time.perf_counter(); sequential(); t1 = time.perf_counter(); batched(); t2 = time.perf_counter()
+            ts.append((t1 - t0) * 1e3)
+            tb.append((t2 - t1) * 1e3)
+        same = bool(all((b.winner, b.winner_type_) == (p.winner, p.winner_type_) and np.array_equal(b.gradient, p.gradient) for b, p in zip(batch.envs, singles)))
+        # the batched step in two: the rollout call up to its sync, then the update call alone (the fleet planner's own calls, on its context)
+        ctx = batch.ctx
+        plans = [batch._resample(p, H) for p in batch.envs]
+        times, nominal = np.stack([pl.times() for pl in plans]), np.stack([pl.values() for pl in plans])
+        tr, tu = [], []
+        for i in range(steps):
+            t0 = time.perf_counter()
+            batch._push_states()
+            ctx.rollout_sample_gradient_batched(n, G, H, batch.interpolation_, times, nominal, batch.noise_exploration, seed=7, iteration=1000 + i, num_envs=E)
+            ctx.sync()
+            t1 = time.perf_counter()
+            ctx.sample_gradient_update_batched(E, G, 0, batch.gradient_filter_, batch.gradient_max_step_size, batch.gradient_min_step_size, batch.noise_exploration)
+            t2 = time.perf_counter()
+            tr.append((t1 - t0) * 1e3)
+            tu.append((t2 - t1) * 1e3)
+        rec = {"planner": "sample_gradient", "task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "num_gradient": G,
+               "steps": steps, "warmup": warmup, "mixed_params": bool(mixed), "context_kernel": ctx.kernel_name.split(" (")[0],
+               "sequential_ms": stats(ts), "batched_ms": stats(tb), "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)),
+               "beyond_spread": bool(np.max(tb) < np.min(ts)), "batched_inside_sequential_range": bool(np.min(ts) <= np.median(tb) <= np.max(ts)),
+               "batched_rollout_ms": stats(tr), "batched_update_ms": stats(tu), "same_choice": same}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+        out.flush()
+        for p in singles + [batch]:
+            p.ctx.close()
+
+
 ILQG_SHAPES = [("QuadrupedFlat", 64, 36, [(1, 10), (2, 10), (4, 10), (8, 10), (16, 10)])]
 
 
@@ -401,19 +481,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "robust"], default="sampling")
+    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "robust", "sample_gradient"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
     ap.add_argument("--mixed-params", action="store_true", help="every environment its own task weights, parameters and risk")
     ap.add_argument("--robust", default="16x4", help="--planner robust: candidates x repetitions")
+    ap.add_argument("--gradient-candidates", type=int, default=32, help="--planner sample_gradient: gradient candidates per environment")
     ap.add_argument("--no-device-chain", action="store_true", help="--planner ilqg: the sequential middle (the A/B of ilqg_step_batched)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl", "robust": "batch_sweep_robust.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
+        a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl", "robust": "batch_sweep_robust.jsonl",
+                                                       "sample_gradient": "batch_sweep_sample_gradient.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
     keep = None if a.shapes is None else {tuple(int(x) for x in sh.split("x")) for sh in a.shapes.split(",")}
     if a.steps < 10:
         raise SystemExit("batch_sweep.py: at least 10 timed steps")
     with open(a.out, "w") as out:
-        for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES, "robust": ROBUST_SHAPES}.get(a.planner, SHAPES):
+        for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES, "robust": ROBUST_SHAPES,
+                                             "sample_gradient": SAMPLE_GRADIENT_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
             if shapes and (a.only is None or a.only == name):
                 if a.planner == "gradient":
@@ -421,6 +504,8 @@ def main():
                 elif a.planner == "robust":
                     k, R = (int(x) for x in a.robust.split("x"))
                     sweep_robust(name, precision, H, shapes, a.steps, a.warmup, out, k, R, a.mixed_params)
+                elif a.planner == "sample_gradient":
+                    sweep_sample_gradient(name, precision, H, shapes, a.steps, a.warmup, out, a.gradient_candidates, a.mixed_params)
                 elif a.planner == "ilqg":
                     sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out, False if a.no_device_chain else None, a.mixed_params)
                 else:
