@@ -1,6 +1,7 @@
 """-m gpu: device pieces of the iLQG planner vs the CPU oracle.
    transition_fd   <-> oracle otransition_fd   (mjd_transitionFD restatement)       tol: see below
-   cost_derivatives<-> oracle ocost_derivatives (cost_derivatives.cc restatement)    1e-10 relative
+   cost_derivatives<-> oracle ocost_derivatives (cost_derivatives.cc restatement)    1e-10 relative, on rollouts; exact answers at
+                       chosen residuals, edges and shapes: tests/test_gpu_cost_derivatives.py
    backward_pass   <-> oracle oriccati (pinned by backward_pass_test.cc golden)      1e-9
    rollout_feedback<-> oracle orollout_feedback                                      1e-9
 Finite differences with eps = 1e-6 amplify the ~1e-16 rounding differences between the two step
