@@ -1486,6 +1486,14 @@ QNOINLINE double cylinder_contact(const double* geo_in, double r2, double h2, do
 // nearest points for the pairs that pass; a pair within its margin becomes a RELATIVE contact (QContact::rel) in the own lane's list --
 // and, for a leg-leg pair, identically in the partner's lane, which walks the same pair from its side with the same arithmetic (the two
 // geoms are always taken in MuJoCo's order: geom1 first). pmask collects 1 << (own leg xor partner leg) of the leg-leg contacts.
+// QEXP_PAIRS_WALK_ALL (off in the product; tests/test_quad_pair_walk_emulator.py builds the emulator with it): the leg-level cull and the
+// pretests pass everything -- every pair of pg_active reaches the exact test, in the same ascending order, and every partner geom and link
+// is fetched. What the culls may skip is only what the exact test rejects, so the two builds must agree in every output bit.
+#ifdef QEXP_PAIRS_WALK_ALL
+constexpr bool kQPairsWalkAll = true;
+#else
+constexpr bool kQPairsWalkAll = false;
+#endif
 // what the tests need of the lane's state: handed over in memory (the function is out of line: below)
 struct QPairArgs {
   QPairGeoms pg;
@@ -1493,8 +1501,8 @@ struct QPairArgs {
   int need;                      // bit 0: the trunk's pair geoms, bit 1: the own leg's pairs, bit 1 + d: the leg d lanes on (quad-uniform)
   int ncon, flags, pmask, nrel;  // in / out
 };
-// Out of line and COMPACT: one instance of the bounding-sphere test, of the exact tests and of the contact's creation, in rolled loops over
-// arrays that live in memory and are indexed at run time. (Inlined into the forward pass and unrolled over the 8 x 8 grid of a partner the
+// Out of line and COMPACT: one instance of the exact tests and of the contact's creation, in rolled loops over arrays that live in memory
+// and are indexed at run time; one 8 x 8 grid of pretests (unrolled: below), walked by every source. (Inlined into the forward pass and unrolled over the 8 x 8 grid of a partner the
 // stage was 30 % of the launch -- 52.7 -> 37.1 ms with the stage skipped at run time, same box -- although the north-star batch never
 // has a pair within reach: tens of kilobytes of cold straight-line code per step.) Called only at the steps at which the leg-level cull
 // (pair_contacts) leaves something to test for some candidate of the wavefront.
@@ -1540,21 +1548,23 @@ QNOINLINE void pair_contacts_tests(const QuadModel& m_in, const QuadTables& tab,
     const int d = src - 1, o = src == 0 ? kQLegs : (src == 1 ? leg : ((leg + d) & 3));
     const int on = !mine ? 0 : (src == 0 ? m.ntpg : m.leg[o & 3].npg);
     QPROF_SUBCOUNT(pf, 54, 1);
-    // the pretest: a ROLLED loop over the other side's geoms (centre and half extents of geom j arrive -- through the quad rotation for
-    // another leg -- and meet the eight own geoms in registers): a hundred instructions instead of the 8 x 8 grid unrolled
+    // the pretest: centre and half extents of the other side's geom j arrive -- through the quad rotation for another leg -- and meet the
+    // eight own geoms in registers. The loop over j is UNROLLED (round 8), so that a leg's geom j comes out of the registers by a
+    // compile-time index: rolled, it was picked by 0 / 1 weights, 48 select-FMAs per trip for what is a register name -- by count some 140 of
+    // a trip's 350 instructions. (One instance of the 8 x 8 grid per call of this function, shared by the sources: the loop over src stays rolled. The
+    // grid inlined into the forward pass was the 30 % above; out of line it is 0.56 ms FASTER than the rolled loop)
     unsigned long long mask = 0;
-    for (int j = 0; j < (src == 0 ? kQTrunkPairGeom : kQPairGeom); j++) {
+    QUNROLL for (int j = 0; j < kQPairGeom; j++) {
+      if (src == 0 && j >= kQTrunkPairGeom) continue;
       double xj[3], ej[3];
       if (src == 0) {  // (a trunk geom: constant in the trunk's axes)
         const QuadGeom& g = m.trunk_geom[m.tpg_slot[j < m.ntpg ? j : 0]];
         const double half = g.type == MJPCX_GEOM_CAPSULE ? g.size[1] : 0.0, rad = g.type == MJPCX_GEOM_CAPSULE ? g.size[0] : g.bound;
         QUNROLL for (int k = 0; k < 3; k++) { xj[k] = g.pos[k]; ej[k] = half * fabs(g.rot[3 * k + 2]) + rad; }
       } else {
-        QUNROLL for (int k = 0; k < 3; k++) {  // (the own geom j by 0 / 1 weights: a run-time index would put the arrays in memory)
-          double vx = 0, ve = 0;
-          QUNROLL for (int q = 0; q < kQPairGeom; q++) { const double w = j == q ? 1.0 : 0.0; vx += w * xs[q][k]; ve += w * es[q][k]; }
-          xj[k] = src == 1 ? vx : qd_rotv(vx, d);
-          ej[k] = src == 1 ? ve : qd_rotv(ve, d);
+        QUNROLL for (int k = 0; k < 3; k++) {  // (the partner lane's geom j is its own geom j: the same registers, rotated)
+          xj[k] = src == 1 ? xs[j][k] : qd_rotv(xs[j][k], d);
+          ej[k] = src == 1 ? es[j][k] : qd_rotv(es[j][k], d);
         }
       }
       if (j >= on) continue;
@@ -1563,15 +1573,28 @@ QNOINLINE void pair_contacts_tests(const QuadModel& m_in, const QuadTables& tab,
         const double reach = own_reach[i] + oreach;
         const double dx = xs[i][0] - xj[0], dy = xs[i][1] - xj[1], dz = xs[i][2] - xj[2];
         const bool boxes = fabs(dx) < es[i][0] + ej[0] + bmg && fabs(dy) < es[i][1] + ej[1] + bmg && fabs(dz) < es[i][2] + ej[2] + bmg;
-        if (i < L.npg && boxes && dx * dx + dy * dy + dz * dz < reach * reach) mask |= 1ull << (8 * i + j);
+        if (i < L.npg && (kQPairsWalkAll || (boxes && dx * dx + dy * dy + dz * dz < reach * reach))) mask |= 1ull << (8 * i + j);
       }
     }
     mask &= L.pg_active[o];
     QPROF_SUB(pf, 53);
     if (src >= 2) {
       if (qd_or(mask != 0 ? 1 : 0) == 0) continue;  // (quad-uniform: the axes and velocities are only fetched for a partner that is near)
-      for (int j = 0; j < kQPairGeom; j++) for (int k = 0; k < 3; k++) { oc[j][k] = qd_rotv(args->pg.c[j][k], d); oa[j][k] = qd_rotv(args->pg.a[j][k], d); }
-      for (int j = 0; j < 3; j++) for (int k = 0; k < 6; k++) ov[j][k] = qd_rotv(args->cvel[j][k], d);
+      // Only the partner geoms the surviving pairs name, and their links' velocities (round 8; before: all 48 + 18 values, 132 crossbar
+      // trips and 66 scratch loads per near partner) -- by ballot: every lane takes part in a rotation the wavefront walks; the ballot decides
+      // whether it is walked, and the exact tests read nothing of oc / oa / ov that the lane's own mask does not name.
+      int jm = 0, lm = 0;
+      QUNROLL for (int i = 0; i < kQPairGeom; i++) jm |= (int)((mask >> (8 * i)) & 0xffull);
+      for (int j = 0; j < kQPairGeom; j++) {
+        const bool want = ((jm >> j) & 1) != 0;
+        if (want) lm |= 1 << m.leg[o & 3].geom[m.leg[o & 3].pg_slot[j]].link;
+        if (!qw_any(want)) continue;
+        for (int k = 0; k < 3; k++) { oc[j][k] = qd_rotv(args->pg.c[j][k], d); oa[j][k] = qd_rotv(args->pg.a[j][k], d); }
+      }
+      for (int j = 0; j < 3; j++) {
+        if (!qw_any(((lm >> j) & 1) != 0)) continue;
+        for (int k = 0; k < 6; k++) ov[j][k] = qd_rotv(args->cvel[j][k], d);
+      }
       QPROF_COUNT(pf, 45, 1);
     } else if (mask != 0) {
       if (src == 0) {
@@ -1745,6 +1768,7 @@ QD void pair_contacts(const QuadModel& m, const QuadTables& tab, int leg, QPairA
     }
     need |= qd_or(apart ? 0 : 1) << (1 + d);  // (quad-uniform: clear only if all four (leg, leg + d) pairs are)
   }
+  if (kQPairsWalkAll) need = (L.pg_active[kQLegs] != 0 ? 1 : 0) | (L.pg_active[leg] != 0 ? 2 : 0) | 0x1c;
   QPROF_SUB(pf, 50);
   if (qd_or(need) == 0) return;
 #ifdef QEXP_PAIRS_SKIP2
@@ -1959,7 +1983,9 @@ QD int forward_smooth(const QuadModel& m, const QuadTables& tab, const QStaticPo
     QPairBoxes pbox;
     pair_boxes_init(pbox);
     QPROF_T0(pf);  // (sub-stamps 46..48: pose + boxes, bounding test + candidate points, contact creation)
-    for (int i = 0; i < kQPairGeom; i++) for (int k = 0; k < 3; k++) { pargs.pg.c[i][k] = 0; pargs.pg.a[i][k] = 0; }
+    // (the slots without a pair geom: the loop below writes the pose of every pair geom the leg has, pgi = 0 .. npg - 1, at every step -- zeroing
+    // all 48 doubles first was 48 scratch stores per lane and step for nothing, 0.53 ms of the bench's launch)
+    for (int i = L.npg; i < kQPairGeom; i++) for (int k = 0; k < 3; k++) { pargs.pg.c[i][k] = 0; pargs.pg.a[i][k] = 0; }
     // A geom goes on to its orientation and to collide_geom only if static_pretest leaves something to find for SOME lane of the wavefront
     // -- in a gait that is the feet and the calves; hips, thighs and the trunk's geoms cost their centre and axis. (The ballot only decides
     // whether the wavefront walks the code: a lane's own contacts do not depend on the other lanes. Trip counts are the wavefront's -- the

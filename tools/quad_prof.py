@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # lines an MJPCX_QUAD_STAMPS=1 run prints) with their names, per launch: cycles of wavefront 0 over the launch's steps, counts per launch
 SUB = {46: "floor: centre + axis + pair boxes, orientation", 47: "floor: bounding tests + candidate points", 48: "floor: contact creation",
        49: "#floor: contact-creation trips", 50: "pairs: leg-level cull", 51: "pairs: hand-over + call", 52: "pairs: own geoms' boxes",
-       53: "pairs: pretests", 54: "#pairs: sources walked", 55: "pairs: partner fetch", 56: "pairs: exact tests", 57: "pairs: return",
+       53: "pairs: pretests", 54: "#pairs: sources walked", 55: "pairs: partner fetch", 56: "pairs: exact tests", 57: "pairs: other quads' sources (+ return)",
        58: "#pairs: calls of the tests", 59: "#floor: geoms the wavefront skipped"}
 if len(sys.argv) > 2 and sys.argv[1] == "--stamps":
     rows = [[int(x) for x in l.split(":")[1].split()] for l in open(sys.argv[2]) if "raw counters 40..63" in l]
