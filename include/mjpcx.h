@@ -356,7 +356,8 @@ int mjpcx_set_residual_states(mjpcx_ctx* ctx, int num_envs, const int32_t* resid
  * All four NULL: everything shared again. After mjpcx_set_states with the same E (MJPCX_EINVAL otherwise).
  *   - Every batched entry point reads the rows: mjpcx_rollout_splines_batched, mjpcx_rollout_splines_noisy_batched,
  *     mjpcx_rollout_noise_batched, mjpcx_rollout_noise_batched_ce, mjpcx_robust_step_batched, mjpcx_rollout_sample_gradient_batched,
- *     mjpcx_sample_gradient_update_batched, mjpcx_rollout_feedback_batched, mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched.
+ *     mjpcx_sample_gradient_update_batched, mjpcx_rollout_feedback_batched, mjpcx_gradient_step_batched, mjpcx_ilqg_step_batched and
+ *     mjpcx_ilqg_step_batched_from (ctx's rows, not the source's).
  *     Environment e of such a call behaves exactly like the plain call after mjpcx_set_task_params(row e): equal bits.
  *   - mjpcx_set_task_params and the plain entry points neither read nor clear the rows: plain and batched values live side by
  *     side, as the states of mjpcx_set_state and mjpcx_set_states do (NOT the rule of mjpcx_set_residual_state above: a plain
@@ -632,6 +633,34 @@ int mjpcx_ilqg_step_batched(mjpcx_ctx* ctx, int num_envs, const int32_t* candida
                             double max_reg, int max_iter, double* K, double* du, double* dV, int32_t* status, double* mu_out, double* rate_out,
                             int32_t* retries, double* nominal_return, double* A, double* B, double* cx, double* cu, double* cxx, double* cxu,
                             double* cuu, double* Vx, double* Vxx);
+
+/* mjpcx_ilqg_step_batched for a fleet whose nominals lie in TWO contexts: the middle of iLQSPlanner::OptimizePolicy
+ * (ilqs/planner.cc:87-214) for E environments. In iLQS a robot whose active policy was sampling hands sampling's rollout to iLQG --
+ * ilqg.candidate_policy[0].trajectory = sampling.trajectory[0] -- and that trajectory is in the device buffers of the sampling
+ * context, while a robot whose active policy was iLQG has its nominal among the feedback rollouts of the iLQG context. Environment e's
+ * nominal is
+ *   from_source[e] == 0: local candidate candidate[e] of the last batched rollout of ctx (mjpcx_ilqg_step_batched);
+ *   from_source[e] == 1: local candidate candidate[e] of the last batched rollout of `source` -- of any kind, with its own number of
+ *     candidates per environment, its own horizon >= T and whichever Trajectory layout its kernel left.
+ * candidate[e] == -1 keeps its meaning: the environment takes no part and rides on the first active environment's nominal, read from
+ * whichever context that one names. ONE gather launch reads both sets of buffers with a per-environment selector; nothing of a nominal
+ * passes through the host. Everything after the gather is mjpcx_ilqg_step_batched's chain (ilqg/planner.cc:377-520 with
+ * model_derivatives.cc:45-165, cost_derivatives.cc:112-230 and backward_pass.cc:65-356) on ctx's stream, which is put behind what
+ * source's stream holds at the call by an event, with ctx's plan records from mjpcx_set_states / mjpcx_set_residual_states and ctx's
+ * task parameters: ONE device-to-host block, ONE sync, the same outputs.
+ *   - With every from_source[e] == 0 the call is mjpcx_ilqg_step_batched, bit for bit, whatever `source` is (NULL included).
+ *   - With every active environment on the source, ctx needs mjpcx_set_states of num_envs environments and no rollout of its own.
+ *   - source == ctx is allowed.
+ * MJPCX_EINVAL, beyond mjpcx_ilqg_step_batched's: a from_source value other than 0 or 1; source NULL while some from_source[e] == 1;
+ * the two contexts differ in device, precision or in nq, nv, na, nu, nr; the last rollout of a context an active environment names was
+ * not a batched one of num_envs environments, or its horizon is shorter than T; a candidate outside [-1, n_per_env) of the context its
+ * environment names; ctx without mjpcx_set_states of num_envs environments. MJPCX_EUNSUPPORTED: what mjpcx_ilqg_step_batched refuses,
+ * of either context (sharded with mjpcx_comm_init, fp32 on the wavefront-per-candidate family). */
+int mjpcx_ilqg_step_batched_from(mjpcx_ctx* ctx, mjpcx_ctx* source, const int32_t* from_source, int num_envs, const int32_t* candidate, int T,
+                                 int num_eval, const int32_t* evaluate, double eps, int centered, int reg_type, int use_limits, const double* mu,
+                                 const double* rate, double factor, double min_reg, double max_reg, int max_iter, double* K, double* du,
+                                 double* dV, int32_t* status, double* mu_out, double* rate_out, int32_t* retries, double* nominal_return,
+                                 double* A, double* B, double* cx, double* cu, double* cxx, double* cxu, double* cuu, double* Vx, double* Vxx);
 
 /* mjpcx_rollout_feedback for E environments in one launch: for every environment e exactly mjpcx_rollout_feedback(n_per_env, ...) with
  * row e of every array -- times E x Tn, states E x Tn x (nq+nv), actions E x Tn x nu, gains E x Tn x nu x ndx, improvement E x Tn x nu,

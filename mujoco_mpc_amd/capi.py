@@ -30,7 +30,7 @@ EXPORTS = [
     "mjpcx_elite_allreduce", "mjpcx_comm_barrier", "mjpcx_comm_destroy",
     "mjpcx_set_states", "mjpcx_set_residual_states", "mjpcx_set_task_params_batched", "mjpcx_rollout_splines_batched", "mjpcx_rollout_noise_batched", "mjpcx_best_batched",
     "mjpcx_rollout_noise_batched_ce", "mjpcx_ce_update_batched", "mjpcx_gradient_step_batched",
-    "mjpcx_rollout_feedback_batched", "mjpcx_ilqg_step_batched",
+    "mjpcx_rollout_feedback_batched", "mjpcx_ilqg_step_batched", "mjpcx_ilqg_step_batched_from",
     "mjpcx_rollout_splines_noisy_batched", "mjpcx_robust_step_batched",
     "mjpcx_rollout_sample_gradient_batched", "mjpcx_sample_gradient_update_batched",
 ]
@@ -90,6 +90,7 @@ def lib():
         L.mjpcx_gradient_step_batched.argtypes = ([vp] + [C.c_int] * 4 + [c_i32p, C.c_double] + [C.c_int] * 3 + [c_f64p] * 9)
         L.mjpcx_ilqg_step_batched.argtypes = ([vp, C.c_int, c_i32p, C.c_int, C.c_int, c_i32p, C.c_double] + [C.c_int] * 3 + [c_f64p] * 2 +
                                               [C.c_double] * 3 + [C.c_int] + [c_f64p] * 3 + [c_i32p] + [c_f64p] * 2 + [c_i32p] + [c_f64p] * 10)
+        L.mjpcx_ilqg_step_batched_from.argtypes = [vp, vp, c_i32p] + L.mjpcx_ilqg_step_batched.argtypes[1:]
         L.mjpcx_sync.argtypes = [vp]
         L.mjpcx_get_returns.argtypes = [vp, c_f64p, c_i32p]
         L.mjpcx_get_return_at.argtypes = [vp, C.c_int, C.POINTER(C.c_double), c_i32p]
@@ -530,12 +531,30 @@ class Context:
         rollout, on the device, one sync (mjpcx_ilqg_step_batched). candidate: E local indices, -1 = the environment takes no part.
         Dict of K (E x T x nu x ndx), du (E x T x nu), dV (E x 2), status (E: 1 ok, 0 failed every retry, -1 took no part), mu, rate,
         retries (E), nominal_return (E) and, with with_matrices (tests), A, B, cx, cu, cxx, cxu, cuu, Vx, Vxx."""
+        return self._ilqg_step_batched(None, candidate, T, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg, max_reg,
+                                       max_iter, with_matrices, num_envs)
+
+    def ilqg_step_batched_from(self, source, from_source, candidate, T, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg,
+                               max_reg, max_iter, with_matrices=False, num_envs=None):
+        """ilqg_step_batched for a fleet whose nominals lie in two contexts (mjpcx_ilqg_step_batched_from): environment e's nominal is
+        local candidate candidate[e] of the last batched rollout of this context (from_source[e] == 0) or of `source`'s (== 1), gathered
+        on the device; the chain runs here, with this context's set_states. source: a Context or None (then every from_source is 0).
+        The same dict."""
+        frm = np.ascontiguousarray(from_source, dtype=np.int32).reshape(-1)
+        return self._ilqg_step_batched((source, frm), candidate, T, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg,
+                                       max_reg, max_iter, with_matrices, num_envs)
+
+    def _ilqg_step_batched(self, frm, candidate, T, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg, max_reg, max_iter,
+                           with_matrices, num_envs):
+        name = "ilqg_step_batched" if frm is None else "ilqg_step_batched_from"
         cand = np.ascontiguousarray(candidate, dtype=np.int32).reshape(-1)
         E, T = (cand.size if num_envs is None else int(num_envs)), int(T)
         ev = np.ascontiguousarray(evaluate, dtype=np.int32).reshape(-1)
         mu_in, rate_in = _f(mu).reshape(-1), _f(rate).reshape(-1)
         if E >= 1 and (cand.size, mu_in.size, rate_in.size) != (E, E, E):
-            raise ValueError(f"ilqg_step_batched: {cand.size} candidates, {mu_in.size} mu, {rate_in.size} rate for {E} environments")
+            raise ValueError(f"{name}: {cand.size} candidates, {mu_in.size} mu, {rate_in.size} rate for {E} environments")
+        if frm is not None and E >= 1 and frm[1].size != E:
+            raise ValueError(f"{name}: {frm[1].size} from_source entries for {E} environments")
         n, m, Ea, Ta = 2 * self.nv, self.nu, max(E, 1), max(T, 1)
         out = dict(K=np.zeros((Ea, Ta, m, n)), du=np.zeros((Ea, Ta, m)), dV=np.zeros((Ea, 2)), status=np.zeros(Ea, np.int32), mu=np.zeros(Ea),
                    rate=np.zeros(Ea), retries=np.zeros(Ea, np.int32), nominal_return=np.zeros(Ea))
@@ -544,12 +563,17 @@ class Context:
             shapes = ((n, n), (n, m), (n,), (m,), (n, n), (n, m), (m, m), (n,), (n, n))
             out.update({k: np.zeros((Ea, Ta) + sh) for k, sh in zip(names, shapes)})
         opt = [as_f64p(out[k]) if with_matrices else None for k in names]
-        self._chk(lib().mjpcx_ilqg_step_batched(self.handle, E, as_i32p(cand) if cand.size else as_i32p(np.zeros(1, np.int32)), T, ev.size,
-                                                as_i32p(ev) if ev.size else as_i32p(np.zeros(1, np.int32)), float(eps), int(centered),
-                                                int(reg_type), int(use_limits), as_f64p(mu_in), as_f64p(rate_in), float(factor), float(min_reg),
-                                                float(max_reg), int(max_iter), as_f64p(out["K"]), as_f64p(out["du"]), as_f64p(out["dV"]),
-                                                as_i32p(out["status"]), as_f64p(out["mu"]), as_f64p(out["rate"]), as_i32p(out["retries"]),
-                                                as_f64p(out["nominal_return"]), *opt))
+        args = (E, as_i32p(cand) if cand.size else as_i32p(np.zeros(1, np.int32)), T, ev.size,
+                as_i32p(ev) if ev.size else as_i32p(np.zeros(1, np.int32)), float(eps), int(centered),
+                int(reg_type), int(use_limits), as_f64p(mu_in), as_f64p(rate_in), float(factor), float(min_reg),
+                float(max_reg), int(max_iter), as_f64p(out["K"]), as_f64p(out["du"]), as_f64p(out["dV"]),
+                as_i32p(out["status"]), as_f64p(out["mu"]), as_f64p(out["rate"]), as_i32p(out["retries"]),
+                as_f64p(out["nominal_return"]), *opt)
+        if frm is None:
+            self._chk(lib().mjpcx_ilqg_step_batched(self.handle, *args))
+        else:
+            self._chk(lib().mjpcx_ilqg_step_batched_from(self.handle, None if frm[0] is None else frm[0].handle,
+                                                         as_i32p(frm[1]) if frm[1].size else as_i32p(np.zeros(1, np.int32)), *args))
         return out
 
     def transition_fd(self, times, states, actions, eps=1e-6, centered=0):

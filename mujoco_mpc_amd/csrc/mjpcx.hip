@@ -816,7 +816,7 @@ struct mjpcx_ctx {
   int next_slot = 0;
   // pinned + device-mapped result record of mjpcx_best
   void* best_host = nullptr; void* best_dev = nullptr; size_t best_cap = 0;
-  hipEvent_t source_done = nullptr;  // mjpcx_robust_step_batched: orders this stream behind the source context's
+  hipEvent_t source_done = nullptr;  // mjpcx_robust_step_batched, mjpcx_ilqg_step_batched_from: orders this stream behind the source context's
   // the Sample-Gradient planner's state between plan steps (mjpcx_rollout_sample_gradient_batched / mjpcx_sample_gradient_update_batched)
   struct SampleGradient {
     PinnedBlock h_in, h_up;       // pinned sides of d_in (marked: the rollout call does not sync) and d_up (the update ends in a sync)
@@ -3064,7 +3064,7 @@ int mjpcx_gradient_pass(mjpcx_ctx* c, int n, int m, int T, const double* A, cons
 namespace {
 // The shared front and tail of mjpcx_gradient_step_batched and mjpcx_ilqg_step_batched: ModelDerivatives::Compute for E environments from
 // the last batched rollout, enqueued on the context's stream, and the one download. One device workspace (d_grad), carved in this order:
-//   [evaluate | ctrllimited | ctrlrange | candidates | sources | active | cost rows | the caller's inputs]  one upload from h_grad
+//   [evaluate | ctrllimited | ctrlrange | candidates | sources | active | from | cost rows | the caller's inputs]  one upload from h_grad
 //   [gathered nominal | finite-difference workspace | A, B, C, D at all T steps | the caller's arrays]
 //   [nominal_return | the caller's results]                                                                 one download into h_grad
 // The caller carves its own fields with carve() after the constructor, after carve_work() and after carve_results(); then stage(), its
@@ -3076,10 +3076,13 @@ struct StepChain {
   int E, Tn, ne;
   size_t ds, ndx, nu, nr, nc, sE, sT, rows, sA, sB, sC, sD;
   size_t off = 0, in_bytes = 0, o_out = 0;
-  size_t o_eval, o_lim, o_range, o_cand, o_src, o_act, o_rows, o_ft = 0, o_fs = 0, o_fa = 0, o_res = 0, o_A = 0, o_B = 0, o_C = 0, o_D = 0, o_ret = 0;
+  size_t o_eval, o_lim, o_range, o_cand, o_src, o_act, o_from, o_rows, o_ft = 0, o_fs = 0, o_fa = 0, o_res = 0, o_A = 0, o_B = 0, o_C = 0, o_D = 0, o_ret = 0;
   FdCarve fd{};
   PlanRecords rec{};
   char *base = nullptr, *hin = nullptr, *hout = nullptr;
+  // mjpcx_ilqg_step_batched_from: the environments with from[e] != 0 take their nominal from the last batched rollout of `other`
+  mjpcx_ctx* other = nullptr;
+  const int32_t* from = nullptr;
 
   size_t carve(size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; }
   double* f64(size_t o) const { return (double*)(base + o); }
@@ -3089,7 +3092,7 @@ struct StepChain {
     ds = c->nq + c->nv; ndx = 2 * (size_t)c->nv; nu = c->nu; nr = c->nr; nc = 1 + 2 * (ndx + nu);
     sE = E; sT = Tn; rows = sE * ne; sA = ndx * ndx; sB = ndx * nu; sC = nr * ndx; sD = nr * nu;
     o_eval = carve((size_t)ne * 4); o_lim = carve(nu * 4); o_range = carve(2 * nu * sizeof(T));
-    o_cand = carve(sE * 4); o_src = carve(sE * 4); o_act = carve(sE * 4);
+    o_cand = carve(sE * 4); o_src = carve(sE * 4); o_act = carve(sE * 4); o_from = carve(sE * 4);
     o_rows = carve(has_env_task_params(c) ? sE * sizeof(CostRow) : 0);  // (mjpcx_set_task_params_batched: each environment's cost parameters)
   }
   // what the cost kernels take as their rows: nullptr while every environment shares the context's task parameters
@@ -3121,6 +3124,7 @@ struct StepChain {
       ((int*)(hin + o_cand))[e] = candidate[on ? e : first];
       ((int*)(hin + o_src))[e] = on ? e : first;
       ((int*)(hin + o_act))[e] = on ? 1 : 0;
+      ((int*)(hin + o_from))[e] = from && from[on ? e : first] ? 1 : 0;
     }
     if (has_env_task_params(c)) {  // the environment's own fields where given, the context's (cs) elsewhere
       const size_t nt = c->nterm;
@@ -3144,6 +3148,12 @@ struct StepChain {
     g.states = (const T*)c->d_states.p; g.actions = (const T*)c->d_actions.p; g.times = (const T*)c->d_times.p; g.residual = (const T*)c->d_residual.p;
     g.total_return = (const double*)c->d_ret.p;
     g.N = c->N; g.H = c->H; g.n_per_env = c->env_n; g.candidate_major = c->traj_candidate_major ? 1 : 0;
+    if (other) {
+      g.alt.states = (const T*)other->d_states.p; g.alt.actions = (const T*)other->d_actions.p; g.alt.times = (const T*)other->d_times.p;
+      g.alt.residual = (const T*)other->d_residual.p; g.alt.total_return = (const double*)other->d_ret.p;
+      g.alt.N = other->N; g.alt.H = other->H; g.alt.n_per_env = other->env_n; g.alt.candidate_major = other->traj_candidate_major ? 1 : 0;
+      g.from_alt = i32(o_from);
+    }
     g.cands = i32(o_cand); g.source = i32(o_src); g.active = i32(o_act);
     g.E = E; g.Tn = Tn; g.ne = ne; g.evaluate = i32(o_eval);
     g.ds_roll = c->nq + c->nv + c->na; g.ds = (int)ds; g.nu = (int)nu; g.nr = (int)nr;
@@ -3211,9 +3221,9 @@ int do_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int Tn, int ne, cons
   return s.finish(optional, 4, {{s.o_ret, 8, nominal_return}, {o_k, sT * nu * 8, k}, {o_g, sP * nu * 8, gradient}, {o_dV, 16, dV}});
 }
 
-// mjpcx_ilqg_step_batched after validation
+// mjpcx_ilqg_step_batched and mjpcx_ilqg_step_batched_from (other, from: StepChain; nullptr for the former) after validation
 template <typename T>
-int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, int ne, const int32_t* evaluate, double eps, int centered, int reg_type,
+int do_ilqg_step_batched(mjpcx_ctx* c, mjpcx_ctx* other, const int32_t* from, int E, const int32_t* candidate, int Tn, int ne, const int32_t* evaluate, double eps, int centered, int reg_type,
                          int use_limits, const double* mu, const double* rate, double factor, double min_reg, double max_reg, int max_iter, double* K,
                          double* du, double* dV, int32_t* status, double* mu_out, double* rate_out, int32_t* retries, double* nominal_return,
                          double* const (&opt)[9]) {
@@ -3221,6 +3231,7 @@ int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, 
   CostSpec cs{};
   if ((rc = make_cost_spec(c, &cs)) != MJPCX_OK) return rc;
   StepChain<T> s(c, E, Tn, ne);
+  s.other = other; s.from = from;
   if (s.too_large()) return fail(c, MJPCX_EUNSUPPORTED, "mjpcx_ilqg_step_batched: too many environments x steps");
   const size_t sE = E, sT = Tn, ndx = s.ndx, nu = s.nu, sA = s.sA, sB = s.sB;
   // the optional outputs A, B, cx, cu, cxx, cxu, cuu, Vx, Vxx: elements per environment
@@ -3250,6 +3261,11 @@ int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, 
   std::memcpy(s.hin + o_limits, c->ctrlrange.data(), 2 * nu * 8);
   // (Vx .. retries are contiguous: what a failed sweep or an environment that takes no part does not write reads as zero)
   HIPCHK(c, hipMemsetAsync(s.base + o_Vx, 0, s.off - o_Vx, c->stream));
+  if (other && other != c) {  // the gather reads the other context's rollout: this stream goes behind what that one holds now
+    if (!c->source_done) HIPCHK(c, hipEventCreateWithFlags(&c->source_done, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->source_done, other->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->source_done, 0));
+  }
   if ((rc = s.run(eps, centered, nullptr, s.f64(o_actions))) != MJPCX_OK) return rc;
   // ---- CostDerivatives::Compute: workgroup e * Tn + t forms step t of environment e (every array is environment-major)
   const size_t at[9] = {s.o_A, s.o_B, o_cx, o_cu, o_cxx, o_cxu, o_cuu, o_Vx, o_Vxx};
@@ -3276,6 +3292,66 @@ int do_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int Tn, 
     return rc;
   for (int e = 0; e < E; e++) if (candidate[e] < 0) unpack_inactive(e);
   return MJPCX_OK;
+}
+
+// mjpcx_ilqg_step_batched (src == nullptr, from == nullptr) and mjpcx_ilqg_step_batched_from (some from[e] == 1, src given): validation
+int ilqg_step_batched_entry(const char* who_, mjpcx_ctx* c, mjpcx_ctx* src, const int32_t* from, int E, const int32_t* candidate, int T, int ne,
+                            const int32_t* evaluate, double eps, int centered, int reg_type, int use_limits, const double* mu, const double* rate,
+                            double factor, double min_reg, double max_reg, int max_iter, double* K, double* du, double* dV, int32_t* status,
+                            double* mu_out, double* rate_out, int32_t* retries, double* nominal_return, double* const (&opt)[9]) {
+  const std::string who = who_;
+  if (!c || !candidate || !evaluate || !mu || !rate || !K || !du || !dV || !status || !mu_out || !rate_out || !retries)
+    return fail(c, MJPCX_EINVAL, who + "null argument");
+  if (src && (src->device != c->device || src->precision != c->precision || src->nq != c->nq || src->nv != c->nv || src->na != c->na ||
+              src->nu != c->nu || src->nr != c->nr))
+    return fail(c, MJPCX_EINVAL, who + "the two contexts differ in device, precision or model dimensions (nq, nv, na, nu, nr)");
+  // which context the active environments name: this one (also with nobody active, as mjpcx_ilqg_step_batched), the source
+  bool own = !from, other = false, active = false;
+  for (int e = 0; from && e < E; e++)
+    if (candidate[e] >= 0) { active = true; (from[e] ? other : own) = true; }
+  if (from && !active) own = true;
+  if (own) {
+    if (!c->have_rollout && from)  // (somebody names the source, somebody this context, which has none)
+      return fail(c, MJPCX_EINVAL, who + "the last rollout was not a batched one of " + std::to_string(E) + " environments (there is none)");
+    if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+    if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N || c->env_E != E)
+      return fail(c, MJPCX_EINVAL, who + "the last rollout was not a batched one of " + std::to_string(E) + " environments");
+  } else if (c->env_E != E) {  // every nominal comes from the source: this context brings the plan records alone
+    return fail(c, MJPCX_EINVAL, c->env_E == 0 ? who + "before mjpcx_set_states"
+                                               : who + std::to_string(E) + " environments after mjpcx_set_states of " + std::to_string(c->env_E));
+  }
+  if (other && (!src->have_rollout || src->env_n < 1 || (long long)E * src->env_n != src->N))
+    return fail(c, MJPCX_EINVAL, who + "the source's last rollout was not a batched one of " + std::to_string(E) + " environments");
+  for (int e = 0; e < E; e++) {
+    const mjpcx_ctx* x = from && from[e] ? src : c;
+    if (candidate[e] < -1 || (candidate[e] >= 0 && candidate[e] >= x->env_n))
+      return fail(c, MJPCX_EINVAL, who + "candidate outside [-1, n_per_env) (environment " + std::to_string(e) + ")");
+  }
+  if (T < 2 || (own && T > c->H)) return fail(c, MJPCX_EINVAL, who + "T must be >= 2 and within the rollout's horizon");
+  if (other && T > src->H) return fail(c, MJPCX_EINVAL, who + "T must be within the horizon of the source's rollout");
+  if (ne < 1 || ne > T) return fail(c, MJPCX_EINVAL, who + "num_eval outside [1, T]");
+  for (int i = 0; i < ne; i++)
+    if (evaluate[i] < 0 || evaluate[i] >= T || (i > 0 && evaluate[i] <= evaluate[i - 1]))
+      return fail(c, MJPCX_EINVAL, who + "the evaluate list must be strictly increasing and within [0, T)");
+  if (!(eps > 0)) return fail(c, MJPCX_EINVAL, who + "epsilon must be > 0");
+  if (reg_type < 0 || reg_type > 2) return fail(c, MJPCX_EINVAL, who + "unknown regularization type");
+  if (max_iter < 1 || max_iter > 64) return fail(c, MJPCX_EINVAL, who + "max_iter outside [1, 64]");
+  for (int e = 0; e < E; e++)
+    if (!std::isfinite(mu[e]) || !(mu[e] > 0) || !std::isfinite(rate[e]) || !(rate[e] > 0))
+      return fail(c, MJPCX_EINVAL, who + "mu and rate must be finite and > 0 (environment " + std::to_string(e) + ")");
+  if (!std::isfinite(factor) || !(factor > 0)) return fail(c, MJPCX_EINVAL, who + "factor must be finite and > 0");
+  if (!std::isfinite(min_reg) || !std::isfinite(max_reg) || !(min_reg <= max_reg))
+    return fail(c, MJPCX_EINVAL, who + "min_reg and max_reg must be finite, min_reg <= max_reg");
+  if (c->comm_world > 1 || (src && src->comm_world > 1)) return fail(c, MJPCX_EUNSUPPORTED, who + "not implemented on a context sharded with mjpcx_comm_init");
+  if ((c->wave && c->precision != 64) || (src && src->wave && src->precision != 64))
+    return fail(c, MJPCX_EUNSUPPORTED, (from ? who : std::string()) + "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
+  if (2 * c->nv > kGradMaxN || c->nu > kGradMaxM || T > kGradMaxT)
+    return fail(c, MJPCX_EUNSUPPORTED, who + "covers n <= 48, m <= 16, T <= 512 (kMaxTrajectoryHorizon)");
+  HIPCHK(c, hipSetDevice(c->device));
+  return c->precision == 64 ? do_ilqg_step_batched<double>(c, src, from, E, candidate, T, ne, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor,
+                                                           min_reg, max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt)
+                            : do_ilqg_step_batched<float>(c, src, from, E, candidate, T, ne, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor,
+                                                          min_reg, max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt);
 }
 }  // namespace
 
@@ -3317,39 +3393,31 @@ int mjpcx_ilqg_step_batched(mjpcx_ctx* c, int E, const int32_t* candidate, int T
                             int use_limits, const double* mu, const double* rate, double factor, double min_reg, double max_reg, int max_iter, double* K,
                             double* du, double* dV, int32_t* status, double* mu_out, double* rate_out, int32_t* retries, double* nominal_return, double* A,
                             double* B, double* cx, double* cu, double* cxx, double* cxu, double* cuu, double* Vx, double* Vxx) {
-  const char* who = "mjpcx_ilqg_step_batched: ";
-  if (!c || !candidate || !evaluate || !mu || !rate || !K || !du || !dV || !status || !mu_out || !rate_out || !retries)
-    return fail(c, MJPCX_EINVAL, std::string(who) + "null argument");
-  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
-  if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N || c->env_E != E)
-    return fail(c, MJPCX_EINVAL, std::string(who) + "the last rollout was not a batched one of " + std::to_string(E) + " environments");
-  for (int e = 0; e < E; e++)
-    if (candidate[e] < -1 || candidate[e] >= c->env_n)
-      return fail(c, MJPCX_EINVAL, std::string(who) + "candidate outside [-1, n_per_env) (environment " + std::to_string(e) + ")");
-  if (T < 2 || T > c->H) return fail(c, MJPCX_EINVAL, std::string(who) + "T must be >= 2 and within the rollout's horizon");
-  if (ne < 1 || ne > T) return fail(c, MJPCX_EINVAL, std::string(who) + "num_eval outside [1, T]");
-  for (int i = 0; i < ne; i++)
-    if (evaluate[i] < 0 || evaluate[i] >= T || (i > 0 && evaluate[i] <= evaluate[i - 1]))
-      return fail(c, MJPCX_EINVAL, std::string(who) + "the evaluate list must be strictly increasing and within [0, T)");
-  if (!(eps > 0)) return fail(c, MJPCX_EINVAL, std::string(who) + "epsilon must be > 0");
-  if (reg_type < 0 || reg_type > 2) return fail(c, MJPCX_EINVAL, std::string(who) + "unknown regularization type");
-  if (max_iter < 1 || max_iter > 64) return fail(c, MJPCX_EINVAL, std::string(who) + "max_iter outside [1, 64]");
-  for (int e = 0; e < E; e++)
-    if (!std::isfinite(mu[e]) || !(mu[e] > 0) || !std::isfinite(rate[e]) || !(rate[e] > 0))
-      return fail(c, MJPCX_EINVAL, std::string(who) + "mu and rate must be finite and > 0 (environment " + std::to_string(e) + ")");
-  if (!std::isfinite(factor) || !(factor > 0)) return fail(c, MJPCX_EINVAL, std::string(who) + "factor must be finite and > 0");
-  if (!std::isfinite(min_reg) || !std::isfinite(max_reg) || !(min_reg <= max_reg))
-    return fail(c, MJPCX_EINVAL, std::string(who) + "min_reg and max_reg must be finite, min_reg <= max_reg");
-  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "not implemented on a context sharded with mjpcx_comm_init");
-  if (c->wave && c->precision != 64) return fail(c, MJPCX_EUNSUPPORTED, "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
-  if (2 * c->nv > kGradMaxN || c->nu > kGradMaxM || T > kGradMaxT)
-    return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "covers n <= 48, m <= 16, T <= 512 (kMaxTrajectoryHorizon)");
-  HIPCHK(c, hipSetDevice(c->device));
   double* const opt[9] = {A, B, cx, cu, cxx, cxu, cuu, Vx, Vxx};
-  return c->precision == 64 ? do_ilqg_step_batched<double>(c, E, candidate, T, ne, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg,
-                                                           max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt)
-                            : do_ilqg_step_batched<float>(c, E, candidate, T, ne, evaluate, eps, centered, reg_type, use_limits, mu, rate, factor, min_reg,
-                                                          max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt);
+  return ilqg_step_batched_entry("mjpcx_ilqg_step_batched: ", c, nullptr, nullptr, E, candidate, T, ne, evaluate, eps, centered, reg_type, use_limits, mu,
+                                 rate, factor, min_reg, max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return, opt);
+}
+
+int mjpcx_ilqg_step_batched_from(mjpcx_ctx* c, mjpcx_ctx* source, const int32_t* from_source, int E, const int32_t* candidate, int T, int ne,
+                                 const int32_t* evaluate, double eps, int centered, int reg_type, int use_limits, const double* mu, const double* rate,
+                                 double factor, double min_reg, double max_reg, int max_iter, double* K, double* du, double* dV, int32_t* status,
+                                 double* mu_out, double* rate_out, int32_t* retries, double* nominal_return, double* A, double* B, double* cx,
+                                 double* cu, double* cxx, double* cxu, double* cuu, double* Vx, double* Vxx) {
+  const char* who = "mjpcx_ilqg_step_batched_from: ";
+  if (!c || !from_source || !candidate) return fail(c, MJPCX_EINVAL, std::string(who) + "null argument");
+  if (E < 1) return fail(c, MJPCX_EINVAL, std::string(who) + "num_envs must be >= 1");
+  bool any = false;
+  for (int e = 0; e < E; e++) {
+    if (from_source[e] != 0 && from_source[e] != 1)
+      return fail(c, MJPCX_EINVAL, std::string(who) + "from_source must be 0 or 1 (environment " + std::to_string(e) + ")");
+    any = any || from_source[e] == 1;
+  }
+  if (any && !source) return fail(c, MJPCX_EINVAL, std::string(who) + "from_source names a source, but source is NULL");
+  double* const opt[9] = {A, B, cx, cu, cxx, cxu, cuu, Vx, Vxx};
+  // nobody reads the source: mjpcx_ilqg_step_batched, whatever the source is
+  return ilqg_step_batched_entry(who, c, any ? source : nullptr, any ? from_source : nullptr, E, candidate, T, ne, evaluate, eps, centered, reg_type,
+                                 use_limits, mu, rate, factor, min_reg, max_reg, max_iter, K, du, dV, status, mu_out, rate_out, retries, nominal_return,
+                                 opt);
 }
 
 }  // extern "C"

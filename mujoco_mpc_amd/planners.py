@@ -419,6 +419,7 @@ class GpuBatchSamplingPlanner(_FleetTasks):
         self.iteration = 0
         self.rollouts_compute_time = self.policy_update_compute_time = 0.0
         self._last = None  # what the context's last rollout was: "plan" (n candidates per environment) or "nominal"
+        self.differentiable = False  # plan on the differentiable model copy (GpuSamplingPlanner's): on in GpuBatchILQSPlanner
         # the members never roll out themselves: they are handed the shared context instead of creating their own
         self.envs = [GpuSamplingPlanner(device, precision, seed + e, backend_factory=lambda task: self.ctx) for e in range(self.num_envs)]
 
@@ -445,7 +446,7 @@ class GpuBatchSamplingPlanner(_FleetTasks):
         if self._backend_factory is not None:
             self.ctx = self._backend_factory(self.task)
         else:
-            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+            self.ctx = capi.Context(self.task.packed_model(differentiable=self.differentiable), self.task.packed(), self.device, self.precision)
         for p in self.envs:
             p.allocate()
 
@@ -1917,14 +1918,27 @@ class GpuBatchILQGPlanner(_FleetTasks):
         self.ctx.set_state(p.state, p.time, p.mocap, p.userdata)
         return p._iteration_before_rollouts(horizon)
 
+    def _step_args(self, T):
+        """what ilqg_step_batched takes after the candidates: the steps, the settings and every member's regularisation"""
+        st = self.settings
+        return (T, derivative_steps(T, self.derivative_skip_), st.fd_tolerance, int(st.fd_mode), st.regularization_type, st.action_limits,
+                [p.regularization for p in self.envs], [p.regularization_rate for p in self.envs], self.envs[0].regularization_factor,
+                st.min_regularization, st.max_regularization, st.max_regularization_iterations)
+
     def _device_middle(self, horizon):
         """GpuILQGPlanner._iteration_before_rollouts of every member from ONE ilqg_step_batched; the line search's requests"""
-        st, T = self.settings, horizon
         t0 = _time.perf_counter()
-        out = self.ctx.ilqg_step_batched([p.nominal_index for p in self.envs], T, derivative_steps(T, self.derivative_skip_), st.fd_tolerance,
-                                         int(st.fd_mode), st.regularization_type, st.action_limits, [p.regularization for p in self.envs],
-                                         [p.regularization_rate for p in self.envs], self.envs[0].regularization_factor,
-                                         st.min_regularization, st.max_regularization, st.max_regularization_iterations)
+        out = self.ctx.ilqg_step_batched([p.nominal_index for p in self.envs], *self._step_args(horizon))
+        requests = self._scatter_step(out, horizon)
+        call_us = (_time.perf_counter() - t0) * 1e6
+        for e, p in enumerate(self.envs):
+            if out["status"][e] < 0:
+                requests[e] = self._sequential_middle(p, horizon)
+        return requests, call_us
+
+    def _scatter_step(self, out, T):
+        """the results of one ilqg_step_batched[_from] into the members; per member the line search's request, None for one that took
+        no part (status -1: untouched) or whose backward pass failed every retry (status 0)"""
         requests = []
         for e, p in enumerate(self.envs):
             status = int(out["status"][e])
@@ -1944,11 +1958,7 @@ class GpuBatchILQGPlanner(_FleetTasks):
             c0.feedback_gain[:T] = out["K"][e]
             c0.action_improvement[:T] = out["du"][e]
             requests.append((tr.times[:T], tr.states[:T], tr.actions[:T], c0.feedback_gain[:T], c0.action_improvement[:T], p._linesearch_steps()))
-        call_us = (_time.perf_counter() - t0) * 1e6
-        for e, p in enumerate(self.envs):
-            if out["status"][e] < 0:
-                requests[e] = self._sequential_middle(p, horizon)
-        return requests, call_us
+        return requests
 
     # ---- OptimizePolicy, ilqg/planner.cc:156-164, for every environment
     def optimize_policy(self, horizon, pool=None):
@@ -2440,6 +2450,9 @@ class GpuILQSPlanner:
     def reset(self, horizon, initial_repeated_action=None):
         self.sampling.reset(horizon, initial_repeated_action)
         self.ilqg.reset(horizon, initial_repeated_action)
+        self._reset_own()
+
+    def _reset_own(self):
         self.active_policy = self.previous_active_policy = self.SAMPLING
         self.ilqg_ran = False
         self.fit_status, self.fit_unreached = SPLINE_FIT_NONE, 0
@@ -2482,14 +2495,16 @@ class GpuILQSPlanner:
 
     def _handoff(self, horizon):
         """ilqg.candidate_policy[0].trajectory = sampling.trajectory[0] (buffers keep their capacity)"""
-        got = self.sampling.ctx.fetch_trajectory(0)
+        self._take_handoff(self.sampling.ctx.fetch_trajectory(0), horizon)
+        # its nominal_trajectory did not run, so its context has not seen this plan's state (the derivatives read its mocap)
+        g = self.ilqg
+        g.ctx.set_state(g.state, g.time, g.mocap, g.userdata)
+
+    def _take_handoff(self, got, horizon):
         tr = self.ilqg.candidate0.trajectory
         for name in ("states", "actions", "times", "residual", "costs", "trace"):
             getattr(tr, name)[:horizon] = getattr(got, name)[:horizon]
         tr.horizon, tr.total_return, tr.failure = horizon, got.total_return, got.failure
-        # its nominal_trajectory did not run, so its context has not seen this plan's state (the derivatives read its mocap)
-        g = self.ilqg
-        g.ctx.set_state(g.state, g.time, g.mocap, g.userdata)
 
     # ---- OptimizePolicy, planner.cc:87-214
     def optimize_policy(self, horizon, pool=None):
@@ -2544,3 +2559,196 @@ class GpuILQSPlanner:
 
     def num_parameters(self):
         return self.sampling.num_parameters() + self.ilqg.num_parameters()
+
+
+class _ILQSMember(GpuILQSPlanner):
+    """GpuILQSPlanner over two members of fleet planners instead of two planners of its own: convert_policy, action_from_policy and the
+    per-member state are its; the plan step is GpuBatchILQSPlanner's"""
+
+    def __init__(self, sampling, ilqg):
+        self.sampling, self.ilqg = sampling, ilqg
+
+
+class GpuBatchILQSPlanner:
+    """iLQS for `num_envs` environments (robots): a GpuBatchSamplingPlanner and a GpuBatchILQGPlanner, one context each, both on the
+    differentiable model unless agent_differentiable = 0. Member e plans exactly like GpuILQSPlanner(seed = seed + e); the member
+    logic (convert_policy, the comparisons of ilqs/planner.cc:87-214, ActionFromPolicy) IS that planner's. In one plan step the fleet
+    is mixed -- some members' active policy is sampling, others' iLQG -- and the step is, whatever E:
+      1. the nominal rollouts of the members whose active policy is iLQG (P): one `rollout_feedback_batched` on the iLQG context, the
+         others riding on the first P member's request and ignored; then each P member's spline fit, on the host;
+      2. sampling for all: one `rollout_noise_batched` + `best_batched` on the sampling context;
+      3. per member the comparison; C = the members that go on to iLQG;
+      4. the hand-off: a C member outside P takes candidate 0 of its share of the sampling rollout into candidate0.trajectory (the
+         host needs it for the line search and the policy bookkeeping); `set_states` on the iLQG context;
+      5. ONE `ilqg_step_batched_from`: hand-off members name the sampling context's candidate 0, P members their own best nominal
+         rollout, members outside C -1. The nominals never pass through the host. (`device_chain = False`, a fleet
+         GpuBatchILQGPlanner._use_device_chain turns away, or a P member whose nominal rollouts all failed: the sequential chain.);
+      6. ONE line-search `rollout_feedback_batched`; members outside C and members whose backward pass failed ride along with zero steps.
+    At most four syncs and the hand-off fetches. `backend_factory(task, half)`, half in ("sampling", "ilqg"), gives test backends.
+    timers: nominal, fit, sampling, handoff, derivatives_backward, rollouts (us). last_step: (from_source, candidate, status) of the
+    plan step's ilqg_step_batched_from, None when there was none."""
+    SAMPLING, ILQG = GpuILQSPlanner.SAMPLING, GpuILQSPlanner.ILQG
+
+    def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
+        if int(num_envs) < 1:
+            raise ValueError("GpuBatchILQSPlanner needs at least one environment")
+        self.num_envs, self.device, self.precision, self.seed = int(num_envs), device, precision, seed
+        half = lambda name: (lambda task: backend_factory(task, name)) if backend_factory is not None else None
+        self.sampling = GpuBatchSamplingPlanner(num_envs, device, precision, seed, backend_factory=half("sampling"))
+        self.ilqg = GpuBatchILQGPlanner(num_envs, device, precision, backend_factory=half("ilqg"))
+        self.envs = [_ILQSMember(s, g) for s, g in zip(self.sampling.envs, self.ilqg.envs)]
+        self.model = self.task = None
+        self.device_chain = None    # None: ilqg_step_batched_from whenever the iLQG context has it; False: the sequential middle
+        self.used_device_chain = False
+        self.last_step = None
+        self.timers = {}
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        self.sampling.initialize(model, task)
+        self.ilqg.initialize(model, task)
+        for m in self.envs:
+            m.model, m.task = model, task
+
+    def set_tasks(self, tasks):
+        """one Task per environment, for both halves (_FleetTasks.set_tasks)"""
+        self.sampling.set_tasks(tasks)
+        self.ilqg.set_tasks(tasks)
+        for e, m in enumerate(self.envs):
+            m.task = self.task if tasks is None else self.sampling.envs[e].task
+
+    def allocate(self):
+        # the iLQG half reads agent_differentiable (default 1) itself; the sampling half is told the same
+        self.sampling.differentiable = bool(int(self.model.get_number("agent_differentiable", 1)))
+        self.sampling.allocate()
+        self.ilqg.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.sampling.reset(horizon, initial_repeated_action)
+        self.ilqg.reset(horizon, initial_repeated_action)
+        for m in self.envs:
+            m._reset_own()
+        self.last_step = None
+        self.timers = {}
+
+    def set_states(self, states):
+        """one State per environment (Planner::SetState for each)"""
+        self.sampling.set_states(states)
+        self.ilqg.set_states(states)
+
+    def _use_device_chain(self):
+        g = self.ilqg
+        if self.device_chain is not None and not self.device_chain:
+            return False
+        if not hasattr(g.ctx, "ilqg_step_batched_from"):
+            if self.device_chain:
+                raise ValueError("GpuBatchILQSPlanner: device_chain on a context without ilqg_step_batched_from")
+            return False
+        return g._use_device_chain()
+
+    # ---- OptimizePolicy, ilqs/planner.cc:87-214, for every environment
+    def optimize_policy(self, horizon, pool=None):
+        s, g, E = self.sampling, self.ilqg, self.num_envs
+        s._check_n(s.num_trajectory_)
+        g._prepare()
+        self.timers = dict.fromkeys(("nominal", "fit", "sampling", "handoff", "derivatives_backward", "rollouts"), 0.0)
+        self.last_step = None
+        for m in self.envs:
+            m.previous_active_policy = m.active_policy
+            m.ilqg_ran = False
+            m.fit_status, m.fit_unreached = SPLINE_FIT_NONE, 0
+            m.timers = {}
+        P = [e for e, m in enumerate(self.envs) if m.previous_active_policy == self.ILQG]
+        in_P = set(P)
+        # ---- 1. iLQG's nominal for the members it was active for, and their policy conversion
+        if P:
+            t0 = _time.perf_counter()
+            first = g.envs[P[0]]
+            requests = {e: g.envs[e]._nominal_request(horizon) for e in P}
+            shares = g._rollout(horizon, 1, first.policy.representation, first.settings.nominal_feedback_scaling,
+                                [requests.get(e, requests[P[0]]) for e in range(E)])
+            for e in P:
+                g.envs[e]._nominal_select(horizon, *shares[e])
+            self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
+            t0 = _time.perf_counter()
+            for e in P:
+                self.envs[e].convert_policy(horizon)
+            self.timers["fit"] = (_time.perf_counter() - t0) * 1e6
+        # ---- 2. sampling, every member
+        t0 = _time.perf_counter()
+        s.optimize_policy(horizon)
+        self.timers["sampling"] = (_time.perf_counter() - t0) * 1e6
+        # ---- 3. who goes on to iLQG
+        C = []
+        for e, m in enumerate(self.envs):
+            sp, gp = s.envs[e], g.envs[e]
+            reference = sp.nominal_return if e not in in_P else gp.candidate0.trajectory.total_return
+            if sp.winner > 0 and sp.best_return < reference:
+                m.active_policy = self.SAMPLING
+            else:
+                C.append(e)
+        if not C:
+            return
+        # ---- 4. ilqg.candidate_policy[0].trajectory = sampling.trajectory[0], the host's copy; the iLQG context sees this plan's states
+        t0 = _time.perf_counter()
+        n = s.num_trajectory_
+        for e in C:
+            if e not in in_P:
+                self.envs[e]._take_handoff(s.ctx.fetch_trajectory(e * n), horizon)
+        g._push_states()
+        self.timers["handoff"] = (_time.perf_counter() - t0) * 1e6
+        # ---- 5. derivatives and the backward pass: one call for the fleet, each nominal gathered from the context that holds it
+        t0 = _time.perf_counter()
+        requests = [None] * E
+        self.used_device_chain = self._use_device_chain()
+        candidate, from_source = [-1] * E, [0] * E
+        for e in C:
+            if e not in in_P:
+                candidate[e], from_source[e] = 0, 1
+            else:
+                candidate[e] = g.envs[e].nominal_index      # -1: every nominal rollout failed, the nominal is the host's policy trajectory
+        if self.used_device_chain and max(candidate) >= 0:
+            out = g.ctx.ilqg_step_batched_from(s.ctx, from_source, candidate, *g._step_args(horizon))
+            requests = g._scatter_step(out, horizon)
+            self.last_step = (list(from_source), list(candidate), [int(x) for x in out["status"]])
+        else:
+            candidate = [-1] * E
+        for e in C:
+            if candidate[e] < 0:
+                requests[e] = g._sequential_middle(g.envs[e], horizon)
+        self.timers["derivatives_backward"] = (_time.perf_counter() - t0) * 1e6
+        # ---- 6. the line search of the members that got that far: one launch; the others ride along with zero steps and are ignored
+        self.sat_out = [r is None for r in requests]
+        if not all(self.sat_out):
+            t0 = _time.perf_counter()
+            lead = next(r for r in requests if r is not None)
+            zero = lead[:5] + (np.zeros(len(lead[5])),)
+            shares = g._rollout(horizon, 0, 0, 1, [zero if r is None else r for r in requests])
+            for e in range(E):
+                if not self.sat_out[e]:
+                    g.envs[e]._iteration_after_rollouts(horizon, *shares[e])
+            self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
+        for e in C:
+            m, sp, gp = self.envs[e], s.envs[e], g.envs[e]
+            m.ilqg_ran = True
+            reference = sp.best_return if e not in in_P else gp.linesearch0_return
+            if gp.iteration_completed and gp.winner_return < reference:
+                m.active_policy = self.ILQG
+
+    def action_from_policy(self, env, action, state, time, use_previous=False):
+        return self.envs[env].action_from_policy(action, state, time, use_previous)
+
+    def best_trajectory(self, env):
+        if self.envs[env].active_policy == self.SAMPLING:
+            return self.sampling.best_trajectory(env)
+        return self.ilqg.best_trajectory(env)
+
+    def num_parameters(self):
+        return self.sampling.num_parameters() + self.ilqg.num_parameters()
+
+    active_policy = property(lambda self: [m.active_policy for m in self.envs])
+    previous_active_policy = property(lambda self: [m.previous_active_policy for m in self.envs])
+    ilqg_ran = property(lambda self: [m.ilqg_ran for m in self.envs])
+    fit_status = property(lambda self: [m.fit_status for m in self.envs])
+    fit_unreached = property(lambda self: [m.fit_unreached for m in self.envs])
+    last_fit = property(lambda self: [m.last_fit for m in self.envs])
