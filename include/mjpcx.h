@@ -368,6 +368,35 @@ int mjpcx_set_residual_states(mjpcx_ctx* ctx, int num_envs, const int32_t* resid
 int mjpcx_set_task_params_batched(mjpcx_ctx* ctx, int num_envs, const double* weight, const double* norm_parameter,
                                   const double* parameters, const double* risk);
 
+/* A model per environment: robots of one fleet that differ PHYSICALLY (a payload, ice under the feet, weaker motors). models[e] serves
+ * environment e of mjpcx_rollout_splines_batched, mjpcx_rollout_noise_batched, mjpcx_rollout_noise_batched_ce,
+ * mjpcx_rollout_splines_noisy_batched, mjpcx_rollout_sample_gradient_batched and of the rollout inside mjpcx_robust_step_batched:
+ * environment e of such a call behaves exactly like the plain call on a context CREATED on models[e]: equal bits.
+ *   - Everything is deep-copied. Call it after mjpcx_create, between launches; it waits for the work already enqueued on the context's
+ *     stream. It is a setup call: the context's builders run once per model on the host (milliseconds each) -- not for a plan loop.
+ *   - models == NULL or num_envs == 0: the context's one model for every environment again (on any context: one that can hold no
+ *     models has none, and the call does nothing). The models persist until replaced.
+ *   - A batched call with another E than num_envs fails with MJPCX_EINVAL (unlike the task rows, nothing is dropped silently).
+ *   - The plain entry points and mjpcx_kinematics keep using the context's own model.
+ *   - Every model must equal the context's in all sizes, options, integer arrays and real arrays, EXCEPT
+ *       inertial   body_mass, body_inertia, body_ipos
+ *       passive    dof_armature, dof_damping, dof_frictionloss, jnt_stiffness
+ *       actuation  actuator_gear, actuator_gainprm, actuator_biasprm
+ *       contact    geom_friction, geom_solref, geom_solimp
+ *       derived    body_subtreemass, body_invweight0, dof_invweight0, tendon_invweight0, meaninertia (the caller supplies them consistent)
+ *     and there a value may change, but not whether it is zero, nor its sign: constraint rows, friction sets and every decision a
+ *     kernel's builder takes stay equal across the fleet. A violation is MJPCX_EINVAL; the message names the environment and the field.
+ *   - A model one of the context's builders refuses is MJPCX_EUNSUPPORTED, with the builder's text and the environment.
+ *   - All or nothing: on any failure the context keeps what it had.
+ *   - MJPCX_EUNSUPPORTED on a context of the lane-per-candidate family (its model constants are fixed when the library is built) and on
+ *     one sharded with mjpcx_comm_init.
+ *   - The quad, limb and registered-model kernels serve the fleet in the one launch they always make: each workgroup stages its
+ *     environment's model image. The generic wavefront-per-candidate kernel (no registered configuration, RK4) reads its model through
+ *     its kernel arguments and is launched once per environment instead, back to back on the context's stream.
+ *   - While models are set, mjpcx_rollout_feedback_batched, mjpcx_gradient_step_batched, mjpcx_ilqg_step_batched and
+ *     mjpcx_ilqg_step_batched_from fail with MJPCX_EUNSUPPORTED: the derivative chain on a model per environment is not implemented. */
+int mjpcx_set_models_batched(mjpcx_ctx* ctx, int num_envs, const mjpcx_model* const* models);
+
 /* mjpcx_rollout_splines for E environments: node_times E x P, node_values E x n_per_env x P x nu. */
 int mjpcx_rollout_splines_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,
                                   const double* node_times, const double* node_values);

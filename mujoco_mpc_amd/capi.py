@@ -33,6 +33,7 @@ EXPORTS = [
     "mjpcx_rollout_feedback_batched", "mjpcx_ilqg_step_batched", "mjpcx_ilqg_step_batched_from",
     "mjpcx_rollout_splines_noisy_batched", "mjpcx_robust_step_batched",
     "mjpcx_rollout_sample_gradient_batched", "mjpcx_sample_gradient_update_batched",
+    "mjpcx_set_models_batched",
 ]
 
 SG_COMPUTE_WEIGHTS, SG_ZERO_GRADIENT = 1, 2   # MJPCX_SG_* flags of mjpcx_sample_gradient_update_batched
@@ -77,6 +78,7 @@ def lib():
         L.mjpcx_set_states.argtypes = [vp, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_set_residual_states.argtypes = [vp, C.c_int, c_i32p, c_f64p]
         L.mjpcx_set_task_params_batched.argtypes = [vp, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]
+        L.mjpcx_set_models_batched.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(MjpcxModel))]
         L.mjpcx_rollout_splines_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p]
         L.mjpcx_rollout_splines_noisy_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.c_double, C.c_double, C.c_uint64, C.c_int]
         L.mjpcx_robust_step_batched.argtypes = ([vp, vp] + [C.c_int] * 5 + [c_f64p, C.c_double, C.c_double, C.c_uint64, C.c_int] +
@@ -285,6 +287,17 @@ class Context:
             if a is not None and a.shape[1] != n:
                 raise ValueError(f"set_task_params_batched: {name} has {a.shape[1]} columns, the task has {n}")
         self._chk(lib().mjpcx_set_task_params_batched(self.handle, E, *[None if a is None else as_f64p(a) for a in arrs]))
+
+    def set_models_batched(self, packed_models):
+        """A model per environment (mjpcx_set_models_batched): one PackedModel per environment of the batched rollouts, each the context's
+        model but for its inertial, passive, actuation and contact parameters (mjcf.variant). None, or an empty list: the context's one model
+        for every environment again. A setup call (the builders run once per model on the host); the models persist until replaced."""
+        models = list(packed_models) if packed_models is not None else []
+        if not models:
+            self._chk(lib().mjpcx_set_models_batched(self.handle, 0, None))
+            return
+        ptrs = (C.POINTER(MjpcxModel) * len(models))(*[C.pointer(pm.struct) for pm in models])
+        self._chk(lib().mjpcx_set_models_batched(self.handle, len(models), ptrs))
 
     def rollout_splines_batched(self, horizon, interp, node_times, node_values, num_envs=None, n_per_env=None):
         """node_times E x P, node_values E x n_per_env x P x nu."""

@@ -115,14 +115,23 @@ struct LdsModelT {
   const T *wrap_prm, *tendon_range, *tendon_margin, *tendon_solref_lim, *tendon_solimp_lim, *tendon_invweight0;
   const unsigned* tendon_dofmask;
 
-  __device__ __forceinline__ explicit LdsModelT(const WaveModelT<T>& m)
+  // `off`: the bytes from the model allocation m points into to the allocation of the workgroup's environment (a model per environment,
+  // mjpcx_set_models_batched: E allocations of one layout, back to back; 0: the one model). Every cold pointer moves by it, and the one
+  // by-value scalar that follows from the inertial fields, meaninertia, is read from the allocation (WaveModelT::env_scalars), not from
+  // the kernel arguments, where it could only be environment 0's.
+  __device__ __forceinline__ explicit LdsModelT(const WaveModelT<T>& m, size_t off = 0)
       : cone(m.cone), disableflags(m.disableflags), solver_iterations(m.solver_iterations), any_damping(m.any_damping), nlevel(m.nlevel),
-        npair(m.npair), full(m.full), timestep(m.timestep), solver_tolerance(m.solver_tolerance), meaninertia(m.meaninertia), impratio(m.impratio),
-        geom_friction(m.geom_friction), geom_solref(m.geom_solref), geom_solimp(m.geom_solimp), geom_gap(m.geom_gap), geom_solmix(m.geom_solmix),
-        key_mpos(m.key_mpos), pair_g1(m.pair_g1), pair_g2(m.pair_g2), tendon_adr(m.tendon_adr), tendon_num(m.tendon_num), tendon_limited(m.tendon_limited),
-        wrap_objid(m.wrap_objid), wrap_prm(m.wrap_prm), tendon_range(m.tendon_range), tendon_margin(m.tendon_margin), tendon_solref_lim(m.tendon_solref_lim),
-        tendon_solimp_lim(m.tendon_solimp_lim), tendon_invweight0(m.tendon_invweight0), tendon_dofmask(m.tendon_dofmask) {
+        npair(m.npair), full(m.full), timestep(m.timestep), solver_tolerance(m.solver_tolerance), meaninertia(at(m.env_scalars, off)[0]), impratio(m.impratio),
+        geom_friction(at(m.geom_friction, off)), geom_solref(at(m.geom_solref, off)), geom_solimp(at(m.geom_solimp, off)), geom_gap(at(m.geom_gap, off)),
+        geom_solmix(at(m.geom_solmix, off)), key_mpos(at(m.key_mpos, off)), pair_g1(at(m.pair_g1, off)), pair_g2(at(m.pair_g2, off)),
+        tendon_adr(at(m.tendon_adr, off)), tendon_num(at(m.tendon_num, off)), tendon_limited(at(m.tendon_limited, off)), wrap_objid(at(m.wrap_objid, off)),
+        wrap_prm(at(m.wrap_prm, off)), tendon_range(at(m.tendon_range, off)), tendon_margin(at(m.tendon_margin, off)),
+        tendon_solref_lim(at(m.tendon_solref_lim, off)), tendon_solimp_lim(at(m.tendon_solimp_lim, off)), tendon_invweight0(at(m.tendon_invweight0, off)),
+        tendon_dofmask(at(m.tendon_dofmask, off)) {
     for (int k = 0; k < 3; k++) gravity[k] = m.gravity[k];
+  }
+  template <typename P> __device__ __forceinline__ static const P* at(const P* p, size_t off) {
+    return reinterpret_cast<const P*>(reinterpret_cast<const char*>(p) + off);
   }
 };
 

@@ -170,12 +170,15 @@ constexpr size_t wave_reals(int LS) { return wave_con(LS) + wave_ml(LS) + wave_m
 
 // Workgroup = W wavefronts sharing one model image. stats[0]: candidates handed to the fallback kernel, stats[1 + b]: by reason bit b.
 template <typename R, int LS>
-__global__ __launch_bounds__(256) void rollout_limb_kernel(const LimbModelT<R>* __restrict__ gm, const R* __restrict__ blob0, const LBlob bo, const LArgs<R> a0,
-                                                           const R* __restrict__ key_mpos, int* __restrict__ stats) {
+__global__ __launch_bounds__(256) void rollout_limb_kernel(const LimbModelT<R>* __restrict__ gm0, const R* __restrict__ blob0, const LBlob bo, const LArgs<R> a0,
+                                                           const R* __restrict__ key_mpos, int* __restrict__ stats, unsigned model_stride) {
   // the workgroup's environment (env_select.h; 0 of one unless a0.env_n is set), from its first candidate: that environment's blob, node
   // times, nominal spline and noise stream. The cost terms staged below are then the environment's.
   const int env = env_of(a0, (int)((blockIdx.x * blockDim.x) >> 6) * (a0.cpw > 0 && a0.cpw <= LS / 4 ? a0.cpw : LS / 4));
   const R* __restrict__ blob = env_ptr(blob0, env, a0.env_stride);
+  // and that environment's model image (mjpcx_set_models_batched: model_stride bytes between consecutive environments' images, 0: the one
+  // model). A kernel argument of its own, not a member of LArgs: the request the step functions take by reference stays the struct it was
+  const LimbModelT<R>* __restrict__ gm = env_ptr(gm0, env, model_stride);
   LArgs<R> a = a0;
   env_rebase(a, env);
   a.param_variance = env_ptr(a.param_variance, env, a0.env_stride);  // (CE: the environment's own variance row)

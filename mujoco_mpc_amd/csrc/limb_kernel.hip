@@ -25,7 +25,7 @@ static int pick_cpw(int N, int cpw) {
 }
 int limb_waves(int N, int cpw) { const int c = pick_cpw(N, cpw); return (N + c - 1) / c; }
 template <typename R, int LS>
-static hipError_t launch_ls(const void* image, const R* blob, const LBlob& bo, const LArgs<R>& q, const R* key_mpos, int* stats, hipStream_t stream) {
+static hipError_t launch_ls(const void* image, const R* blob, const LBlob& bo, const LArgs<R>& q, const R* key_mpos, int* stats, unsigned model_stride, hipStream_t stream) {
   const int waves = (q.N + q.cpw - 1) / q.cpw;
   constexpr size_t img = ((sizeof(LimbModelT<R>) + 15) & ~(size_t)15) + ((3 * kMaxTerm * sizeof(R) + 15) & ~(size_t)15), per_wave = wave_reals(LS) * sizeof(R);
   int W = (int)((160 * 1024 - img) / per_wave);
@@ -37,26 +37,26 @@ static hipError_t launch_ls(const void* image, const R* blob, const LBlob& bo, c
   auto kern = rollout_limb_kernel<R, LS>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((waves + W - 1) / W), dim3(64 * W), lds, stream, static_cast<const LimbModelT<R>*>(image), blob, bo, q, key_mpos, stats);
+  hipLaunchKernelGGL(kern, dim3((waves + W - 1) / W), dim3(64 * W), lds, stream, static_cast<const LimbModelT<R>*>(image), blob, bo, q, key_mpos, stats, model_stride);
   return hipGetLastError();
 }
 template <typename R>
-static hipError_t launch(const void* image, const R* blob, const LBlob& bo, const LArgs<R>& a, const R* key_mpos, int* stats, hipStream_t stream) {
+static hipError_t launch(const void* image, const R* blob, const LBlob& bo, const LArgs<R>& a, const R* key_mpos, int* stats, unsigned model_stride, hipStream_t stream) {
   LArgs<R> q = a;
   q.cpw = pick_cpw(a.N, a.cpw);
   // up to eight candidates per wavefront: the half-width layout (half the LDS per wavefront: four wavefronts per CU)
-  if (q.cpw <= 4) return launch_ls<R, 16>(image, blob, bo, q, key_mpos, stats, stream);
-  if (q.cpw <= 8) return launch_ls<R, 32>(image, blob, bo, q, key_mpos, stats, stream);
-  return launch_ls<R, 64>(image, blob, bo, q, key_mpos, stats, stream);
+  if (q.cpw <= 4) return launch_ls<R, 16>(image, blob, bo, q, key_mpos, stats, model_stride, stream);
+  if (q.cpw <= 8) return launch_ls<R, 32>(image, blob, bo, q, key_mpos, stats, model_stride, stream);
+  return launch_ls<R, 64>(image, blob, bo, q, key_mpos, stats, model_stride, stream);
 }
-hipError_t launch_rollout_limb(const void* image, const float* blob, const LBlob& bo, const LArgs<float>& a, const float* key_mpos, int* stats, hipStream_t stream) {
-  return launch<float>(image, blob, bo, a, key_mpos, stats, stream);
+hipError_t launch_rollout_limb(const void* image, const float* blob, const LBlob& bo, const LArgs<float>& a, const float* key_mpos, int* stats, unsigned model_stride, hipStream_t stream) {
+  return launch<float>(image, blob, bo, a, key_mpos, stats, model_stride, stream);
 }
-hipError_t launch_rollout_limb(const void* image, const double* blob, const LBlob& bo, const LArgs<double>& a, const double* key_mpos, int* stats, hipStream_t stream) {
+hipError_t launch_rollout_limb(const void* image, const double* blob, const LBlob& bo, const LArgs<double>& a, const double* key_mpos, int* stats, unsigned model_stride, hipStream_t stream) {
 #ifdef LIMB_F32_ONLY   // (tuning builds: the fp32 kernel alone compiles in half the time)
   return hipErrorNotSupported;
 #else
-  return launch<double>(image, blob, bo, a, key_mpos, stats, stream);
+  return launch<double>(image, blob, bo, a, key_mpos, stats, model_stride, stream);
 #endif
 }
 } }

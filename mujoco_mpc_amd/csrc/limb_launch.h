@@ -16,6 +16,6 @@ std::string build_images(const mjpcx_model* m, const mjpcx_task* t, std::vector<
 // wavefronts of a launch of N candidates (cpw: LArgs::cpw, 0 = chosen from the batch size)
 int limb_waves(int N, int cpw);
 // stats: nullptr, or 8 ints (zeroed by the caller): [0] candidates handed on, [1 + b] by reason (limb_step.h kFlag* bit b)
-hipError_t launch_rollout_limb(const void* image, const float* blob, const LBlob& bo, const LArgs<float>& a, const float* key_mpos, int* stats, hipStream_t stream);
-hipError_t launch_rollout_limb(const void* image, const double* blob, const LBlob& bo, const LArgs<double>& a, const double* key_mpos, int* stats, hipStream_t stream);
+hipError_t launch_rollout_limb(const void* image, const float* blob, const LBlob& bo, const LArgs<float>& a, const float* key_mpos, int* stats, unsigned model_stride, hipStream_t stream);
+hipError_t launch_rollout_limb(const void* image, const double* blob, const LBlob& bo, const LArgs<double>& a, const double* key_mpos, int* stats, unsigned model_stride, hipStream_t stream);
 } }

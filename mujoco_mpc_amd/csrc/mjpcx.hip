@@ -852,6 +852,22 @@ struct mjpcx_ctx {
   // Only the batched entry points read them; mjpcx_set_task_params neither reads nor clears them.
   std::vector<double> env_weight, env_normp, env_normq, env_param, env_risk;  // E x nterm (three), E x nparam, E
   int env_n = 0;  // candidates per environment of the last rollout (0: not a batched one)
+  // and, when given, a model per environment (mjpcx_set_models_batched): E records of every image the context holds for its own model, back
+  // to back on the device. Only the batched rollouts read them. own_model / own_task: deep copies of what mjpcx_create was given (the
+  // builders run on them again, once per environment's model; every model is compared with own_model field by field).
+  struct OwnedModel {
+    mjpcx_model m{};
+    mjpcx_task t{};
+    int given_integrator = 0;  // (before mjpcx_create's implicitfast -> Euler rewrite)
+    std::vector<std::vector<unsigned char>> store;
+  } own;
+  struct EnvModels {
+    int E = 0;
+    DevBuf cold, image, qmodel, qtab, limb;  // WaveModel allocations | LdsLayout images | QuadModel | QuadTables | LimbModelT, E of each
+    unsigned cold_stride = 0, image_stride = 0, qmodel_stride = 0, qtab_stride = 0, limb_stride = 0;
+    std::vector<double> meaninertia;  // E (the generic kernel's by-value copy, per launch)
+    void release() { cold.release(); image.release(); qmodel.release(); qtab.release(); limb.release(); E = 0; }
+  } em;
   bool have_rollout = false;
   // wavefront-per-candidate family
   bool wave = false;
@@ -919,6 +935,90 @@ int fail(mjpcx_ctx* c, int code, const std::string& msg) {
   } while (0)
 
 size_t esize(const mjpcx_ctx* c) { return c->precision == 64 ? 8 : 4; }
+
+// Every array of mjpcx_model with its length: X(I | D, name, count, may_differ). may_differ: a field the models of a fleet may differ in
+// (mjpcx_set_models_batched, include/mjpcx.h) -- the inertial, passive, actuation and contact parameters and what mj_setConst derives from them.
+#define MJPCX_MODEL_ARRAYS(X)                                                                                                              \
+  X(I, body_parentid, m->nbody, 0) X(I, body_rootid, m->nbody, 0) X(I, body_jntnum, m->nbody, 0) X(I, body_jntadr, m->nbody, 0)           \
+  X(I, body_dofnum, m->nbody, 0) X(I, body_dofadr, m->nbody, 0) X(I, body_mocapid, m->nbody, 0) X(D, body_pos, 3 * m->nbody, 0)           \
+  X(D, body_quat, 4 * m->nbody, 0) X(D, body_ipos, 3 * m->nbody, 1) X(D, body_iquat, 4 * m->nbody, 0) X(D, body_mass, m->nbody, 1)        \
+  X(D, body_inertia, 3 * m->nbody, 1) X(I, jnt_type, m->njnt, 0) X(I, jnt_qposadr, m->njnt, 0) X(I, jnt_dofadr, m->njnt, 0)               \
+  X(I, jnt_bodyid, m->njnt, 0) X(I, jnt_limited, m->njnt, 0) X(D, jnt_pos, 3 * m->njnt, 0) X(D, jnt_axis, 3 * m->njnt, 0)                 \
+  X(D, jnt_stiffness, m->njnt, 1) X(D, jnt_range, 2 * m->njnt, 0) X(D, jnt_margin, m->njnt, 0) X(D, jnt_solref, 2 * m->njnt, 0)           \
+  X(D, jnt_solimp, 5 * m->njnt, 0) X(I, dof_bodyid, m->nv, 0) X(I, dof_jntid, m->nv, 0) X(I, dof_parentid, m->nv, 0)                      \
+  X(D, dof_armature, m->nv, 1) X(D, dof_damping, m->nv, 1) X(D, dof_frictionloss, m->nv, 1) X(D, dof_invweight0, m->nv, 1)                \
+  X(D, qpos0, m->nq, 0) X(D, qpos_spring, m->nq, 0) X(I, site_bodyid, m->nsite, 0) X(D, site_pos, 3 * m->nsite, 0)                        \
+  X(D, site_quat, 4 * m->nsite, 0) X(I, actuator_trnid, m->nu, 0) X(I, actuator_gaintype, m->nu, 0) X(I, actuator_biastype, m->nu, 0)     \
+  X(I, actuator_ctrllimited, m->nu, 0) X(I, actuator_forcelimited, m->nu, 0) X(D, actuator_gear, m->nu, 1)                                \
+  X(D, actuator_gainprm, 3 * m->nu, 1) X(D, actuator_biasprm, 3 * m->nu, 1) X(D, actuator_ctrlrange, 2 * m->nu, 0)                        \
+  X(D, actuator_forcerange, 2 * m->nu, 0) X(I, geom_type, m->ngeom, 0) X(I, geom_bodyid, m->ngeom, 0) X(I, geom_contype, m->ngeom, 0)     \
+  X(I, geom_conaffinity, m->ngeom, 0) X(I, geom_condim, m->ngeom, 0) X(I, geom_priority, m->ngeom, 0) X(I, geom_group, m->ngeom, 0)       \
+  X(D, geom_size, 3 * m->ngeom, 0) X(D, geom_pos, 3 * m->ngeom, 0) X(D, geom_quat, 4 * m->ngeom, 0) X(D, geom_friction, 3 * m->ngeom, 1)  \
+  X(D, geom_solref, 2 * m->ngeom, 1) X(D, geom_solimp, 5 * m->ngeom, 1) X(D, geom_margin, m->ngeom, 0) X(D, geom_gap, m->ngeom, 0)        \
+  X(D, geom_solmix, m->ngeom, 0) X(D, body_invweight0, 2 * m->nbody, 1) X(D, body_subtreemass, m->nbody, 1) X(D, dof_solref, 2 * m->nv, 0) \
+  X(D, dof_solimp, 5 * m->nv, 0) X(D, key_qpos, (size_t)m->nkey * m->nq, 0) X(I, tendon_adr, m->ntendon, 0) X(I, tendon_num, m->ntendon, 0) \
+  X(I, tendon_limited, m->ntendon, 0) X(I, wrap_objid, m->nwrap, 0) X(D, wrap_prm, m->nwrap, 0) X(D, tendon_range, 2 * m->ntendon, 0)     \
+  X(D, tendon_margin, m->ntendon, 0) X(D, tendon_solref_lim, 2 * m->ntendon, 0) X(D, tendon_solimp_lim, 5 * m->ntendon, 0)                \
+  X(D, tendon_invweight0, m->ntendon, 1) X(I, exclude_signature, m->nexclude, 0) X(I, body_weldid, m->nbody, 0)                           \
+  X(D, key_mpos, (size_t)m->nkey * m->nmocap * 3, 0)
+#define MJPCX_TASK_ARRAYS(X)                                                                                                          \
+  X(I, dim_norm_residual, t->num_term) X(I, norm, t->num_term) X(I, num_norm_parameter, t->num_term) X(D, weight, t->num_term)        \
+  X(D, parameters, t->num_parameter) X(I, trace_site, t->num_trace) X(I, residual_int, t->num_residual_int)                           \
+  X(D, residual_real, t->num_residual_real)
+
+// deep copies of a caller's model and task headers (a NULL array stays NULL)
+template <typename E>
+const E* own_array(mjpcx_ctx::OwnedModel& o, const E* p, size_t n) {
+  if (!p) return nullptr;
+  o.store.emplace_back(n * sizeof(E) + 8);
+  if (n) std::memcpy(o.store.back().data(), p, n * sizeof(E));
+  return reinterpret_cast<const E*>(o.store.back().data());
+}
+void own_copy(mjpcx_ctx::OwnedModel& o, const mjpcx_model* m, const mjpcx_task* t, int given_integrator) {
+  o.store.clear();
+  o.m = *m; o.t = *t; o.given_integrator = given_integrator;
+#define X(kind, name, count, differ) o.m.name = own_array(o, m->name, (size_t)(count));
+  MJPCX_MODEL_ARRAYS(X)
+#undef X
+#define X(kind, name, count) o.t.name = own_array(o, t->name, (size_t)(count));
+  MJPCX_TASK_ARRAYS(X)
+#undef X
+  size_t nnorm = 0;
+  for (int k = 0; k < t->num_term; k++) nnorm += t->num_norm_parameter[k];
+  o.t.norm_parameter = own_array(o, t->norm_parameter, nnorm);
+}
+
+// "" if model `m` may serve an environment of a context created on `ref` (include/mjpcx.h, mjpcx_set_models_batched): every size, option,
+// integer array and real array equal, except the fields a fleet's models may differ in -- and those with the zeros and the signs where ref has them
+std::string compare_env_model(const mjpcx_model* ref, const mjpcx_model* m, int given_integrator) {
+#define S(name) if (ref->name != m->name) return std::string(#name) + " differs from the context's model";
+  S(nq) S(nv) S(nu) S(na) S(nbody) S(njnt) S(nsite) S(nmocap) S(nuserdata) S(timestep) S(gravity[0]) S(gravity[1]) S(gravity[2])
+  S(disableflags) S(solver_iterations) S(solver_tolerance) S(ngeom) S(nkey) S(cone) S(impratio) S(ntendon) S(nwrap) S(nexclude)
+#undef S
+  if (m->integrator != given_integrator) return "integrator differs from the context's model";
+  if (!(m->meaninertia > 0) != !(ref->meaninertia > 0)) return "meaninertia changes sign or zero pattern";
+  auto same = [](const void* a, const void* b, size_t bytes) { return (!a && !b) || (a && b && std::memcmp(a, b, bytes) == 0); };
+  auto pattern = [](const double* a, const double* b, size_t n) {
+    if (!a || !b) return !a && !b;
+    for (size_t i = 0; i < n; i++) {
+      if (!(b[i] == b[i])) return false;
+      if ((a[i] == 0) != (b[i] == 0) || (a[i] > 0) != (b[i] > 0)) return false;
+    }
+    return true;
+  };
+  static const char* const shared = " differs from the context's model (only the inertial, passive, actuation and contact parameters may)";
+  // (the sizes are equal by now: the counts, written in terms of m, hold for both)
+#define CMP_FIELD_I(name, n, differ) if (!same(ref->name, m->name, sizeof(int32_t) * (n))) return std::string(#name) + shared;
+#define CMP_FIELD_D(name, n, differ)                                                                                                \
+  if (differ) { if (!pattern(ref->name, m->name, (n))) return std::string(#name) + " changes which entries are zero, or their sign"; } \
+  else if (!same(ref->name, m->name, sizeof(double) * (n))) return std::string(#name) + shared;
+#define X(kind, name, count, differ) CMP_FIELD_##kind(name, (size_t)(count), differ)
+  MJPCX_MODEL_ARRAYS(X)
+#undef X
+#undef CMP_FIELD_I
+#undef CMP_FIELD_D
+  return "";
+}
 
 template <typename T>
 void fill_model(LaneModel<T>& d, const mjpcx_model* m) {
@@ -1199,8 +1299,20 @@ hipError_t launch_tree(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
   return launch_tree_pass<C, T, true>(c, wm, wt2, a2, image, blob_bytes, N, P);
 }
 
+// The model records a rollout launch reads: the context's own (strides of 0), or -- a batched rollout while mjpcx_set_models_batched's models
+// are set -- environment 0's of the E records, with the bytes between consecutive environments'. do_rollout decides and hands it down.
+struct ModelRecords {
+  bool per_env;
+  const void *qmodel, *qtab, *limb, *image;
+  unsigned qmodel_stride, qtab_stride, limb_stride;
+};
+ModelRecords model_records(const mjpcx_ctx* c, bool per_env, bool f32) {
+  if (per_env) return {true, c->em.qmodel.p, c->em.qtab.p, c->em.limb.p, c->em.image.p, c->em.qmodel_stride, c->em.qtab_stride, c->em.limb_stride};
+  return {false, c->d_qmodel.p, c->d_qtab.p, c->d_limb.p, f32 ? c->wh.dev_image32 : c->wh.dev_image, 0u, 0u, 0u};
+}
+
 // quad kernel (quad_kernel.h), then the wavefront-per-candidate kernel for the candidates it handed on
-hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, const RolloutArgs<double>& a, int N, int P) {
+hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, const RolloutArgs<double>& a, int N, int P, const ModelRecords& mr) {
   quad::QArgs q{};
   q.N = a.N; q.H = a.H; q.P = a.P; q.interp = a.interp; q.node_times = a.node_times; q.nodes = a.nodes; q.nominal = a.nominal;
   q.noise_mode = a.noise.mode; q.seed = a.noise.seed; q.iteration = a.noise.iteration; q.candidate_offset = a.noise.candidate_offset;
@@ -1209,6 +1321,7 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
   q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
   q.total_return = a.total_return; q.failure = a.failure; q.con_cap = c->quad_con_cap; q.cpw = c->quad_cpw;
   q.env_n = a.env_n; q.env_stride = a.env_stride;
+  q.model_stride = mr.qmodel_stride; q.tables_stride = mr.qtab_stride;  // (a model per environment; 0: the one model)
   const quad::QBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
   hipError_t e;
   if (quad::quad_uses_ovf_slab()) {  // (a build with QEXP_OVF_SLAB: contacts beyond a lane's LDS slots in global memory, 150 KB per wavefront)
@@ -1230,8 +1343,8 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
     if ((e = c->d_qclass.reserve(wb)) != hipSuccess || (e = hipMemsetAsync(c->d_qclass.p, 0, wb, c->stream)) != hipSuccess) return e;
     q.wave_class = (long long*)c->d_qclass.p;
   }
-  if ((e = quad::launch_rollout_quad(c->d_qmodel.p, c->d_qtab.p, wt.blob, bo, q, (int*)c->d_qstats.p,
-                                     c->stream)) != hipSuccess) return e;
+  if ((e = quad::launch_rollout_quad(mr.qmodel, mr.qtab, wt.blob, bo, q,
+                                     (int*)c->d_qstats.p, c->stream)) != hipSuccess) return e;
   if (classes) {
     std::vector<long long> w((size_t)nwave * 64), tot(64, 0);
     (void)hipStreamSynchronize(c->stream);
@@ -1291,7 +1404,7 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
   }
   RolloutArgs<double> a2 = a;
   a2.noise.mode = -1;  // the quad kernel left every candidate's spline nodes in a.nodes
-  e = launch_tree<TreeCfgA1, double>(c, wm, wt, a2, c->wh.dev_image, c->wh.blob_bytes, N, P, /*only_flagged=*/true);
+  e = launch_tree<TreeCfgA1, double>(c, wm, wt, a2, mr.image, c->wh.blob_bytes, N, P, /*only_flagged=*/true);
   if (e == hipSuccess && c->quad_stats) {
     int h[8] = {0};
     (void)hipStreamSynchronize(c->stream);
@@ -1304,7 +1417,7 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
 
 // limb kernel (limb_kernel.h), then the wavefront-per-candidate kernel for the candidates it handed on
 template <typename T>
-hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>& wt, const RolloutArgs<T>& a, int N, int P) {
+hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>& wt, const RolloutArgs<T>& a, int N, int P, const ModelRecords& mr) {
   limb::LArgs<T> q{};
   q.N = a.N; q.H = a.H; q.P = a.P; q.interp = a.interp; q.node_times = a.node_times; q.nodes = a.nodes; q.nominal = a.nominal;
   q.noise_mode = a.noise.mode; q.seed = a.noise.seed; q.iteration = a.noise.iteration; q.candidate_offset = a.noise.candidate_offset;
@@ -1323,7 +1436,7 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
     if ((e = c->d_qwave.reserve((size_t)N * 4)) != hipSuccess) return e;
     q.iters = (int*)c->d_qwave.p;
   }
-  if ((e = limb::launch_rollout_limb(c->d_limb.p, wt.blob, bo, q, wm.key_mpos, (int*)c->d_qstats.p, c->stream)) != hipSuccess) return e;
+  if ((e = limb::launch_rollout_limb(mr.limb, wt.blob, bo, q, wm.key_mpos, (int*)c->d_qstats.p, mr.limb_stride, c->stream)) != hipSuccess) return e;
   if (stamps) {
     long long h[64];
     std::vector<int> it((size_t)N);
@@ -1355,7 +1468,8 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
   }
   RolloutArgs<T> a2 = a;
   a2.noise.mode = -1;  // the limb kernel left every candidate's spline nodes in a.nodes
-  e = launch_tree<TreeCfgHumanoid, T>(c, wm, wt, a2, sizeof(T) == 8 ? c->wh.dev_image : c->wh.dev_image32, sizeof(T) == 8 ? c->wh.blob_bytes : c->wh.blob_bytes32, N, P, /*only_flagged=*/true);
+  e = launch_tree<TreeCfgHumanoid, T>(c, wm, wt, a2, mr.image,
+                                      sizeof(T) == 8 ? c->wh.blob_bytes : c->wh.blob_bytes32, N, P, /*only_flagged=*/true);
   if (e == hipSuccess && c->quad_stats) {
     int h[8] = {0};
     (void)hipStreamSynchronize(c->stream);
@@ -1364,6 +1478,21 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
                  "indefinite matrix %d, non-finite %d, both limits %d, trunk on the floor %d)\n", h[0], N, h[1], h[2], h[3], h[4], h[5], h[6]);
   }
   return e;
+}
+
+// the context's WaveModel with every pointer moved from the context's own model allocation to environment 0's record of c->em.cold (the
+// records have the allocation's layout; the kernel adds its environment's offset, RolloutArgs::model_stride)
+template <typename T>
+WaveModelT<T> env_models_view(const mjpcx_ctx* c, const WaveModelT<T>& own, int env = 0) {
+  WaveModelT<T> wm = own;
+  const char* from = (const char*)own.base;
+  const char* to = (const char*)c->em.cold.p + (size_t)env * c->em.cold_stride;
+  wm.meaninertia = c->em.meaninertia[env];  // (read by the generic kernel alone, which is launched per environment)
+#define X(name) wm.name = reinterpret_cast<decltype(wm.name)>(to + ((const char*)own.name - from));
+  MJPCX_WAVE_MODEL_POINTERS(X)
+#undef X
+  wm.base = (const unsigned char*)to;
+  return wm;
 }
 
 template <typename T>
@@ -1380,6 +1509,10 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   const int np = P * c->nu;
   RolloutArgs<T> a{};
   a.N = N; a.H = H; a.P = P; a.interp = interp;
+  // a model per environment (mjpcx_set_models_batched; check_batched_args has compared the two E): the batched launches read the
+  // environments' records, with their strides; everything else the context's own model, with strides of 0
+  const ModelRecords mr = model_records(c, E > 0 && c->em.E > 0, sizeof(T) == 4);
+  if (mr.per_env) { a.model_stride = c->em.cold_stride; a.image_stride = c->em.image_stride; }
   a.nodes = (T*)c->d_nodes.p;
   a.noise.mode = -1;
   const double* d_var = nullptr;
@@ -1448,21 +1581,22 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
         wt.stamps = (long long*)c->d_stage.p;
         wt.stamp_step = c->stamp_step;
       }
-      const WaveModel& wm = c->wh.m;
+      const WaveModel wm = mr.per_env ? env_models_view(c, c->wh.m) : c->wh.m;
+      const void* image = mr.image;
       // A rank's share of the batch decides the kernel: the quad kernel packs 16 candidates into a wavefront, which fills the 1024 SIMDs
       // at N = 16384 but leaves most of them idle below a quarter of that, where one wavefront per candidate (a third of the latency per
       // step) is quicker -- measured cross-over on MI355X: N = 4096 (tools/quad_n_sweep.py; MJPCX_QUAD_MIN_N moves it)
       if (c->wh.registered == 0 && c->quad_ok && a.xfrc_scale == 0 && !wt.stamps && N >= c->quad_min_n) {
-        le = launch_quad(c, wm, wt, a, N, P);
+        le = launch_quad(c, wm, wt, a, N, P, mr);
       } else if (c->wh.registered == 0) {
         if (c->quad_ok) (void)hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream);  // (mjpcx_quad_stats reports the LAST rollout: nothing was handed on in this one)
-        le = launch_tree<TreeCfgA1, double>(c, wm, wt, a, c->wh.dev_image, c->wh.blob_bytes, N, P);
+        le = launch_tree<TreeCfgA1, double>(c, wm, wt, a, image, c->wh.blob_bytes, N, P);
         if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
       } else if (c->wh.registered == 1 && c->limb_ok && a.xfrc_scale == 0 && !wt.stamps && N >= c->limb_min_n) {
-        le = launch_limb<double>(c, wm, wt, a, N, P);
+        le = launch_limb<double>(c, wm, wt, a, N, P, mr);
       } else if (c->wh.registered == 1 && wm.integrator != MJPCX_INT_RK4) {
         if (c->limb_ok) (void)hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream);
-        le = launch_tree<TreeCfgHumanoid, double>(c, wm, wt, a, c->wh.dev_image, c->wh.blob_bytes, N, P);
+        le = launch_tree<TreeCfgHumanoid, double>(c, wm, wt, a, image, c->wh.blob_bytes, N, P);
         if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
       } else {
       const bool tree = c->wh.tree_ok && !c->no_tree;
@@ -1482,21 +1616,33 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
                 : wm.nv <= 28 ? w64::rollout_wave_kernel<28> : w64::rollout_wave_kernel<32>;
       auto kern = !two_pass ? kern_big
                 : w64::rollout_wave_kernel<32, true, false, true>;
+      // one launch over the N candidates -- or, with a model per environment, one per environment on its model (this kernel reads the model
+      // through the pointers of its arguments: RolloutArgs::cand_base)
+      auto launch_generic = [&](decltype(kern_big) k, size_t lds_bytes, const RolloutArgs<double>& args) -> hipError_t {
+        if (!mr.per_env) {
+          hipLaunchKernelGGL(k, dim3(N), dim3(64), lds_bytes, c->stream, wm, wt, args);
+          return hipGetLastError();
+        }
+        const int n = N / E;
+        for (int e = 0; e < E; e++) {
+          const WaveModel wme = env_models_view(c, c->wh.m, e);
+          RolloutArgs<double> ae = args;
+          ae.cand_base = e * n;
+          hipLaunchKernelGGL(k, dim3(n), dim3(64), lds_bytes, c->stream, wme, wt, ae);
+          const hipError_t he = hipGetLastError();
+          if (he != hipSuccess) return he;
+        }
+        return hipSuccess;
+      };
       le = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (le == hipSuccess) {
-        hipLaunchKernelGGL(kern, dim3(N), dim3(64), lds, c->stream, wm, wt, a);
-        le = hipGetLastError();
-      }
+      if (le == hipSuccess) le = launch_generic(kern, lds, a);
       if (two_pass && le == hipSuccess) {
         if (c->timing && c->cur_main) { if ((le = hipEventRecord(c->cur_main, c->stream)) == hipSuccess) c->cur_main = nullptr; }
         RolloutArgs<double> a2 = a;
         a2.noise.mode = -1;  // the first pass left every candidate's spline nodes in a.nodes
         a2.only_overflowed = 1;
         if (le == hipSuccess) le = hipFuncSetAttribute((const void*)kern_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big);
-        if (le == hipSuccess) {
-          hipLaunchKernelGGL(kern_big, dim3(N), dim3(64), lds_big, c->stream, wm, wt, a2);
-          le = hipGetLastError();
-        }
+        if (le == hipSuccess) le = launch_generic(kern_big, lds_big, a2);
       }
       if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, lds, tree);
       }
@@ -1514,15 +1660,16 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
       wt.stamps = (long long*)c->d_stage.p;
       wt.stamp_step = c->stamp_step;
     }
-    const WaveModelT<float>& wm = c->wh.m32;
+    const WaveModelT<float> wm = mr.per_env ? env_models_view(c, c->wh.m32) : c->wh.m32;
+    const void* image = mr.image;
     if (c->wh.registered == 0) {
-      le = launch_tree<TreeCfgA1, float>(c, wm, wt, a, c->wh.dev_image32, c->wh.blob_bytes32, N, P);
+      le = launch_tree<TreeCfgA1, float>(c, wm, wt, a, image, c->wh.blob_bytes32, N, P);
       if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
     } else if (c->wh.registered == 1 && c->limb_ok && a.xfrc_scale == 0 && !wt.stamps && N >= c->limb_min_n) {
-      le = launch_limb<float>(c, wm, wt, a, N, P);
+      le = launch_limb<float>(c, wm, wt, a, N, P, mr);
     } else if (c->wh.registered == 1 && wm.integrator != MJPCX_INT_RK4) {
       if (c->limb_ok) (void)hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream);
-      le = launch_tree<TreeCfgHumanoid, float>(c, wm, wt, a, c->wh.dev_image32, c->wh.blob_bytes32, N, P);
+      le = launch_tree<TreeCfgHumanoid, float>(c, wm, wt, a, image, c->wh.blob_bytes32, N, P);
       if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
     } else {
     // (the Jacobian-free constraint path in fp32 for the models it covers, as in fp64: in two passes under Euler, in one with the long
@@ -1537,13 +1684,24 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
     if (lds_big > 160 * 1024) return fail(c, MJPCX_EUNSUPPORTED, "model state does not fit the 160 KB LDS of a CU");
     const int kern_big = rk4 ? (tree ? kW32TreeRk4 : kW32Rk4) : tree ? kW32Tree
                        : wm.nv <= 18 ? kW32Rows18 : wm.nv <= 20 ? kW32Rows20 : wm.nv <= 28 ? kW32Rows28 : kW32Rows32;
-    le = launch_wave_kernel_f32(two_pass ? kW32TreeSmall : kern_big, N, lds, wm, wt, a, c->stream);  // (the fp32 kernels live in wave32.hip)
+    auto launch_generic = [&](int which, size_t lds_bytes, const RolloutArgs<float>& args) -> hipError_t {  // (as in fp64: per environment with a model each)
+      if (!mr.per_env) return launch_wave_kernel_f32(which, N, lds_bytes, wm, wt, args, c->stream);
+      const int n = N / E;
+      for (int e = 0; e < E; e++) {
+        RolloutArgs<float> ae = args;
+        ae.cand_base = e * n;
+        const hipError_t he = launch_wave_kernel_f32(which, n, lds_bytes, env_models_view(c, c->wh.m32, e), wt, ae, c->stream);
+        if (he != hipSuccess) return he;
+      }
+      return hipSuccess;
+    };
+    le = launch_generic(two_pass ? kW32TreeSmall : kern_big, lds, a);  // (the fp32 kernels live in wave32.hip)
     if (two_pass && le == hipSuccess) {
       if (c->timing && c->cur_main) { if ((le = hipEventRecord(c->cur_main, c->stream)) == hipSuccess) c->cur_main = nullptr; }
       RolloutArgs<float> a2 = a;
       a2.noise.mode = -1;
       a2.only_overflowed = 1;
-      if (le == hipSuccess) le = launch_wave_kernel_f32(kern_big, N, lds_big, wm, wt, a2, c->stream);
+      if (le == hipSuccess) le = launch_generic(kern_big, lds_big, a2);
     }
     if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, lds, tree);
     }
@@ -1607,6 +1765,7 @@ int mjpcx_create(const mjpcx_model* m, const mjpcx_task* t, int device, int prec
   if (precision != 64 && precision != 32) return bad(MJPCX_EINVAL, "precision must be 64 or 32");
   // ---- features the device kernels cover today
   if (m->na != 0) return bad(MJPCX_EUNSUPPORTED, "actuator activations (na > 0) unsupported");
+  const int given_integrator = m->integrator;
   mjpcx_model m_euler;
   if (m->integrator == MJPCX_INT_IMPLICITFAST) {
     // mj_implicit with qDeriv = d qfrc_smooth / d qvel restricted to passive damping + actuator velocity terms: without the latter the
@@ -1667,6 +1826,7 @@ int mjpcx_create(const mjpcx_model* m, const mjpcx_task* t, int device, int prec
     c->ctrlrange.assign(m->actuator_ctrlrange, m->actuator_ctrlrange + 2 * m->nu);
     const std::string err = c->wh.build(m, t, precision == 32);
     if (!err.empty()) { mjpcx_destroy(c); return bad(MJPCX_EUNSUPPORTED, err); }
+    own_copy(c->own, m, t, given_integrator);  // (mjpcx_set_models_batched builds and compares against them)
     if (c->wh.tree_ok && !c->no_tree && !c->no_lds_model && lds_model_matches<TreeCfgA1>(m, t, c->wh)) {
       // registered model: the LDS image of its hot arrays (lds_model.h), in the context's precision
       std::vector<unsigned char> img = precision == 64 ? lds_model_image<TreeCfgA1, double>(m, t, c->wh) : lds_model_image<TreeCfgA1, float>(m, t, c->wh);
@@ -1858,6 +2018,7 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
   if (c->source_done) (void)hipEventDestroy(c->source_done);
   c->sg.release();
+  c->em.release();
   (void)mjpcx_comm_destroy(c);
   c->wh.release();
   DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
@@ -2009,6 +2170,99 @@ int mjpcx_set_task_params_batched(mjpcx_ctx* c, int E, const double* weight, con
 }
 
 namespace {
+hipError_t upload_records(DevBuf& d, const std::vector<unsigned char>& h) {
+  hipError_t e = d.reserve(h.size());
+  return e != hipSuccess ? e : hipMemcpy(d.p, h.data(), h.size(), hipMemcpyHostToDevice);
+}
+}  // namespace
+
+int mjpcx_set_models_batched(mjpcx_ctx* c, int E, const mjpcx_model* const* models) {
+  if (!c) return MJPCX_EINVAL;
+  const std::string who = "mjpcx_set_models_batched: ";
+  if (E < 0) return fail(c, MJPCX_EINVAL, who + "the number of environments must be >= 0");
+  if (!models || E == 0) {  // the context's one model for every environment again (a context that can hold none has none: nothing to do)
+    if (c->em.E == 0) return MJPCX_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, MJPCX_EDEVICE, "hipSetDevice failed");
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (a launch in flight may be reading the records)
+    c->em.release();
+    return MJPCX_OK;
+  }
+  if (!c->wave)
+    return fail(c, MJPCX_EUNSUPPORTED, who + "this context runs a lane-per-candidate kernel, whose model constants are fixed when the library is built "
+                                             "(generated/static_models.h): a model per environment needs a context of the contact family");
+  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, who + "not implemented on a context sharded with mjpcx_comm_init (the batched rollouts are not either)");
+  if (hipSetDevice(c->device) != hipSuccess) return fail(c, MJPCX_EDEVICE, "hipSetDevice failed");
+  const mjpcx_model* ref = &c->own.m;
+  const mjpcx_task* t = &c->own.t;
+  for (int e = 0; e < E; e++) {
+    if (!models[e]) return fail(c, MJPCX_EINVAL, who + "environment " + std::to_string(e) + ": null model");
+    const std::string why = compare_env_model(ref, models[e], c->own.given_integrator);
+    if (!why.empty()) return fail(c, MJPCX_EINVAL, who + "environment " + std::to_string(e) + ": " + why);
+  }
+  // the context's builders once per model, into host records of the layouts the context holds; nothing of the context changes before all succeeded
+  const bool want32 = c->precision == 32;
+  const size_t cold_bytes = (size_t)(want32 ? c->wh.m32.bytes : c->wh.m.bytes);
+  std::vector<unsigned char> h_cold, h_image, h_qmodel, h_qtab, h_limb, one, two;
+  size_t image_bytes = 0, qmodel_bytes = 0, qtab_bytes = 0, limb_bytes = 0;
+  std::vector<double> meaninertia;
+  for (int e = 0; e < E; e++) {
+    const std::string env = who + "environment " + std::to_string(e) + ": ";
+    mjpcx_model m = *models[e];
+    if (m.integrator == MJPCX_INT_IMPLICITFAST) m.integrator = MJPCX_INT_EULER;  // (as mjpcx_create: the velocity-dependent terms are the context's model's, compared above)
+    WaveHost wh;
+    std::string why = wh.build(&m, t, want32, &one);
+    if (!why.empty()) return fail(c, MJPCX_EUNSUPPORTED, env + why);
+    const WaveModel& w0 = c->wh.m;
+    if (one.size() != cold_bytes || wh.m.nbody != w0.nbody || wh.m.nsite != w0.nsite || wh.m.npair != w0.npair || wh.m.full != w0.full ||
+        wh.m.nlevel != w0.nlevel || wh.m.any_damping != w0.any_damping || wh.tree_ok != c->wh.tree_ok)
+      return fail(c, MJPCX_EUNSUPPORTED, env + "the model bakes to another layout than the context's (pair list, constraint classes or sizes)");
+    h_cold.insert(h_cold.end(), one.begin(), one.end());
+    meaninertia.push_back(m.meaninertia);
+    if (c->wh.registered < 0) continue;  // (the generic kernel: the model allocation is all it reads)
+    if (!(c->wh.registered == 0 ? lds_model_matches<TreeCfgA1>(&m, t, wh) : lds_model_matches<TreeCfgHumanoid>(&m, t, wh)))
+      return fail(c, MJPCX_EUNSUPPORTED, env + "the model does not match the registered configuration the context's does (tree_registry.h)");
+    if (c->wh.registered == 0) one = want32 ? lds_model_image<TreeCfgA1, float>(&m, t, wh) : lds_model_image<TreeCfgA1, double>(&m, t, wh);
+    else one = want32 ? lds_model_image<TreeCfgHumanoid, float>(&m, t, wh) : lds_model_image<TreeCfgHumanoid, double>(&m, t, wh);
+    image_bytes = one.size();
+    h_image.insert(h_image.end(), one.begin(), one.end());
+    if (c->d_qmodel.p) {  // (the context built the quad kernel's images)
+      why = quad::build_images(&m, t, one, two);
+      if (!why.empty()) return fail(c, MJPCX_EUNSUPPORTED, env + "the quad kernel's builder: " + why);
+      qmodel_bytes = one.size(); qtab_bytes = two.size();
+      h_qmodel.insert(h_qmodel.end(), one.begin(), one.end());
+      h_qtab.insert(h_qtab.end(), two.begin(), two.end());
+    }
+    if (c->d_limb.p) {
+      why = limb::build_images(&m, t, one, two);
+      if (!why.empty()) return fail(c, MJPCX_EUNSUPPORTED, env + "the limb kernel's builder: " + why);
+      const std::vector<unsigned char>& img = want32 ? one : two;
+      limb_bytes = img.size();
+      h_limb.insert(h_limb.end(), img.begin(), img.end());
+    }
+  }
+  // upload into fresh buffers (synchronous copies: the records are on the device when this call returns), then wait for the work already
+  // enqueued on the context's stream, which may read the records being replaced, and swap
+  mjpcx_ctx::EnvModels em;
+  hipError_t he = upload_records(em.cold, h_cold);
+  if (he == hipSuccess && !h_image.empty()) he = upload_records(em.image, h_image);
+  if (he == hipSuccess && !h_qmodel.empty()) he = upload_records(em.qmodel, h_qmodel);
+  if (he == hipSuccess && !h_qtab.empty()) he = upload_records(em.qtab, h_qtab);
+  if (he == hipSuccess && !h_limb.empty()) he = upload_records(em.limb, h_limb);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+  if (he != hipSuccess) {
+    em.release();
+    return fail(c, he == hipErrorOutOfMemory ? MJPCX_ENOMEM : MJPCX_EDEVICE, who + "upload of the models: " + hipGetErrorString(he));
+  }
+  em.E = E;
+  em.meaninertia = meaninertia;
+  em.cold_stride = (unsigned)cold_bytes; em.image_stride = (unsigned)image_bytes;
+  em.qmodel_stride = (unsigned)qmodel_bytes; em.qtab_stride = (unsigned)qtab_bytes; em.limb_stride = (unsigned)limb_bytes;
+  c->em.release();
+  c->em = em;  // (DevBuf is a plain pair: the records now belong to the context)
+  return MJPCX_OK;
+}
+
+namespace {
 int check_batched_args(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times) {
   if (!c || !node_times) return fail(c, MJPCX_EINVAL, "null argument");
   if (E < 1) return fail(c, MJPCX_EINVAL, "batched rollout: the number of environments must be >= 1");
@@ -2019,6 +2273,10 @@ int check_batched_args(mjpcx_ctx* c, int E, int n, int H, int P, int interp, con
   if (c->env_E != E)
     return fail(c, MJPCX_EINVAL, c->env_E == 0 ? std::string("batched rollout before mjpcx_set_states")
                                                : "batched rollout of " + std::to_string(E) + " environments after mjpcx_set_states of " + std::to_string(c->env_E));
+  // (planning silently on the wrong physics is worse than an error: unlike the task rows, the models of another fleet size are not dropped)
+  if (c->em.E > 0 && c->em.E != E)
+    return fail(c, MJPCX_EINVAL, "batched rollout of " + std::to_string(E) + " environments on a context that holds " + std::to_string(c->em.E) +
+                                     " models (mjpcx_set_models_batched)");
   for (int e = 0; e < E; e++) {
     const int rc = check_rollout_args(c, E * n, H, P, interp, node_times + (size_t)e * (P > 0 ? P : 0));
     if (rc != MJPCX_OK) return rc;
@@ -2897,6 +3155,7 @@ int mjpcx_rollout_feedback_batched(mjpcx_ctx* c, int E, int n, int H, int mode, 
                                    const double* alpha) {
   const std::string who = "mjpcx_rollout_feedback_batched: ";
   if (!c || !times || !states || !actions || !gains || !improvement || !alpha) return fail(c, MJPCX_EINVAL, who + "null argument");
+  if (c->em.E > 0) return fail(c, MJPCX_EUNSUPPORTED, who + "the derivative chain on a model per environment (mjpcx_set_models_batched) is not implemented: clear the models, or plan these environments on contexts of their own");
   if (E < 1) return fail(c, MJPCX_EINVAL, who + "the number of environments must be >= 1");
   if (n < 1 || H < 1 || Tn < 1) return fail(c, MJPCX_EINVAL, who + "n_per_env, H and Tn must be >= 1");
   if ((long long)E * n > 0x7fffffffLL / 64 || (long long)E * Tn * (1 + 2 * c->nv * c->nu) > 0x7fffffffLL / 64)
@@ -3343,6 +3602,7 @@ int ilqg_step_batched_entry(const char* who_, mjpcx_ctx* c, mjpcx_ctx* src, cons
   if (!std::isfinite(min_reg) || !std::isfinite(max_reg) || !(min_reg <= max_reg))
     return fail(c, MJPCX_EINVAL, who + "min_reg and max_reg must be finite, min_reg <= max_reg");
   if (c->comm_world > 1 || (src && src->comm_world > 1)) return fail(c, MJPCX_EUNSUPPORTED, who + "not implemented on a context sharded with mjpcx_comm_init");
+  if (c->em.E > 0 || (src && src->em.E > 0)) return fail(c, MJPCX_EUNSUPPORTED, who + "the derivative chain on a model per environment (mjpcx_set_models_batched) is not implemented: clear the models, or plan these environments on contexts of their own");
   if ((c->wave && c->precision != 64) || (src && src->wave && src->precision != 64))
     return fail(c, MJPCX_EUNSUPPORTED, (from ? who : std::string()) + "the iLQG kernels of the wavefront-per-candidate family are fp64 only");
   if (2 * c->nv > kGradMaxN || c->nu > kGradMaxM || T > kGradMaxT)
@@ -3362,6 +3622,7 @@ int mjpcx_gradient_step_batched(mjpcx_ctx* c, int E, int cand, int T, int ne, co
                                 double* B, double* cx, double* cu) {
   const char* who = "mjpcx_gradient_step_batched: ";
   if (!c || !evaluate || !node_times || !k || !gradient || !dV) return fail(c, MJPCX_EINVAL, std::string(who) + "null argument");
+  if (c->em.E > 0) return fail(c, MJPCX_EUNSUPPORTED, std::string(who) + "the derivative chain on a model per environment (mjpcx_set_models_batched) is not implemented: clear the models, or plan these environments on contexts of their own");
   if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
   if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N || c->env_E != E)
     return fail(c, MJPCX_EINVAL, std::string(who) + "the last rollout was not a batched one of " + std::to_string(E) + " environments");

@@ -32,6 +32,8 @@ struct QArgs {
   int con_cap;        // a lane that collects more contacts than this hands its candidate on (0: kQMaxCon, the store's capacity; MJPCX_QUAD_CON_CAP lowers it, for tests of the hand-on)
   int env_n;          // several environments in one launch (env_select.h): candidates per environment, a multiple of 64 (0: one environment) ...
   unsigned env_stride;  // ... and the bytes between the plan records of consecutive environments (node_times, nominal and the blob are environment 0's)
+  unsigned model_stride, tables_stride;  // a model per environment (mjpcx_set_models_batched): the bytes between consecutive environments' QuadModel / QuadTables
+                                         // records (0: the one model for every environment; the kernel's model pointers are environment 0's)
 };
 
 // the feedback policy of the iLQG rollouts (FeedbackArgs of ilqg_kernels.h): nullptr members = the spline policy of QArgs

@@ -219,12 +219,15 @@ constexpr size_t kQWaveLds = (kQWaveCon + kQWaveMl + kQWaveMt) * sizeof(double);
 // Workgroup = W wavefronts (W = 4 for the large batches: one per SIMD of a CU, sharing one model image; W = 1 spreads small batches
 // over the CUs). stats[0]: candidates handed to the fallback kernel, stats[1 + log2(flag)]: by reason.
 template <bool FEEDBACK>
-__device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob0,
+__device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ gm0, const QuadTables* __restrict__ tab0, const double* __restrict__ blob0,
                                                  const QBlob& bo, const QArgs& a0, const QFeedback& fb, int* __restrict__ stats) {
   // the workgroup's environment (env_select.h; 0 of one unless a0.env_n is set), from its first candidate: that environment's blob, node
   // times, nominal spline and noise stream. What the workgroup shares below (static_pose from the mocap pose) is then the environment's.
   const int env = env_of(a0, (int)((blockIdx.x * blockDim.x) >> 6) * (a0.cpw > 0 ? a0.cpw : 16));
   const double* __restrict__ blob = env_ptr(blob0, env, a0.env_stride);
+  // and that environment's model and pair tables (mjpcx_set_models_batched; strides of 0: the one model): scalar adds, once, before the step loop
+  const QuadModel* __restrict__ gm = env_ptr(gm0, env, a0.model_stride);
+  const QuadTables* __restrict__ tab = env_ptr(tab0, env, a0.tables_stride);
   QArgs a = a0;
   env_rebase(a, env);
   a.param_variance = env_ptr(a.param_variance, env, a0.env_stride);  // (CE: the environment's own variance row)

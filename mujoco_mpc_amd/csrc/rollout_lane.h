@@ -138,6 +138,12 @@ struct RolloutArgs {
   int env_n;
   unsigned env_stride;
   const LaneInit<T>* init;  // lane family: the initial condition and the task parameters (in the record)
+  // a model per environment (mjpcx_set_models_batched; rollout_tree_kernel): the bytes between consecutive environments' model allocations
+  // (the pointers of the kernel's WaveModelT are environment 0's) and LDS images. 0: the one model for every environment.
+  unsigned model_stride, image_stride;
+  // rollout_wave_kernel, the generic kernel, reads its model through the pointers of its kernel arguments (no image to stage): with a model
+  // per environment it is launched once per environment, on that environment's model, over env_n workgroups -- workgroup b is candidate cand_base + b
+  int cand_base;
 };
 
 // NOISE = false: a pass that draws no noise (noise.mode < 0) and so has no use for the variance pointer

@@ -29,8 +29,13 @@ __global__ __launch_bounds__(TREE_KERNEL_THREADS) void rollout_tree_kernel(const
   const int env = (int)blockIdx.x / wg_per_env, env_block = (int)blockIdx.x - env * wg_per_env;
   const int env_count = a.env_n > 0 ? a.env_n : a.N, env_first = env * env_count;
   if (env >= num_env) return;  // (never with the host's grid; the whole workgroup leaves)
+  // a model per environment (mjpcx_set_models_batched): the workgroup stages ITS environment's image, and the cold arrays and
+  // meaninertia are read behind its environment's offset (LdsModelT). Strides of 0: the one model -- the same code.
+  // (the quotient above goes through the vector unit's reciprocal: said to be uniform once, the offsets are scalar arithmetic)
+  const int env_s = __builtin_amdgcn_readfirstlane(env);
+  const size_t model_off = (size_t)env_s * a.model_stride;
   {
-    const uint4* src = reinterpret_cast<const uint4*>(image);
+    const uint4* src = reinterpret_cast<const uint4*>(image + (size_t)env_s * a.image_stride);
     uint4* dst = reinterpret_cast<uint4*>(mjpcx_lds);
     for (unsigned i = tid; i < L::kBytes / 16; i += nth) dst[i] = src[i];
     const uint4* bs = reinterpret_cast<const uint4*>(env_ptr(tk_in.blob, env, a.env_stride));
@@ -38,13 +43,13 @@ __global__ __launch_bounds__(TREE_KERNEL_THREADS) void rollout_tree_kernel(const
     for (unsigned i = tid; i < blob_bytes / 16; i += nth) bd[i] = bs[i];
   }
   __syncthreads();
-  const LdsModelT<C, wreal> m(m_in);
+  const LdsModelT<C, wreal> m(m_in, model_off);
   const LdsTaskT<C, wreal> tk(tk_in, reinterpret_cast<const wreal*>(mjpcx_lds + L::kBytes));
   const int wave = tid >> 6, lane = tid & 63;
   unsigned char* arena = mjpcx_lds + L::kBytes + blob_bytes + (unsigned)wave * arena_bytes;
   if (mode & 2) {
     int bad = 0;
-#define CHK(name, n) for (int i = tid; i < (n); i += nth) bad += m.name[i] != m_in.name[i];
+#define CHK(name, n) for (int i = tid; i < (n); i += nth) bad += m.name[i] != m.at(m_in.name, model_off)[i];
     CHK(body_parentid, C::NB) CHK(body_rootid, C::NB) CHK(body_jntnum, C::NB) CHK(body_jntadr, C::NB) CHK(body_dofnum, C::NB) CHK(body_dofadr, C::NB)
     CHK(body_mocapid, C::NB) CHK(body_pos, 3 * C::NB) CHK(body_quat, 4 * C::NB) CHK(body_ipos, 3 * C::NB) CHK(body_iquat, 4 * C::NB) CHK(body_mass, C::NB)
     CHK(body_inertia, 3 * C::NB) CHK(body_invweight0, 2 * C::NB) CHK(body_subtreemass, C::NB)

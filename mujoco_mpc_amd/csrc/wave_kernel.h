@@ -305,16 +305,17 @@ __device__ __forceinline__ void wave_rollout_body(const MODEL& m, const TASK& tk
 template <int NMAX, bool TREE = false, bool RK4 = false, bool SMALL = false>
 __global__ __launch_bounds__(64) WAVE_KERNEL_ATTR void rollout_wave_kernel(const WModel m, const WTask tk, const RolloutArgs<wreal> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  if (a.only_overflowed && !((a.failure[blockIdx.x] >> 8) & 32)) return;  // (wave-uniform)
+  const int cand = (int)blockIdx.x + a.cand_base;  // (cand_base: 0 but for the per-environment launches of a fleet with a model per environment)
+  if (a.only_overflowed && !((a.failure[cand] >> 8) & 32)) return;  // (wave-uniform)
   // The model and task structs stay in the kernel-argument segment (scalar loads). Staging the model allocation into
   // LDS was tried: no shorter step, fewer candidates per CU, and a run-time-rebased copy of this struct
   // ends up in the private segment -- every pointer fetch becomes a scratch load. (Registered models: tree_kernel.h.)
   // the candidate's environment (0 of one unless a.env_n is set): its own blob, node times, nominal spline and noise stream
   // (rollout_lane.h, env_view). WTask and RolloutArgs hold scalars and pointers only: the rebased copies stay in SGPRs.
-  const int env = env_of(a, blockIdx.x);
+  const int env = env_of(a, cand);
   WTask tke = tk;
   tke.blob = env_ptr(tk.blob, env, a.env_stride);
-  wave_rollout_body<NMAX, TREE, SMALL ? kTreeMaxSimple : kTreeMaxSimpleBig, SMALL ? kTreeMaxCone : kTreeMaxConeBig, RK4>(m, tke, env_view(a, env), smem_raw, blockIdx.x, threadIdx.x);
+  wave_rollout_body<NMAX, TREE, SMALL ? kTreeMaxSimple : kTreeMaxSimpleBig, SMALL ? kTreeMaxCone : kTreeMaxConeBig, RK4>(m, tke, env_view(a, env), smem_raw, cand, threadIdx.x);
 }
 
 } }  // namespace mjpcx::WAVE_NS

@@ -65,6 +65,9 @@ struct WaveModelT {
   int nray_geom;
   const unsigned char* base;                    // the single device allocation all pointers above point into
   int bytes;                                    // its size (a multiple of 16): the kernel stages it into LDS
+  // [meaninertia]: the by-value scalars above that follow from the fields a fleet's models may differ in (mjpcx_set_models_batched), once more
+  // IN the allocation -- the rollout kernels that serve a model per environment read them there, behind the environment's offset
+  const double* env_scalars;
 };
 using WaveModel = WaveModelT<double>;  // the parity path, the iLQG kernels and the lane-per-candidate experiment
 
@@ -81,7 +84,7 @@ using WaveModel = WaveModelT<double>;  // the parity path, the iLQG kernels and 
   X(geom_friction) X(geom_solref) X(geom_solimp) X(geom_margin) X(geom_gap) X(geom_solmix) X(key_qpos) X(key_mpos)        \
   X(tendon_adr) X(tendon_num) X(tendon_limited) X(wrap_objid) X(wrap_prm) X(tendon_range) X(tendon_margin)                \
   X(tendon_solref_lim) X(tendon_solimp_lim) X(tendon_invweight0) X(tendon_dofmask) X(pair_g1) X(pair_g2)                  \
-  X(body_subtree_mask) X(body_dofmask) X(level_body) X(static_geom) X(dynamic_geom) X(ray_geom)
+  X(body_subtree_mask) X(body_dofmask) X(level_body) X(static_geom) X(dynamic_geom) X(ray_geom) X(env_scalars)
 
 // Per-plan task values: one small blob re-staged with every rollout (Planner::SetState + the frozen ResidualFn copy)
 template <typename T>
@@ -128,7 +131,9 @@ struct WaveHost {
   }
 
   // Returns "" or an error message. Requires the device to be current.
-  std::string build(const mjpcx_model* src, const mjpcx_task* task, bool want32 = false) {
+  // image_out (mjpcx_set_models_batched: one more model of the layout a context already holds): the host image of the model allocation in
+  // the wanted precision goes there and nothing is allocated or uploaded -- m and t then carry the sizes and the baked scalars, and no pointers.
+  std::string build(const mjpcx_model* src, const mjpcx_task* task, bool want32 = false, std::vector<unsigned char>* image_out = nullptr) {
     if (src->nbody > kWaveMaxBody || src->nv > kWaveMaxDof || src->ngeom > 4 * kWaveMaxGeom) return "model exceeds the wave kernel capacity";
     if (src->nbody > 64) return "more than 64 bodies";
     static_assert(sizeof(WaveModelT<float>) == sizeof(WaveModel) && sizeof(WaveTaskT<float>) == sizeof(WaveTask), "twin layouts");
@@ -317,6 +322,8 @@ struct WaveHost {
         rg.push_back(g);
     m.nray_geom = (int)rg.size();
     reg(&m.ray_geom, rg.data(), sizeof(int) * rg.size());
+    const double env_scalars[2] = {src->meaninertia, 0.0};
+    reg(&m.env_scalars, env_scalars, sizeof env_scalars);
     // static task arrays
     t.residual_id = task->residual_id; t.nr = task->num_residual; t.nterm = task->num_term; t.ntrace = task->num_trace;
     t.nparam = task->num_parameter; t.nri = task->num_residual_int; t.nrr = task->num_residual_real;
@@ -335,6 +342,13 @@ struct WaveHost {
     const auto o_toff = put2(term_off.data(), sizeof(int32_t) * term_off.size());
     const auto o_rterm = put2(res_term.data(), sizeof(int32_t) * res_term.size());
     host.resize((host.size() + 15) & ~(size_t)15);
+    if (image_out) {
+      host32.resize((host32.size() + 15) & ~(size_t)15);
+      m.bytes = (int)(want32 ? host32.size() : host.size());
+      m.nbody = nb_live; m.nsite = ns_live; m.nbody_model = nb;
+      image_out->swap(want32 ? host32 : host);
+      return "";
+    }
     if (hipMalloc(&dev, host.size()) != hipSuccess) return "hipMalloc of the model failed";
     if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) return "model upload failed";
     for (const Fix& f : fixes) *(const void**)((char*)&m + f.field_off) = (const char*)dev + f.data_off;

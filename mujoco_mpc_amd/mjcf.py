@@ -839,6 +839,35 @@ def load_xml(path: str, include_root: str = None) -> FlatModel:
     return _Compiler(root, path).compile()
 
 
+# the arrays the models of one fleet may differ in (include/mjpcx.h, mjpcx_set_models_batched); what mj_setConst derives from them
+# (body_subtreemass, body_invweight0, dof_invweight0, tendon_invweight0, meaninertia) follows, it is not given
+VARIANT_FIELDS = ("body_mass", "body_inertia", "body_ipos",
+                  "dof_armature", "dof_damping", "dof_frictionloss", "jnt_stiffness",
+                  "actuator_gear", "actuator_gainprm", "actuator_biasprm",
+                  "geom_friction", "geom_solref", "geom_solimp")
+
+
+def variant(fm: FlatModel, **arrays) -> FlatModel:
+    """A copy of a compiled model with the named arrays replaced and the derived quantities recomputed (_set_const): the same robot with
+    other physical parameters -- a payload, another floor, weaker motors. Same source, names, keyframes and custom numerics; only the
+    names of VARIANT_FIELDS are taken, in the shape the model holds them."""
+    import copy
+    for k in arrays:
+        if k not in VARIANT_FIELDS:
+            raise ValueError(f"variant: {k!r} is not a field the models of a fleet may differ in ({', '.join(VARIANT_FIELDS)})")
+    new = {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else copy.deepcopy(v)) for k, v in fm.arrays.items()}
+    for k, v in arrays.items():
+        old = np.asarray(fm.arrays[k])
+        v = np.asarray(v, dtype=float)
+        if v.size != old.size:
+            raise ValueError(f"variant: {k} has {v.size} entries, the model's has {old.size}")
+        new[k] = v.reshape(old.shape).copy()
+    out = FlatModel(arrays=new, scalars=dict(fm.scalars), names=fm.names, numeric=fm.numeric, text=fm.text, sensors=fm.sensors,
+                    keyframes=fm.keyframes, nuser_sensor=fm.nuser_sensor, source=fm.source)
+    _set_const(out)
+    return out
+
+
 # ----------------------------------------------------------------------------- binary blob for the C++ host
 _SENSOR_TYPE = {"user": 100, "framepos": 25}   # mjtSensor values the host code inspects; others -> 0
 _OBJ_TYPE = {"body": 1, "site": 6}             # mjtObj

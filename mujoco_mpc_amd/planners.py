@@ -17,6 +17,7 @@ import time as _time
 import numpy as np
 
 from . import capi
+from .cstructs import PackedModel
 from .spline import CUBIC, LINEAR, ZERO, TimeSpline
 from .task import Task
 
@@ -387,6 +388,55 @@ class _FleetTasks:
         for p, t in zip(self.envs, tasks):
             p.task = t
 
+    # ---- a model per environment: robots that differ physically (mjcf.variant: a payload, another floor, weaker motors)
+    _models = None
+    _models_on = (None, None)    # the context and the models of the last successful push: a push of the same pair again is skipped
+    _MODELS_FOLLOW_UP = ("a model per environment is not implemented for the planners with a derivative chain (Gradient, iLQG, iLQS): "
+                         "their batched derivative calls use the context's one model -- plan such robots on planners of their own")
+
+    def set_models(self, models):
+        """One compiled model per environment -- the fleet's robot with other inertial, passive, actuation or contact parameters
+        (`mjcf.variant`). Each is packed as `Task.packed_model` packs the fleet's (planning timestep and integrator, the differentiable
+        flag) and handed to the context (`set_models_batched`, a setup call: not for a plan loop). Member e then plans exactly like the
+        single planner of its kind created on models[e]. After `allocate`; the models are pushed again when `allocate` re-creates the
+        context. None: the fleet's one model for every environment again. Composes with `set_tasks`."""
+        previous = self._models
+        if models is None:
+            self._models = None
+        else:
+            models = list(models)
+            if len(models) != self.num_envs:
+                raise ValueError(f"{len(models)} models for {self.num_envs} environments")
+            if self.task is None or self.ctx is None:
+                raise ValueError("set_models before allocate")
+            for e, m in enumerate(models):
+                if m.source != self.task.model.source:
+                    raise ValueError(f"set_models: the model of environment {e} was compiled from {m.source!r}, the fleet's from "
+                                     f"{self.task.model.source!r}")
+            self._models = models
+        try:
+            self._push_models()
+        except Exception:
+            self._models = previous      # the context refused (all or nothing there): the planner keeps what it had as well
+            raise
+
+    def _push_models(self):
+        """hand the environments' models to the context (from set_models, and from allocate when it made a new context: the builders run
+        once per model, so a context that already holds these models is left alone)"""
+        if self.ctx is None or (self._models_on[0] is self.ctx and self._models_on[1] is self._models):
+            return
+        if self._models is None:
+            if self._models_on[0] is self.ctx:     # (a new context has none to clear)
+                self.ctx.set_models_batched(None)
+            self._models_on = (self.ctx, None)
+            return
+        ref = self.task.model
+        ts = ref.get_number("agent_timestep", ref.timestep)
+        integ = int(ref.get_number("agent_integrator", ref.integrator))
+        self.ctx.set_models_batched([PackedModel(m, timestep=ts, integrator=integ, differentiable=bool(getattr(self, "differentiable", False)))
+                                     for m in self._models])
+        self._models_on = (self.ctx, self._models)
+
     def _push_task_rows(self):
         """after ctx.set_states: the environments' own task parameters and frozen residual state, or nothing without set_tasks"""
         ts = self._tasks
@@ -449,6 +499,7 @@ class GpuBatchSamplingPlanner(_FleetTasks):
             self.ctx = capi.Context(self.task.packed_model(differentiable=self.differentiable), self.task.packed(), self.device, self.precision)
         for p in self.envs:
             p.allocate()
+        self._push_models()
 
     def reset(self, horizon, initial_repeated_action=None):
         for p in self.envs:
@@ -705,6 +756,17 @@ class GpuBatchRobustPlanner(_FleetTasks):
             self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
         for p in self.envs:
             p.ctx = self.ctx
+        self._push_models()
+
+    def set_models(self, models):
+        """both contexts: the delegate fleet's candidates and the rollouts under force noise run on the environment's model"""
+        previous = self._models
+        super().set_models(models)           # (refused: nothing changed anywhere)
+        try:
+            self.delegate.set_models(models)
+        except Exception:
+            super().set_models(previous)     # the delegate's context kept what it had: this one goes back to the same
+            raise
 
     def reset(self, horizon, initial_repeated_action=None):
         self.delegate.reset(horizon, initial_repeated_action)
@@ -897,6 +959,7 @@ class GpuBatchSampleGradientPlanner(_FleetTasks):
             p.previous_policy.allocate(m, self.task, K_MAX_TRAJECTORY_HORIZON)
             p.gradient = np.zeros(p.policy.num_spline_points * m.nu)
         self._zero_gradient, self._candidates_for = True, None
+        self._push_models()
 
     # ---- Reset, planner.cc:115-163: the gradient is zeroed, the shaping weights are kept
     def reset(self, horizon, initial_repeated_action=None):
@@ -1288,6 +1351,7 @@ class GpuBatchCrossEntropyPlanner(_FleetTasks):
             self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
         for p in self.envs:
             p.allocate()
+        self._push_models()
 
     def reset(self, horizon, initial_repeated_action=None):
         for p in self.envs:
@@ -1839,6 +1903,10 @@ class GpuBatchILQGPlanner(_FleetTasks):
     derivative_skip_ = _fleet_setting("derivative_skip_")
     settings = _fleet_setting("settings")
 
+    def set_models(self, models):
+        """not for a planner with a derivative chain: the batched derivative calls use the context's one model"""
+        raise NotImplementedError(_FleetTasks._MODELS_FOLLOW_UP)
+
     def allocate(self):
         if self._backend_factory is not None:
             self.ctx = self._backend_factory(self.task)
@@ -2284,6 +2352,10 @@ class GpuBatchGradientPlanner(_FleetTasks):
             raise ValueError(f"GpuBatchGradientPlanner: {n} candidates per environment; a batched launch needs a positive multiple "
                              "of 64 (every wavefront serves one environment) -- set gradient_num_trajectory / num_trajectory accordingly")
 
+    def set_models(self, models):
+        """not for a planner with a derivative chain: the batched derivative calls use the context's one model"""
+        raise NotImplementedError(_FleetTasks._MODELS_FOLLOW_UP)
+
     def allocate(self):
         if self._backend_factory is not None:
             self.ctx = self._backend_factory(self.task)
@@ -2616,6 +2688,10 @@ class GpuBatchILQSPlanner:
         self.ilqg.set_tasks(tasks)
         for e, m in enumerate(self.envs):
             m.task = self.task if tasks is None else self.sampling.envs[e].task
+
+    def set_models(self, models):
+        """not for a planner with a derivative chain: the batched derivative calls use the context's one model"""
+        raise NotImplementedError(_FleetTasks._MODELS_FOLLOW_UP)
 
     def allocate(self):
         # the iLQG half reads agent_differentiable (default 1) itself; the sampling half is told the same

@@ -50,6 +50,12 @@ cross_entropy: set_task_params_batched after set_states, and the plain set_task_
 step; gradient and ilqg: the fleet planner's set_tasks, and every sequential planner on its own task). The kernels do the same work
 either way; the record carries "mixed_params". Compare with the same run without the switch.
 
+--mixed-models (sampling and cross_entropy, the contact tasks): every environment rolls out on a model of its own -- payload, friction and
+actuator-strength variations of the robot (mjcf.variant), handed to the context once per shape with set_models_batched (the record
+carries that call's time, "set_models_ms": the builders run once per model on the host -- a setup call). The sequential side then plans
+on E contexts, each created on its environment's model. The kernels do the same work either way; compare with the same run without
+the switch.
+
 Kernel thresholds are the library's defaults: the sequential side of 8 x 2048 runs eight launches of the kernel a 2048-candidate batch gets,
 the batched side one launch of the kernel a 16384-candidate batch gets -- that is the feature."""
 import argparse
@@ -111,6 +117,32 @@ def mixed_tasks(task, E):
                         for k, v in zip(names, task.parameters)]
         t.risk = 0.2 * (e % 2)
         out.append(t)
+    return out
+
+
+def mixed_models(task, E):
+    """E packed models of the task's robot: the model itself, then in turn a payload on the first moving body (+ 10 % .. of its mass and
+    inertia per robot), a slipperier world (sliding friction x 0.9 ..) and weaker actuators (x 0.95 ..), growing with the robot's number"""
+    from mujoco_mpc_amd import mjcf
+    from mujoco_mpc_amd.cstructs import PackedModel
+    m = task.model
+    a = {k: np.asarray(m.arrays[k], float) for k in ("body_mass", "body_inertia", "geom_friction", "actuator_gear", "actuator_gainprm")}
+    trunk = int(np.flatnonzero(np.asarray(m.arrays["body_dofnum"]) > 0)[0])
+    gain = "actuator_gainprm" if np.any(np.asarray(m.arrays["actuator_biastype"]) == 0) and np.unique(a["actuator_gear"]).size == 1 else "actuator_gear"
+    ts, integ = m.get_number("agent_timestep", m.timestep), int(m.get_number("agent_integrator", m.integrator))
+    out = []
+    for e in range(E):
+        mass, inertia, friction, act = a["body_mass"].copy(), a["body_inertia"].copy(), a["geom_friction"].copy(), a[gain].copy()
+        step = 1 + e // 4
+        if e % 4 == 1:
+            mass[trunk] *= 1 + 0.1 * step
+            inertia[trunk] *= 1 + 0.1 * step
+        elif e % 4 == 2:
+            friction.reshape(-1, 3)[:, 0] *= 0.9 ** step
+        elif e % 4 == 3:
+            act.reshape(len(act), -1)[:, 0] *= 0.95 ** step
+        fm = m if e == 0 else mjcf.variant(m, body_mass=mass, body_inertia=inertia, geom_friction=friction, **{gain: act})
+        out.append(PackedModel(fm, timestep=ts, integrator=integ))
     return out
 
 
@@ -476,7 +508,7 @@ def sweep_ilqs(name, precision, H, shapes, steps, warmup, out, device_chain=None
         c.close()
 
 
-def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mixed=False):
+def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mixed=False, models=False):
     task = load_task(name)
     m = task.model
     rng = np.random.default_rng(1)
@@ -492,10 +524,19 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
         it = [0]
         tasks = mixed_tasks(task, E) if mixed else None
         rows = task_rows(tasks) if mixed else None
+        # --mixed-models: the fleet's context is given the E models (timed: a setup call); the sequential side plans on E contexts, each created on its model
+        set_models_ms, ctxs = None, [ctx] * E
+        if models:
+            packed = mixed_models(task, E)
+            t0 = time.perf_counter()
+            ctx.set_models_batched(packed)
+            set_models_ms = (time.perf_counter() - t0) * 1e3
+            ctxs = [capi.Context(pm, task.packed(), 0, precision) for pm in packed]
+        fleet_ctx = ctx
 
         def plain_params(e):
             if mixed:
-                ctx.set_task_params(tasks[e].weight, tasks[e].norm_parameter, tasks[e].parameters or None, tasks[e].risk)
+                ctxs[e].set_task_params(tasks[e].weight, tasks[e].norm_parameter, tasks[e].parameters or None, tasks[e].risk)
 
         def fleet_states():
             ctx.set_states(states, clocks, mocap)
@@ -506,6 +547,7 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
             it[0] += 1
             for e in range(E):
                 plain_params(e)
+                ctx = ctxs[e]
                 ctx.set_state(states[e], clocks[e], None if mocap is None else mocap[e])
                 ctx.rollout_noise(n, H, interp, times[e], nominal[e], capi.make_noise_spec(seed=7 + e, iteration=it[0], std0=std))
                 ctx.best(0)
@@ -527,6 +569,7 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
             it[0] += 1
             for e in range(E):
                 plain_params(e)
+                ctx = ctxs[e]
                 ctx.set_state(states[e], clocks[e], None if mocap is None else mocap[e])
                 ctx.rollout_noise(n, H, interp, times[e], nominal[e], ce_spec(e, variance[e]))
                 idx, _ = ctx.topk(n_elite + 1)
@@ -553,7 +596,7 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
             ts.append((t1 - t0) * 1e3)
             tb.append((t2 - t1) * 1e3)
         rec = {"task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps, "warmup": warmup,
-               "mixed_params": bool(mixed), "kernel": ctx.kernel_name.split(" (")[0],
+               "mixed_params": bool(mixed), "mixed_models": bool(models), "set_models_ms": set_models_ms, "kernel": ctx.kernel_name.split(" (")[0],
                "sequential_ms": {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))},
                "batched_ms": {"median": float(np.median(tb)), "min": float(np.min(tb)), "max": float(np.max(tb))},
                "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)),
@@ -571,7 +614,10 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
         print(json.dumps(rec), flush=True)
         out.write(json.dumps(rec) + "\n")
         out.flush()
-    ctx.close()
+        if models:
+            for c in ctxs:
+                c.close()
+    fleet_ctx.close()
 
 
 def main():
@@ -583,6 +629,7 @@ def main():
     ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "ilqs", "robust", "sample_gradient"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
     ap.add_argument("--mixed-params", action="store_true", help="every environment its own task weights, parameters and risk")
+    ap.add_argument("--mixed-models", action="store_true", help="sampling, cross_entropy: every environment its own model (payload, friction, actuator strength)")
     ap.add_argument("--robust", default="16x4", help="--planner robust: candidates x repetitions")
     ap.add_argument("--gradient-candidates", type=int, default=32, help="--planner sample_gradient: gradient candidates per environment")
     ap.add_argument("--no-device-chain", action="store_true", help="--planner ilqg, ilqs: the sequential middle (the A/B of ilqg_step_batched[_from])")
@@ -598,6 +645,10 @@ def main():
                                              "sample_gradient": SAMPLE_GRADIENT_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
             if shapes and (a.only is None or a.only == name):
+                if a.mixed_models and (a.planner not in ("sampling", "cross_entropy") or name == "Cartpole"):
+                    if a.planner not in ("sampling", "cross_entropy"):
+                        raise SystemExit("batch_sweep.py: --mixed-models is for --planner sampling and cross_entropy")
+                    continue      # (a lane-family task: its model constants are fixed when the library is built)
                 if a.planner == "gradient":
                     sweep_gradient(name, precision, H, shapes, a.steps, a.warmup, out, a.mixed_params)
                 elif a.planner == "robust":
@@ -612,7 +663,7 @@ def main():
                 elif a.planner == "ilqg":
                     sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out, False if a.no_device_chain else None, a.mixed_params)
                 else:
-                    sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner, a.mixed_params)
+                    sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner, a.mixed_params, a.mixed_models)
 
 
 if __name__ == "__main__":
