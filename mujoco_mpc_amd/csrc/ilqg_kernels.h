@@ -45,7 +45,8 @@ __device__ __forceinline__ void find_interval(const T* xs, T value, int length, 
 // Weights of Zero / Linear / CubicInterpolation (mjpc/utilities.cc:304-422) over the grid xs[0 .. length) at `value`: the
 // interpolant of any series y on that grid is  w[0] y[g - 1] + w[1] y[g] + w[2] y[g + 1] + w[3] y[g + 2]  with g = bounds[0]
 // (indices clamped to the grid where the weight is zero). Cubic = Hermite with finite-difference slopes (mean of the two
-// neighbouring secants, one-sided at the ends of the grid, zero on a two-point grid: FiniteDifferenceSlope).
+// neighbouring secants, one-sided at the ends of the grid; on a two-point grid the left slope is still the secant and only the
+// right-hand one is zero: FiniteDifferenceSlope).
 template <typename T>
 struct InterpWeights { int g; int i[4]; T w[4]; };
 template <typename T>

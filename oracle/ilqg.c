@@ -213,6 +213,7 @@ typedef struct {
   int Tn, mode, representation, use_state;
   const double *times, *states, *actions, *gains, *improvement;
   double alpha;
+  double *dx, *xi, *K; /* scratch of the model's size: 2 nv, nq + nv, nu * 2 nv (the rollout worker's) */
 } FbPolicy;
 
 static void find_interval(const double* xs, double v, int length, int* b) { /* utilities.h:124-144 */
@@ -260,7 +261,7 @@ static void clamp_ctrl(const mjpcx_model* m, double* u) {
 static void fb_action(const FbPolicy* p, double* action, const double* state, double time, int t) {
   const mjpcx_model* m = p->m;
   const int nu = m->nu, ds = m->nq + m->nv, ndx = 2 * m->nv;
-  double dx[64], xi[64], K[64 * 16];
+  double *dx = p->dx, *xi = p->xi, *K = p->K;
   if (p->mode == 0) {
     for (int k = 0; k < nu; k++) action[k] = p->actions[t * nu + k] + p->alpha * p->improvement[t * nu + k];
     ostate_diff(m, dx, p->states + (size_t)t * ds, state, 1.0); /* StateDiff(model, dx, states[t], state, 1.0) */
@@ -307,13 +308,14 @@ static void* fb_worker(void* arg) {
   OBatchOut* out = b->out;
   const int nu = m->nu, ds = m->nq + m->nv, nr = task->num_residual, ntr = task->num_trace, H = b->H;
   OData* d = odata_new(m);
-  double* r = (double*)malloc(sizeof(double) * (size_t)(nr + nu + ds));
+  const size_t ndx = 2 * (size_t)m->nv;
+  double* r = (double*)malloc(sizeof(double) * ((size_t)(nr + nu + ds) + ndx + (size_t)ds + (size_t)nu * ndx));
   if (!d || !r) { __atomic_store_n(&b->failed, 1, __ATOMIC_RELAXED); free(r); if (d) odata_free(d); return NULL; }
-  double *act = r + nr, *st = act + nu;
+  double *act = r + nr, *st = act + nu, *pdx = st + ds, *pxi = pdx + ndx, *pK = pxi + ds;
   for (;;) {
     const int i = __atomic_fetch_add(&b->next, 1, __ATOMIC_RELAXED);
     if (i >= b->N) break;
-    FbPolicy p = {m, b->Tn, b->mode, b->representation, b->use_state, b->times, b->states, b->actions, b->gains, b->improvement, b->alpha[i]};
+    FbPolicy p = {m, b->Tn, b->mode, b->representation, b->use_state, b->times, b->states, b->actions, b->gains, b->improvement, b->alpha[i], pdx, pxi, pK};
     odata_set_state(d, b->state, b->time, b->mocap, NULL);
     memcpy(st, b->state, sizeof(double) * ds);
     memset(act, 0, sizeof(double) * nu);
