@@ -132,7 +132,8 @@ __device__ __forceinline__ void wave_rollout_body(const MODEL& m, const TASK& tk
     const int gi = a.noise.candidate_offset + cand;
     wreal std = a.noise.std0;
     if (a.noise.mode == 0 && a.noise.std1 > 0) {
-      if (bernoulli_uniform(a.noise.seed, (uint32_t)gi, a.noise.iteration) < WL(0.2)) std = a.noise.std1;
+      // compared in double whatever wreal is, as every other copy does: 0.2f > 0.2 would hand std1 to the uniforms in between
+      if (bernoulli_uniform(a.noise.seed, (uint32_t)gi, a.noise.iteration) < 0.2) std = a.noise.std1;
     }
     const bool noised = gi != a.noise.nominal_candidate;
     for (int j0 = 2 * lane; j0 < np; j0 += 128) {

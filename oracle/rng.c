@@ -6,8 +6,9 @@
  * cross_entropy/planner.cc:360), so "identical seeds" cannot be reproduced
  * against it. The build replaces it by Philox4x32-10 + Box-Muller
  * as specified in include/mjpcx.h; this file is the CPU statement of that spec.
- * Philox is pinned by the Random123 known-answer vectors
- * (tests/test_oracle_rng.py). */
+ * Philox is pinned by the Random123 known-answer vectors (tests/test_rng.py);
+ * the Gaussian transform and the candidates' nodes are held to mpmath answers
+ * written from the header's text (tests/sampling_policy_cases.py). */
 #include <math.h>
 #include "oracle.h"
 

@@ -67,8 +67,25 @@ def candidate_bound(g, nominal, gradient, gradient_previous, bound, bound_previo
 
 def resample_exact(times, values, interp, time):
     """TimeSpline::Sample of one scalar spline in exact rational arithmetic -> (value, M): M the magnitude the rounding bound scales with"""
-    ts, vs = [Fraction(float(t)) for t in times], [Fraction(float(v)) for v in values]
-    P, x = len(ts), Fraction(float(time))
+    return resample_rational([Fraction(float(t)) for t in times], [Fraction(float(v)) for v in values], interp, Fraction(float(time)))
+
+
+def resample_weights(times, interp, time):
+    """The sample as a linear form of the node values: {node p: (W_p, A_p)} with value = sum_p W_p v_p and M = sum_p A_p |v_p|, from
+    resample_rational on the unit splines (the sample is linear in the values, M in their absolute values); nodes with W_p = A_p = 0 are
+    left out. tests/sampling_policy_cases.py evaluates many candidates on one grid with it."""
+    ts, x = [Fraction(float(t)) for t in times], Fraction(float(time))
+    out = {}
+    for p in range(len(ts)):
+        w, a = resample_rational(ts, [Fraction(int(q == p)) for q in range(len(ts))], interp, x)
+        if w != 0 or a != 0:
+            out[p] = (w, a)
+    return out
+
+
+def resample_rational(ts, vs, interp, x):
+    """resample_exact on Fractions"""
+    P = len(ts)
     up = 0
     while up < P and not x < ts[up]:
         up += 1

@@ -1,5 +1,7 @@
 """Counter-based candidate noise (include/mjpcx.h noise spec). Philox4x32-10 is pinned by the
-Random123 known-answer vectors; the Gaussian transform by moments."""
+Random123 known-answer vectors. The Gaussian transform is pinned draw by draw against mpmath, with the nodes every
+copy of the candidate noise gives, by tests/sampling_policy_cases.py (tests/test_sampling_policy_cases.py,
+tests/test_gpu_sampling_policy.py); the moments below stay as a statistical cross-check of the oracle."""
 import ctypes as C
 
 import numpy as np
