@@ -723,6 +723,41 @@ int mjpcx_timing_read_main(mjpcx_ctx* ctx, double* main_kernel_ms, int64_t* laun
  * apart (csrc/pair_cull.h). Synchronises. */
 int mjpcx_quad_stats(mjpcx_ctx* ctx, int32_t* handed_on /* 8 */);
 
+/* ---- pruning: candidates that can no longer win the plan step are not rolled to the horizon ---------------------
+ * A step's cost is >= 0 (weights >= 0, norms >= 0, the risk transform maps [0, inf) to [0, inf)), so a candidate's running
+ * sum is a lower bound of its return. With pruning on, rollout_quad_kernel keeps the smallest return that a candidate of
+ * the launch has completed with (the bound, starting at `initial_bound`) and retires every candidate other than the nominal
+ * whose partial return STRICTLY exceeds it: it can neither be nor tie the argmin.
+ *
+ * Sticky. Applies to the following mjpcx_rollout_noise / mjpcx_rollout_splines launches that go to rollout_quad_kernel
+ * (mjpcx_rollout_splines has no nominal: no candidate is exempt there); every other launch (the batched entry points,
+ * with one environment too, the feedback rollouts, the limb, tree and lane kernel families, batches below
+ * MJPCX_QUAD_MIN_N, any launch under the tuning switch MJPCX_QUAD_NO_FALLBACK) ignores it and rolls everything out.
+ * initial_bound: +inf for normal use; a finite value is a bound the caller vouches for (some candidate's return is <= it).
+ * Negative or NaN: MJPCX_EINVAL. MJPCX_PRUNE=0 in the environment, read when the context is created, makes this call do
+ * nothing.
+ *
+ * After a pruned launch:
+ *   - a retired candidate's failure is MJPCX_FAILURE_PRUNED | (retire step << 8), its total_return the partial return at
+ *     that step (a lower bound of the return, strictly above the best), and its trajectory rows after that step are not
+ *     written. It is not handed to another kernel and mjpcx_quad_stats does not count it. Which candidates are retired,
+ *     and when, depends on the order the wavefronts finish in; every candidate not marked equals the unpruned launch's.
+ *   - mjpcx_best (and mjpcx_topk with k = 1) is exact (index, returns, spline), or MJPCX_ESTATE: a step's cost was negative
+ *     (partial returns were no lower bounds), or something was retired and the smallest stored return is above the final
+ *     bound = min(initial_bound, the returns completed inside the launch). With +inf the latter cannot happen. With a
+ *     caller's bound it happens exactly when no stored return reaches down to the bound, i.e. the bound was below every
+ *     return: a wrong bound always shows, also when a candidate passed its last check under the bound and completed above
+ *     it (the last step is not checked). Otherwise every retired candidate is strictly above the winner. Roll out again
+ *     with pruning off after MJPCX_ESTATE.
+ *   - mjpcx_topk with k > 1, mjpcx_elite_moments and mjpcx_merge_topk return MJPCX_ESTATE: their answers would depend on
+ *     timing. mjpcx_get_returns, mjpcx_fetch_trajectory and mjpcx_fetch_spline stay usable. */
+#define MJPCX_FAILURE_PRUNED 0x20000000
+int mjpcx_set_pruning(mjpcx_ctx* ctx, int enabled, double initial_bound);
+/* Of the last rollout (zeros unless it was pruned): [0] candidates retired, [1] the sum of their retire steps, [2] != 0 if a
+ * step's cost was negative, [3] wavefronts all of whose candidates left before the last step. No synchronisation: the
+ * counters came back with the launch. */
+int mjpcx_prune_stats(mjpcx_ctx* ctx, int64_t* out /* 4 */);
+
 /* Algorithmic bytes of one candidate rollout:
  * w*[H*(dim_state+nu+1+nr+3*ntrace+1) + P*nu + P + 2]. */
 int64_t mjpcx_algorithmic_bytes(const mjpcx_ctx* ctx, int horizon, int num_nodes);

@@ -33,7 +33,7 @@ EXPORTS = [
     "mjpcx_rollout_feedback_batched", "mjpcx_ilqg_step_batched", "mjpcx_ilqg_step_batched_from",
     "mjpcx_rollout_splines_noisy_batched", "mjpcx_robust_step_batched",
     "mjpcx_rollout_sample_gradient_batched", "mjpcx_sample_gradient_update_batched",
-    "mjpcx_set_models_batched",
+    "mjpcx_set_models_batched", "mjpcx_set_pruning", "mjpcx_prune_stats",
 ]
 
 SG_COMPUTE_WEIGHTS, SG_ZERO_GRADIENT = 1, 2   # MJPCX_SG_* flags of mjpcx_sample_gradient_update_batched
@@ -113,6 +113,8 @@ def lib():
         L.mjpcx_timing_read.argtypes = [vp, c_f64p, C.POINTER(C.c_int64)]
         L.mjpcx_timing_read_main.argtypes = [vp, c_f64p, C.POINTER(C.c_int64)]
         L.mjpcx_quad_stats.argtypes = [vp, c_i32p]
+        L.mjpcx_set_pruning.argtypes = [vp, C.c_int, C.c_double]
+        L.mjpcx_prune_stats.argtypes = [vp, C.POINTER(C.c_int64)]
         L.mjpcx_algorithmic_bytes.restype = C.c_int64
         L.mjpcx_algorithmic_bytes.argtypes = [vp, C.c_int, C.c_int]
         L.mjpcx_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -649,6 +651,17 @@ class Context:
         self._chk(lib().mjpcx_quad_stats(self.handle, as_i32p(h)))
         return dict(handed_on=int(h[0]), contact_list_full=int(h[1]), leg_leg_contact=int(h[2]), indefinite_hessian=int(h[3]), non_finite=int(h[4]),
                     both_limits=int(h[5]), trunk_leg_contact=int(h[6]), out_of_proof_range=int(h[7]))
+
+    def set_pruning(self, enabled, initial_bound=float("inf")):
+        """mjpcx_set_pruning: the following plain rollouts on rollout_quad_kernel retire candidates that can no longer be the argmin (sticky)"""
+        self._chk(lib().mjpcx_set_pruning(self.handle, int(bool(enabled)), float(initial_bound)))
+
+    def prune_stats(self):
+        """of the last rollout (zeros unless it was pruned): candidates retired, their mean retire step, the negative-cost flag, wavefronts that ended early"""
+        h = (C.c_int64 * 4)()
+        self._chk(lib().mjpcx_prune_stats(self.handle, h))
+        return dict(retired=int(h[0]), retire_step_sum=int(h[1]), mean_retire_step=(h[1] / h[0] if h[0] else 0.0), negative_cost=bool(h[2]),
+                    wavefronts_ended_early=int(h[3]))
 
     def algorithmic_bytes(self, horizon, num_nodes):
         return lib().mjpcx_algorithmic_bytes(self.handle, int(horizon), int(num_nodes))

@@ -913,6 +913,14 @@ struct mjpcx_ctx {
   int quad_ids[7] = {0, 0, 0, 0, 0, 0, 0};  // residual_int[1..7] the quad model was built for (torso, head site, goal mocap, feet)
   DevBuf d_qmodel, d_qtab, d_qstats, d_qstamps, d_qwave, d_qovf, d_qclass;
   void* h_qstats = nullptr;       // pinned copy of d_qstats (whether the hand-on pass has anything to do)
+  // retiring candidates that can no longer be the argmin (mjpcx_set_pruning; quad kernel, one environment). d_qstats is 64 bytes: the 8
+  // hand-on counters, then the bound word (byte 32) and the 4 pruning counters (byte 40) of QArgs::prune_bound / prune_stats
+  bool prune_allowed = true;      // MJPCX_PRUNE=0 at creation: mjpcx_set_pruning does nothing
+  bool prune_on = false;
+  double prune_initial = 0;
+  bool last_pruned = false;       // the last rollout was launched with a bound: its returns hold lower bounds, only the argmin is exact
+  int prune_h[4] = {0, 0, 0, 0};  // ... and its counters, read back with the hand-on count
+  double prune_final = 0;         // ... and the bound word after the launch: min(initial bound, the returns completed inside the launch)
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -1312,7 +1320,8 @@ ModelRecords model_records(const mjpcx_ctx* c, bool per_env, bool f32) {
 }
 
 // quad kernel (quad_kernel.h), then the wavefront-per-candidate kernel for the candidates it handed on
-hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, const RolloutArgs<double>& a, int N, int P, const ModelRecords& mr) {
+// plain: mjpcx_rollout_noise / mjpcx_rollout_splines (E = 0), the launches mjpcx_set_pruning applies to
+hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, const RolloutArgs<double>& a, int N, int P, const ModelRecords& mr, bool plain) {
   quad::QArgs q{};
   q.N = a.N; q.H = a.H; q.P = a.P; q.interp = a.interp; q.node_times = a.node_times; q.nodes = a.nodes; q.nominal = a.nominal;
   q.noise_mode = a.noise.mode; q.seed = a.noise.seed; q.iteration = a.noise.iteration; q.candidate_offset = a.noise.candidate_offset;
@@ -1328,7 +1337,21 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
     if ((e = c->d_qovf.reserve((size_t)quad::quad_waves(N, c->quad_cpw) * quad::quad_ovf_doubles_per_wave() * sizeof(double))) != hipSuccess) return e;
     q.ovf_slab = (double*)c->d_qovf.p;
   }
-  if ((e = hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream)) != hipSuccess) return e;  // (how many candidates are handed on, by reason: mjpcx_quad_stats)
+  // (mjpcx_set_pruning: the plain launches only -- a batched one, of one environment too, is ranked by calls that read every return, and
+  // would need a bound per environment. Not with MJPCX_QUAD_NO_FALLBACK either: that tuning switch skips the readback the counters ride on)
+  const bool pruned = c->prune_on && plain && !c->quad_no_fallback;
+  if ((e = hipMemsetAsync(c->d_qstats.p, 0, pruned ? 64 : 32, c->stream)) != hipSuccess) return e;  // (how many candidates are handed on, by reason: mjpcx_quad_stats)
+  if (pruned) {  // the bound word starts at the caller's bound (+inf: 0x7ff00000 over a low word of zeros), on the stream like the counters
+    unsigned long long bits;
+    std::memcpy(&bits, &c->prune_initial, 8);
+    char* w = (char*)c->d_qstats.p + 32;
+    if ((unsigned)bits != 0 && (e = hipMemsetD32Async((hipDeviceptr_t)w, (int)(unsigned)bits, 1, c->stream)) != hipSuccess) return e;
+    if ((e = hipMemsetD32Async((hipDeviceptr_t)(w + 4), (int)(unsigned)(bits >> 32), 1, c->stream)) != hipSuccess) return e;
+    q.prune_bound = (unsigned long long*)w;
+    q.prune_stats = (int*)(w + 8);
+    if (a.noise.mode < 0) q.nominal_candidate = -1;  // (given splines have no nominal: no candidate is exempt)
+  }
+  c->last_pruned = pruned;
   if (c->quad_stamps) {
     if ((e = hipMemsetAsync(c->d_qstamps.p, 0, 512, c->stream)) != hipSuccess) return e;
     q.stamps = (long long*)c->d_qstamps.p;
@@ -1394,13 +1417,16 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
   if (c->quad_no_fallback) return hipSuccess;
   // the pass over the candidates the quad kernel handed on is 16384 wavefronts that each find their candidate unflagged (0.24 ms) when
   // nothing was handed on -- the usual case: the count comes back first (32 bytes, one synchronisation the plan step pays anyway a moment later)
-  if (!c->quad_stats) {
-    if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 32, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
+  // (a pruned launch's counters ride on the same copy: mjpcx_best and mjpcx_prune_stats need no synchronisation of their own for them)
+  if (!c->quad_stats || pruned) {
+    if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 64, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
     if (c->h_qstats) {
-      if ((e = hipMemcpyAsync(c->h_qstats, c->d_qstats.p, 32, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+      if ((e = hipMemcpyAsync(c->h_qstats, c->d_qstats.p, pruned ? 64 : 32, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
       if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
-      if (static_cast<const int*>(c->h_qstats)[0] == 0) return hipSuccess;
-    }
+      const int* h = static_cast<const int*>(c->h_qstats);
+      if (pruned) { for (int k = 0; k < 4; k++) c->prune_h[k] = h[10 + k]; std::memcpy(&c->prune_final, h + 8, 8); }
+      if (h[0] == 0 && !c->quad_stats) return hipSuccess;
+    } else if (pruned) return hipErrorOutOfMemory;
   }
   RolloutArgs<double> a2 = a;
   a2.noise.mode = -1;  // the quad kernel left every candidate's spline nodes in a.nodes
@@ -1459,7 +1485,7 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
   if (c->timing && c->cur_main) { if ((e = hipEventRecord(c->cur_main, c->stream)) == hipSuccess) c->cur_main = nullptr; else return e; }
   if (c->limb_no_fallback) return hipSuccess;
   if (!c->quad_stats) {  // the count of hand-ons comes back first: nothing handed on (the usual case) -> no second launch
-    if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 32, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
+    if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 64, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
     if (c->h_qstats) {
       if ((e = hipMemcpyAsync(c->h_qstats, c->d_qstats.p, 32, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
       if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
@@ -1506,6 +1532,7 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   // the caller reserved for this shape -- no host splines, no scatter, no sync.
   int rc;
   if ((rc = reserve_rollout(c, N, H, P)) != MJPCX_OK) return rc;
+  c->last_pruned = false;  // (launch_quad sets it)
   const int np = P * c->nu;
   RolloutArgs<T> a{};
   a.N = N; a.H = H; a.P = P; a.interp = interp;
@@ -1587,7 +1614,7 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
       // at N = 16384 but leaves most of them idle below a quarter of that, where one wavefront per candidate (a third of the latency per
       // step) is quicker -- measured cross-over on MI355X: N = 4096 (tools/quad_n_sweep.py; MJPCX_QUAD_MIN_N moves it)
       if (c->wh.registered == 0 && c->quad_ok && a.xfrc_scale == 0 && !wt.stamps && N >= c->quad_min_n) {
-        le = launch_quad(c, wm, wt, a, N, P, mr);
+        le = launch_quad(c, wm, wt, a, N, P, mr, /*plain=*/E == 0);
       } else if (c->wh.registered == 0) {
         if (c->quad_ok) (void)hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream);  // (mjpcx_quad_stats reports the LAST rollout: nothing was handed on in this one)
         le = launch_tree<TreeCfgA1, double>(c, wm, wt, a, image, c->wh.blob_bytes, N, P);
@@ -1844,6 +1871,7 @@ int mjpcx_create(const mjpcx_model* m, const mjpcx_task* t, int device, int prec
       c->quad_no_fallback = getenv("MJPCX_QUAD_NO_FALLBACK") != nullptr;
       c->no_quad_feedback = getenv("MJPCX_NO_QUAD_FEEDBACK") != nullptr;
       if (const char* e = getenv("MJPCX_QUAD_CON_CAP")) c->quad_con_cap = std::atoi(e);
+      if (const char* e = getenv("MJPCX_PRUNE")) c->prune_allowed = std::atoi(e) != 0;  // (0: mjpcx_set_pruning does nothing -- the same binary, A/B)
       if (const char* e = getenv("MJPCX_QUAD_MIN_N")) c->quad_min_n = std::atoi(e);
       if (const char* e = getenv("MJPCX_QUAD_CPW")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) c->quad_cpw = v; }
       if (precision == 64 && !getenv("MJPCX_NO_QUAD")) {
@@ -1851,8 +1879,8 @@ int mjpcx_create(const mjpcx_model* m, const mjpcx_task* t, int device, int prec
         std::vector<unsigned char> hq, ht;
         c->quad_why = quad::build_images(m, t, hq, ht);
         if (c->quad_why.empty()) {
-          if (c->d_qmodel.reserve(hq.size()) != hipSuccess || c->d_qtab.reserve(ht.size()) != hipSuccess || c->d_qstats.reserve(32) != hipSuccess ||
-              c->d_qstamps.reserve(512) != hipSuccess || hipMemset(c->d_qstats.p, 0, 32) != hipSuccess ||
+          if (c->d_qmodel.reserve(hq.size()) != hipSuccess || c->d_qtab.reserve(ht.size()) != hipSuccess || c->d_qstats.reserve(64) != hipSuccess ||
+              c->d_qstamps.reserve(512) != hipSuccess || hipMemset(c->d_qstats.p, 0, 64) != hipSuccess ||
               hipMemcpy(c->d_qmodel.p, hq.data(), hq.size(), hipMemcpyHostToDevice) != hipSuccess ||
               hipMemcpy(c->d_qtab.p, ht.data(), ht.size(), hipMemcpyHostToDevice) != hipSuccess) {
             mjpcx_destroy(c);
@@ -2680,10 +2708,34 @@ int mjpcx_get_return_at(mjpcx_ctx* c, int cand, double* total_return, int32_t* f
   return MJPCX_OK;
 }
 
+// which candidates a pruned launch (mjpcx_set_pruning) retires, and when, depends on the order its wavefronts finish in: only the argmin is exact
+static_assert(MJPCX_FAILURE_PRUNED == mjpcx::kQPruned, "the header documents the kernel's marker");
+// The argmin of a pruned launch, before and after it is known. The counters and the final bound came back with the launch's hand-on count:
+// no synchronisation here.
+//   before: a negative step cost means the partial returns were no lower bounds.
+//   after: the smallest STORED return r* (partial returns for the retired candidates) must be <= the final bound Bf = min(initial bound,
+//   the returns completed inside the launch). Every retired candidate's return >= its partial > the bound at that time >= Bf, so r* <= Bf
+//   says that r* belongs to a candidate that completed and that every retired candidate is strictly above it: the argmin is exact, ties
+//   included. With +inf as the initial bound r* <= Bf always holds (r* is <= every completed return). With a caller's bound it fails exactly
+//   when no stored return reaches down to the bound -- a wrong bound always shows, also when a candidate slipped past it at the last step.
+static int pruned_launch_valid(mjpcx_ctx* c) {
+  if (c->last_pruned && c->prune_h[2])
+    return fail(c, MJPCX_ESTATE, "pruned rollout: a step's cost was negative, so partial returns are no lower bounds (roll out again with pruning off)");
+  return MJPCX_OK;
+}
+static int pruned_argmin_valid(mjpcx_ctx* c, double best_return) {
+  if (c->last_pruned && c->prune_h[0] > 0 && !(best_return <= c->prune_final))
+    return fail(c, MJPCX_ESTATE, "pruned rollout: every stored return is above the bound, so the initial bound was below every return (roll out again with pruning off)");
+  return MJPCX_OK;
+}
+static const char* const kPrunedRanking ="the last rollout was pruned (mjpcx_set_pruning): beyond the argmin its returns are lower bounds that depend on timing";
+
 int mjpcx_best(mjpcx_ctx* c, int ref_candidate, int32_t* index, double* best_return, double* ref_return,
                double* spline_values) {
   if (!c || !index) return fail(c, MJPCX_EINVAL, "null argument");
   if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  int rc;
+  if ((rc = pruned_launch_valid(c)) != MJPCX_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
   const size_t bytes = sizeof(BestRecord) + (size_t)np * 8;
@@ -2703,6 +2755,7 @@ int mjpcx_best(mjpcx_ctx* c, int ref_candidate, int32_t* index, double* best_ret
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const BestRecord* r = (const BestRecord*)c->best_host;
+  if ((rc = pruned_argmin_valid(c, r->best_return)) != MJPCX_OK) return rc;
   *index = r->best_index;
   if (best_return) *best_return = r->best_return;
   if (ref_return) *ref_return = r->ref_return;
@@ -2714,6 +2767,9 @@ int mjpcx_topk(mjpcx_ctx* c, int k, int32_t* index, double* total_return) {
   if (!c || !index) return fail(c, MJPCX_EINVAL, "null argument");
   if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
   if (k < 1 || k > c->N) return fail(c, MJPCX_EINVAL, "k out of range");
+  if (k > 1 && c->last_pruned) return fail(c, MJPCX_ESTATE, kPrunedRanking);
+  int rc;
+  if ((rc = pruned_launch_valid(c)) != MJPCX_OK) return rc;  // (k = 1 is the argmin: mjpcx_best's checks)
   HIPCHK(c, hipSetDevice(c->device));
   int n2 = 1;
   while (n2 < c->N) n2 <<= 1;
@@ -2727,6 +2783,7 @@ int mjpcx_topk(mjpcx_ctx* c, int k, int32_t* index, double* total_return) {
   std::vector<RetIdx> h(k);
   HIPCHK(c, hipMemcpyAsync(h.data(), c->d_sort.p, (size_t)k * sizeof(RetIdx), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = pruned_argmin_valid(c, h[0].r)) != MJPCX_OK) return rc;
   for (int i = 0; i < k; i++) {
     index[i] = h[i].i;
     if (total_return) total_return[i] = h[i].r;
@@ -2741,6 +2798,7 @@ int mjpcx_elite_moments(mjpcx_ctx* c, int n, const int32_t* candidates, const do
   if (n < 0) return fail(c, MJPCX_EINVAL, "negative count");
   for (int i = 0; i < n; i++)
     if (candidates[i] < 0 || candidates[i] >= c->N) return fail(c, MJPCX_EINVAL, "candidate out of range");
+  if (c->last_pruned) return fail(c, MJPCX_ESTATE, kPrunedRanking);
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
   // staging: [cand (n i32) | mean (np f64) | out (np+1 f64)]
@@ -2869,6 +2927,20 @@ int mjpcx_timing_read_main(mjpcx_ctx* c, double* main_kernel_ms, int64_t* launch
   }
   if (main_kernel_ms) *main_kernel_ms = total;
   if (launches) *launches = (int64_t)c->events_used;
+  return MJPCX_OK;
+}
+
+int mjpcx_set_pruning(mjpcx_ctx* c, int enabled, double initial_bound) {
+  if (!c) return MJPCX_EINVAL;
+  if (enabled && !(initial_bound >= 0)) return fail(c, MJPCX_EINVAL, "the initial bound is a return: >= 0 (+inf for none)");
+  c->prune_on = enabled != 0 && c->prune_allowed;
+  c->prune_initial = initial_bound;
+  return MJPCX_OK;
+}
+
+int mjpcx_prune_stats(mjpcx_ctx* c, int64_t* out) {
+  if (!c || !out) return MJPCX_EINVAL;
+  for (int k = 0; k < 4; k++) out[k] = c->last_pruned ? c->prune_h[k] : 0;
   return MJPCX_OK;
 }
 
@@ -3011,7 +3083,7 @@ int do_feedback(mjpcx_ctx* c, int E, int n, int H, int mode, int representation,
       const quad::QFeedback qf{d[0], d[1], d[2], d[3], d[4], d[5], Tn, mode, representation, use_state};
       HIPCHK(c, hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream));
       HIPCHK(c, quad::launch_feedback_quad(c->d_qmodel.p, c->d_qtab.p, wt.blob, bo, q, qf, (int*)c->d_qstats.p, c->stream));
-      if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 32, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
+      if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 64, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
       if (c->h_qstats) {  // (the one sync of the call: the hand-on count)
         HIPCHK(c, hipMemcpyAsync(c->h_qstats, c->d_qstats.p, 32, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3031,6 +3103,7 @@ int do_feedback(mjpcx_ctx* c, int E, int n, int H, int mode, int representation,
   HIPCHK(c, rec.slot->host.mark(c->stream));
   c->N = N; c->H = H; c->P = a.P;
   c->env_n = env_n;
+  c->last_pruned = false;
   c->have_rollout = true;
   c->rollout_serial++;
   c->traj_candidate_major = c->wave;
@@ -3846,6 +3919,7 @@ int mjpcx_exchange_best(mjpcx_ctx* c, int32_t* index, double* best_return, doubl
 
 int mjpcx_merge_topk(mjpcx_ctx* c, int k, int64_t* index, double* total_return) {
   if (!c || k < 1 || !index || !total_return) return fail(c, MJPCX_EINVAL, "null argument");
+  if (c->last_pruned) return fail(c, MJPCX_ESTATE, kPrunedRanking);
   if (!c->comm) return c->comm_world == 1 ? MJPCX_OK : fail(c, MJPCX_ESTATE, "mjpcx_comm_init has not been called");
   std::vector<double> mine(2 * (size_t)k);
   for (int i = 0; i < k; i++) {

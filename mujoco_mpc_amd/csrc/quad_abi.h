@@ -7,6 +7,8 @@
 
 namespace mjpcx {
 constexpr int kQFallback = 0x40000000;  // failure[] marker of a candidate the quad kernel handed on (cleared by the fallback pass)
+constexpr int kQPruned = 0x20000000;   // failure[] marker of a candidate retired because it could no longer be the argmin (QArgs::prune_bound): | (retire step << 8);
+                                        // a bit of its own -- the fallback pass does not re-roll it and the hand-on statistics do not count it
 namespace quad {
 // the rollout request (RolloutArgs<double> of rollout_lane.h, flattened so that the CPU emulator can fill it too)
 struct QArgs {
@@ -34,6 +36,11 @@ struct QArgs {
   unsigned env_stride;  // ... and the bytes between the plan records of consecutive environments (node_times, nominal and the blob are environment 0's)
   unsigned model_stride, tables_stride;  // a model per environment (mjpcx_set_models_batched): the bytes between consecutive environments' QuadModel / QuadTables
                                          // records (0: the one model for every environment; the kernel's model pointers are environment 0's)
+  unsigned long long* prune_bound;  // nullptr: every candidate is rolled to the horizon. Otherwise one word holding the bits of a non-negative double in RETURN units (for those the
+                                    // unsigned order of the bits is the numeric order): a return some candidate of this launch has achieved, or the caller's initial bound. A
+                                    // candidate whose partial return strictly exceeds it is retired (kQPruned); one that completes lowers it. rollout_quad_kernel with env_n == 0 only
+  int* prune_stats;   // nullptr, or 4 ints: [0] candidates retired, [1] the sum of their retire steps, [2] != 0 if a step's cost was negative (the partial return is then no lower
+                      // bound: the launch's pruning is invalid), [3] wavefronts all of whose candidates left before the last step
 };
 
 // the feedback policy of the iLQG rollouts (FeedbackArgs of ilqg_kernels.h): nullptr members = the spline policy of QArgs

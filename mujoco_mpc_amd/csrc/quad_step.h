@@ -74,6 +74,26 @@ QD void q_sqrt_rsqrt(double x, double& s, double& r) { s = sqrt(x); r = 1.0 / s;
 QD double q_rcp(double x) { return 1.0 / x; }
 #endif
 QD bool qbad(double x) { return !(x <= kQMaxVal && x >= -kQMaxVal); }
+// the words the candidates of a launch share when it prunes (QArgs::prune_bound, prune_stats): relaxed, device-wide; on the host (the
+// emulator: a thread per lane, several quads at a time) the same operations on plain memory
+#ifdef __HIPCC__
+QD unsigned long long q_bound_load(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+QD void q_bound_min(unsigned long long* p, unsigned long long v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+QD void q_count_add(int* p, int v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+QD void q_count_set(int* p) { __hip_atomic_store(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+QD unsigned long long q_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
+QD double q_from_bits(unsigned long long b) { return __longlong_as_double((long long)b); }
+#else
+QD unsigned long long q_bound_load(const unsigned long long* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+QD void q_bound_min(unsigned long long* p, unsigned long long v) {
+  unsigned long long cur = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v < cur && !__atomic_compare_exchange_n(p, &cur, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+}
+QD void q_count_add(int* p, int v) { (void)__atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+QD void q_count_set(int* p) { __atomic_store_n(p, 1, __ATOMIC_RELAXED); }
+QD unsigned long long q_bits(double v) { unsigned long long b; __builtin_memcpy(&b, &v, 8); return b; }
+QD double q_from_bits(unsigned long long b) { double v; __builtin_memcpy(&v, &b, 8); return v; }
+#endif
 QD void q_mul(double* r, const double* a, const double* b) {
   const double w = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
   const double x = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
@@ -2560,6 +2580,11 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
   double total = 0;
   double ctrl[3] = {0, 0, 0};
   int flags = 0, flag_step = 0;
+  // retiring candidates that can no longer be the argmin (QArgs::prune_bound): every step's cost is >= 0, so the running sum is a lower
+  // bound of the return; the nominal is always rolled out (its return is the plan step's `improvement` reference)
+  const bool prune = !FEEDBACK && a.prune_bound != nullptr;
+  const bool prunable = prune && a.candidate_offset + cand != a.nominal_candidate;
+  bool pruned = false;
   for (int t = 0; t < H; t++) {
     flag_step = t;
     const long long step_t0 = QCLASS_NOW(a);
@@ -2610,6 +2635,8 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
     QSense f;
     flags = forward_smooth(m, tab, sp, leg, S, ctrl, cs, ms, D, f, pf);
     if (flags) break;
+    // (the bound is read here, once per step, so that the load's latency passes under the sensor stage)
+    const unsigned long long bound_bits = prune && !last ? q_bound_load(a.prune_bound) : 0ull;
     // the sensor stage (residual, cost, traces) does not depend on the constraint solve: evaluated and recorded first, so that
     // nothing of it is live during the solve
     QResidual r;
@@ -2632,6 +2659,13 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
     }
     total += cost;
     if (a.con_cap > 0 && qd_or(D.ncon > a.con_cap ? 1 : 0)) { flags = kFlagOverflow; break; }
+    if (prune) {
+      if (cost < 0 && leg == 0 && a.prune_stats) q_count_set(a.prune_stats + 2);
+      // in RETURN units and strictly greater: return >= partial return (adding terms >= 0 and dividing by H are monotone in floating
+      // point) > bound = a return that was achieved, so the retired candidate cannot even tie the argmin. `total` is the same in the
+      // quad's four lanes: the quad leaves together, the way a handed-on candidate does
+      if (prunable && !last && total / (double)(H > 1 ? H : 1) > q_from_bits(bound_bits)) { pruned = true; break; }
+    }
     QPROF(pf, 5);
     if (last) break;  // (the last step's mj_forward only feeds the sensor stage)
     double al[3], at[6], fc_l[3], fc_t[6];
@@ -2666,8 +2700,22 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
   }
 #undef QNODE
   if (leg == 0) {
-    a.total_return[cand] = flags ? 1.0e6 : total / (double)(H > 1 ? H : 1);
-    a.failure[cand] = flags ? (kQFallback | flags | (flag_step << 8)) : 0;  // (the step it was handed on at: diagnostics)
+    a.total_return[cand] = flags ? 1.0e6 : total / (double)(H > 1 ? H : 1);  // (a retired candidate's: its partial return, a lower bound above the bound)
+    a.failure[cand] = flags ? (kQFallback | flags | (flag_step << 8)) : pruned ? (kQPruned | (flag_step << 8)) : 0;  // (the step it was handed on / retired at)
+  }
+  if (prune) {
+    if (leg == 0) {
+      if (pruned) {
+        if (a.prune_stats) { q_count_add(a.prune_stats, 1); q_count_add(a.prune_stats + 1, flag_step); }
+      } else if (!flags) {
+        // a completed rollout's return is one the argmin can take: it lowers the bound (NaN and negative totals never do)
+        const double ret = total / (double)(H > 1 ? H : 1);
+        if (ret >= 0 && ret <= 1.79769313486231570815e308) q_bound_min(a.prune_bound, q_bits(ret));
+      }
+    }
+    // a wavefront all of whose candidates left before the last step has ended early and freed its SIMD
+    const bool to_the_end = !pruned && (!flags || flag_step >= H - 1);
+    if (a.prune_stats && !qw_any(to_the_end) && leg == 0 && cand % (a.cpw > 0 ? a.cpw : 16) == 0) q_count_add(a.prune_stats + 3, 1);
   }
   return flags;
 }

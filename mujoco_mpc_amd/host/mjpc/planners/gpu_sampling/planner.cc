@@ -2,6 +2,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <limits>
 #include <mutex>
 
 #include "../../utilities.h"
@@ -106,7 +108,23 @@ void GpuSamplingPlanner::SetSharding(int rank, int world, ExchangeFn exchange, v
 }
 
 // the device fan-out: noise + N rollouts + returns, one launch (sampling/planner.cc:355-393)
-void GpuSamplingPlanner::Rollouts(int num_trajectory, int horizon) {
+// A step's cost is sum_k weight_k * norm_k(residual_k), then the risk transform. Pruning needs it >= 0 in floating point, so it is on
+// only for weights >= 0, no risk transform, and the norm kinds whose computed value is shown to be >= 0 (DESIGN.md 4.6 has the
+// argument per kind): quadratic, L2 and smooth-abs (sqrt(c + p^2) - p with a correctly rounded, monotone sqrt), power loss, rectify.
+// kNull (the raw residual), and L22, cosh and smooth-abs2 (differences of pow / cosh values whose rounding is not shown) turn it off.
+bool GpuSamplingPlanner::CostIsNonNegative() const {
+  if (!(std::fabs(task->risk) < 1.0e-6)) return false;
+  for (size_t k = 0; k < task->weight.size(); k++) {
+    if (!(task->weight[k] >= 0)) return false;
+    switch (task->norm[k]) {
+      case kQuadratic: case kL2: case kPowerLoss: case kSmoothAbsLoss: case kRectifyLoss: break;
+      default: return false;
+    }
+  }
+  return true;
+}
+
+void GpuSamplingPlanner::Rollouts(int num_trajectory, int horizon, bool prune) {
   // this rank's slice of the global batch: contiguous ranges, the first (num_trajectory % world) ranks take one more
   if (world_ > num_trajectory) throw gpu::Error(MJPCX_EINVAL, "more ranks than candidates: every rank needs at least one rollout");
   const int q = num_trajectory / world_, r = num_trajectory % world_;
@@ -123,8 +141,13 @@ void GpuSamplingPlanner::Rollouts(int num_trajectory, int horizon) {
   const TimeSpline& plan = policy.plan;
   ctx_->SyncTask(*task);  // the per-plan frozen ResidualFn copy (agent.cc:319)
   ctx_->Check(mjpcx_set_state(ctx_->handle(), state.data(), time, mocap.data(), userdata.data()));
-  ctx_->Check(mjpcx_rollout_noise(ctx_->handle(), n_local, horizon, (int)plan.Size(), (int)plan.Interpolation(),
-                                  plan.times().data(), plan.values().data(), &ns));
+  // (the switch is sticky and the context is shared with the planners built on this one: on for this launch alone)
+  const bool pruned = prune && CostIsNonNegative();
+  if (pruned) ctx_->Check(mjpcx_set_pruning(ctx_->handle(), 1, std::numeric_limits<double>::infinity()));
+  const int rc = mjpcx_rollout_noise(ctx_->handle(), n_local, horizon, (int)plan.Size(), (int)plan.Interpolation(),
+                                     plan.times().data(), plan.values().data(), &ns);
+  if (pruned) (void)mjpcx_set_pruning(ctx_->handle(), 0, 0.0);
+  ctx_->Check(rc);
   num_rolled_ = n_local;
   best_valid_ = false;
   candidate_values_.clear();
@@ -200,13 +223,22 @@ void GpuSamplingPlanner::OptimizePolicy(int horizon, ThreadPool& pool) {
   UpdateNominalPolicy(horizon);
   const auto start = std::chrono::steady_clock::now();
   policy.plan.SetInterpolation(interpolation_);
-  Rollouts(num_trajectory_, horizon);
+  // only the argmin, the nominal's return and the winner's spline of this launch reach the policy: candidates that can no longer be the
+  // argmin are retired early
+  Rollouts(num_trajectory_, horizon, /*prune=*/true);
   // argmin + winner spline + trajectory[0].total_return in one launch and one sync
   int32_t index = 0;
   double best_return = 0, nominal_return = 0;
   std::vector<double> values(policy.plan.Size() * (size_t)model->nu);
-  ctx_->Check(mjpcx_best(ctx_->handle(), /*ref_candidate=*/offset_ == 0 ? 0 : -1, &index, &best_return, &nominal_return,
-                         values.data()));
+  int rc = mjpcx_best(ctx_->handle(), /*ref_candidate=*/offset_ == 0 ? 0 : -1, &index, &best_return, &nominal_return, values.data());
+  if (rc == MJPCX_ESTATE) {
+    // the pruned launch reported a negative step cost: its partial returns were no lower bounds (the only way to MJPCX_ESTATE with
+    // +inf as the initial bound -- a launch in which everything but the nominal was retired is valid and the nominal wins it). The
+    // same candidates again (same seed and iteration), all to the horizon: the policy stays exact
+    Rollouts(num_trajectory_, horizon, /*prune=*/false);
+    rc = mjpcx_best(ctx_->handle(), /*ref_candidate=*/offset_ == 0 ? 0 : -1, &index, &best_return, &nominal_return, values.data());
+  }
+  ctx_->Check(rc);
   index += offset_;  // global candidate index
   if (world_ > 1) {
     if (exchange_) {  // a transport lent by the caller (gloo in the CPU-side tests)

@@ -49,7 +49,10 @@ class GpuSamplingPlanner : public RankedPlanner {
   // candidates out again on the device (GpuRobustPlanner)
   void CandidatePlan(int candidate, spline::TimeSpline* out);
   void UpdateNominalPolicy(int horizon);
-  void Rollouts(int num_trajectory, int horizon);
+  // prune: candidates that can no longer be the argmin are retired early (mjpcx_set_pruning): only mjpcx_best may follow
+  void Rollouts(int num_trajectory, int horizon, bool prune = false);
+  // every step's cost is provably >= 0 (weights, norm kinds, risk): what pruning rests on
+  bool CostIsNonNegative() const;
 
   // Multi-GPU: one process per GPU, rank r rolls out global candidates [r*n, (r+1)*n) of num_trajectory_
   // (noise is keyed on the GLOBAL index, so results do not depend on the rank count). After the local

@@ -410,6 +410,13 @@ class HostPlanner:
         capi.lib().mjpcx_quad_stats(self._ctx(), capi.as_i32p(hh))
         return [int(x) for x in hh]
 
+    def prune_stats(self):
+        """mjpcx_prune_stats of the planner's last rollout: [0] candidates retired, [1] the sum of their retire steps, [2] the negative-cost
+        flag, [3] wavefronts that ended early (zeros unless the rollout was pruned)"""
+        h = (C.c_int64 * 4)()
+        capi.lib().mjpcx_prune_stats(self._ctx(), h)
+        return [int(x) for x in h]
+
     def algorithmic_bytes(self, horizon, num_nodes):
         return capi.lib().mjpcx_algorithmic_bytes(self._ctx(), horizon, num_nodes)
 
