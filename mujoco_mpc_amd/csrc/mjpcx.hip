@@ -338,7 +338,9 @@ __device__ __forceinline__ void lane_merge(RetIdx& v, int i, int k) {  // the st
   if (k > 2) lane_cmpx<2>(v, i, k);
   lane_cmpx<1>(v, i, k);
 }
+constexpr int kSortKeyBytes = sizeof(double) + sizeof(int);  // env_sort_keys' layout: n2 returns, then n2 indices
 constexpr int kCeLdsKeys = 8192;  // 12 bytes a key: 96 KiB of a CU's 160 KiB of LDS
+static_assert(kCeLdsKeys * kSortKeyBytes == 96 * 1024, "the keys sorted in LDS take 96 KiB");
 struct CeRecord { size_t bytes, off_index, off_ret, off_mean, off_var; };  // avg_return at 0
 // The selection (step 1 above), shared by ce_update_kernel and robust_select_kernel: every thread of a workgroup of 1024 calls it; on
 // return keys[0..n2) / idx[0..n2) hold the environment's returns and local indices in less_ri order, visible to the whole workgroup.
@@ -793,6 +795,21 @@ struct PinnedBlock {
     p = nullptr; cap = 0; last = nullptr; pending = false;
   }
 };
+// Grow-only pinned host block that kernels write through its device mapping (`dev`): the result records of the selection entry points,
+// each of which ends in a stream sync before it reads `p`.
+struct MappedBlock {
+  void* p = nullptr; void* dev = nullptr;
+  size_t cap = 0;
+  hipError_t reserve(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&dev, p, 0);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+  void release() { if (p) (void)hipHostFree(p); p = dev = nullptr; cap = 0; }
+};
 
 struct mjpcx_ctx {
   int device = 0, precision = 64;
@@ -814,8 +831,7 @@ struct mjpcx_ctx {
   struct Slot { PinnedBlock host; DevBuf dev; };  // host is marked behind the kernel that reads dev
   Slot slots[kSlots];
   int next_slot = 0;
-  // pinned + device-mapped result record of mjpcx_best
-  void* best_host = nullptr; void* best_dev = nullptr; size_t best_cap = 0;
+  MappedBlock result;  // the result record(s) of mjpcx_best and of the batched selection entry points
   hipEvent_t source_done = nullptr;  // mjpcx_robust_step_batched, mjpcx_ilqg_step_batched_from: orders this stream behind the source context's
   // the Sample-Gradient planner's state between plan steps (mjpcx_rollout_sample_gradient_batched / mjpcx_sample_gradient_update_batched)
   struct SampleGradient {
@@ -840,9 +856,8 @@ struct mjpcx_ctx {
   DevBuf d_grad;       // workspace of mjpcx_gradient_step_batched / mjpcx_ilqg_step_batched: inputs, every intermediate, the result block
   PinnedBlock h_grad;  // its pinned [inputs | result block] (those calls end in a sync)
   DevBuf d_states, d_actions, d_times, d_residual, d_costs, d_trace, d_ret, d_fail, d_sort, d_stage;
-  bool traj_candidate_major = false;
+  bool traj_candidate_major = false;  // layout of the last rollout's Trajectory buffers (true: wavefront-per-candidate kernels)
   int nsite_model = 0;
-  double xfrc_std = 0, xfrc_rate = 1; uint64_t xfrc_seed = 0; int xfrc_offset = 0;  // pending NoisyRollout request (0: plain Rollout)  // layout of the last rollout's Trajectory buffers (true: wavefront-per-candidate kernels)
   int N = 0, H = 0, P = 0;  // shape of the last rollout
   // several environments (mjpcx_set_states): E x [state | time | mocap] and, when given, E x the frozen residual state
   int env_E = 0;
@@ -1308,7 +1323,7 @@ hipError_t launch_tree(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
 }
 
 // The model records a rollout launch reads: the context's own (strides of 0), or -- a batched rollout while mjpcx_set_models_batched's models
-// are set -- environment 0's of the E records, with the bytes between consecutive environments'. do_rollout decides and hands it down.
+// are set -- environment 0's of the E records, with the bytes between consecutive environments'. do_rollout decides and hands it down to launch_wave.
 struct ModelRecords {
   bool per_env;
   const void *qmodel, *qtab, *limb, *image;
@@ -1521,21 +1536,184 @@ WaveModelT<T> env_models_view(const mjpcx_ctx* c, const WaveModelT<T>& own, int 
   return wm;
 }
 
+// What launch_wave takes from the context in one precision, and the one step that differs between the two: launching a generic kernel
+// (rollout_wave_kernel) by its id of wave32_launch.h over n candidates. fp64: this translation unit's instantiations; fp32: wave32.hip's.
+template <typename T> struct WaveSide;
+template <> struct WaveSide<double> {
+  static const WaveModel& model(const mjpcx_ctx* c) { return c->wh.m; }
+  static const WaveTask& task(const mjpcx_ctx* c) { return c->wh.t; }
+  static size_t blob_bytes(const mjpcx_ctx* c) { return c->wh.blob_bytes; }
+  static hipError_t launch(int which, int n, size_t lds, const WaveModel& m, const WaveTask& wt, const RolloutArgs<double>& a, hipStream_t stream) {
+    auto kern = which == kW32Rk4 ? w64::rollout_wave_kernel<32, false, true>
+              : which == kW32TreeRk4 ? w64::rollout_wave_kernel<32, true, true>
+              : which == kW32Tree ? w64::rollout_wave_kernel<32, true>
+              : which == kW32TreeSmall ? w64::rollout_wave_kernel<32, true, false, true>
+              : which == kW32Rows18 ? w64::rollout_wave_kernel<18> : which == kW32Rows20 ? w64::rollout_wave_kernel<20>
+              : which == kW32Rows28 ? w64::rollout_wave_kernel<28> : w64::rollout_wave_kernel<32>;
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(n), dim3(64), lds, stream, m, wt, a);
+    return hipGetLastError();
+  }
+};
+template <> struct WaveSide<float> {
+  static const WaveModelT<float>& model(const mjpcx_ctx* c) { return c->wh.m32; }
+  static const WaveTaskT<float>& task(const mjpcx_ctx* c) { return c->wh.t32; }
+  static size_t blob_bytes(const mjpcx_ctx* c) { return c->wh.blob_bytes32; }
+  template <class... Args> static hipError_t launch(Args&&... args) { return launch_wave_kernel_f32(args...); }
+};
+
+int reserve_wave_stamps(mjpcx_ctx* c) {  // (MJPCX_STAMPS: 48 zeroed cycle stamps)
+  HIPCHK(c, c->d_stage.reserve(48 * 8));
+  HIPCHK(c, hipMemsetAsync(c->d_stage.p, 0, 48 * 8, c->stream));
+  return MJPCX_OK;
+}
+
+// The rollout of a wavefront-per-candidate context (c->wave), both precisions: the kernel family is chosen and launched, and c->cur_main
+// recorded behind its first (dominant) kernel -- by launch_quad, launch_limb, launch_tree's first pass (unless only_flagged), here behind
+// the first of two generic passes, otherwise by do_rollout. *refused: a refusal that is no launch error, already reported through fail().
 template <typename T>
-int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node_times,
-               const double* node_values, const double* nominal, const mjpcx_noise_spec* ns, int E = 0, const double* variance_rows = nullptr,
-               bool nodes_on_device = false) {
-  // E = 0: the plain entry points (one environment, the state of mjpcx_set_state). E >= 1: N = E x n_per_env candidates, environment-major,
-  // from the states of mjpcx_set_states; node_times is E x P and nominal E x P*nu. Same launch code, same kernels. variance_rows
-  // (mjpcx_rollout_noise_batched_ce): E x P*nu cross-entropy variances, one row per environment, instead of ns->param_variance for all.
-  // nodes_on_device (mjpcx_robust_step_batched): a kernel enqueued on this stream has already written the N splines into d_nodes, which
-  // the caller reserved for this shape -- no host splines, no scatter, no sync.
+hipError_t launch_wave(mjpcx_ctx* c, const RolloutArgs<T>& a, const void* d_blob, const ModelRecords& mr, int E, int* refused) {
+  using Side = WaveSide<T>;
+  constexpr bool f64 = sizeof(T) == 8;
+  const int N = a.N, P = a.P, registered = c->wh.registered;
+  WaveTaskT<T> wt = Side::task(c);
+  wt.blob = (const T*)d_blob;
+  wt.stamps = nullptr;
+  if (c->stamp_step >= 0) {
+    if ((*refused = reserve_wave_stamps(c)) != MJPCX_OK) return hipSuccess;
+    wt.stamps = (long long*)c->d_stage.p;
+    wt.stamp_step = c->stamp_step;
+  }
+  const WaveModelT<T> wm = mr.per_env ? env_models_view(c, Side::model(c)) : Side::model(c);
+  const size_t blob_bytes = Side::blob_bytes(c);
+  const bool packed = a.xfrc_scale == 0 && !wt.stamps;  // the quad and limb kernels draw no force noise and carry no stamps
+  // A rank's share of the batch decides the kernel: the quad kernel packs 16 candidates into a wavefront, which fills the 1024 SIMDs
+  // at N = 16384 but leaves most of them idle below a quarter of that, where one wavefront per candidate (a third of the latency per
+  // step) is quicker -- measured cross-over on MI355X: N = 4096 (tools/quad_n_sweep.py; MJPCX_QUAD_MIN_N moves it)
+  if constexpr (f64)  // (the quad kernel is fp64 only: quad_ok is never set on an fp32 context)
+    if (registered == 0 && c->quad_ok && packed && N >= c->quad_min_n) return launch_quad(c, wm, wt, a, N, P, mr, /*plain=*/E == 0);
+  if (registered == 1 && c->limb_ok && packed && N >= c->limb_min_n) return launch_limb<T>(c, wm, wt, a, N, P, mr);
+  if (registered == 0 || (registered == 1 && wm.integrator != MJPCX_INT_RK4)) {
+    // mjpcx_quad_stats reports the LAST rollout, so a context that owns a hand-on counter (quad_ok: fp64 contexts only; limb_ok: either
+    // precision) clears it whenever it rolls out on the tree kernel instead: nothing was handed on in this one. An fp32 context of the A1
+    // has no counter and no mjpcx_quad_stats output to go stale, so one rule serves both precisions.
+    if (registered == 0 ? c->quad_ok : c->limb_ok) (void)hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream);
+    const hipError_t le = registered == 0 ? launch_tree<TreeCfgA1, T>(c, wm, wt, a, mr.image, blob_bytes, N, P)
+                                          : launch_tree<TreeCfgHumanoid, T>(c, wm, wt, a, mr.image, blob_bytes, N, P);
+    if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
+    return le;
+  }
+  // the generic kernels. The Jacobian-free constraint path for the models it covers: in two passes under Euler -- short contact lists for
+  // everybody, the long ones for the candidates that overflowed -- in one with the long lists under RK4 (one NMAX = 32 instantiation per
+  // kernel family carries mj_RungeKutta; the row-table kernel's lists overflow on a folded Humanoid)
+  const bool tree = c->wh.tree_ok && !c->no_tree;
+  const bool rk4 = wm.integrator == MJPCX_INT_RK4;
+  const bool two_pass = tree && !rk4 && !c->no_second_pass;
+  auto tree_lds = [&](bool big) {
+    const int caps = big ? (f64 ? w64::kTreeMaxSimpleBig : w32::kTreeMaxSimpleBig) : (f64 ? w64::kTreeMaxSimple : w32::kTreeMaxSimple);
+    const int capc = big ? (f64 ? w64::kTreeMaxConeBig : w32::kTreeMaxConeBig) : (f64 ? w64::kTreeMaxCone : w32::kTreeMaxCone);
+    const size_t elems = f64 ? w64::wave_lds_elems_tree(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, a.xfrc_scale > 0, caps, capc)
+                             : w32::wave_lds_elems_tree(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, a.xfrc_scale > 0, caps, capc);
+    return (sizeof(T) * elems + 15) & ~(size_t)15;
+  };
+  const size_t rows_elems = f64 ? w64::wave_lds_elems(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, wm.cone, /*nodes_in_lds=*/false, a.xfrc_scale > 0)
+                                : w32::wave_lds_elems(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, wm.cone, /*nodes_in_lds=*/false, a.xfrc_scale > 0);
+  const size_t lds_big = tree ? tree_lds(true) : (sizeof(T) * rows_elems + 15) & ~(size_t)15;
+  const size_t lds = two_pass ? tree_lds(false) : lds_big;
+  if (lds_big > 160 * 1024) { *refused = fail(c, MJPCX_EUNSUPPORTED, "model state does not fit the 160 KB LDS of a CU"); return hipSuccess; }
+  // the register-resident Cholesky is unrolled to NMAX columns: instantiations that fit the registered models exactly (A1:
+  // nv = 18, humanoid: 27) skip the padding columns' updates (humanoid: 30 % of the factorisation's instructions); the shipped tree
+  // models are registered, so one width serves the unregistered ones
+  const int kern_big = rk4 ? (tree ? kW32TreeRk4 : kW32Rk4) : tree ? kW32Tree
+                     : wm.nv <= 18 ? kW32Rows18 : wm.nv <= 20 ? kW32Rows20 : wm.nv <= 28 ? kW32Rows28 : kW32Rows32;
+  // one launch over the N candidates -- or, with a model per environment, one per environment on its model (this kernel reads the model
+  // through the pointers of its arguments: RolloutArgs::cand_base)
+  auto launch_generic = [&](int which, size_t lds_bytes, const RolloutArgs<T>& args) -> hipError_t {
+    if (!mr.per_env) return Side::launch(which, N, lds_bytes, wm, wt, args, c->stream);
+    const int n = N / E;
+    for (int e = 0; e < E; e++) {
+      RolloutArgs<T> ae = args;
+      ae.cand_base = e * n;
+      const hipError_t he = Side::launch(which, n, lds_bytes, env_models_view(c, Side::model(c), e), wt, ae, c->stream);
+      if (he != hipSuccess) return he;
+    }
+    return hipSuccess;
+  };
+  hipError_t le = launch_generic(two_pass ? kW32TreeSmall : kern_big, lds, a);
+  if (two_pass && le == hipSuccess) {
+    if (c->timing && c->cur_main) { if ((le = hipEventRecord(c->cur_main, c->stream)) == hipSuccess) c->cur_main = nullptr; }
+    RolloutArgs<T> a2 = a;
+    a2.noise.mode = -1;  // the first pass left every candidate's spline nodes in a.nodes
+    a2.only_overflowed = 1;
+    if (le == hipSuccess) le = launch_generic(kern_big, lds_big, a2);
+  }
+  if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, lds, tree);
+  return le;
+}
+
+// an event pair around one launch (kernel_ms of mjpcx_backward_pass / mjpcx_gradient_pass); destroyed on every way out of the call
+struct LaunchTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~LaunchTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  hipError_t start(hipStream_t s) {
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    return e == hipSuccess ? hipEventRecord(e0, s) : e;
+  }
+  hipError_t stop(hipStream_t s) { return hipEventRecord(e1, s); }
+  double ms() const { float t = 0; (void)hipEventElapsedTime(&t, e0, e1); return t; }  // (after the call's sync)
+};
+// The rollouts' timer (mjpcx_timing_*) keeps its events: with c->timing the context's next triple, created on first use, is this rollout's.
+// The first is recorded here, c->cur_main behind the rollout's first (dominant) kernel by whoever launches it, *e1 by do_rollout at the end.
+int begin_rollout_timing(mjpcx_ctx* c, hipEvent_t* e1) {
+  *e1 = nullptr;
+  if (!c->timing) return MJPCX_OK;
+  if (c->events_used == c->events.size()) {
+    hipEvent_t x, y, z;
+    HIPCHK(c, hipEventCreate(&x));
+    HIPCHK(c, hipEventCreate(&y));
+    c->events.emplace_back(x, y);
+    HIPCHK(c, hipEventCreate(&z));
+    c->events_main.push_back(z);
+  }
+  const hipEvent_t e0 = c->events[c->events_used].first;
+  *e1 = c->events[c->events_used].second;
+  c->cur_main = c->events_main[c->events_used];
+  c->events_used++;
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  return MJPCX_OK;
+}
+
+// One rollout, as every entry point asks for it. Exactly one source of the N splines: node_values, nominal + noise, or nodes_on_device.
+struct RolloutRequest {
+  int N, H, P, interp;
+  const double* node_times;  // P, or E x P
+  // 0: the plain entry points (one environment, the state of mjpcx_set_state). E >= 1: N = E x n_per_env candidates, environment-major,
+  // from the states of mjpcx_set_states; node_times is E x P and nominal E x P*nu. Same launch code, same kernels.
+  int E = 0;
+  const double* node_values = nullptr;  // N x P*nu host splines, candidate-major: scattered onto the device, and the call syncs
+  const double* nominal = nullptr; const mjpcx_noise_spec* noise = nullptr;  // the spline the device draws the candidates around, and how
+  // (mjpcx_rollout_noise_batched_ce) E x P*nu cross-entropy variances, one row per environment, instead of noise->param_variance for all
+  const double* variance_rows = nullptr;
+  // (mjpcx_robust_step_batched, mjpcx_rollout_sample_gradient_batched) a kernel enqueued on this stream has already written the N splines
+  // into d_nodes, which the caller reserved for this shape -- no host splines, no scatter, no sync
+  bool nodes_on_device = false;
+  // NoisyRollout: force noise of this standard deviation and rate (0: plain Rollout); given splines draw candidate j's stream at xfrc_offset + j
+  double xfrc_std = 0, xfrc_rate = 1; uint64_t xfrc_seed = 0; int xfrc_offset = 0;
+};
+
+template <typename T>
+int do_rollout(mjpcx_ctx* c, const RolloutRequest& r) {
+  const int N = r.N, H = r.H, P = r.P, E = r.E;
+  const double *const node_values = r.node_values, *const variance_rows = r.variance_rows;
+  const mjpcx_noise_spec* const ns = r.noise;
   int rc;
   if ((rc = reserve_rollout(c, N, H, P)) != MJPCX_OK) return rc;
   c->last_pruned = false;  // (launch_quad sets it)
   const int np = P * c->nu;
   RolloutArgs<T> a{};
-  a.N = N; a.H = H; a.P = P; a.interp = interp;
+  a.N = N; a.H = H; a.P = P; a.interp = r.interp;
   // a model per environment (mjpcx_set_models_batched; check_batched_args has compared the two E): the batched launches read the
   // environments' records, with their strides; everything else the context's own model, with strides of 0
   const ModelRecords mr = model_records(c, E > 0 && c->em.E > 0, sizeof(T) == 4);
@@ -1547,7 +1725,7 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   const bool ce = ns && ns->mode == MJPCX_NOISE_CROSS_ENTROPY;
   if (ce && !ns->param_variance && !variance_rows) return fail(c, MJPCX_EINVAL, "cross-entropy noise needs param_variance");
   const void* d_blob = nullptr;
-  if ((rc = stage_plan_inputs<T>(c, P, E, node_times, nominal, !ce ? nullptr : variance_rows ? variance_rows : ns->param_variance, variance_rows != nullptr, &a.node_times,
+  if ((rc = stage_plan_inputs<T>(c, P, E, r.node_times, r.nominal, !ce ? nullptr : variance_rows ? variance_rows : ns->param_variance, variance_rows != nullptr, &a.node_times,
                                  &a.nominal, &d_var, &slot, &d_blob, &a.env_stride)) != MJPCX_OK) return rc;
   a.env_n = E > 1 ? N / E : 0;
   if (!c->wave) a.init = (const LaneInit<T>*)d_blob;
@@ -1562,7 +1740,7 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
                        (const double*)c->d_in_nodes.p, (T*)c->d_nodes.p, N, np);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));  // pageable source buffer: make caller reuse safe
-  } else if (!nodes_on_device) {
+  } else if (!r.nodes_on_device) {
     a.noise.mode = ns->mode;
     a.noise.seed = ns->seed; a.noise.iteration = ns->iteration;
     a.noise.candidate_offset = ns->candidate_offset; a.noise.nominal_candidate = ns->nominal_candidate;
@@ -1573,165 +1751,22 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   a.residual = (T*)c->d_residual.p; a.costs = (T*)c->d_costs.p; a.trace = (T*)c->d_trace.p;
   a.total_return = (double*)c->d_ret.p; a.failure = (int*)c->d_fail.p;
   a.xfrc_decay = 0; a.xfrc_scale = 0; a.xfrc_seed = 0;
-  if (c->xfrc_std > 0) {  // Ornstein-Uhlenbeck in discrete time (trajectory.cc:149-150), at the planning timestep
-    a.xfrc_decay = std::exp(-(c->wave ? c->wh.m.timestep : c->hm64.timestep) / c->xfrc_rate);
-    a.xfrc_scale = c->xfrc_std * std::sqrt(1 - a.xfrc_decay * a.xfrc_decay);
-    a.xfrc_seed = c->xfrc_seed;
-    if (a.noise.mode < 0) a.noise.candidate_offset = c->xfrc_offset;
+  if (r.xfrc_std > 0) {  // Ornstein-Uhlenbeck in discrete time (trajectory.cc:149-150), at the planning timestep
+    a.xfrc_decay = std::exp(-(c->wave ? c->wh.m.timestep : c->hm64.timestep) / r.xfrc_rate);
+    a.xfrc_scale = r.xfrc_std * std::sqrt(1 - a.xfrc_decay * a.xfrc_decay);
+    a.xfrc_seed = r.xfrc_seed;
+    if (a.noise.mode < 0) a.noise.candidate_offset = r.xfrc_offset;
   }
 
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->timing) {
-    if (c->events_used == c->events.size()) {
-      hipEvent_t x, y;
-      HIPCHK(c, hipEventCreate(&x));
-      HIPCHK(c, hipEventCreate(&y));
-      c->events.emplace_back(x, y);
-      hipEvent_t z;
-      HIPCHK(c, hipEventCreate(&z));
-      c->events_main.push_back(z);
-    }
-    e0 = c->events[c->events_used].first; e1 = c->events[c->events_used].second;
-    c->cur_main = c->events_main[c->events_used];
-    c->events_used++;
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-  }
+  hipEvent_t e1;
+  if ((rc = begin_rollout_timing(c, &e1)) != MJPCX_OK) return rc;
   hipError_t le;
-  if constexpr (sizeof(T) == 8) {
-    if (c->wave) {
-      WaveTask wt = c->wh.t;
-      wt.blob = (const double*)d_blob;
-      wt.stamps = nullptr;
-      if (c->stamp_step >= 0) {
-        HIPCHK(c, c->d_stage.reserve(48 * 8));
-        HIPCHK(c, hipMemsetAsync(c->d_stage.p, 0, 48 * 8, c->stream));
-        wt.stamps = (long long*)c->d_stage.p;
-        wt.stamp_step = c->stamp_step;
-      }
-      const WaveModel wm = mr.per_env ? env_models_view(c, c->wh.m) : c->wh.m;
-      const void* image = mr.image;
-      // A rank's share of the batch decides the kernel: the quad kernel packs 16 candidates into a wavefront, which fills the 1024 SIMDs
-      // at N = 16384 but leaves most of them idle below a quarter of that, where one wavefront per candidate (a third of the latency per
-      // step) is quicker -- measured cross-over on MI355X: N = 4096 (tools/quad_n_sweep.py; MJPCX_QUAD_MIN_N moves it)
-      if (c->wh.registered == 0 && c->quad_ok && a.xfrc_scale == 0 && !wt.stamps && N >= c->quad_min_n) {
-        le = launch_quad(c, wm, wt, a, N, P, mr, /*plain=*/E == 0);
-      } else if (c->wh.registered == 0) {
-        if (c->quad_ok) (void)hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream);  // (mjpcx_quad_stats reports the LAST rollout: nothing was handed on in this one)
-        le = launch_tree<TreeCfgA1, double>(c, wm, wt, a, image, c->wh.blob_bytes, N, P);
-        if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
-      } else if (c->wh.registered == 1 && c->limb_ok && a.xfrc_scale == 0 && !wt.stamps && N >= c->limb_min_n) {
-        le = launch_limb<double>(c, wm, wt, a, N, P, mr);
-      } else if (c->wh.registered == 1 && wm.integrator != MJPCX_INT_RK4) {
-        if (c->limb_ok) (void)hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream);
-        le = launch_tree<TreeCfgHumanoid, double>(c, wm, wt, a, image, c->wh.blob_bytes, N, P);
-        if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
-      } else {
-      const bool tree = c->wh.tree_ok && !c->no_tree;
-      const bool rk4 = wm.integrator == MJPCX_INT_RK4;  // one (NMAX = 32) instantiation per kernel family carries mj_RungeKutta
-      // Jacobian-free path, Euler: two launches -- short contact lists for everybody, the long ones for the candidates that overflowed
-      const bool two_pass = tree && !rk4 && !c->no_second_pass;
-      auto tree_lds = [&](int caps, int capc) { return (8 * w64::wave_lds_elems_tree(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, a.xfrc_scale > 0, caps, capc) + 15) & ~(size_t)15; };
-      const size_t lds_big = tree ? tree_lds(w64::kTreeMaxSimpleBig, w64::kTreeMaxConeBig)
-                                  : (8 * w64::wave_lds_elems(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, wm.cone, /*nodes_in_lds=*/false, a.xfrc_scale > 0) + 15) & ~(size_t)15;
-      const size_t lds = two_pass ? tree_lds(w64::kTreeMaxSimple, w64::kTreeMaxCone) : lds_big;
-      if (lds_big > 160 * 1024) return fail(c, MJPCX_EUNSUPPORTED, "model state does not fit the 160 KB LDS of a CU");
-      // the register-resident Cholesky is unrolled to NMAX columns: instantiations that fit the registered models exactly (A1:
-      // nv = 18, humanoid: 27) skip the padding columns' updates (humanoid: 30 % of the factorisation's instructions)
-      auto kern_big = rk4 ? (tree ? w64::rollout_wave_kernel<32, true, true> : w64::rollout_wave_kernel<32, false, true>)
-                : tree ? w64::rollout_wave_kernel<32, true>  // (the shipped tree models are registered: one width serves the unregistered ones)
-                : wm.nv <= 18 ? w64::rollout_wave_kernel<18> : wm.nv <= 20 ? w64::rollout_wave_kernel<20>
-                : wm.nv <= 28 ? w64::rollout_wave_kernel<28> : w64::rollout_wave_kernel<32>;
-      auto kern = !two_pass ? kern_big
-                : w64::rollout_wave_kernel<32, true, false, true>;
-      // one launch over the N candidates -- or, with a model per environment, one per environment on its model (this kernel reads the model
-      // through the pointers of its arguments: RolloutArgs::cand_base)
-      auto launch_generic = [&](decltype(kern_big) k, size_t lds_bytes, const RolloutArgs<double>& args) -> hipError_t {
-        if (!mr.per_env) {
-          hipLaunchKernelGGL(k, dim3(N), dim3(64), lds_bytes, c->stream, wm, wt, args);
-          return hipGetLastError();
-        }
-        const int n = N / E;
-        for (int e = 0; e < E; e++) {
-          const WaveModel wme = env_models_view(c, c->wh.m, e);
-          RolloutArgs<double> ae = args;
-          ae.cand_base = e * n;
-          hipLaunchKernelGGL(k, dim3(n), dim3(64), lds_bytes, c->stream, wme, wt, ae);
-          const hipError_t he = hipGetLastError();
-          if (he != hipSuccess) return he;
-        }
-        return hipSuccess;
-      };
-      le = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (le == hipSuccess) le = launch_generic(kern, lds, a);
-      if (two_pass && le == hipSuccess) {
-        if (c->timing && c->cur_main) { if ((le = hipEventRecord(c->cur_main, c->stream)) == hipSuccess) c->cur_main = nullptr; }
-        RolloutArgs<double> a2 = a;
-        a2.noise.mode = -1;  // the first pass left every candidate's spline nodes in a.nodes
-        a2.only_overflowed = 1;
-        if (le == hipSuccess) le = hipFuncSetAttribute((const void*)kern_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big);
-        if (le == hipSuccess) le = launch_generic(kern_big, lds_big, a2);
-      }
-      if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, lds, tree);
-      }
-    } else {
-      le = c->kernel->launch64(c->hm64, c->ht64, a, c->stream);
-    }
-  } else if (c->wave) {
-    // the fp32 instantiation of the wavefront-per-candidate kernel (BASELINE configs[3]'s precision)
-    WaveTaskT<float> wt = c->wh.t32;
-    wt.blob = (const float*)d_blob;
-    wt.stamps = nullptr;
-    if (c->stamp_step >= 0) {
-      HIPCHK(c, c->d_stage.reserve(48 * 8));
-      HIPCHK(c, hipMemsetAsync(c->d_stage.p, 0, 48 * 8, c->stream));
-      wt.stamps = (long long*)c->d_stage.p;
-      wt.stamp_step = c->stamp_step;
-    }
-    const WaveModelT<float> wm = mr.per_env ? env_models_view(c, c->wh.m32) : c->wh.m32;
-    const void* image = mr.image;
-    if (c->wh.registered == 0) {
-      le = launch_tree<TreeCfgA1, float>(c, wm, wt, a, image, c->wh.blob_bytes32, N, P);
-      if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
-    } else if (c->wh.registered == 1 && c->limb_ok && a.xfrc_scale == 0 && !wt.stamps && N >= c->limb_min_n) {
-      le = launch_limb<float>(c, wm, wt, a, N, P, mr);
-    } else if (c->wh.registered == 1 && wm.integrator != MJPCX_INT_RK4) {
-      if (c->limb_ok) (void)hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream);
-      le = launch_tree<TreeCfgHumanoid, float>(c, wm, wt, a, image, c->wh.blob_bytes32, N, P);
-      if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, 0, true);
-    } else {
-    // (the Jacobian-free constraint path in fp32 for the models it covers, as in fp64: in two passes under Euler, in one with the long
-    // contact lists under RK4 -- the row-table kernel's lists overflow on a folded Humanoid)
-    const bool tree = c->wh.tree_ok && !c->no_tree;
-    const bool rk4 = wm.integrator == MJPCX_INT_RK4;
-    const bool two_pass = tree && !rk4 && !c->no_second_pass;
-    auto tree_lds = [&](int caps, int capc) { return (4 * w32::wave_lds_elems_tree(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, a.xfrc_scale > 0, caps, capc) + 15) & ~(size_t)15; };
-    const size_t lds_big = tree ? tree_lds(w32::kTreeMaxSimpleBig, w32::kTreeMaxConeBig)
-                                : (4 * w32::wave_lds_elems(wm.nq, wm.nv, wm.nu, wm.nbody, wm.njnt, wm.nsite, wt.nr, wt.nterm, P, wm.cone, /*nodes_in_lds=*/false, a.xfrc_scale > 0) + 15) & ~(size_t)15;
-    const size_t lds = two_pass ? tree_lds(w32::kTreeMaxSimple, w32::kTreeMaxCone) : lds_big;
-    if (lds_big > 160 * 1024) return fail(c, MJPCX_EUNSUPPORTED, "model state does not fit the 160 KB LDS of a CU");
-    const int kern_big = rk4 ? (tree ? kW32TreeRk4 : kW32Rk4) : tree ? kW32Tree
-                       : wm.nv <= 18 ? kW32Rows18 : wm.nv <= 20 ? kW32Rows20 : wm.nv <= 28 ? kW32Rows28 : kW32Rows32;
-    auto launch_generic = [&](int which, size_t lds_bytes, const RolloutArgs<float>& args) -> hipError_t {  // (as in fp64: per environment with a model each)
-      if (!mr.per_env) return launch_wave_kernel_f32(which, N, lds_bytes, wm, wt, args, c->stream);
-      const int n = N / E;
-      for (int e = 0; e < E; e++) {
-        RolloutArgs<float> ae = args;
-        ae.cand_base = e * n;
-        const hipError_t he = launch_wave_kernel_f32(which, n, lds_bytes, env_models_view(c, c->wh.m32, e), wt, ae, c->stream);
-        if (he != hipSuccess) return he;
-      }
-      return hipSuccess;
-    };
-    le = launch_generic(two_pass ? kW32TreeSmall : kern_big, lds, a);  // (the fp32 kernels live in wave32.hip)
-    if (two_pass && le == hipSuccess) {
-      if (c->timing && c->cur_main) { if ((le = hipEventRecord(c->cur_main, c->stream)) == hipSuccess) c->cur_main = nullptr; }
-      RolloutArgs<float> a2 = a;
-      a2.noise.mode = -1;
-      a2.only_overflowed = 1;
-      if (le == hipSuccess) le = launch_generic(kern_big, lds_big, a2);
-    }
-    if (wt.stamps && le == hipSuccess) print_wave_stamps(c, wt.stamps, wt.stamp_step, lds, tree);
-    }
+  if (c->wave) {
+    int refused = MJPCX_OK;
+    le = launch_wave<T>(c, a, d_blob, mr, E, &refused);
+    if (refused != MJPCX_OK) return refused;
+  } else if constexpr (sizeof(T) == 8) {
+    le = c->kernel->launch64(c->hm64, c->ht64, a, c->stream);
   } else {
     convert_task(c->ht32, c->ht64);
     le = c->kernel->launch32(c->hm32, c->ht32, a, c->stream);
@@ -1747,6 +1782,38 @@ int do_rollout(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node
   c->traj_candidate_major = c->wave;
   return MJPCX_OK;
 }
+int rollout(mjpcx_ctx* c, const RolloutRequest& r) { return c->precision == 64 ? do_rollout<double>(c, r) : do_rollout<float>(c, r); }
+
+// run(double{}) or run(float{}): one launch in the context's precision, for kernels that differ only in the element type of their buffers
+template <class Run>
+auto by_precision(const mjpcx_ctx* c, Run&& run) { return c->precision == 64 ? run(double{}) : run(float{}); }
+
+// A sort of every environment's n candidates by env_sort_keys (ce_update_kernel, robust_select_kernel, sg_update_kernel), one workgroup of
+// 1024 threads per environment and chunk: n2 keys (a power of two and a multiple of the workgroup) in dynamic LDS up to kCeLdsKeys, beyond
+// that in slabs of c->d_sort, the slab of (environment e, chunk k) at (e * chunks + k) * n2 keys.
+struct EnvSort {
+  int n2 = 1024;
+  bool in_lds;
+  size_t lds;
+  hipError_t reserve(mjpcx_ctx* c, int n, int E, int chunks = 1) {
+    while (n2 < n) n2 <<= 1;
+    in_lds = n2 <= kCeLdsKeys;
+    lds = in_lds ? (size_t)n2 * kSortKeyBytes : 0;
+    return in_lds ? hipSuccess : c->d_sort.reserve((size_t)E * chunks * n2 * kSortKeyBytes);
+  }
+  double* slabs(const mjpcx_ctx* c) const { return in_lds ? nullptr : (double*)c->d_sort.p; }
+  // launch(kernel, T{}) once kernel = pick(T{}, IN_LDS{}), a generic lambda that names the caller's Kernel<T, IN_LDS>, is allowed its LDS
+  template <class Pick, class Launch>
+  hipError_t dispatch(const mjpcx_ctx* c, Pick&& pick, Launch&& launch) const {
+    auto go = [&](auto tag, auto kern) {
+      const hipError_t e = in_lds ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+      if (e != hipSuccess) return e;
+      launch(kern, tag);
+      return hipGetLastError();
+    };
+    return by_precision(c, [&](auto tag) { return in_lds ? go(tag, pick(tag, std::true_type{})) : go(tag, pick(tag, std::false_type{})); });
+  }
+};
 
 int check_rollout_args(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node_times) {
   if (!c || !node_times) return fail(c, MJPCX_EINVAL, "null argument");
@@ -2042,7 +2109,7 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   for (auto& sl : c->slots) { sl.host.release(); sl.dev.release(); }
   c->h_ilqg.release();
   c->h_grad.release();
-  if (c->best_host) (void)hipHostFree(c->best_host);
+  c->result.release();
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
   if (c->source_done) (void)hipEventDestroy(c->source_done);
   c->sg.release();
@@ -2112,8 +2179,9 @@ int mjpcx_rollout_splines(mjpcx_ctx* c, int N, int H, int P, int interp, const d
   int rc = check_rollout_args(c, N, H, P, interp, node_times);
   if (rc != MJPCX_OK) return rc;
   if (!node_values) return fail(c, MJPCX_EINVAL, "null node_values");
-  return c->precision == 64 ? do_rollout<double>(c, N, H, P, interp, node_times, node_values, nullptr, nullptr)
-                            : do_rollout<float>(c, N, H, P, interp, node_times, node_values, nullptr, nullptr);
+  RolloutRequest r{N, H, P, interp, node_times};
+  r.node_values = node_values;
+  return rollout(c, r);
 }
 
 int mjpcx_rollout_splines_noisy(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node_times, const double* node_values,
@@ -2122,11 +2190,10 @@ int mjpcx_rollout_splines_noisy(mjpcx_ctx* c, int N, int H, int P, int interp, c
   if (rc != MJPCX_OK) return rc;
   if (!node_values) return fail(c, MJPCX_EINVAL, "null node_values");
   if (!(xfrc_std >= 0) || !(xfrc_rate > 0)) return fail(c, MJPCX_EINVAL, "xfrc_std must be >= 0 and xfrc_rate > 0");
-  c->xfrc_std = xfrc_std; c->xfrc_rate = xfrc_rate; c->xfrc_seed = seed; c->xfrc_offset = candidate_offset;
-  rc = c->precision == 64 ? do_rollout<double>(c, N, H, P, interp, node_times, node_values, nullptr, nullptr)
-                          : do_rollout<float>(c, N, H, P, interp, node_times, node_values, nullptr, nullptr);
-  c->xfrc_std = 0;
-  return rc;
+  RolloutRequest r{N, H, P, interp, node_times};
+  r.node_values = node_values;
+  r.xfrc_std = xfrc_std; r.xfrc_rate = xfrc_rate; r.xfrc_seed = seed; r.xfrc_offset = candidate_offset;
+  return rollout(c, r);
 }
 
 int mjpcx_rollout_noise(mjpcx_ctx* c, int N, int H, int P, int interp, const double* node_times,
@@ -2135,8 +2202,9 @@ int mjpcx_rollout_noise(mjpcx_ctx* c, int N, int H, int P, int interp, const dou
   if (rc != MJPCX_OK) return rc;
   if (!nominal || !ns) return fail(c, MJPCX_EINVAL, "null argument");
   if (ns->mode != MJPCX_NOISE_SAMPLING && ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "unknown noise mode");
-  return c->precision == 64 ? do_rollout<double>(c, N, H, P, interp, node_times, nullptr, nominal, ns)
-                            : do_rollout<float>(c, N, H, P, interp, node_times, nullptr, nominal, ns);
+  RolloutRequest r{N, H, P, interp, node_times};
+  r.nominal = nominal; r.noise = ns;
+  return rollout(c, r);
 }
 
 // ---- several environments per launch
@@ -2317,8 +2385,9 @@ int mjpcx_rollout_splines_batched(mjpcx_ctx* c, int E, int n, int H, int P, int 
   int rc = check_batched_args(c, E, n, H, P, interp, node_times);
   if (rc != MJPCX_OK) return rc;
   if (!node_values) return fail(c, MJPCX_EINVAL, "null node_values");
-  return c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E)
-                            : do_rollout<float>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E);
+  RolloutRequest r{E * n, H, P, interp, node_times, E};
+  r.node_values = node_values;
+  return rollout(c, r);
 }
 
 int mjpcx_rollout_splines_noisy_batched(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* node_values,
@@ -2327,11 +2396,10 @@ int mjpcx_rollout_splines_noisy_batched(mjpcx_ctx* c, int E, int n, int H, int P
   if (rc != MJPCX_OK) return rc;
   if (!node_values) return fail(c, MJPCX_EINVAL, "null node_values");
   if (!(xfrc_std >= 0) || !(xfrc_rate > 0)) return fail(c, MJPCX_EINVAL, "xfrc_std must be >= 0 and xfrc_rate > 0");
-  c->xfrc_std = xfrc_std; c->xfrc_rate = xfrc_rate; c->xfrc_seed = seed; c->xfrc_offset = candidate_offset;
-  rc = c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E)
-                          : do_rollout<float>(c, E * n, H, P, interp, node_times, node_values, nullptr, nullptr, E);
-  c->xfrc_std = 0;
-  return rc;
+  RolloutRequest r{E * n, H, P, interp, node_times, E};
+  r.node_values = node_values;
+  r.xfrc_std = xfrc_std; r.xfrc_rate = xfrc_rate; r.xfrc_seed = seed; r.xfrc_offset = candidate_offset;
+  return rollout(c, r);
 }
 
 int mjpcx_rollout_noise_batched(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* nominal,
@@ -2340,8 +2408,9 @@ int mjpcx_rollout_noise_batched(mjpcx_ctx* c, int E, int n, int H, int P, int in
   if (rc != MJPCX_OK) return rc;
   if (!nominal || !ns) return fail(c, MJPCX_EINVAL, "null argument");
   if (ns->mode != MJPCX_NOISE_SAMPLING && ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "unknown noise mode");
-  return c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E)
-                            : do_rollout<float>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E);
+  RolloutRequest r{E * n, H, P, interp, node_times, E};
+  r.nominal = nominal; r.noise = ns;
+  return rollout(c, r);
 }
 
 int mjpcx_rollout_noise_batched_ce(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* nominal,
@@ -2350,8 +2419,9 @@ int mjpcx_rollout_noise_batched_ce(mjpcx_ctx* c, int E, int n, int H, int P, int
   if (rc != MJPCX_OK) return rc;
   if (!nominal || !variance || !ns) return fail(c, MJPCX_EINVAL, "null argument");
   if (ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "mjpcx_rollout_noise_batched_ce: the noise mode must be MJPCX_NOISE_CROSS_ENTROPY");
-  return c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E, variance)
-                            : do_rollout<float>(c, E * n, H, P, interp, node_times, nullptr, nominal, ns, E, variance);
+  RolloutRequest r{E * n, H, P, interp, node_times, E};
+  r.nominal = nominal; r.noise = ns; r.variance_rows = variance;
+  return rollout(c, r);
 }
 
 int mjpcx_ce_update_batched(mjpcx_ctx* c, int E, int n_elite, int skip_candidate, int32_t* index, double* total_return, double* mean,
@@ -2366,39 +2436,23 @@ int mjpcx_ce_update_batched(mjpcx_ctx* c, int E, int n_elite, int skip_candidate
                                  " (the candidates of an environment without the skipped one)");
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
-  int n2 = 1024;  // (a multiple of the workgroup: ce_update_kernel)
-  while (n2 < n) n2 <<= 1;
   CeRecord rec;
   rec.off_index = 8;
   rec.off_ret = (rec.off_index + (size_t)n_elite * 4 + 7) & ~(size_t)7;
   rec.off_mean = rec.off_ret + (size_t)n_elite * 8;
   rec.off_var = rec.off_mean + (size_t)np * 8;
   rec.bytes = rec.off_var + (size_t)np * 8;
-  const size_t bytes = rec.bytes * E;
-  if (bytes > c->best_cap) {
-    if (c->best_host) (void)hipHostFree(c->best_host);
-    c->best_host = nullptr; c->best_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
-    c->best_cap = bytes;
-  }
-  const bool in_lds = n2 <= kCeLdsKeys;
-  const size_t lds = in_lds ? (size_t)n2 * 12 : 0;
-  if (!in_lds) HIPCHK(c, c->d_sort.reserve((size_t)E * n2 * 12));
-  auto launch = [&](auto kern, auto* nodes) {
-    hipError_t e = in_lds ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(E), dim3(1024), lds, c->stream, (const double*)c->d_ret.p, nodes, c->N, n, n2, np, n_elite, skip_candidate,
-                       in_lds ? nullptr : (double*)c->d_sort.p, (unsigned char*)c->best_dev, rec);
-    return hipGetLastError();
-  };
-  hipError_t le;
-  if (c->precision == 64) le = in_lds ? launch(ce_update_kernel<double, true>, (const double*)c->d_nodes.p) : launch(ce_update_kernel<double, false>, (const double*)c->d_nodes.p);
-  else le = in_lds ? launch(ce_update_kernel<float, true>, (const float*)c->d_nodes.p) : launch(ce_update_kernel<float, false>, (const float*)c->d_nodes.p);
+  HIPCHK(c, c->result.reserve(rec.bytes * E));
+  EnvSort sort;
+  HIPCHK(c, sort.reserve(c, n, E));
+  const hipError_t le = sort.dispatch(c, [](auto t, auto in_lds) { return ce_update_kernel<decltype(t), decltype(in_lds)::value>; }, [&](auto kern, auto t) {
+    hipLaunchKernelGGL(kern, dim3(E), dim3(1024), sort.lds, c->stream, (const double*)c->d_ret.p, (const decltype(t)*)c->d_nodes.p, c->N, n, sort.n2, np,
+                       n_elite, skip_candidate, sort.slabs(c), (unsigned char*)c->result.dev, rec);
+  });
   HIPCHK(c, le);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int e = 0; e < E; e++) {
-    const char* r = (const char*)c->best_host + rec.bytes * e;
+    const char* r = (const char*)c->result.p + rec.bytes * e;
     std::memcpy(index + (size_t)e * n_elite, r + rec.off_index, (size_t)n_elite * 4);
     if (total_return) std::memcpy(total_return + (size_t)e * n_elite, r + rec.off_ret, (size_t)n_elite * 8);
     if (mean) std::memcpy(mean + (size_t)e * np, r + rec.off_mean, (size_t)np * 8);
@@ -2415,24 +2469,17 @@ int mjpcx_best_batched(mjpcx_ctx* c, int E, int ref_candidate, int32_t* index, d
     return fail(c, MJPCX_EINVAL, "mjpcx_best_batched: the last rollout was not a batched one of " + std::to_string(E) + " environments");
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
-  const size_t rec = kBestHeader + (size_t)np * 8, bytes = rec * E;
-  if (bytes > c->best_cap) {
-    if (c->best_host) (void)hipHostFree(c->best_host);
-    c->best_host = nullptr; c->best_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
-    c->best_cap = bytes;
-  }
-  if (c->precision == 64)
-    hipLaunchKernelGGL((best_segmented_kernel<double>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
-                       (const double*)c->d_nodes.p, c->N, c->env_n, np, ref_candidate, (unsigned char*)c->best_dev, (unsigned)rec);
-  else
-    hipLaunchKernelGGL((best_segmented_kernel<float>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
-                       (const float*)c->d_nodes.p, c->N, c->env_n, np, ref_candidate, (unsigned char*)c->best_dev, (unsigned)rec);
+  const size_t rec = kBestHeader + (size_t)np * 8;
+  HIPCHK(c, c->result.reserve(rec * E));
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((best_segmented_kernel<T>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
+                       (const T*)c->d_nodes.p, c->N, c->env_n, np, ref_candidate, (unsigned char*)c->result.dev, (unsigned)rec);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int e = 0; e < E; e++) {
-    const BestRecord* r = (const BestRecord*)((const char*)c->best_host + rec * e);
+    const BestRecord* r = (const BestRecord*)((const char*)c->result.p + rec * e);
     index[e] = r->best_index;
     if (best_return) best_return[e] = r->best_return;
     if (ref_return) ref_return[e] = r->ref_return;
@@ -2471,52 +2518,33 @@ int mjpcx_robust_step_batched(mjpcx_ctx* c, mjpcx_ctx* src, int E, int k, int R,
   rec.off_valid = rec.off_score + (size_t)k * 8;
   rec.off_spline = (rec.off_valid + (size_t)k * 4 + 7) & ~(size_t)7;
   rec.bytes = rec.off_spline + (size_t)np * 8;
-  const size_t bytes = rec.bytes * E;
-  if (bytes > c->best_cap) {
-    if (c->best_host) (void)hipHostFree(c->best_host);
-    c->best_host = nullptr; c->best_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
-    c->best_cap = bytes;
-  }
-  int n2 = 1024;  // (a multiple of the workgroup: env_sort_keys)
-  while (n2 < n_src) n2 <<= 1;
-  const bool in_lds = n2 <= kCeLdsKeys;
-  const size_t lds = in_lds ? (size_t)n2 * 12 : 0;
-  if (!in_lds) HIPCHK(c, c->d_sort.reserve((size_t)E * n2 * 12));
+  HIPCHK(c, c->result.reserve(rec.bytes * E));
+  EnvSort sort;
+  HIPCHK(c, sort.reserve(c, n_src, E));
   // everything below is enqueued on this context's stream, behind what the source's stream holds now
   if (!c->source_done) HIPCHK(c, hipEventCreateWithFlags(&c->source_done, hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->source_done, src->stream));
   HIPCHK(c, hipStreamWaitEvent(c->stream, c->source_done, 0));
-  auto select = [&](auto kern, const auto* src_nodes, auto* nodes) {
-    hipError_t e = in_lds ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(E), dim3(1024), lds, c->stream, (const double*)src->d_ret.p, src_nodes, src->N, n_src, n2, np, k, R, n_pad,
-                       in_lds ? nullptr : (double*)c->d_sort.p, nodes, (unsigned char*)c->best_dev, rec);
-    return hipGetLastError();
-  };
-  hipError_t le;
-  if (c->precision == 64) le = in_lds ? select(robust_select_kernel<double, true>, (const double*)src->d_nodes.p, (double*)c->d_nodes.p)
-                                      : select(robust_select_kernel<double, false>, (const double*)src->d_nodes.p, (double*)c->d_nodes.p);
-  else le = in_lds ? select(robust_select_kernel<float, true>, (const float*)src->d_nodes.p, (float*)c->d_nodes.p)
-                   : select(robust_select_kernel<float, false>, (const float*)src->d_nodes.p, (float*)c->d_nodes.p);
+  const hipError_t le = sort.dispatch(c, [](auto t, auto in_lds) { return robust_select_kernel<decltype(t), decltype(in_lds)::value>; }, [&](auto kern, auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(kern, dim3(E), dim3(1024), sort.lds, c->stream, (const double*)src->d_ret.p, (const T*)src->d_nodes.p, src->N, n_src, sort.n2, np, k, R,
+                       n_pad, sort.slabs(c), (T*)c->d_nodes.p, (unsigned char*)c->result.dev, rec);
+  });
   HIPCHK(c, le);
   // local rollout j of environment e draws the stream (seed + e, candidate_offset + j): one launch of k x R rollouts per environment
-  c->xfrc_std = xfrc_std; c->xfrc_rate = xfrc_rate; c->xfrc_seed = seed; c->xfrc_offset = candidate_offset;
-  rc = c->precision == 64 ? do_rollout<double>(c, N, H, P, interp, node_times, nullptr, nullptr, nullptr, E, nullptr, /*nodes_on_device=*/true)
-                          : do_rollout<float>(c, N, H, P, interp, node_times, nullptr, nullptr, nullptr, E, nullptr, /*nodes_on_device=*/true);
-  c->xfrc_std = 0;
-  if (rc != MJPCX_OK) return rc;
-  if (c->precision == 64)
-    hipLaunchKernelGGL((robust_score_kernel<double>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
-                       (const double*)c->d_nodes.p, np, k, R, n_pad, (unsigned char*)c->best_dev, rec);
-  else
-    hipLaunchKernelGGL((robust_score_kernel<float>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
-                       (const float*)c->d_nodes.p, np, k, R, n_pad, (unsigned char*)c->best_dev, rec);
+  RolloutRequest noisy{N, H, P, interp, node_times, E};
+  noisy.nodes_on_device = true;
+  noisy.xfrc_std = xfrc_std; noisy.xfrc_rate = xfrc_rate; noisy.xfrc_seed = seed; noisy.xfrc_offset = candidate_offset;
+  if ((rc = rollout(c, noisy)) != MJPCX_OK) return rc;
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((robust_score_kernel<T>), dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
+                       (const T*)c->d_nodes.p, np, k, R, n_pad, (unsigned char*)c->result.dev, rec);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int e = 0; e < E; e++) {
-    const char* r = (const char*)c->best_host + rec.bytes * e;
+    const char* r = (const char*)c->result.p + rec.bytes * e;
     std::memcpy(best + e, r, 4);
     if (candidate) std::memcpy(candidate + (size_t)e * k, r + rec.off_index, (size_t)k * 4);
     if (candidate_return) std::memcpy(candidate_return + (size_t)e * k, r + rec.off_ret, (size_t)k * 8);
@@ -2579,13 +2607,15 @@ int mjpcx_rollout_sample_gradient_batched(mjpcx_ctx* c, int E, int n, int G, int
   a.grad_times = upload ? din + i_gt : dst + o_gt;
   a.grad_values = upload ? din + i_gv : dst + o_gv;
   a.noise_exploration = noise_exploration; a.seed = seed; a.iteration = (uint32_t)iteration;
-  if (c->precision == 64) hipLaunchKernelGGL((sg_candidates_kernel<double>), dim3((unsigned)(per_env * E)), dim3(256), 0, c->stream, a, (double*)c->d_nodes.p);
-  else hipLaunchKernelGGL((sg_candidates_kernel<float>), dim3((unsigned)(per_env * E)), dim3(256), 0, c->stream, a, (float*)c->d_nodes.p);
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((sg_candidates_kernel<T>), dim3((unsigned)(per_env * E)), dim3(256), 0, c->stream, a, (T*)c->d_nodes.p);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, s.h_in.mark(c->stream));
-  rc = c->precision == 64 ? do_rollout<double>(c, E * n, H, P, interp, node_times, nullptr, nullptr, nullptr, E, nullptr, /*nodes_on_device=*/true)
-                          : do_rollout<float>(c, E * n, H, P, interp, node_times, nullptr, nullptr, nullptr, E, nullptr, /*nodes_on_device=*/true);
-  if (rc != MJPCX_OK) return rc;
+  RolloutRequest r{E * n, H, P, interp, node_times, E};
+  r.nodes_on_device = true;
+  if ((rc = rollout(c, r)) != MJPCX_OK) return rc;
   s.serial = c->rollout_serial; s.n = n; s.seed = seed; s.iteration = (uint32_t)iteration;
   return MJPCX_OK;
 }
@@ -2627,40 +2657,24 @@ int mjpcx_sample_gradient_update_batched(mjpcx_ctx* c, int E, int G, int flags, 
   rec.off_spline = 32;
   rec.off_grad = rec.off_spline + (size_t)np * 8;
   rec.bytes = rec.off_grad + (size_t)np * 8;
-  const size_t bytes = rec.bytes * E;
-  if (bytes > c->best_cap) {
-    if (c->best_host) (void)hipHostFree(c->best_host);
-    c->best_host = nullptr; c->best_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
-    c->best_cap = bytes;
-  }
-  int n2 = 1024;  // (a multiple of the workgroup: env_sort_keys)
-  while (n2 < n) n2 <<= 1;
-  const bool in_lds = n2 <= kCeLdsKeys;
-  const size_t lds = in_lds ? (size_t)n2 * 12 : 0;
+  HIPCHK(c, c->result.reserve(rec.bytes * E));
   const int chunks = G > 0 ? (npairs + 3) / 4 : 1;
-  if (!in_lds) HIPCHK(c, c->d_sort.reserve(sE * chunks * n2 * 12));
+  EnvSort sort;
+  HIPCHK(c, sort.reserve(c, n, E, chunks));
   const double* din = (const double*)s.d_in.p;
   double* dst = (double*)s.d_state.p;
   SgUpdateArgs a{};
-  a.n = n; a.n2 = n2; a.P = P; a.nu = nu; a.G = G; a.num_noisy = nn; a.flags = flags;
+  a.n = n; a.n2 = sort.n2; a.P = P; a.nu = nu; a.G = G; a.num_noisy = nn; a.flags = flags;
   a.filter = filter; a.noise_exploration = noise_exploration; a.f0 = std::log(0.5 * nn + 1.0);
   a.seed = s.seed; a.iteration = s.iteration;
   a.times = din; a.nominal = din + sE * P; a.range = din + sE * P + sE * np;
   a.steps = (const double*)s.d_up.p; a.logs = a.steps + G;
   a.gradient = dst; a.gradient_previous = dst + sE * np; a.weights = (double*)s.d_weights.p;
   a.grad_times = dst + 2 * sE * np; a.grad_values = a.grad_times + sE * P;
-  auto launch = [&](auto kern, const auto* nodes) {
-    hipError_t e = in_lds ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(E, chunks), dim3(1024), lds, c->stream, (const double*)c->d_ret.p, nodes, a, in_lds ? nullptr : (double*)c->d_sort.p,
-                       (unsigned char*)c->best_dev, rec);
-    return hipGetLastError();
-  };
-  hipError_t le;
-  if (c->precision == 64) le = in_lds ? launch(sg_update_kernel<double, true>, (const double*)c->d_nodes.p) : launch(sg_update_kernel<double, false>, (const double*)c->d_nodes.p);
-  else le = in_lds ? launch(sg_update_kernel<float, true>, (const float*)c->d_nodes.p) : launch(sg_update_kernel<float, false>, (const float*)c->d_nodes.p);
+  const hipError_t le = sort.dispatch(c, [](auto t, auto in_lds) { return sg_update_kernel<decltype(t), decltype(in_lds)::value>; }, [&](auto kern, auto t) {
+    hipLaunchKernelGGL(kern, dim3(E, chunks), dim3(1024), sort.lds, c->stream, (const double*)c->d_ret.p, (const decltype(t)*)c->d_nodes.p, a, sort.slabs(c),
+                       (unsigned char*)c->result.dev, rec);
+  });
   HIPCHK(c, le);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (G > 0) {
@@ -2668,7 +2682,7 @@ int mjpcx_sample_gradient_update_batched(mjpcx_ctx* c, int E, int G, int flags, 
     if (compute) { s.weights_E = E; s.weights_n = nn; }
   }
   for (int e = 0; e < E; e++) {
-    const char* r = (const char*)c->best_host + rec.bytes * e;
+    const char* r = (const char*)c->result.p + rec.bytes * e;
     std::memcpy(index + e, r, 4);
     if (winner_type) std::memcpy(winner_type + e, r + 4, 4);
     if (best_return) std::memcpy(best_return + e, r + 8, 8);
@@ -2738,23 +2752,15 @@ int mjpcx_best(mjpcx_ctx* c, int ref_candidate, int32_t* index, double* best_ret
   if ((rc = pruned_launch_valid(c)) != MJPCX_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
-  const size_t bytes = sizeof(BestRecord) + (size_t)np * 8;
-  if (bytes > c->best_cap) {
-    if (c->best_host) (void)hipHostFree(c->best_host);
-    c->best_host = nullptr; c->best_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->best_host, bytes, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(&c->best_dev, c->best_host, 0));
-    c->best_cap = bytes;
-  }
-  if (c->precision == 64)
-    hipLaunchKernelGGL((best_kernel<double>), dim3(1), dim3(1024), 0, c->stream, (const double*)c->d_ret.p,
-                       (const int*)c->d_fail.p, (const double*)c->d_nodes.p, c->N, np, ref_candidate, (BestRecord*)c->best_dev);
-  else
-    hipLaunchKernelGGL((best_kernel<float>), dim3(1), dim3(1024), 0, c->stream, (const double*)c->d_ret.p,
-                       (const int*)c->d_fail.p, (const float*)c->d_nodes.p, c->N, np, ref_candidate, (BestRecord*)c->best_dev);
+  HIPCHK(c, c->result.reserve(sizeof(BestRecord) + (size_t)np * 8));
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((best_kernel<T>), dim3(1), dim3(1024), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p,
+                       (const T*)c->d_nodes.p, c->N, np, ref_candidate, (BestRecord*)c->result.dev);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const BestRecord* r = (const BestRecord*)c->best_host;
+  const BestRecord* r = (const BestRecord*)c->result.p;
   if ((rc = pruned_argmin_valid(c, r->best_return)) != MJPCX_OK) return rc;
   *index = r->best_index;
   if (best_return) *best_return = r->best_return;
@@ -2810,12 +2816,11 @@ int mjpcx_elite_moments(mjpcx_ctx* c, int n, const int32_t* candidates, const do
   if (n) HIPCHK(c, hipMemcpyAsync(d, candidates, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   if (mean) HIPCHK(c, hipMemcpyAsync(d + off_mean, mean, (size_t)np * 8, hipMemcpyHostToDevice, c->stream));
   const double* dmean = mean ? (const double*)(d + off_mean) : nullptr;
-  if (c->precision == 64)
-    hipLaunchKernelGGL((elite_moments_kernel<double>), dim3(np + 1), dim3(256), 0, c->stream, (const double*)c->d_nodes.p,
-                       (const double*)c->d_ret.p, (const int*)d, n, c->N, np, dmean, (double*)(d + off_out));
-  else
-    hipLaunchKernelGGL((elite_moments_kernel<float>), dim3(np + 1), dim3(256), 0, c->stream, (const float*)c->d_nodes.p,
-                       (const double*)c->d_ret.p, (const int*)d, n, c->N, np, dmean, (double*)(d + off_out));
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((elite_moments_kernel<T>), dim3(np + 1), dim3(256), 0, c->stream, (const T*)c->d_nodes.p, (const double*)c->d_ret.p,
+                       (const int*)d, n, c->N, np, dmean, (double*)(d + off_out));
+  });
   HIPCHK(c, hipGetLastError());
   std::vector<double> h(np + 1);
   HIPCHK(c, hipMemcpyAsync(h.data(), d + off_out, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2836,16 +2841,12 @@ int mjpcx_fetch_trajectory(mjpcx_ctx* c, int cand, mjpcx_traj_view* out) {
   const size_t total = (size_t)H * row;
   HIPCHK(c, c->d_stage.reserve((total + 2) * 8));
   const int blocks = (int)std::min<size_t>((total + 255) / 256, 1024);
-  if (c->precision == 64)
-    hipLaunchKernelGGL((gather_traj_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, (const double*)c->d_states.p,
-                       (const double*)c->d_actions.p, (const double*)c->d_times.p, (const double*)c->d_residual.p,
-                       (const double*)c->d_costs.p, (const double*)c->d_trace.p, c->N, H, ds, nu, nr, ntr3, cand,
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((gather_traj_kernel<T>), dim3(blocks), dim3(256), 0, c->stream, (const T*)c->d_states.p, (const T*)c->d_actions.p,
+                       (const T*)c->d_times.p, (const T*)c->d_residual.p, (const T*)c->d_costs.p, (const T*)c->d_trace.p, c->N, H, ds, nu, nr, ntr3, cand,
                        (double*)c->d_stage.p, c->traj_candidate_major ? 1 : 0);
-  else
-    hipLaunchKernelGGL((gather_traj_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, (const float*)c->d_states.p,
-                       (const float*)c->d_actions.p, (const float*)c->d_times.p, (const float*)c->d_residual.p,
-                       (const float*)c->d_costs.p, (const float*)c->d_trace.p, c->N, H, ds, nu, nr, ntr3, cand,
-                       (double*)c->d_stage.p, c->traj_candidate_major ? 1 : 0);
+  });
   HIPCHK(c, hipGetLastError());
   c->h_stage.resize(total);
   double ret = 0; int32_t fl = 0;
@@ -2878,12 +2879,10 @@ int mjpcx_fetch_spline(mjpcx_ctx* c, int cand, double* node_values) {
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
   HIPCHK(c, c->d_stage.reserve((size_t)np * 8));
-  if (c->precision == 64)
-    hipLaunchKernelGGL((gather_spline_kernel<double>), dim3((np + 63) / 64), dim3(64), 0, c->stream,
-                       (const double*)c->d_nodes.p, c->N, np, cand, (double*)c->d_stage.p);
-  else
-    hipLaunchKernelGGL((gather_spline_kernel<float>), dim3((np + 63) / 64), dim3(64), 0, c->stream,
-                       (const float*)c->d_nodes.p, c->N, np, cand, (double*)c->d_stage.p);
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((gather_spline_kernel<T>), dim3((np + 63) / 64), dim3(64), 0, c->stream, (const T*)c->d_nodes.p, c->N, np, cand, (double*)c->d_stage.p);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(node_values, c->d_stage.p, (size_t)np * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3195,18 +3194,6 @@ int launch_backward(mjpcx_ctx* c, Kernel kernel12, Kernel kernel16, int n, int m
   HIPCHK(c, hipGetLastError());
   return MJPCX_OK;
 }
-// an event pair around one launch (kernel_ms of mjpcx_backward_pass / mjpcx_gradient_pass); destroyed on every way out of the call
-struct LaunchTimer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~LaunchTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-  hipError_t start(hipStream_t s) {
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    return e == hipSuccess ? hipEventRecord(e0, s) : e;
-  }
-  hipError_t stop(hipStream_t s) { return hipEventRecord(e1, s); }
-  double ms() const { float t = 0; (void)hipEventElapsedTime(&t, e0, e1); return t; }  // (after the call's sync)
-};
 }  // namespace
 
 extern "C" {
@@ -3267,7 +3254,7 @@ int mjpcx_transition_fd(mjpcx_ctx* c, int Tn, const double* times, const double*
     HIPCHK(c, rec.slot->host.mark(c->stream));
     return download(c, {{A, base + w.A, sT * ndx * ndx * 8}, {B, base + w.B, sT * ndx * nu * 8}, {C, base + w.C, sT * nr * ndx * 8}, {D, base + w.D, sT * nr * nu * 8}});
   };
-  return c->precision == 64 ? run(double{}) : run(float{});
+  return by_precision(c, run);
 }
 
 int mjpcx_kinematics(mjpcx_ctx* c, double* xpos, double* xquat, double* xmat, double* xipos, double* site_xpos, double* subtree_com,

@@ -151,10 +151,10 @@ def test_resampling_against_exact_arithmetic(interp, nodes):
 # ------------------------------------------------------------------------------------------------ the update on injected returns
 class Fleet:
     """a context with a Sample-Gradient rollout of E environments to inject returns into; Cartpole (P = 3: an odd number of parameters,
-    the last pair half empty) or the A1 (P = 4, 48 parameters: six chunks of four pairs)"""
+    the last pair half empty; or `nodes` of them) or the A1 (P = 4, 48 parameters: six chunks of four pairs)"""
 
-    def __init__(self, model, precision, n):
-        self.model, self.precision, self.n = model, precision, n
+    def __init__(self, model, precision, n, num_envs=E, nodes=sel.P):
+        self.model, self.precision, self.n, self.num_envs = model, precision, n, num_envs
         if model == "A1":
             self.case = make_case("tree_a1")
             self.ctx = self.case.make_context()
@@ -162,27 +162,29 @@ class Fleet:
         else:
             self.case = None
             self.ctx = sel.make_context(model, precision)
-            self.times, self.task = np.tile(sel.TIMES, (E, 1)) + 0.01 * np.arange(E)[:, None], sel._task(model)
+            self.times = np.tile(np.linspace(sel.TIMES[0], sel.TIMES[-1], nodes), (num_envs, 1)) + 0.01 * np.arange(num_envs)[:, None]
+            self.task = sel._task(model)
         self.range = ctrlrange_of(self.task)
         self.nodes_per_spline = self.times.shape[1]
         self.num_parameters = self.nodes_per_spline * self.ctx.nu
-        self.nominal = np.random.default_rng(n).uniform(-0.2, 0.2, (E, self.nodes_per_spline, self.ctx.nu))
+        self.nominal = np.random.default_rng(n).uniform(-0.2, 0.2, (num_envs, self.nodes_per_spline, self.ctx.nu))
         self.seed, self.iteration = 77, 4
         self._normals = {}
 
     def normals(self, iteration):
         if iteration not in self._normals:
-            self._normals[iteration] = [oracle_normals(self.seed + e, self.n, self.num_parameters, iteration, first=1) for e in range(E)]
+            self._normals[iteration] = [oracle_normals(self.seed + e, self.n, self.num_parameters, iteration, first=1) for e in range(self.num_envs)]
         return self._normals[iteration]
 
     def rollout(self, num_gradient, upload):
+        num_envs = self.num_envs
         if self.case is not None:
-            push_states(self.case, self.ctx, list(range(E)))
+            push_states(self.case, self.ctx, list(range(num_envs)))
         else:
-            sel.set_fleet(self.ctx, self.model, E)
-        gv = np.zeros((E, num_gradient, self.nodes_per_spline, self.ctx.nu)) if upload else None
+            sel.set_fleet(self.ctx, self.model, num_envs)
+        gv = np.zeros((num_envs, num_gradient, self.nodes_per_spline, self.ctx.nu)) if upload else None
         self.ctx.rollout_sample_gradient_batched(self.n, num_gradient, 2, CUBIC, self.times, self.nominal, EXPLORATION, seed=self.seed,
-                                                 iteration=self.iteration, gradient_values=gv, gradient_times=self.times if upload else None, num_envs=E)
+                                                 iteration=self.iteration, gradient_values=gv, gradient_times=self.times if upload else None, num_envs=num_envs)
 
     def spline(self, e, c):
         return self.ctx.fetch_spline(e * self.n + c).reshape(-1)
@@ -240,26 +242,38 @@ def check_next_candidates(fleet, num_noisy, refs, gradient_filter, where):
 NOISY = (1, 63, 64, 65, 255, 256, 257)
 
 
-@pytest.mark.parametrize("n", [64, 256, 320, 1088])
-@pytest.mark.parametrize("model,precision", [("Cartpole", 64), ("Cartpole", 32), ("A1", 64)], ids=["Cartpole64", "Cartpole32", "A1"])
-def test_update_on_injected_returns(model, precision, n):
+SLAB_NODES = 9   # Cartpole: 9 parameters = 5 pairs = 2 chunks of four pairs (sel.P = 3 is one chunk: one slab per environment, no chunk factor)
+UPDATE_MODELS = {"Cartpole64": ("Cartpole", 64), "Cartpole32": ("Cartpole", 32), "A1": ("A1", 64)}
+UPDATE_CASES = [(name, n) for n in (64, 256, 320, 1088) for name in UPDATE_MODELS] + [("Cartpole64", sc.SCRATCH_FIRST), ("Cartpole32", sc.SCRATCH_FIRST)]
+
+
+@pytest.mark.parametrize("name,n", UPDATE_CASES, ids=[f"{name}-{n}" for name, n in UPDATE_CASES])
+def test_update_on_injected_returns(name, n):
     """mjpcx_sample_gradient_update_batched on returns the test chose (selection_cases: the minimum at every place and across every
     boundary of the reductions, ties, NaN, signed zeros, infinities, failed rollouts, the nominal as the minimum), a different case in each of
     the three environments, for every num_noisy that changes a path: index, winner_type and the winner's spline bit for bit,
     improvement and the returns exactly, the gradient within sample_gradient_cases.gradient_bound of planners.sample_gradient_update
     fed the oracle's normals, the next candidates within candidate_bound. Per num_noisy a two-step chain: the first step computes the
     weights from a zero gradient, the second (filter 0.3) uses them cached on the order over all candidates, with the gradient of the
-    first as gradient_previous."""
-    fleet = Fleet(model, precision, n)
-    ctx = fleet.ctx
-    rounds = sc.segmented_rounds(n)
+    first as gradient_previous.
+
+    n = 8256 is the first size sorted in the global slab (n2 = 16384), sg_update_kernel<T, false>: there the Cartpole alone, two
+    environments and SLAB_NODES nodes, so that with gradient candidates the grid is 2 environments x 2 chunks and slab (e, chunk)
+    must lie at (e * chunks + chunk) * 1.5 n2 doubles. What changes a path at that size is the number of chunks (num_gradient = 0: one;
+    > 0: two) and what is sorted (the noisy candidates when the weights are computed, every candidate otherwise): num_noisy = n, n - 1
+    and 257 cover them, each on every fifth round of cases; the boundaries of the reductions inside num_noisy are the smaller sizes'."""
+    model, precision = UPDATE_MODELS[name]
+    slab = n > sc.LDS_LAST
+    fleet = Fleet(model, precision, n, 2, SLAB_NODES) if slab else Fleet(model, precision, n)
+    ctx, E = fleet.ctx, fleet.num_envs
+    rounds = sc.segmented_rounds(n, E)
     nominal_best = [sc.Case("nominal-min", sc.with_min(n, 300 + n + e, 0)) for e in range(E)]
     rounds.append(nominal_best)
-    for num_noisy in sorted({m for m in NOISY + (n - 1, n) if 1 <= m <= n}):
+    for num_noisy in (257, n - 1, n) if slab else sorted({m for m in NOISY + (n - 1, n) if 1 <= m <= n}):
         num_gradient = n - num_noisy
         fleet.iteration = 4
         fleet.rollout(num_gradient, upload=num_gradient > 0)
-        for ri, cases in enumerate(rounds if num_noisy in (1, 64, n - 1, n) else rounds[::5] + [nominal_best]):
+        for ri, cases in enumerate(rounds if num_noisy in (1, 64, n - 1, n) and not slab else rounds[::5] + [nominal_best]):
             where = (model, precision, n, num_noisy, ri)
             sc.inject(ctx, np.concatenate([c.ret for c in cases]), np.concatenate([c.fail for c in cases]))
             out = update(ctx, E, BOTH, 1.0, num_gradient)
