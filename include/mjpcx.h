@@ -758,6 +758,31 @@ int mjpcx_set_pruning(mjpcx_ctx* ctx, int enabled, double initial_bound);
  * counters came back with the launch. */
 int mjpcx_prune_stats(mjpcx_ctx* ctx, int64_t* out /* 4 */);
 
+/* ---- parking: an UNPROVEN estimate of the launch's best return, used from the first step on ------------------------------
+ * Pruning's bound exists only once some candidate has completed. `hint` is the caller's guess of the best return the launch
+ * will find (a planner's previous best, say); nobody vouches for it. In a pruned launch a candidate other than the nominal
+ * whose partial return strictly exceeds the hint, and which the proven bound does not retire, is PARKED: it saves what it
+ * carries from step to step and leaves its wavefront. A settling pass on the stream right after the launch reads the final
+ * bound: a parked candidate whose partial return is strictly above it is retired exactly as pruning retires (same marker,
+ * same counters); every other one is resumed from its saved state in a second, smaller launch, pruned against the same
+ * bound, and ends bit-identical to an uninterrupted rollout. So the hint changes no result: a good one lets the likely
+ * losers leave before they slow their wavefronts, a bad one costs the remaining work of the candidates it parked, never
+ * a second rollout of the batch and never MJPCX_ESTATE. All of "After a pruned launch" above holds unchanged.
+ *
+ * Sticky. +inf turns it off (the default); negative or NaN: MJPCX_EINVAL. Ignored unless pruning is on and applies to the
+ * launch (mjpcx_set_pruning lists the launches that ignore pruning; they ignore the hint too). MJPCX_PARK=0 in the
+ * environment, read when the context is created, makes this call do nothing. */
+int mjpcx_set_park_hint(mjpcx_ctx* ctx, double hint);
+/* Of the last rollout (zeros unless it was pruned with a hint): counts [0] candidates parked, [1] of them retired by the
+ * settling pass, [2] resumed ([0] = [1] + [2]); resume_ms (may be NULL): the resume launch's time between two stream events,
+ * 0 if there was none. mjpcx_prune_stats counts [1] among its retirements, and those of the resume launch too. No
+ * synchronisation. */
+int mjpcx_park_stats(mjpcx_ctx* ctx, int64_t* counts /* 3 */, double* resume_ms);
+/* Which candidates the last rollout resumed and the step each was parked at (the first min(count, cap) of them, in the order of the
+ * resume list, which is not defined). Returns the count (>= 0), or a negative error code. For tests and tools: synchronises and copies
+ * candidate by candidate. */
+int mjpcx_park_resumed(mjpcx_ctx* ctx, int32_t* index, int32_t* step, int cap);
+
 /* Algorithmic bytes of one candidate rollout:
  * w*[H*(dim_state+nu+1+nr+3*ntrace+1) + P*nu + P + 2]. */
 int64_t mjpcx_algorithmic_bytes(const mjpcx_ctx* ctx, int horizon, int num_nodes);

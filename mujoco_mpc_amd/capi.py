@@ -34,6 +34,7 @@ EXPORTS = [
     "mjpcx_rollout_splines_noisy_batched", "mjpcx_robust_step_batched",
     "mjpcx_rollout_sample_gradient_batched", "mjpcx_sample_gradient_update_batched",
     "mjpcx_set_models_batched", "mjpcx_set_pruning", "mjpcx_prune_stats",
+    "mjpcx_set_park_hint", "mjpcx_park_stats", "mjpcx_park_resumed",
 ]
 
 SG_COMPUTE_WEIGHTS, SG_ZERO_GRADIENT = 1, 2   # MJPCX_SG_* flags of mjpcx_sample_gradient_update_batched
@@ -115,6 +116,9 @@ def lib():
         L.mjpcx_quad_stats.argtypes = [vp, c_i32p]
         L.mjpcx_set_pruning.argtypes = [vp, C.c_int, C.c_double]
         L.mjpcx_prune_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.mjpcx_set_park_hint.argtypes = [vp, C.c_double]
+        L.mjpcx_park_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        L.mjpcx_park_resumed.argtypes = [vp, c_i32p, c_i32p, C.c_int]
         L.mjpcx_algorithmic_bytes.restype = C.c_int64
         L.mjpcx_algorithmic_bytes.argtypes = [vp, C.c_int, C.c_int]
         L.mjpcx_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -662,6 +666,28 @@ class Context:
         self._chk(lib().mjpcx_prune_stats(self.handle, h))
         return dict(retired=int(h[0]), retire_step_sum=int(h[1]), mean_retire_step=(h[1] / h[0] if h[0] else 0.0), negative_cost=bool(h[2]),
                     wavefronts_ended_early=int(h[3]))
+
+    def set_park_hint(self, hint=float("inf")):
+        """mjpcx_set_park_hint: an unproven estimate of the next pruned launches' best return (sticky; +inf: off). No result depends on it"""
+        self._chk(lib().mjpcx_set_park_hint(self.handle, float(hint)))
+
+    def park_stats(self):
+        """of the last rollout (zeros unless it was pruned with a hint): candidates parked, of them retired by the settling pass / resumed, the resume launch's ms"""
+        h = (C.c_int64 * 3)()
+        ms = C.c_double(0.0)
+        self._chk(lib().mjpcx_park_stats(self.handle, h, C.byref(ms)))
+        return dict(parked=int(h[0]), settled_retired=int(h[1]), resumed=int(h[2]), resume_ms=float(ms.value))
+
+    def park_resumed(self):
+        """mjpcx_park_resumed: the candidates the last rollout resumed and the step each was parked at, sorted by candidate"""
+        n = lib().mjpcx_park_resumed(self.handle, None, None, 0)
+        if n < 0:
+            self._chk(n)
+        idx, step = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        if n > 0:
+            self._chk(min(lib().mjpcx_park_resumed(self.handle, as_i32p(idx), as_i32p(step), n), 0))
+        order = np.argsort(idx[:n])
+        return idx[:n][order], step[:n][order]
 
     def algorithmic_bytes(self, horizon, num_nodes):
         return lib().mjpcx_algorithmic_bytes(self.handle, int(horizon), int(num_nodes))

@@ -23,6 +23,7 @@
 #include "ilqg_batched.h"
 #include "rollout_wave.h"
 #include "quad_launch.h"
+#include "park_settle.h"
 #include "limb_launch.h"
 #include "wave32_launch.h"
 #include <type_traits>
@@ -936,6 +937,14 @@ struct mjpcx_ctx {
   bool last_pruned = false;       // the last rollout was launched with a bound: its returns hold lower bounds, only the argmin is exact
   int prune_h[4] = {0, 0, 0, 0};  // ... and its counters, read back with the hand-on count
   double prune_final = 0;         // ... and the bound word after the launch: min(initial bound, the returns completed inside the launch)
+  // parking on an unproven estimate of the launch's best return (mjpcx_set_park_hint; pruned launches only): the candidates the estimate
+  // condemns are set aside with their state, settled against the final bound (park_settle.h) and, if not retired, resumed in a second launch
+  bool park_allowed = true;       // MJPCX_PARK=0 at creation: mjpcx_set_park_hint does nothing
+  double park_hint = HUGE_VAL;    // +inf: off
+  DevBuf d_park_rec, d_resume;    // QArgs::park_records, the resume list
+  int64_t park_h[3] = {0, 0, 0};  // the last rollout's: candidates parked, retired by the settling pass, resumed
+  double park_resume_ms = 0;      // ... and its resume launch's event time
+  hipEvent_t park_ev[2] = {nullptr, nullptr};
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -1367,6 +1376,16 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
     if (a.noise.mode < 0) q.nominal_candidate = -1;  // (given splines have no nominal: no candidate is exempt)
   }
   c->last_pruned = pruned;
+  // (mjpcx_set_park_hint: a pruned launch only -- the settling pass needs its bound word)
+  const bool parking = pruned && c->park_allowed && c->park_hint < HUGE_VAL;
+  c->park_h[0] = c->park_h[1] = c->park_h[2] = 0; c->park_resume_ms = 0;
+  if (parking) {
+    if ((e = c->d_park_rec.reserve((size_t)N * quad::kQParkRec * sizeof(double))) != hipSuccess || (e = c->d_resume.reserve((size_t)N * sizeof(int))) != hipSuccess) return e;
+    q.park_hint = c->park_hint; q.park_records = (double*)c->d_park_rec.p;
+    // (a resumed candidate may get a wavefront of its own: a slab build needs one slab per candidate then)
+    if (quad::quad_uses_ovf_slab() && (e = c->d_qovf.reserve((size_t)N * quad::quad_ovf_doubles_per_wave() * sizeof(double))) != hipSuccess) return e;
+    if (quad::quad_uses_ovf_slab()) q.ovf_slab = (double*)c->d_qovf.p;
+  }
   if (c->quad_stamps) {
     if ((e = hipMemsetAsync(c->d_qstamps.p, 0, 512, c->stream)) != hipSuccess) return e;
     q.stamps = (long long*)c->d_qstamps.p;
@@ -1400,6 +1419,12 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
                      tot[2 * k] ? (double)tot[2 * k + 1] / tot[2 * k] : 0.0);
   }
   if (c->timing && c->cur_main) { if ((e = hipEventRecord(c->cur_main, c->stream)) != hipSuccess) return e; c->cur_main = nullptr; }
+  // the settling pass: parked candidates against the launch's final bound; its two counts ride on the readback below (words 14 and 15)
+  if (parking) {
+    hipLaunchKernelGGL(park_settle_kernel, dim3((N + 255) / 256), dim3(256), 0, c->stream, N, (const double*)a.total_return, a.failure,
+                       (const unsigned long long*)q.prune_bound, q.prune_stats, (int*)c->d_resume.p, (int*)c->d_qstats.p + 14);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
   if (c->quad_stamps) {
     long long h[64];
     (void)hipStreamSynchronize(c->stream);
@@ -1439,6 +1464,22 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
       if ((e = hipMemcpyAsync(c->h_qstats, c->d_qstats.p, pruned ? 64 : 32, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
       if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
       const int* h = static_cast<const int*>(c->h_qstats);
+      if (parking && h[15] > 0) {
+        // what the settling pass could not retire goes on from its records, pruned against the same bound word and never parked again; its
+        // hand-ons, retirements and the bound it may lower come back with a second copy of the block
+        const int parked = h[14], resumed = h[15];
+        quad::QArgs r = q;
+        r.park_hint = HUGE_VAL; r.resume_list = (const int*)c->d_resume.p; r.resume_n = resumed; r.cpw = 0;
+        for (int k = 0; k < 2; k++) if (!c->park_ev[k] && (e = hipEventCreate(&c->park_ev[k])) != hipSuccess) return e;
+        if ((e = hipEventRecord(c->park_ev[0], c->stream)) != hipSuccess) return e;
+        if ((e = quad::launch_resume_quad(mr.qmodel, mr.qtab, wt.blob, bo, r, (int*)c->d_qstats.p, c->stream)) != hipSuccess) return e;
+        if ((e = hipEventRecord(c->park_ev[1], c->stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(c->h_qstats, c->d_qstats.p, 64, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->park_ev[0], c->park_ev[1]) == hipSuccess) c->park_resume_ms = ms;
+        c->park_h[0] = parked; c->park_h[1] = parked - resumed; c->park_h[2] = resumed;
+      } else if (parking) { c->park_h[0] = c->park_h[1] = h[14]; }
       if (pruned) { for (int k = 0; k < 4; k++) c->prune_h[k] = h[10 + k]; std::memcpy(&c->prune_final, h + 8, 8); }
       if (h[0] == 0 && !c->quad_stats) return hipSuccess;
     } else if (pruned) return hipErrorOutOfMemory;
@@ -1938,6 +1979,7 @@ int mjpcx_create(const mjpcx_model* m, const mjpcx_task* t, int device, int prec
       c->quad_no_fallback = getenv("MJPCX_QUAD_NO_FALLBACK") != nullptr;
       c->no_quad_feedback = getenv("MJPCX_NO_QUAD_FEEDBACK") != nullptr;
       if (const char* e = getenv("MJPCX_QUAD_CON_CAP")) c->quad_con_cap = std::atoi(e);
+      if (const char* e = getenv("MJPCX_PARK")) c->park_allowed = std::atoi(e) != 0;    // (0: mjpcx_set_park_hint does nothing)
       if (const char* e = getenv("MJPCX_PRUNE")) c->prune_allowed = std::atoi(e) != 0;  // (0: mjpcx_set_pruning does nothing -- the same binary, A/B)
       if (const char* e = getenv("MJPCX_QUAD_MIN_N")) c->quad_min_n = std::atoi(e);
       if (const char* e = getenv("MJPCX_QUAD_CPW")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) c->quad_cpw = v; }
@@ -2111,12 +2153,13 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   c->h_grad.release();
   c->result.release();
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
+  for (hipEvent_t ev : c->park_ev) if (ev) (void)hipEventDestroy(ev);
   if (c->source_done) (void)hipEventDestroy(c->source_done);
   c->sg.release();
   c->em.release();
   (void)mjpcx_comm_destroy(c);
   c->wh.release();
-  DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
+  DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_park_rec, &c->d_resume, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
                     &c->d_states, &c->d_actions, &c->d_times, &c->d_residual, &c->d_costs, &c->d_trace, &c->d_ret,
                     &c->d_fail, &c->d_sort, &c->d_stage};
   for (DevBuf* b : bufs) b->release();
@@ -2935,6 +2978,35 @@ int mjpcx_set_pruning(mjpcx_ctx* c, int enabled, double initial_bound) {
   c->prune_on = enabled != 0 && c->prune_allowed;
   c->prune_initial = initial_bound;
   return MJPCX_OK;
+}
+
+int mjpcx_set_park_hint(mjpcx_ctx* c, double hint) {
+  if (!c) return MJPCX_EINVAL;
+  if (!(hint >= 0)) return fail(c, MJPCX_EINVAL, "the park hint is an estimate of a return: >= 0 (+inf for none)");
+  c->park_hint = c->park_allowed ? hint : HUGE_VAL;
+  return MJPCX_OK;
+}
+
+int mjpcx_park_stats(mjpcx_ctx* c, int64_t* counts, double* resume_ms) {
+  if (!c || !counts) return MJPCX_EINVAL;
+  for (int k = 0; k < 3; k++) counts[k] = c->last_pruned ? c->park_h[k] : 0;
+  if (resume_ms) *resume_ms = c->last_pruned ? c->park_resume_ms : 0.0;
+  return MJPCX_OK;
+}
+
+int mjpcx_park_resumed(mjpcx_ctx* c, int32_t* index, int32_t* step, int cap) {
+  if (!c || cap < 0 || (cap > 0 && (!index || !step))) return MJPCX_EINVAL;
+  const int n = c->last_pruned ? (int)c->park_h[2] : 0;
+  if (n == 0 || cap == 0) return n;
+  const int m = std::min(n, cap);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(index, c->d_resume.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<double> rec(quad::kQParkRec);
+  for (int i = 0; i < m; i++) {  // (a test's call: one small copy per resumed candidate)
+    HIPCHK(c, hipMemcpy(rec.data(), (const double*)c->d_park_rec.p + (size_t)index[i] * quad::kQParkRec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+    step[i] = (int32_t)rec[21];
+  }
+  return n;
 }
 
 int mjpcx_prune_stats(mjpcx_ctx* c, int64_t* out) {

@@ -9,7 +9,12 @@ namespace mjpcx {
 constexpr int kQFallback = 0x40000000;  // failure[] marker of a candidate the quad kernel handed on (cleared by the fallback pass)
 constexpr int kQPruned = 0x20000000;   // failure[] marker of a candidate retired because it could no longer be the argmin (QArgs::prune_bound): | (retire step << 8);
                                         // a bit of its own -- the fallback pass does not re-roll it and the hand-on statistics do not count it
+constexpr int kQParked = 0x10000000;   // failure[] marker of a candidate set aside on QArgs::park_hint: | (park step << 8). Never outlives a launch_quad: the settling pass
+                                        // (park_settle.h) rewrites it to kQPruned or puts the candidate on the resume list
 namespace quad {
+// doubles of a parked candidate's record (QArgs::park_records): trunk qpos 0-6, qvel 7-12, warm start 13-18, time 19, the total BEFORE the park
+// step's cost 20, the park step 21; then per leg l at 22 + 9 l: joint positions, velocities, warm start. What a candidate carries into a step
+constexpr int kQParkRec = 58;
 // the rollout request (RolloutArgs<double> of rollout_lane.h, flattened so that the CPU emulator can fill it too)
 struct QArgs {
   int N, H, P, interp;
@@ -39,6 +44,11 @@ struct QArgs {
   unsigned long long* prune_bound;  // nullptr: every candidate is rolled to the horizon. Otherwise one word holding the bits of a non-negative double in RETURN units (for those the
                                     // unsigned order of the bits is the numeric order): a return some candidate of this launch has achieved, or the caller's initial bound. A
                                     // candidate whose partial return strictly exceeds it is retired (kQPruned); one that completes lowers it. rollout_quad_kernel with env_n == 0 only
+  double park_hint = __builtin_huge_val();  // an UNPROVEN estimate of the launch's best return (+inf: off). A prunable candidate whose partial return strictly exceeds it, and
+                      // that prune_bound does not retire, writes its record, stores its partial return, is flagged kQParked and leaves; it never touches the bound word
+  double* park_records;  // [N][kQParkRec]; needed when park_hint is finite or resume_list is set
+  const int* resume_list;  // nullptr: every candidate from the plan state. Otherwise rollout_quad_resume_kernel: resume_n candidate indices; each continues from its record,
+  int resume_n;            // at the recorded step, with its nodes as they stand in `nodes`, pruned against prune_bound and never parked
   int* prune_stats;   // nullptr, or 4 ints: [0] candidates retired, [1] the sum of their retire steps, [2] != 0 if a step's cost was negative (the partial return is then no lower
                       // bound: the launch's pruning is invalid), [3] wavefronts all of whose candidates left before the last step
 };

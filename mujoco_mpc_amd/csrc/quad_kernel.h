@@ -218,7 +218,8 @@ constexpr size_t kQWaveLds = (kQWaveCon + kQWaveMl + kQWaveMt) * sizeof(double);
 
 // Workgroup = W wavefronts (W = 4 for the large batches: one per SIMD of a CU, sharing one model image; W = 1 spreads small batches
 // over the CUs). stats[0]: candidates handed to the fallback kernel, stats[1 + log2(flag)]: by reason.
-template <bool FEEDBACK>
+// RESUME: the wavefront's candidates are entries of a.resume_list (rollout<FEEDBACK, RESUME> of quad_step.h)
+template <bool FEEDBACK, bool RESUME = false>
 __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ gm0, const QuadTables* __restrict__ tab0, const double* __restrict__ blob0,
                                                  const QBlob& bo, const QArgs& a0, const QFeedback& fb, int* __restrict__ stats) {
   // the workgroup's environment (env_select.h; 0 of one unless a0.env_n is set), from its first candidate: that environment's blob, node
@@ -248,8 +249,9 @@ __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ g
   // its first lanes), so that its lock-step is over fewer candidates and it still uses every SIMD
   const int cpw = a.cpw > 0 ? a.cpw : 16;
   const int quad = (threadIdx.x & 63) >> 2, leg = threadIdx.x & 3;
-  const int cand = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * cpw + quad;
-  if (quad >= cpw || cand >= a.N) return;  // (whole quads leave together)
+  const int slot = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * cpw + quad;
+  if (quad >= cpw || slot >= (RESUME ? a.resume_n : a.N)) return;  // (whole quads leave together)
+  const int cand = RESUME ? a.resume_list[slot] : slot;
   QTask tk;
   tk.mocap = blob + bo.off_mocap; tk.weight = blob + bo.off_weight; tk.norm_p = blob + bo.off_normp; tk.norm_q = blob + bo.off_normq;
   tk.param = blob + bo.off_param; tk.re = blob + bo.off_rreal; tk.ri = reinterpret_cast<const int*>(blob + bo.off_rint); tk.risk = blob[bo.off_risk];
@@ -265,7 +267,7 @@ __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ g
   QProf pf{nullptr, 0};
   if (a.stamps && blockIdx.x == 0 && threadIdx.x < 64) { pf.buf = a.stamps; pf.last = __builtin_readcyclecounter(); }
   const long long wave_t0 = a.wave_times ? __builtin_readcyclecounter() : 0;
-  const int flags = rollout<FEEDBACK>(sm, *tab, sp, tk, blob, blob[bo.off_time], a, fb, cand, leg, cs, ms, pf);
+  const int flags = rollout<FEEDBACK, RESUME>(sm, *tab, sp, tk, blob, blob[bo.off_time], a, fb, cand, leg, cs, ms, pf);
   if (a.wave_times && (threadIdx.x & 63) == 0) a.wave_times[4 * ((blockIdx.x * blockDim.x + threadIdx.x) >> 6)] = __builtin_readcyclecounter() - wave_t0;
   if (flags && leg == 0 && stats) {
     atomicAdd(stats, 1);
@@ -275,6 +277,12 @@ __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ g
 __global__ __launch_bounds__(256) void rollout_quad_kernel(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob,
                                                            const QBlob bo, const QArgs a, int* __restrict__ stats) {
   quad_kernel_body<false>(gm, tab, blob, bo, a, QFeedback{}, stats);
+}
+// The candidates a launch with QArgs::park_hint set aside and its settling pass (park_settle.h) could not retire: a.resume_n of them, a.cpw per
+// wavefront, each from its record. Same outputs, flags and hand-on counters as rollout_quad_kernel
+__global__ __launch_bounds__(256) void rollout_quad_resume_kernel(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob,
+                                                                  const QBlob bo, const QArgs a, int* __restrict__ stats) {
+  quad_kernel_body<false, true>(gm, tab, blob, bo, a, QFeedback{}, stats);
 }
 // The iLQG rollouts (the nominal under iLQGPolicy::Action, the line search's under the index policy) on the same step function: one or ten
 // candidates, ONE per wavefront (QArgs::cpw = 1) -- pure per-step latency, and the quad form's step is the shortest of the kernels' (0.145 ms

@@ -22,4 +22,6 @@ bool quad_uses_ovf_slab();  // (whether this build keeps a lane's contacts beyon
 hipError_t launch_feedback_quad(const void* model, const void* tables, const double* blob, const QBlob& bo, const QArgs& a, const QFeedback& fb, int* stats,
                                 hipStream_t stream);
 hipError_t launch_rollout_quad(const void* model, const void* tables, const double* blob, const QBlob& bo, const QArgs& a, int* stats, hipStream_t stream);
+// the candidates of a.resume_list (device memory, a.resume_n entries, known to the host) from their park records; outputs, flags and hand-on as launch_rollout_quad
+hipError_t launch_resume_quad(const void* model, const void* tables, const double* blob, const QBlob& bo, const QArgs& a, int* stats, hipStream_t stream);
 } }

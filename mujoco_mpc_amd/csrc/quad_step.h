@@ -2533,11 +2533,23 @@ QD void feedback_ctrl(const QFeedback& fb, double alpha, int t, const QState& S,
   }
 }
 
+// A parked candidate's record (QArgs::park_records, kQParkRec doubles: quad_abi.h): the quad's four lanes share it as they share a trajectory
+// row. Out of line: the rare path's stores stay out of the step loop's register allocation
+QNOINLINE void park_write(double* rec, const QState* S_in, double total_before, int t, int leg) {
+  const QState& S = *S_in;
+  if (leg == 0) { QUNROLL for (int k = 0; k < 7; k++) rec[k] = S.tq[k]; rec[19] = S.time; rec[20] = total_before; rec[21] = (double)t; }
+  if (leg == 1) QUNROLL for (int k = 0; k < 6; k++) rec[7 + k] = S.tv[k];
+  if (leg == 2) QUNROLL for (int k = 0; k < 6; k++) rec[13 + k] = S.wt[k];
+  QUNROLL for (int j = 0; j < 3; j++) { rec[22 + 9 * leg + j] = S.lq[j]; rec[25 + 9 * leg + j] = S.lv[j]; rec[28 + 9 * leg + j] = S.wl[j]; }
+}
+
 // One lane's share of one candidate's rollout. `state0` = qpos[19] qvel[18] of the plan (Planner::SetState), `con` the lane's contact
 // list storage (kQMaxCon records). Returns the flag bits (0: rolled out; otherwise failure[cand] carries kQFallback and the
 // wavefront-per-candidate kernel takes the candidate over).
 // FEEDBACK: the candidate follows the iLQG feedback policy `fb` (Trajectory::RolloutDiscrete / Rollout with iLQGPolicy::Action) instead of a spline
-template <bool FEEDBACK, class CS, class MS, class QProfT>
+// RESUME: the candidate was parked (QArgs::park_hint) by an earlier launch: its nodes stand in a.nodes, and it continues from its record
+// (a.park_records) at the recorded step. The candidates of a wavefront are then at different steps and times
+template <bool FEEDBACK, bool RESUME = false, class CS, class MS, class QProfT>
 QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp, const QTask& tk, const double* state0, double time0, const QArgs& a,
                const QFeedback& fb, int cand, int leg, CS& cs, MS& ms, QProfT& pf) {
   const QuadLeg& L = m.leg[leg];
@@ -2545,7 +2557,7 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
   const size_t N = (size_t)a.N;
   const double fb_alpha = FEEDBACK ? fb.alpha[cand] : 0.0;
   // ---- the candidate's spline nodes of this leg's three actuators (AddNoiseToPolicy)
-  if (!FEEDBACK && a.noise_mode >= 0) {
+  if (!FEEDBACK && !RESUME && a.noise_mode >= 0) {
     const int gi = a.candidate_offset + cand;
     double std = a.std0;
     if (a.noise_mode == 0 && a.std1 > 0) { if (bernoulli_uniform(a.seed, (uint32_t)gi, a.iteration) < 0.2) std = a.std1; }
@@ -2572,20 +2584,30 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
   }
 #define QNODE(p, e) a.nodes[(size_t)((p) * nu + 3 * leg + (e)) * N + cand]
   QState S;
-  QUNROLL for (int k = 0; k < 7; k++) S.tq[k] = state0[k];
-  QUNROLL for (int j = 0; j < 3; j++) { S.lq[j] = state0[7 + 3 * leg + j]; S.lv[j] = state0[19 + 6 + 3 * leg + j]; S.wl[j] = 0; }
-  QUNROLL for (int k = 0; k < 6; k++) { S.tv[k] = state0[19 + k]; S.wt[k] = 0; }
-  S.time = time0;
-  const size_t ds = 37;
   double total = 0;
+  int t_first = 0;
+  if (RESUME) {
+    // what the candidate carried into its park step, as the park branch below wrote it
+    const double* rec = a.park_records + (size_t)cand * kQParkRec;
+    QUNROLL for (int k = 0; k < 7; k++) S.tq[k] = rec[k];
+    QUNROLL for (int k = 0; k < 6; k++) { S.tv[k] = rec[7 + k]; S.wt[k] = rec[13 + k]; }
+    QUNROLL for (int j = 0; j < 3; j++) { S.lq[j] = rec[22 + 9 * leg + j]; S.lv[j] = rec[25 + 9 * leg + j]; S.wl[j] = rec[28 + 9 * leg + j]; }
+    S.time = rec[19]; total = rec[20]; t_first = (int)rec[21];
+  } else {
+    QUNROLL for (int k = 0; k < 7; k++) S.tq[k] = state0[k];
+    QUNROLL for (int j = 0; j < 3; j++) { S.lq[j] = state0[7 + 3 * leg + j]; S.lv[j] = state0[19 + 6 + 3 * leg + j]; S.wl[j] = 0; }
+    QUNROLL for (int k = 0; k < 6; k++) { S.tv[k] = state0[19 + k]; S.wt[k] = 0; }
+    S.time = time0;
+  }
+  const size_t ds = 37;
   double ctrl[3] = {0, 0, 0};
   int flags = 0, flag_step = 0;
   // retiring candidates that can no longer be the argmin (QArgs::prune_bound): every step's cost is >= 0, so the running sum is a lower
   // bound of the return; the nominal is always rolled out (its return is the plan step's `improvement` reference)
   const bool prune = !FEEDBACK && a.prune_bound != nullptr;
   const bool prunable = prune && a.candidate_offset + cand != a.nominal_candidate;
-  bool pruned = false;
-  for (int t = 0; t < H; t++) {
+  bool pruned = false, parked = false;
+  for (int t = t_first; t < H; t++) {
     flag_step = t;
     const long long step_t0 = QCLASS_NOW(a);
     const bool last = t == H - 1;
@@ -2595,7 +2617,7 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
       if (FEEDBACK) feedback_ctrl(fb, fb_alpha, t, S, leg, ufb);
       // policy: TimeSpline::Sample + Clamp (SamplingPolicy::Action)
       int up = 0;
-      const double now = QUNIFORM_TIME(S.time);
+      const double now = RESUME ? S.time : QUNIFORM_TIME(S.time);
       while (!FEEDBACK && up < P && a.node_times[up] <= now) up++;
       QUNROLL for (int e = 0; e < 3; e++) {
         double u;
@@ -2657,6 +2679,7 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
       if (leg == 0) { QREC(a.times[(size_t)cand * H + t], S.time); QREC(a.costs[(size_t)cand * H + t], cost); }
       if (leg == 1) { QUNROLL for (int q = 0; q < kQMaxTrace; q++) if (q < m.ntrace) QUNROLL for (int k = 0; k < 3; k++) QREC(a.trace[((size_t)cand * H + t) * 3 * m.ntrace + 3 * q + k], f.trace[q][k]); }
     }
+    const double total_before = total;
     total += cost;
     if (a.con_cap > 0 && qd_or(D.ncon > a.con_cap ? 1 : 0)) { flags = kFlagOverflow; break; }
     if (prune) {
@@ -2665,6 +2688,14 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
       // point) > bound = a return that was achieved, so the retired candidate cannot even tie the argmin. `total` is the same in the
       // quad's four lanes: the quad leaves together, the way a handed-on candidate does
       if (prunable && !last && total / (double)(H > 1 ? H : 1) > q_from_bits(bound_bits)) { pruned = true; break; }
+      // not retired, but above the caller's estimate of the launch's best return: set aside. The estimate proves nothing, so the candidate
+      // keeps what it carried into this step (S is untouched until euler below; the total without this step's cost); the settling pass
+      // retires it if its partial return is above a return that WAS achieved, and rollout<RESUME> repeats this step and goes on otherwise
+      if (!RESUME && prunable && !last && total / (double)(H > 1 ? H : 1) > a.park_hint) {
+        park_write(a.park_records + (size_t)cand * kQParkRec, &S, total_before, t, leg);
+        parked = true;
+        break;
+      }
     }
     QPROF(pf, 5);
     if (last) break;  // (the last step's mj_forward only feeds the sensor stage)
@@ -2700,22 +2731,22 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
   }
 #undef QNODE
   if (leg == 0) {
-    a.total_return[cand] = flags ? 1.0e6 : total / (double)(H > 1 ? H : 1);  // (a retired candidate's: its partial return, a lower bound above the bound)
-    a.failure[cand] = flags ? (kQFallback | flags | (flag_step << 8)) : pruned ? (kQPruned | (flag_step << 8)) : 0;  // (the step it was handed on / retired at)
+    a.total_return[cand] = flags ? 1.0e6 : total / (double)(H > 1 ? H : 1);  // (a retired candidate's: its partial return, a lower bound above the bound; a parked one's: its partial return, which the settling pass compares with the final bound)
+    a.failure[cand] = flags ? (kQFallback | flags | (flag_step << 8)) : pruned ? (kQPruned | (flag_step << 8)) : parked ? (kQParked | (flag_step << 8)) : 0;  // (the step it was handed on / retired / parked at)
   }
   if (prune) {
     if (leg == 0) {
       if (pruned) {
         if (a.prune_stats) { q_count_add(a.prune_stats, 1); q_count_add(a.prune_stats + 1, flag_step); }
-      } else if (!flags) {
+      } else if (!flags && !parked) {
         // a completed rollout's return is one the argmin can take: it lowers the bound (NaN and negative totals never do)
         const double ret = total / (double)(H > 1 ? H : 1);
         if (ret >= 0 && ret <= 1.79769313486231570815e308) q_bound_min(a.prune_bound, q_bits(ret));
       }
     }
     // a wavefront all of whose candidates left before the last step has ended early and freed its SIMD
-    const bool to_the_end = !pruned && (!flags || flag_step >= H - 1);
-    if (a.prune_stats && !qw_any(to_the_end) && leg == 0 && cand % (a.cpw > 0 ? a.cpw : 16) == 0) q_count_add(a.prune_stats + 3, 1);
+    const bool to_the_end = !pruned && !parked && (!flags || flag_step >= H - 1);
+    if (!RESUME && a.prune_stats && !qw_any(to_the_end) && leg == 0 && cand % (a.cpw > 0 ? a.cpw : 16) == 0) q_count_add(a.prune_stats + 3, 1);
   }
   return flags;
 }

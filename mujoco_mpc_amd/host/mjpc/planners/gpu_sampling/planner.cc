@@ -22,6 +22,7 @@ void GpuSamplingPlanner::Initialize(mjModel* m, const Task& t) {
   num_trajectory_ = GetNumberOrDefault(10, m, "sampling_trajectories");
   interpolation_ = (SplineInterpolation)GetNumberOrDefault((int)spline::kCubicSpline, m, "sampling_representation");
   sliding_plan_ = GetNumberOrDefault(0, m, "sampling_sliding_plan");
+  park_slack = GetNumberOrDefault(kDefaultParkSlack, m, "sampling_park_slack");
   winner = 0;
 }
 
@@ -55,6 +56,17 @@ void GpuSamplingPlanner::Reset(int horizon, const double* initial_repeated_actio
   improvement = 0.0;
   best_return = nominal_return = 0.0;
   winner = 0;
+  hint_valid_ = false;
+}
+
+// what a step's cost is made of besides the state: a best return found under other values says nothing about the next launch's
+std::vector<double> GpuSamplingPlanner::TaskSignature() const {
+  std::vector<double> s(task->weight);
+  s.insert(s.end(), task->parameters.begin(), task->parameters.end());
+  for (NormType k : task->norm) s.push_back((double)(int)k);
+  s.insert(s.end(), task->norm_parameter.begin(), task->norm_parameter.end());
+  s.push_back(task->risk);
+  return s;
 }
 
 double GpuSamplingPlanner::PlanningTimestep() const {
@@ -124,7 +136,7 @@ bool GpuSamplingPlanner::CostIsNonNegative() const {
   return true;
 }
 
-void GpuSamplingPlanner::Rollouts(int num_trajectory, int horizon, bool prune) {
+void GpuSamplingPlanner::Rollouts(int num_trajectory, int horizon, bool prune, double park_hint) {
   // this rank's slice of the global batch: contiguous ranges, the first (num_trajectory % world) ranks take one more
   if (world_ > num_trajectory) throw gpu::Error(MJPCX_EINVAL, "more ranks than candidates: every rank needs at least one rollout");
   const int q = num_trajectory / world_, r = num_trajectory % world_;
@@ -144,9 +156,10 @@ void GpuSamplingPlanner::Rollouts(int num_trajectory, int horizon, bool prune) {
   // (the switch is sticky and the context is shared with the planners built on this one: on for this launch alone)
   const bool pruned = prune && CostIsNonNegative();
   if (pruned) ctx_->Check(mjpcx_set_pruning(ctx_->handle(), 1, std::numeric_limits<double>::infinity()));
+  if (pruned) ctx_->Check(mjpcx_set_park_hint(ctx_->handle(), park_hint >= 0 ? park_hint : std::numeric_limits<double>::infinity()));
   const int rc = mjpcx_rollout_noise(ctx_->handle(), n_local, horizon, (int)plan.Size(), (int)plan.Interpolation(),
                                      plan.times().data(), plan.values().data(), &ns);
-  if (pruned) (void)mjpcx_set_pruning(ctx_->handle(), 0, 0.0);
+  if (pruned) { (void)mjpcx_set_pruning(ctx_->handle(), 0, 0.0); (void)mjpcx_set_park_hint(ctx_->handle(), std::numeric_limits<double>::infinity()); }
   ctx_->Check(rc);
   num_rolled_ = n_local;
   best_valid_ = false;
@@ -225,7 +238,14 @@ void GpuSamplingPlanner::OptimizePolicy(int horizon, ThreadPool& pool) {
   policy.plan.SetInterpolation(interpolation_);
   // only the argmin, the nominal's return and the winner's spline of this launch reach the policy: candidates that can no longer be the
   // argmin are retired early
-  Rollouts(num_trajectory_, horizon, /*prune=*/true);
+  // ... and the ones the previous plan's best return condemns are set aside from the first step on, to be settled once the launch's own
+  // bound is known (mjpcx_set_park_hint: no result depends on the hint)
+  const std::vector<double> signature = TaskSignature();
+  double hint = std::numeric_limits<double>::infinity();
+  if (hint_valid_ && park_slack > -1.0 && signature == hint_task_) hint = hint_best_ * (1.0 + park_slack);
+  park_hint_used = hint;
+  Rollouts(num_trajectory_, horizon, /*prune=*/true, hint);
+  ctx_->Check(mjpcx_park_stats(ctx_->handle(), park_counts, nullptr));
   // argmin + winner spline + trajectory[0].total_return in one launch and one sync
   int32_t index = 0;
   double best_return = 0, nominal_return = 0;
@@ -261,6 +281,10 @@ void GpuSamplingPlanner::OptimizePolicy(int horizon, ThreadPool& pool) {
   SetWinner(index, values);
   this->best_return = best_return;
   this->nominal_return = nominal_return;
+  // the next plan's hint: the best of all ranks, unless this plan's resume launch shows that the estimate it ran on was stale
+  hint_best_ = best_return;
+  hint_task_ = signature;
+  hint_valid_ = std::isfinite(best_return) && best_return >= 0 && !((double)park_counts[2] > kParkMaxResumeShare * (double)std::max(num_rolled_, 1));
   improvement = mju_max(nominal_return - best_return, 0.0);
   policy_update_compute_time = GetDuration(update_start);
 }

@@ -10,6 +10,7 @@
 #pragma once
 #include <atomic>
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <shared_mutex>
 #include <vector>
@@ -50,7 +51,8 @@ class GpuSamplingPlanner : public RankedPlanner {
   void CandidatePlan(int candidate, spline::TimeSpline* out);
   void UpdateNominalPolicy(int horizon);
   // prune: candidates that can no longer be the argmin are retired early (mjpcx_set_pruning): only mjpcx_best may follow
-  void Rollouts(int num_trajectory, int horizon, bool prune = false);
+  // park_hint: an unproven estimate of the launch's best return for a pruned launch (mjpcx_set_park_hint; +inf: none)
+  void Rollouts(int num_trajectory, int horizon, bool prune = false, double park_hint = std::numeric_limits<double>::infinity());
   // every step's cost is provably >= 0 (weights, norm kinds, risk): what pruning rests on
   bool CostIsNonNegative() const;
 
@@ -101,6 +103,16 @@ class GpuSamplingPlanner : public RankedPlanner {
   // plan on the differentiable model copy (MakeDifferentiable, agent.cc:156-164); set before Allocate. Off, as in the reference,
   // for sampling on its own; GpuILQSPlanner turns it on so that both of its halves plan on one model.
   bool differentiable = false;
+  // OptimizePolicy's park hint is the previous plan's best return x (1 + park_slack): the nominal is the previous winner, so the launch's
+  // best is at most the nominal's return, which is near the previous best while the state moves little between plans. slack <= -1: no hint.
+  // ("sampling_park_slack" in the model; the default is read off the closed-loop slack table)
+  double park_slack = kDefaultParkSlack;
+  static constexpr double kDefaultParkSlack = 0.05;
+  // a plan whose resume launch held more than this share of the batch was planned on a stale estimate: the next plan gets no hint
+  static constexpr double kParkMaxResumeShare = 0.25;
+  // of the last OptimizePolicy: candidates parked, retired by the settling pass, resumed (mjpcx_park_stats), and the hint it used (+inf: none)
+  std::int64_t park_counts[3] = {0, 0, 0};
+  double park_hint_used = std::numeric_limits<double>::infinity();
   mutable std::shared_mutex mtx_;
 
  private:
@@ -122,6 +134,11 @@ class GpuSamplingPlanner : public RankedPlanner {
   Trajectory best_;
   bool best_valid_ = false;
   int num_rolled_ = 0;
+  // the park hint's source: the previous OptimizePolicy's (global) best return, valid while the task's cost terms are what they were
+  bool hint_valid_ = false;
+  double hint_best_ = 0;
+  std::vector<double> hint_task_;  // weights, parameters, norm kinds and parameters, risk of the plan hint_best_ came from
+  std::vector<double> TaskSignature() const;
 };
 
 }  // namespace mjpc

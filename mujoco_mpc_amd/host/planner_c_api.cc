@@ -468,6 +468,21 @@ int mjpc_planner_best_trajectory(void* h, double* states, double* actions, doubl
     return -1;
   }
 }
+// the sampling planner's park hint (GpuSamplingPlanner::park_slack; <= -1: no hint). Returns -1 for the other planners
+int mjpc_planner_park_set(void* h, double slack) {
+  Handle* H = static_cast<Handle*>(h);
+  if (!H->ps) return -1;
+  H->ps->park_slack = slack;
+  return 0;
+}
+// of the last OptimizePolicy: out[0..2] candidates parked, retired by the settling pass, resumed; out[3] the hint it used (+inf: none)
+int mjpc_planner_park_info(void* h, double* out) {
+  Handle* H = static_cast<Handle*>(h);
+  if (!H->ps) return -1;
+  for (int k = 0; k < 3; k++) out[k] = (double)H->ps->park_counts[k];
+  out[3] = H->ps->park_hint_used;
+  return 0;
+}
 // the underlying mjpcx context (timing, algorithmic bytes, kernel name)
 mjpcx_ctx* mjpc_planner_ctx(void* h) { return static_cast<Handle*>(h)->context()->handle(); }
 

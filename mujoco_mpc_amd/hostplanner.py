@@ -84,6 +84,8 @@ def lib():
         L.mjpc_planner_best_score.restype = C.c_double
         L.mjpc_planner_best_score.argtypes = [vp]
         L.mjpc_planner_policy.argtypes = [vp, c_f64p, c_f64p, C.c_int]
+        L.mjpc_planner_park_set.argtypes = [vp, C.c_double]
+        L.mjpc_planner_park_info.argtypes = [vp, c_f64p]
         L.mjpc_planner_ctx.restype = vp
         L.mjpc_planner_ctx.argtypes = [vp]
         _LIB = L
@@ -416,6 +418,16 @@ class HostPlanner:
         h = (C.c_int64 * 4)()
         capi.lib().mjpcx_prune_stats(self._ctx(), h)
         return [int(x) for x in h]
+
+    def park_set(self, slack):
+        """the sampling planner's park hint is its previous best return x (1 + slack) (mjpcx_set_park_hint); slack <= -1: no hint"""
+        self._chk(lib().mjpc_planner_park_set(self.h, float(slack)))
+
+    def park_info(self):
+        """of the last optimize_policy: candidates parked, retired by the settling pass, resumed, and the hint it used (inf: none)"""
+        h = np.zeros(4)
+        self._chk(lib().mjpc_planner_park_info(self.h, as_f64p(h)))
+        return dict(parked=int(h[0]), settled_retired=int(h[1]), resumed=int(h[2]), hint=float(h[3]))
 
     def algorithmic_bytes(self, horizon, num_nodes):
         return capi.lib().mjpcx_algorithmic_bytes(self._ctx(), horizon, num_nodes)

@@ -1,0 +1,86 @@
+// quademu_park.cc -- TEST INFRASTRUCTURE: the emulator (quademu.cc, included whole) running the three stages of a launch with a park hint
+// (QArgs::park_hint, quad_abi.h) on the host: the main pass (rollout<false>), the settling rule of csrc/park_settle.h as a plain loop, and
+// the resume pass (rollout<false, true>) over the candidates the rule could not retire. The emulator's wavefront is one quad, so each
+// candidate may be given a hint of its own: that is how a test parks a chosen candidate at a chosen step.
+// tests/test_quad_park_emulator.py drives it.
+#include "quademu.cc"
+
+extern "C" {
+
+// Given candidates. bound_bits in/out: the bits of the initial bound; the final bound afterwards (NULL: a plain launch, nothing retired
+// or parked -- the reference the tests compare with, under the same con_cap). hints[N]: each candidate's park hint
+// (+inf: never parked). resume_unpruned != 0: the resume pass runs without a bound word, every resumed candidate to the horizon (the round
+// trip of a record is then comparable with the uninterrupted rollout for every candidate). con_cap: QArgs::con_cap.
+// Out: prune_stats[4]; park_step[N] (-1: never parked); resumed[N] (1: went through the resume pass); counts[3] parked, retired by the
+// settling rule, resumed; bound_settle: the bound the settling rule read.
+int quademu_rollout_parked(const mjpcx_model* model, const mjpcx_task* task, const double* state, double time, const double* mocap, int N, int H, int P,
+                           int interp, const double* node_times, const double* node_values, int nominal_candidate, unsigned long long* bound_bits,
+                           const double* hints, int resume_unpruned, int con_cap, int* prune_stats, int* park_step, int* resumed, int* counts,
+                           double* bound_settle, double* states, double* actions, double* times, double* residual, double* costs, double* trace,
+                           double* total_return, int* failure) {
+  Built* b = new Built;
+  if (!build(model, task, mocap, *b).empty()) { delete b; return -1; }
+  const int nu = model->nu;
+  std::vector<double> nodes((size_t)P * nu * N, 0.0);  // [P][nu][N]
+  for (int c = 0; c < N; c++) for (int j = 0; j < P * nu; j++) nodes[(size_t)j * N + c] = node_values[(size_t)c * P * nu + j];
+  std::vector<double> records((size_t)N * kQParkRec, 0.0);
+  QArgs a{};
+  a.N = N; a.H = H; a.P = P; a.interp = interp; a.node_times = node_times; a.nodes = nodes.data();
+  a.noise_mode = -1; a.nominal_candidate = nominal_candidate; a.cpw = 1; a.con_cap = con_cap;
+  a.states = states; a.actions = actions; a.times = times; a.residual = residual; a.costs = costs; a.trace = trace; a.total_return = total_return; a.failure = failure;
+  a.prune_bound = bound_bits; a.prune_stats = bound_bits ? prune_stats : nullptr; a.park_records = records.data();
+  for (int s = 0; s < b->qm.nstatic; s++) static_pose(b->qm, mocap, s, b->sp[s]);
+  // (at most 16 threads: a GPU test runs this on a machine that reports far more CPUs than the process may use)
+  const unsigned hw = std::min(std::thread::hardware_concurrency(), 16u);
+  const int nquads = (int)std::max(1u, std::min(hw / 4, (unsigned)N));
+  // a pass over `count` slots, a quad of threads per candidate, several quads at a time
+  auto pass = [&](int count, auto&& one) {
+    std::atomic<int> next{0};
+    std::vector<std::thread> pool;
+    for (int q = 0; q < nquads; q++)
+      pool.emplace_back([&] {
+        for (;;) {
+          const int slot = next.fetch_add(1);
+          if (slot >= count) break;
+          run_quad([&](int leg) {
+            QContact con[kQMaxCon];
+            EmuStore cs{con};
+            EmuProf pf;
+            EmuM ms;
+            one(slot, leg, cs, ms, pf);
+          });
+        }
+      });
+    for (auto& t : pool) t.join();
+  };
+  pass(N, [&](int cand, int leg, EmuStore& cs, EmuM& ms, EmuProf& pf) {
+    QArgs mine = a;
+    mine.park_hint = hints[cand];
+    (void)rollout<false>(b->qm, b->qt, b->sp, b->tk, state, time, mine, QFeedback{}, cand, leg, cs, ms, pf);
+  });
+  // the settling rule (csrc/park_settle.h), against the bound the main pass left
+  counts[0] = counts[1] = counts[2] = 0;
+  for (int c = 0; c < N; c++) { park_step[c] = -1; resumed[c] = 0; }
+  if (!bound_bits) { delete b; return 0; }
+  const double bf = q_from_bits(*bound_bits);
+  *bound_settle = bf;
+  std::vector<int> list;
+  for (int c = 0; c < N; c++) {
+    const int f = failure[c];
+    if (!(f & kQParked) || (f & (kQFallback | kQPruned))) continue;
+    counts[0]++;
+    park_step[c] = (f >> 8) & 0xFFFF;
+    if (total_return[c] > bf) { failure[c] = (f & ~kQParked) | kQPruned; prune_stats[0] += 1; prune_stats[1] += park_step[c]; counts[1]++; }
+    else { list.push_back(c); resumed[c] = 1; counts[2]++; }
+  }
+  QArgs r = a;
+  r.resume_list = list.data(); r.resume_n = (int)list.size();
+  if (resume_unpruned) { r.prune_bound = nullptr; r.prune_stats = nullptr; }
+  pass((int)list.size(), [&](int slot, int leg, EmuStore& cs, EmuM& ms, EmuProf& pf) {
+    (void)rollout<false, true>(b->qm, b->qt, b->sp, b->tk, state, time, r, QFeedback{}, r.resume_list[slot], leg, cs, ms, pf);
+  });
+  delete b;
+  return 0;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """the reports of tools/ab_prune.sh: `compare OUT` (bench.py --dump-outputs of the two builds, array by array), `line NAME FILE` (one bench
 line's kernel_ms, ms_per_step, value, hand-ons) and `summary LOG` (median, min, max per build; the pruned build's range against the parent's,
-the gain against three times the parent's max - min; the MJPCX_PRUNE=0 build against the parent's spread)"""
+the gain against three times the parent's max - min; the MJPCX_PRUNE=0 build (tools/ab_park.sh: the MJPCX_PARK=0 build) against the parent's spread)"""
 import json, os, sys
 import numpy as np
 mode = sys.argv[1]
@@ -34,7 +34,7 @@ else:
         p = np.array([r[i] for r in rows["parent"]])
         sp = p.max() - p.min()
         txt = f"{key} parent median {np.median(p):.3f} ({p.min():.3f}-{p.max():.3f}, spread {sp:.3f})"
-        for v in ("new", "noprune"):
+        for v in ["new"] + [k for k in rows if k not in ("parent", "new")]:   # (the third build: `noprune` of ab_prune.sh, `nopark` of ab_park.sh)
             x = np.array([r[i] for r in rows[v]])
             gain = np.median(p) - np.median(x)
             txt += f"  {v} median {np.median(x):.3f} ({x.min():.3f}-{x.max():.3f}) gain {gain:.3f} ({100 * gain / np.median(p):.1f} %)"
