@@ -199,8 +199,7 @@ __global__ __launch_bounds__(64) void rollout_feedback_kernel(const LaneModel<T>
     if (bad) failed = true;
     total += (double)cost;
     if (last) break;
-    lane_integrate<TP, T>(m, tk, qpos, qvel, ctrl, qacc, qfrc, qfrc_c, M, nullptr, site_xpos);
-    if (m.integrator == 1 && live && !failed) lane_record_trace<TP, TK, T>(a, t, cand, site_xpos);
+    lane_integrate<TP, T>(m, tk, qpos, qvel, ctrl, qacc, qfrc, qfrc_c, M);
     time += h;
   }
   if (live) {

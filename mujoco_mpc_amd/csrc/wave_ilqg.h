@@ -310,10 +310,6 @@ __device__ __forceinline__ void feedback_rollout_body(const MODEL& m, const TASK
     if constexpr (RK4) {
       if (m.integrator == 1) {
         const bool warned = wave_rk4_step<NMAX, TREE>(m, tk, d, tree, lane, time, /*have_warm=*/t > 0);
-        if (lane < 3 * tk.ntrace) {  // the trace of an RK4 step is the last stage's (wave_kernel.h)
-          const int ts = tk.trace_site[lane / 3];
-          a.trace[((size_t)cand * H + t) * 3 * tk.ntrace + lane] = ts >= 0 ? d.site_xpos[3 * ts + lane % 3] : d.xpos[3 * (-1 - ts) + lane % 3];
-        }
         if (warned) { failed = true; break; }
         continue;
       }

@@ -66,8 +66,8 @@ __device__ __forceinline__ WaveData wave_carve(unsigned char* smem_raw, const MO
 // qacc) of that pass; stages 1..3 at X_0 + h A_i F_{i-1} with A = (1/2, 1/2, 1), no sensor stage, the solver warm-started from the
 // previous STEP in every stage; then X_0 + h sum B_i F_i, B = (1/6, 1/3, 1/3, 1/6), and the last stage's qacc becomes the next
 // step's warm start. No implicit joint damping. The stage values live in registers (one lane per coordinate: nq, nv <= 64), so
-// the LDS arena is the Euler kernel's. On return d holds the last stage's kinematics (site_xpos / xpos: the trace of the step) and
-// the advanced state; the result says whether any stage raised a solver / capacity warning (wave-uniform).
+// the LDS arena is the Euler kernel's. On return d holds the last stage's kinematics (not the step's trace: that is a sensor, recorded with
+// stage 0) and the advanced state; the result says whether any stage raised a solver / capacity warning (wave-uniform).
 template <int NMAX, bool TREE, class MODEL, class TASK>
 __device__ __forceinline__ bool wave_rk4_step(const MODEL& m, const TASK& tk, WaveData& d, TreeData& tree, int lane, wreal& time, bool have_warm) {
   const int nq = m.nq, nv = m.nv;
@@ -276,13 +276,9 @@ __device__ __forceinline__ void wave_rollout_body(const MODEL& m, const TASK& tk
     WSTAMP(13);
     if constexpr (RK4) {
       if (m.integrator == 1) {
+        // (the trace is a framepos SENSOR (GetTraces, utilities.cc:268-286) and stages 1..3 run no sensor stage: the row recorded above
+        // with the step's own forward pass stands)
         const bool warned = wave_rk4_step<NMAX, TREE>(m, tk, d, tree, lane, time, /*have_warm=*/t > 0);
-        // data->site_xpos / xpos after mj_step are the LAST stage's: that is what Trajectory::Rollout copies into the trace
-        // (trajectory.cc:165), so the row recorded above from the first stage is replaced
-        if (lane < 3 * tk.ntrace) {
-          const int ts = tk.trace_site[lane / 3];
-          a.trace[((size_t)cand * H + t) * 3 * tk.ntrace + lane] = ts >= 0 ? d.site_xpos[3 * ts + lane % 3] : d.xpos[3 * (-1 - ts) + lane % 3];
-        }
         if (warned) { failed = true; fail_info = (d.counters[2] << 8) | (t << 16); break; }  // CheckWarnings after mj_step
         continue;
       }

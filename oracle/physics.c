@@ -51,6 +51,7 @@ struct OData {
   double* xfrc_applied; /* 6 nbody: Cartesian force, torque at each body's centre of mass (mjData.xfrc_applied) */
   double *xpos, *xquat, *xmat, *xipos, *ximat, *xanchor, *xaxis;
   double *site_xpos, *site_xmat, *subtree_com, *subtree_mass;
+  double *sensor_xpos, *sensor_site_xpos; /* xpos / site_xpos as the last sensor stage saw them: the framepos sensors behind the traces */
   double *cinert, *crb, *cdof, *cdof_dot, *cvel, *cacc, *cfrc;
   double *M, *L; /* dense nv x nv */
   double *qfrc_passive, *qfrc_bias, *qfrc_actuator, *qfrc_smooth, *qacc_smooth;
@@ -209,6 +210,7 @@ OData* odata_new(const mjpcx_model* m) {
   d->xipos = dalloc(3 * nb); d->ximat = dalloc(9 * nb);
   d->xanchor = dalloc(3 * nj); d->xaxis = dalloc(3 * nj);
   d->site_xpos = dalloc(3 * ns); d->site_xmat = dalloc(9 * ns);
+  d->sensor_xpos = dalloc(3 * nb); d->sensor_site_xpos = dalloc(3 * ns);
   d->subtree_com = dalloc(3 * nb); d->subtree_mass = dalloc(nb);
   d->cinert = dalloc(10 * nb); d->crb = dalloc(10 * nb);
   d->cdof = dalloc(6 * nv); d->cdof_dot = dalloc(6 * nv);
@@ -262,7 +264,7 @@ void odata_free(OData* d) {
                   &d->qacc_smooth, &d->qfrc_constraint, &d->qacc, &d->actuator_force, &d->efc_J,
                   &d->scratch_minvjt, &d->scratch_qacc, &d->scratch_A, &d->scratch_AR, &d->rk_scratch, &d->geom_xpos, &d->geom_xmat, &d->scratch_jac,
                   &d->nw_jar, &d->nw_jv, &d->nw_grad, &d->nw_search, &d->nw_Ma, &d->nw_H, &d->nw_L, &d->qacc_warmstart,
-                  &d->xfrc_applied};
+                  &d->xfrc_applied, &d->sensor_xpos, &d->sensor_site_xpos};
   for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); i++) free(*p[i]);
   free(d->geom_static); free(d->pair_g1); free(d->pair_g2);
   free(d);
@@ -825,6 +827,10 @@ static void o_euler(OData* d) {
 
 void o_forward_task(OData* d, const mjpcx_task* task, double* r) {
   o_forward(d);
+  /* the sensor stage: the framepos sensors GetTraces reads (utilities.cc:268-286). The RK4 stages that follow in mj_step run none
+   * (mj_forwardSkip(m, d, mjSTAGE_NONE, 1)), so the trace of a step is the position at its start under either integrator */
+  memcpy(d->sensor_xpos, d->xpos, sizeof(double) * 3 * d->m->nbody);
+  memcpy(d->sensor_site_xpos, d->site_xpos, sizeof(double) * 3 * d->m->nsite);
   if (task) oresidual(task, d, r);
 }
 /* mj_step; `task` plays the role of the mjcb_sensor callback at mjSTAGE_ACC */
@@ -840,7 +846,7 @@ void o_step(OData* d) { o_step_task(d, NULL, NULL); }
 const double* odata_site_xpos(const OData* d) { return d->site_xpos; }
 double* odata_xfrc_applied(OData* d) { return d->xfrc_applied; }
 /* GetTraces (utilities.cc:268-286): framepos of a site (id >= 0) or of a body frame (id = -1 - body) */
-const double* odata_trace_point(const OData* d, int id) { return id >= 0 ? d->site_xpos + 3 * id : d->xpos + 3 * (-1 - id); }
+const double* odata_trace_point(const OData* d, int id) { return id >= 0 ? d->sensor_site_xpos + 3 * id : d->sensor_xpos + 3 * (-1 - id); }
 
 /* ------------------------------------------------------------------ residuals */
 /* the ResidualFn::Residual overrides of the covered tasks */
