@@ -733,6 +733,7 @@ int mjpcx_quad_stats(mjpcx_ctx* ctx, int32_t* handed_on /* 8 */);
  * (mjpcx_rollout_splines has no nominal: no candidate is exempt there); every other launch (the batched entry points,
  * with one environment too, the feedback rollouts, the limb, tree and lane kernel families, batches below
  * MJPCX_QUAD_MIN_N, any launch under the tuning switch MJPCX_QUAD_NO_FALLBACK) ignores it and rolls everything out.
+ * A fleet prunes with mjpcx_set_pruning_batched below: a switch of its own, with a bound per environment.
  * initial_bound: +inf for normal use; a finite value is a bound the caller vouches for (some candidate's return is <= it).
  * Negative or NaN: MJPCX_EINVAL. MJPCX_PRUNE=0 in the environment, read when the context is created, makes this call do
  * nothing.
@@ -782,6 +783,48 @@ int mjpcx_park_stats(mjpcx_ctx* ctx, int64_t* counts /* 3 */, double* resume_ms)
  * resume list, which is not defined). Returns the count (>= 0), or a negative error code. For tests and tools: synchronises and copies
  * candidate by candidate. */
 int mjpcx_park_resumed(mjpcx_ctx* ctx, int32_t* index, int32_t* step, int cap);
+
+/* ---- pruning and parking for a fleet: a bound, a hint and a set of counters per environment ------------------------------
+ * Sticky. Applies to the following mjpcx_rollout_noise_batched launches of num_envs environments that go to
+ * rollout_quad_kernel. Environment e of such a launch behaves like the plain pruned launch (mjpcx_set_pruning,
+ * mjpcx_set_park_hint) of that environment alone: its bound starts at initial_bound[e] (NULL: +inf each), is lowered only
+ * by returns that candidates of e complete with and is compared only with partial returns of candidates of e; its nominal
+ * (the LOCAL nominal_candidate) is exempt; park_hint[e] (NULL: +inf each = no parking) parks only its own candidates, which
+ * are settled against e's final bound and resumed, all environments' in one launch. No comparison crosses environments.
+ *
+ * What stays exact: every candidate not marked MJPCX_FAILURE_PRUNED equals the unpruned batched launch's bit for bit; a
+ * retired candidate's total_return is its partial return, strictly above its environment's final bound; no hint changes
+ * any result. It composes with mjpcx_set_task_params_batched and mjpcx_set_models_batched (costs stay >= 0 per
+ * environment).
+ *
+ * After such a launch:
+ *   - mjpcx_best_batched is exact per environment (local index, best return, ref return, spline), or returns MJPCX_ESTATE
+ *     and names the environments in mjpcx_last_error: those where a step's cost was negative, or where something was
+ *     retired and the smallest stored return is above the environment's final bound (the caller's bound was below every
+ *     return) -- the two rules of mjpcx_best above, per environment. Roll out again with the switch off then.
+ *   - mjpcx_ce_update_batched, mjpcx_robust_step_batched (when this context is its source),
+ *     mjpcx_sample_gradient_update_batched, mjpcx_best, mjpcx_topk, mjpcx_elite_moments and mjpcx_merge_topk return
+ *     MJPCX_ESTATE: their answers would depend on timing. mjpcx_get_returns, mjpcx_fetch_trajectory and
+ *     mjpcx_fetch_spline stay usable.
+ *   - mjpcx_prune_stats and mjpcx_park_stats report the sums over the environments, mjpcx_park_resumed global candidate
+ *     indices (environment by environment).
+ *
+ * Negative or NaN bounds or hints: MJPCX_EINVAL. A mjpcx_rollout_noise_batched of another number of environments while
+ * the switch is set: MJPCX_EINVAL (the rule of mjpcx_set_models_batched: nothing is dropped silently). enabled == 0 clears
+ * the switch (the other arguments are not read). MJPCX_PRUNE=0 in the environment makes this call do nothing, MJPCX_PARK=0
+ * makes it ignore the hints.
+ *
+ * Launches that ignore the switch and roll everything out: mjpcx_rollout_splines_batched,
+ * mjpcx_rollout_noise_batched_ce, the noisy, sample-gradient and feedback launches, and any launch that does not reach
+ * rollout_quad_kernel (a total below MJPCX_QUAD_MIN_N, a limb, tree or lane context, MJPCX_QUAD_NO_FALLBACK). The plain
+ * launches ignore it too, as the batched ones keep ignoring mjpcx_set_pruning and mjpcx_set_park_hint. */
+int mjpcx_set_pruning_batched(mjpcx_ctx* ctx, int enabled, int num_envs, const double* initial_bound /* E, or NULL */,
+                              const double* park_hint /* E, or NULL */);
+/* Of the last rollout, per environment (zeros unless it was a pruned batched one): prune[4 e ..] as mjpcx_prune_stats,
+ * park[3 e ..] as mjpcx_park_stats' counts (may be NULL), final_bound[e] the environment's bound after the launch (may be
+ * NULL). No synchronisation. */
+int mjpcx_prune_stats_batched(mjpcx_ctx* ctx, int num_envs, int64_t* prune /* E x 4 */, int64_t* park /* E x 3 */,
+                              double* final_bound /* E */);
 
 /* Algorithmic bytes of one candidate rollout:
  * w*[H*(dim_state+nu+1+nr+3*ntrace+1) + P*nu + P + 2]. */

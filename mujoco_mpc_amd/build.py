@@ -38,7 +38,7 @@ QUAD_ONLY = ["quad_step.h", "quad_kernel.h", "quad_model.h", "limb_step.h", "lim
 # likewise the limb kernel's unit (the Humanoid of configs[3])
 LIMB_DEPS = ["env_select.h", "limb_step.h", "limb_kernel.h", "limb_model.h", "limb_abi.h", "limb_launch.h", "limb_kernel.hip", "pair_cull.h", "solid_pairs.h",
              os.path.join("..", "..", "include", "mjpcx.h")]
-QUAD_DEPS = ["env_select.h", "quad_step.h", "quad_kernel.h", "quad_model.h", "quad_abi.h", "quad_launch.h", "quad_kernel.hip", "solid_pairs.h", "pair_cull.h",
+QUAD_DEPS = ["env_select.h", "quad_step.h", "quad_kernel.h", "quad_model.h", "quad_abi.h", "resume_table.h", "quad_launch.h", "quad_kernel.hip", "solid_pairs.h", "pair_cull.h",
              os.path.join("..", "..", "include", "mjpcx.h")]
 HEADERS = ["device_common.h", "rollout_lane.h", "lane_registry.h", os.path.join("generated", "static_models.h"),
            os.path.join("..", "..", "include", "mjpcx.h")]

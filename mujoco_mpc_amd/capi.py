@@ -35,6 +35,7 @@ EXPORTS = [
     "mjpcx_rollout_sample_gradient_batched", "mjpcx_sample_gradient_update_batched",
     "mjpcx_set_models_batched", "mjpcx_set_pruning", "mjpcx_prune_stats",
     "mjpcx_set_park_hint", "mjpcx_park_stats", "mjpcx_park_resumed",
+    "mjpcx_set_pruning_batched", "mjpcx_prune_stats_batched",
 ]
 
 SG_COMPUTE_WEIGHTS, SG_ZERO_GRADIENT = 1, 2   # MJPCX_SG_* flags of mjpcx_sample_gradient_update_batched
@@ -119,6 +120,8 @@ def lib():
         L.mjpcx_set_park_hint.argtypes = [vp, C.c_double]
         L.mjpcx_park_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
         L.mjpcx_park_resumed.argtypes = [vp, c_i32p, c_i32p, C.c_int]
+        L.mjpcx_set_pruning_batched.argtypes = [vp, C.c_int, C.c_int, c_f64p, c_f64p]
+        L.mjpcx_prune_stats_batched.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f64p]
         L.mjpcx_algorithmic_bytes.restype = C.c_int64
         L.mjpcx_algorithmic_bytes.argtypes = [vp, C.c_int, C.c_int]
         L.mjpcx_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -688,6 +691,35 @@ class Context:
             self._chk(min(lib().mjpcx_park_resumed(self.handle, as_i32p(idx), as_i32p(step), n), 0))
         order = np.argsort(idx[:n])
         return idx[:n][order], step[:n][order]
+
+    def set_pruning_batched(self, enabled, num_envs=0, initial_bound=None, park_hint=None):
+        """mjpcx_set_pruning_batched: the following rollout_noise_batched launches of num_envs environments on rollout_quad_kernel prune, and park,
+        with a bound and a hint per environment (sticky; None: +inf each). enabled false clears the switch"""
+        if not enabled:
+            self._chk(lib().mjpcx_set_pruning_batched(self.handle, 0, 0, None, None))
+            return
+        E = int(num_envs)
+
+        def row(v, what):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (E,)) if np.ndim(v) == 0 else np.asarray(v, np.float64))
+            if v.shape != (E,):
+                raise ValueError(f"{what} must hold one value per environment ({E}), got shape {v.shape}")
+            return v
+        b, h = row(initial_bound, "initial_bound"), row(park_hint, "park_hint")
+        self._chk(lib().mjpcx_set_pruning_batched(self.handle, 1, E, None if b is None else as_f64p(b), None if h is None else as_f64p(h)))
+
+    def prune_stats_batched(self, num_envs):
+        """mjpcx_prune_stats_batched: of the last rollout, per environment (zeros unless it was a pruned batched one): prune_stats' and park_stats'
+        counts as arrays of length E, and each environment's final bound"""
+        E = int(num_envs)
+        pr, pk = (C.c_int64 * (4 * E))(), (C.c_int64 * (3 * E))()
+        fb = np.zeros(E, np.float64)
+        self._chk(lib().mjpcx_prune_stats_batched(self.handle, E, pr, pk, as_f64p(fb)))
+        pr, pk = np.array(pr[:], np.int64).reshape(E, 4), np.array(pk[:], np.int64).reshape(E, 3)
+        return dict(retired=pr[:, 0].copy(), retire_step_sum=pr[:, 1].copy(), negative_cost=pr[:, 2] != 0, wavefronts_ended_early=pr[:, 3].copy(),
+                    parked=pk[:, 0].copy(), settled_retired=pk[:, 1].copy(), resumed=pk[:, 2].copy(), final_bound=fb)
 
     def algorithmic_bytes(self, horizon, num_nodes):
         return lib().mjpcx_algorithmic_bytes(self.handle, int(horizon), int(num_nodes))

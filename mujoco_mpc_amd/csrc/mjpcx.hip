@@ -945,6 +945,19 @@ struct mjpcx_ctx {
   int64_t park_h[3] = {0, 0, 0};  // the last rollout's: candidates parked, retired by the settling pass, resumed
   double park_resume_ms = 0;      // ... and its resume launch's event time
   hipEvent_t park_ev[2] = {nullptr, nullptr};
+  // a bound, a hint and a set of counters per environment (mjpcx_set_pruning_batched; mjpcx_rollout_noise_batched on the quad kernel). The
+  // environments' records (quad_abi.h, kQEnvRec*) follow the 64 bytes above in d_qstats and come back with them in one copy
+  bool bprune_on = false;         // the switch, for launches of bprune_E environments
+  int bprune_E = 0;
+  std::vector<double> bprune_initial, bprune_hint;  // E each
+  bool bprune_req = false;        // do_rollout: the rollout under way is mjpcx_rollout_noise_batched's (the one batched launch the switch applies to)
+  bool last_pruned_batched = false;  // the last rollout was such a launch (last_pruned is set too: prune_h and park_h hold the sums over the environments)
+  std::vector<int64_t> env_prune_h, env_park_h;  // E x 4, E x 3: the last rollout's counters per environment
+  std::vector<double> env_prune_final;            // E: its final bounds
+  PinnedBlock h_envrec;           // [the readback: 64 bytes + E records | the E records as uploaded]
+  DevBuf d_resume_groups;         // the resume launch's workgroup table (resume_table.h)
+  std::vector<quad::ResumeGroup> resume_groups;
+  std::vector<int> resume_count;
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -1361,11 +1374,35 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
     if ((e = c->d_qovf.reserve((size_t)quad::quad_waves(N, c->quad_cpw) * quad::quad_ovf_doubles_per_wave() * sizeof(double))) != hipSuccess) return e;
     q.ovf_slab = (double*)c->d_qovf.p;
   }
-  // (mjpcx_set_pruning: the plain launches only -- a batched one, of one environment too, is ranked by calls that read every return, and
-  // would need a bound per environment. Not with MJPCX_QUAD_NO_FALLBACK either: that tuning switch skips the readback the counters ride on)
-  const bool pruned = c->prune_on && plain && !c->quad_no_fallback;
+  // (mjpcx_set_pruning: the plain launches only -- a batched one, of one environment too, needs a bound per environment and has a switch
+  // of its own for that. Not with MJPCX_QUAD_NO_FALLBACK either: that tuning switch skips the readback the counters ride on)
+  // (mjpcx_set_pruning_batched: mjpcx_rollout_noise_batched only, with a record per environment behind the 64 bytes of the plain launch)
+  const bool bpruned = c->bprune_on && c->bprune_req && !plain && !c->quad_no_fallback && c->bprune_E > 0 && N % c->bprune_E == 0;
+  const int bE = bpruned ? c->bprune_E : 0, bn = bpruned ? N / bE : 0;
+  const size_t brec = (size_t)bE * quad::kQEnvRec;
+  const bool pruned = (c->prune_on && plain && !c->quad_no_fallback) || bpruned;
+  if (bpruned && (e = c->d_qstats.reserve(64 + brec)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(c->d_qstats.p, 0, pruned ? 64 : 32, c->stream)) != hipSuccess) return e;  // (how many candidates are handed on, by reason: mjpcx_quad_stats)
-  if (pruned) {  // the bound word starts at the caller's bound (+inf: 0x7ff00000 over a low word of zeros), on the stream like the counters
+  bool bparking = false;
+  if (bpruned) {
+    // every environment's record starts at its own bound and hint, with its counters at zero: one copy on the stream. (The staged records
+    // are the second half of the pinned block; the launch ends in a synchronisation, so the next one may rewrite them.)
+    if ((e = c->h_envrec.reserve(64 + 2 * brec)) != hipSuccess) return e;
+    char* up = (char*)c->h_envrec.p + 64 + brec;
+    std::memset(up, 0, brec);
+    for (int k = 0; k < bE; k++) {
+      const double hint = c->park_allowed ? c->bprune_hint[k] : HUGE_VAL;
+      bparking = bparking || hint < HUGE_VAL;
+      std::memcpy(up + (size_t)k * quad::kQEnvRec + quad::kQEnvRecBound, &c->bprune_initial[k], 8);
+      std::memcpy(up + (size_t)k * quad::kQEnvRec + quad::kQEnvRecHint, &hint, 8);
+    }
+    char* w = (char*)c->d_qstats.p + 64;
+    if ((e = hipMemcpyAsync(w, up, brec, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return e;
+    q.prune_bound = (unsigned long long*)(w + quad::kQEnvRecBound);
+    q.prune_stats = (int*)(w + quad::kQEnvRecStats);
+    q.rec_stride = quad::kQEnvRec;
+    c->env_prune_h.assign((size_t)bE * 4, 0); c->env_park_h.assign((size_t)bE * 3, 0); c->env_prune_final.assign(bE, 0.0);
+  } else if (pruned) {  // the bound word starts at the caller's bound (+inf: 0x7ff00000 over a low word of zeros), on the stream like the counters
     unsigned long long bits;
     std::memcpy(&bits, &c->prune_initial, 8);
     char* w = (char*)c->d_qstats.p + 32;
@@ -1375,15 +1412,20 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
     q.prune_stats = (int*)(w + 8);
     if (a.noise.mode < 0) q.nominal_candidate = -1;  // (given splines have no nominal: no candidate is exempt)
   }
-  c->last_pruned = pruned;
-  // (mjpcx_set_park_hint: a pruned launch only -- the settling pass needs its bound word)
-  const bool parking = pruned && c->park_allowed && c->park_hint < HUGE_VAL;
+  c->last_pruned = pruned; c->last_pruned_batched = bpruned;
+  // (mjpcx_set_park_hint: a pruned launch only -- the settling pass needs its bound word. A batched one parks on its environments' own hints)
+  const bool parking = bpruned ? bparking : pruned && c->park_allowed && c->park_hint < HUGE_VAL;
   c->park_h[0] = c->park_h[1] = c->park_h[2] = 0; c->park_resume_ms = 0;
+  // the most workgroups a batched resume launch can have (resume_table.h): every environment's own ceil on top of what resume_cpw aims at
+  const size_t group_cap = bpruned ? (size_t)std::min<long long>(N, std::max<long long>(1024, N / 16) + bE) : 0;
   if (parking) {
     if ((e = c->d_park_rec.reserve((size_t)N * quad::kQParkRec * sizeof(double))) != hipSuccess || (e = c->d_resume.reserve((size_t)N * sizeof(int))) != hipSuccess) return e;
-    q.park_hint = c->park_hint; q.park_records = (double*)c->d_park_rec.p;
+    if (bpruned && (e = c->d_resume_groups.reserve(group_cap * sizeof(quad::ResumeGroup))) != hipSuccess) return e;
+    if (!bpruned) q.park_hint = c->park_hint;  // (a batched launch reads each environment's hint from its record)
+    q.park_records = (double*)c->d_park_rec.p;
     // (a resumed candidate may get a wavefront of its own: a slab build needs one slab per candidate then)
-    if (quad::quad_uses_ovf_slab() && (e = c->d_qovf.reserve((size_t)N * quad::quad_ovf_doubles_per_wave() * sizeof(double))) != hipSuccess) return e;
+    // (the fleet's resume launch gives every environment whole workgroups of its own: up to 4 wavefronts per environment more than candidates)
+    if (quad::quad_uses_ovf_slab() && (e = c->d_qovf.reserve(((size_t)N + 4 * (size_t)bE) * quad::quad_ovf_doubles_per_wave() * sizeof(double))) != hipSuccess) return e;
     if (quad::quad_uses_ovf_slab()) q.ovf_slab = (double*)c->d_qovf.p;
   }
   if (c->quad_stamps) {
@@ -1422,7 +1464,8 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
   // the settling pass: parked candidates against the launch's final bound; its two counts ride on the readback below (words 14 and 15)
   if (parking) {
     hipLaunchKernelGGL(park_settle_kernel, dim3((N + 255) / 256), dim3(256), 0, c->stream, N, (const double*)a.total_return, a.failure,
-                       (const unsigned long long*)q.prune_bound, q.prune_stats, (int*)c->d_resume.p, (int*)c->d_qstats.p + 14);
+                       (const unsigned long long*)q.prune_bound, q.prune_stats, (int*)c->d_resume.p,
+                       bpruned ? (int*)((char*)c->d_qstats.p + 64 + quad::kQEnvRecWords) : (int*)c->d_qstats.p + 14, bn, q.rec_stride);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (c->quad_stamps) {
@@ -1458,7 +1501,52 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
   // the pass over the candidates the quad kernel handed on is 16384 wavefronts that each find their candidate unflagged (0.24 ms) when
   // nothing was handed on -- the usual case: the count comes back first (32 bytes, one synchronisation the plan step pays anyway a moment later)
   // (a pruned launch's counters ride on the same copy: mjpcx_best and mjpcx_prune_stats need no synchronisation of their own for them)
-  if (!c->quad_stats || pruned) {
+  if (bpruned) {
+    // the environments' records come back behind the hand-on counters, in the one copy and the one synchronisation of the plan step
+    char* const hb = (char*)c->h_envrec.p;
+    auto rec_int = [&](int env, unsigned off, int k) { int v; std::memcpy(&v, hb + 64 + (size_t)env * quad::kQEnvRec + off + 4 * k, 4); return v; };
+    if ((e = hipMemcpyAsync(hb, c->d_qstats.p, 64 + brec, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+    long long resumed_all = 0;
+    c->resume_count.assign(bE, 0);
+    for (int k = 0; k < bE && parking; k++) {
+      const int parked = rec_int(k, quad::kQEnvRecWords, 0), resumed = rec_int(k, quad::kQEnvRecWords, 1);
+      if (parked < 0 || parked > bn || resumed < 0 || resumed > parked) return hipErrorUnknown;  // (these counts size a launch: never past an environment's segment)
+      c->resume_count[k] = resumed; resumed_all += resumed;
+      c->env_park_h[3 * k] = parked; c->env_park_h[3 * k + 1] = parked - resumed; c->env_park_h[3 * k + 2] = resumed;
+    }
+    if (resumed_all > 0) {
+      // ONE resume launch for the fleet: every environment's list gets whole workgroups of its own (a workgroup stages one environment's
+      // model, poses and blob), and the table that tells a workgroup its environment and its slice of that list goes up ahead of the launch
+      const int cpw = quad::resume_cpw(resumed_all), W = quad::resume_wpg(quad::resume_waves(c->resume_count.data(), bE, cpw));
+      c->resume_groups.resize(group_cap);
+      const long long grid = quad::resume_table_build(c->resume_count.data(), bE, cpw, W, c->resume_groups.data(), (long long)group_cap);
+      if (grid <= 0) return hipErrorUnknown;
+      if ((e = hipMemcpyAsync(c->d_resume_groups.p, c->resume_groups.data(), (size_t)grid * sizeof(quad::ResumeGroup), hipMemcpyHostToDevice, c->stream)) != hipSuccess) return e;
+      quad::QArgs r = q;
+      r.resume_list = (const int*)c->d_resume.p; r.resume_n = (int)resumed_all; r.cpw = cpw;
+      r.resume_groups = (const quad::ResumeGroup*)c->d_resume_groups.p;
+      for (int k = 0; k < 2; k++) if (!c->park_ev[k] && (e = hipEventCreate(&c->park_ev[k])) != hipSuccess) return e;
+      if ((e = hipEventRecord(c->park_ev[0], c->stream)) != hipSuccess) return e;
+      if ((e = quad::launch_resume_quad_groups(mr.qmodel, mr.qtab, wt.blob, bo, r, W, (int)grid, (int*)c->d_qstats.p, c->stream)) != hipSuccess) return e;
+      if ((e = hipEventRecord(c->park_ev[1], c->stream)) != hipSuccess) return e;
+      if ((e = hipMemcpyAsync(hb, c->d_qstats.p, 64 + brec, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+      if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, c->park_ev[0], c->park_ev[1]) == hipSuccess) c->park_resume_ms = ms;
+    }
+    for (int k = 0; k < 4; k++) c->prune_h[k] = 0;
+    c->prune_final = HUGE_VAL;
+    for (int k = 0; k < bE; k++) {
+      for (int j = 0; j < 4; j++) { c->env_prune_h[4 * k + j] = rec_int(k, quad::kQEnvRecStats, j); c->prune_h[j] += rec_int(k, quad::kQEnvRecStats, j); }
+      for (int j = 0; j < 3; j++) c->park_h[j] += c->env_park_h[3 * k + j];
+      std::memcpy(&c->env_prune_final[k], hb + 64 + (size_t)k * quad::kQEnvRec + quad::kQEnvRecBound, 8);
+      c->prune_final = std::min(c->prune_final, c->env_prune_final[k]);
+    }
+    int h0;
+    std::memcpy(&h0, hb, 4);
+    if (h0 == 0 && !c->quad_stats) return hipSuccess;
+  } else if (!c->quad_stats || pruned) {
     if (!c->h_qstats && hipHostMalloc(&c->h_qstats, 64, hipHostMallocDefault) != hipSuccess) c->h_qstats = nullptr;
     if (c->h_qstats) {
       if ((e = hipMemcpyAsync(c->h_qstats, c->d_qstats.p, pruned ? 64 : 32, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
@@ -1742,6 +1830,8 @@ struct RolloutRequest {
   bool nodes_on_device = false;
   // NoisyRollout: force noise of this standard deviation and rate (0: plain Rollout); given splines draw candidate j's stream at xfrc_offset + j
   double xfrc_std = 0, xfrc_rate = 1; uint64_t xfrc_seed = 0; int xfrc_offset = 0;
+  // (mjpcx_rollout_noise_batched) the one batched launch mjpcx_set_pruning_batched applies to
+  bool prune_batched = false;
 };
 
 template <typename T>
@@ -1751,7 +1841,8 @@ int do_rollout(mjpcx_ctx* c, const RolloutRequest& r) {
   const mjpcx_noise_spec* const ns = r.noise;
   int rc;
   if ((rc = reserve_rollout(c, N, H, P)) != MJPCX_OK) return rc;
-  c->last_pruned = false;  // (launch_quad sets it)
+  c->last_pruned = false; c->last_pruned_batched = false;  // (launch_quad sets them)
+  c->bprune_req = r.prune_batched;
   const int np = P * c->nu;
   RolloutArgs<T> a{};
   a.N = N; a.H = H; a.P = P; a.interp = r.interp;
@@ -2151,6 +2242,7 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   for (auto& sl : c->slots) { sl.host.release(); sl.dev.release(); }
   c->h_ilqg.release();
   c->h_grad.release();
+  c->h_envrec.release();
   c->result.release();
   if (c->h_qstats) (void)hipHostFree(c->h_qstats);
   for (hipEvent_t ev : c->park_ev) if (ev) (void)hipEventDestroy(ev);
@@ -2159,7 +2251,7 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   c->em.release();
   (void)mjpcx_comm_destroy(c);
   c->wh.release();
-  DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_park_rec, &c->d_resume, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
+  DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_park_rec, &c->d_resume, &c->d_resume_groups, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
                     &c->d_states, &c->d_actions, &c->d_times, &c->d_residual, &c->d_costs, &c->d_trace, &c->d_ret,
                     &c->d_fail, &c->d_sort, &c->d_stage};
   for (DevBuf* b : bufs) b->release();
@@ -2422,6 +2514,8 @@ int check_batched_args(mjpcx_ctx* c, int E, int n, int H, int P, int interp, con
   }
   return MJPCX_OK;
 }
+// which candidates a pruned launch (mjpcx_set_pruning, mjpcx_set_pruning_batched) retires, and when, depends on the order its wavefronts finish in: only the argmin is exact
+const char* const kPrunedRanking = "the last rollout was pruned (mjpcx_set_pruning): beyond the argmin its returns are lower bounds that depend on timing";
 }  // namespace
 
 int mjpcx_rollout_splines_batched(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* node_values) {
@@ -2453,6 +2547,10 @@ int mjpcx_rollout_noise_batched(mjpcx_ctx* c, int E, int n, int H, int P, int in
   if (ns->mode != MJPCX_NOISE_SAMPLING && ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "unknown noise mode");
   RolloutRequest r{E * n, H, P, interp, node_times, E};
   r.nominal = nominal; r.noise = ns;
+  // (a switch set for another fleet size is an error, not a launch that quietly rolls everything out: the rule of mjpcx_set_models_batched)
+  if (c->bprune_on && c->bprune_E != E)
+    return fail(c, MJPCX_EINVAL, "batched rollout of " + std::to_string(E) + " environments while mjpcx_set_pruning_batched is set for " + std::to_string(c->bprune_E));
+  r.prune_batched = true;
   return rollout(c, r);
 }
 
@@ -2477,6 +2575,7 @@ int mjpcx_ce_update_batched(mjpcx_ctx* c, int E, int n_elite, int skip_candidate
   if (n_elite < 1 || n_elite > left)
     return fail(c, MJPCX_EINVAL, "mjpcx_ce_update_batched: n_elite = " + std::to_string(n_elite) + " outside 1.." + std::to_string(left) +
                                  " (the candidates of an environment without the skipped one)");
+  if (c->last_pruned) return fail(c, MJPCX_ESTATE, kPrunedRanking);
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
   CeRecord rec;
@@ -2510,6 +2609,16 @@ int mjpcx_best_batched(mjpcx_ctx* c, int E, int ref_candidate, int32_t* index, d
   if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
   if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N)
     return fail(c, MJPCX_EINVAL, "mjpcx_best_batched: the last rollout was not a batched one of " + std::to_string(E) + " environments");
+  // after a launch with a bound per environment (mjpcx_set_pruning_batched): the two rules of pruned_launch_valid and pruned_argmin_valid
+  // below, applied to every environment with its own counters and final bound. Exact per environment, or MJPCX_ESTATE naming the environments
+  const bool per_env_bounds = c->last_pruned_batched && (int)c->env_prune_final.size() == E;
+  if (per_env_bounds) {
+    std::string named;
+    for (int e = 0; e < E; e++) if (c->env_prune_h[4 * (size_t)e + 2]) named += (named.empty() ? "" : ", ") + std::to_string(e);
+    if (!named.empty())
+      return fail(c, MJPCX_ESTATE, "pruned batched rollout: a step's cost was negative in environment(s) " + named +
+                                       ", so partial returns are no lower bounds there (roll out again with pruning off)");
+  }
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
   const size_t rec = kBestHeader + (size_t)np * 8;
@@ -2521,6 +2630,16 @@ int mjpcx_best_batched(mjpcx_ctx* c, int E, int ref_candidate, int32_t* index, d
   });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (per_env_bounds) {
+    std::string named;
+    for (int e = 0; e < E; e++) {
+      const BestRecord* r = (const BestRecord*)((const char*)c->result.p + rec * e);
+      if (c->env_prune_h[4 * (size_t)e] > 0 && !(r->best_return <= c->env_prune_final[e])) named += (named.empty() ? "" : ", ") + std::to_string(e);
+    }
+    if (!named.empty())
+      return fail(c, MJPCX_ESTATE, "pruned batched rollout: every stored return of environment(s) " + named +
+                                       " is above its bound, so the initial bound was below every return there (roll out again with pruning off)");
+  }
   for (int e = 0; e < E; e++) {
     const BestRecord* r = (const BestRecord*)((const char*)c->result.p + rec * e);
     index[e] = r->best_index;
@@ -2542,6 +2661,7 @@ int mjpcx_robust_step_batched(mjpcx_ctx* c, mjpcx_ctx* src, int E, int k, int R,
     return fail(c, MJPCX_EINVAL, who + "the two contexts differ in device, precision or model dimensions");
   if (E < 1 || !src->have_rollout || src->env_n < 1 || (long long)E * src->env_n != src->N)
     return fail(c, MJPCX_EINVAL, who + "the source's last rollout was not a batched one of " + std::to_string(E) + " environments");
+  if (src->last_pruned) return fail(c, MJPCX_ESTATE, who + kPrunedRanking);
   if (k < 1 || k > src->env_n || R < 1)
     return fail(c, MJPCX_EINVAL, who + "num_candidates = " + std::to_string(k) + " outside 1.." + std::to_string(src->env_n) + " or repetitions = " + std::to_string(R) + " < 1");
   if (!(xfrc_std >= 0) || !(xfrc_rate > 0)) return fail(c, MJPCX_EINVAL, who + "xfrc_std must be >= 0 and xfrc_rate > 0");
@@ -2670,6 +2790,7 @@ int mjpcx_sample_gradient_update_batched(mjpcx_ctx* c, int E, int G, int flags, 
   const std::string who = "mjpcx_sample_gradient_update_batched: ";
   if (!c || !index) return fail(c, MJPCX_EINVAL, who + "null argument");
   if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (c->last_pruned) return fail(c, MJPCX_ESTATE, who + kPrunedRanking);
   auto& s = c->sg;
   if (E < 1 || s.serial == 0 || s.serial != c->rollout_serial || c->env_n < 1 || (long long)E * c->env_n != c->N || s.E != E || s.G != G)
     return fail(c, MJPCX_EINVAL, who + "the last rollout was not a mjpcx_rollout_sample_gradient_batched of " + std::to_string(E) + " environments with num_gradient = " + std::to_string(G));
@@ -2785,12 +2906,12 @@ static int pruned_argmin_valid(mjpcx_ctx* c, double best_return) {
     return fail(c, MJPCX_ESTATE, "pruned rollout: every stored return is above the bound, so the initial bound was below every return (roll out again with pruning off)");
   return MJPCX_OK;
 }
-static const char* const kPrunedRanking ="the last rollout was pruned (mjpcx_set_pruning): beyond the argmin its returns are lower bounds that depend on timing";
 
 int mjpcx_best(mjpcx_ctx* c, int ref_candidate, int32_t* index, double* best_return, double* ref_return,
                double* spline_values) {
   if (!c || !index) return fail(c, MJPCX_EINVAL, "null argument");
   if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (c->last_pruned_batched) return fail(c, MJPCX_ESTATE, kPrunedRanking);  // (bounds per environment: mjpcx_best_batched)
   int rc;
   if ((rc = pruned_launch_valid(c)) != MJPCX_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -2816,7 +2937,7 @@ int mjpcx_topk(mjpcx_ctx* c, int k, int32_t* index, double* total_return) {
   if (!c || !index) return fail(c, MJPCX_EINVAL, "null argument");
   if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
   if (k < 1 || k > c->N) return fail(c, MJPCX_EINVAL, "k out of range");
-  if (k > 1 && c->last_pruned) return fail(c, MJPCX_ESTATE, kPrunedRanking);
+  if ((k > 1 && c->last_pruned) || c->last_pruned_batched) return fail(c, MJPCX_ESTATE, kPrunedRanking);
   int rc;
   if ((rc = pruned_launch_valid(c)) != MJPCX_OK) return rc;  // (k = 1 is the argmin: mjpcx_best's checks)
   HIPCHK(c, hipSetDevice(c->device));
@@ -2980,6 +3101,34 @@ int mjpcx_set_pruning(mjpcx_ctx* c, int enabled, double initial_bound) {
   return MJPCX_OK;
 }
 
+int mjpcx_set_pruning_batched(mjpcx_ctx* c, int enabled, int num_envs, const double* initial_bound, const double* park_hint) {
+  if (!c) return MJPCX_EINVAL;
+  if (!enabled) { c->bprune_on = false; c->bprune_E = 0; c->bprune_initial.clear(); c->bprune_hint.clear(); return MJPCX_OK; }
+  if (num_envs < 1) return fail(c, MJPCX_EINVAL, "mjpcx_set_pruning_batched: the number of environments must be >= 1");
+  for (int e = 0; e < num_envs; e++) {
+    if (initial_bound && !(initial_bound[e] >= 0)) return fail(c, MJPCX_EINVAL, "environment " + std::to_string(e) + ": the initial bound is a return: >= 0 (+inf for none)");
+    if (park_hint && !(park_hint[e] >= 0)) return fail(c, MJPCX_EINVAL, "environment " + std::to_string(e) + ": the park hint is an estimate of a return: >= 0 (+inf for none)");
+  }
+  if (!c->prune_allowed) return MJPCX_OK;  // (MJPCX_PRUNE=0: the call does nothing)
+  c->bprune_on = true; c->bprune_E = num_envs;
+  c->bprune_initial.assign(num_envs, HUGE_VAL);
+  c->bprune_hint.assign(num_envs, HUGE_VAL);
+  if (initial_bound) std::copy(initial_bound, initial_bound + num_envs, c->bprune_initial.begin());
+  if (park_hint && c->park_allowed) std::copy(park_hint, park_hint + num_envs, c->bprune_hint.begin());  // (MJPCX_PARK=0: the hints are ignored)
+  return MJPCX_OK;
+}
+
+int mjpcx_prune_stats_batched(mjpcx_ctx* c, int num_envs, int64_t* prune, int64_t* park, double* final_bound) {
+  if (!c || !prune || num_envs < 1) return MJPCX_EINVAL;
+  const bool have = c->last_pruned_batched && (int)c->env_prune_final.size() == num_envs;
+  if (c->last_pruned_batched && !have)
+    return fail(c, MJPCX_EINVAL, "mjpcx_prune_stats_batched: the last rollout was a pruned one of " + std::to_string(c->env_prune_final.size()) + " environments");
+  for (int k = 0; k < 4 * num_envs; k++) prune[k] = have ? c->env_prune_h[k] : 0;
+  if (park) for (int k = 0; k < 3 * num_envs; k++) park[k] = have ? c->env_park_h[k] : 0;
+  if (final_bound) for (int k = 0; k < num_envs; k++) final_bound[k] = have ? c->env_prune_final[k] : 0.0;
+  return MJPCX_OK;
+}
+
 int mjpcx_set_park_hint(mjpcx_ctx* c, double hint) {
   if (!c) return MJPCX_EINVAL;
   if (!(hint >= 0)) return fail(c, MJPCX_EINVAL, "the park hint is an estimate of a return: >= 0 (+inf for none)");
@@ -3000,7 +3149,16 @@ int mjpcx_park_resumed(mjpcx_ctx* c, int32_t* index, int32_t* step, int cap) {
   if (n == 0 || cap == 0) return n;
   const int m = std::min(n, cap);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(index, c->d_resume.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+  if (c->last_pruned_batched) {  // (a segment of env_n entries per environment; the indices in them are global)
+    int got = 0;
+    for (size_t e = 0; e < c->env_prune_final.size() && got < m; e++) {
+      const int take = std::min((int)c->env_park_h[3 * e + 2], m - got);
+      if (take > 0) HIPCHK(c, hipMemcpy(index + got, (const int*)c->d_resume.p + e * (size_t)c->env_n, (size_t)take * sizeof(int), hipMemcpyDeviceToHost));
+      got += take;
+    }
+  } else {
+    HIPCHK(c, hipMemcpy(index, c->d_resume.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+  }
   std::vector<double> rec(quad::kQParkRec);
   for (int i = 0; i < m; i++) {  // (a test's call: one small copy per resumed candidate)
     HIPCHK(c, hipMemcpy(rec.data(), (const double*)c->d_park_rec.p + (size_t)index[i] * quad::kQParkRec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -3174,7 +3332,7 @@ int do_feedback(mjpcx_ctx* c, int E, int n, int H, int mode, int representation,
   HIPCHK(c, rec.slot->host.mark(c->stream));
   c->N = N; c->H = H; c->P = a.P;
   c->env_n = env_n;
-  c->last_pruned = false;
+  c->last_pruned = false; c->last_pruned_batched = false;
   c->have_rollout = true;
   c->rollout_serial++;
   c->traj_candidate_major = c->wave;

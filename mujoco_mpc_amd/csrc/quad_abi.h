@@ -5,6 +5,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "resume_table.h"
+
 namespace mjpcx {
 constexpr int kQFallback = 0x40000000;  // failure[] marker of a candidate the quad kernel handed on (cleared by the fallback pass)
 constexpr int kQPruned = 0x20000000;   // failure[] marker of a candidate retired because it could no longer be the argmin (QArgs::prune_bound): | (retire step << 8);
@@ -51,7 +53,15 @@ struct QArgs {
   int resume_n;            // at the recorded step, with its nodes as they stand in `nodes`, pruned against prune_bound and never parked
   int* prune_stats;   // nullptr, or 4 ints: [0] candidates retired, [1] the sum of their retire steps, [2] != 0 if a step's cost was negative (the partial return is then no lower
                       // bound: the launch's pruning is invalid), [3] wavefronts all of whose candidates left before the last step
+  unsigned rec_stride = 0;  // a pruned launch of several environments (mjpcx_set_pruning_batched): the bytes between consecutive environments' records (kQEnvRec*);
+                            // prune_bound and prune_stats are environment 0's and move with the workgroup's environment, and park_hint is read from the record.
+                            // 0: the one record of a plain launch, park_hint as given above
+  const ResumeGroup* resume_groups = nullptr;  // rollout_quad_resume_kernel of such a launch: one entry per workgroup (resume_table.h); resume_list then holds a segment of
+                                               // env_n entries per environment and resume_n is not read. nullptr: the one list of resume_n entries
 };
+// an environment's record of a pruned batched launch, byte offsets: the bound word; prune_stats' four ints; the settling pass's two counts (candidates parked, candidates
+// to resume); the environment's park hint. The first 32 bytes are what a plain launch keeps behind its hand-on counters, in the same order
+constexpr unsigned kQEnvRecBound = 0, kQEnvRecStats = 8, kQEnvRecWords = 24, kQEnvRecHint = 32, kQEnvRec = 64;
 
 // the feedback policy of the iLQG rollouts (FeedbackArgs of ilqg_kernels.h): nullptr members = the spline policy of QArgs
 struct QFeedback {

@@ -219,12 +219,21 @@ constexpr size_t kQWaveLds = (kQWaveCon + kQWaveMl + kQWaveMt) * sizeof(double);
 // Workgroup = W wavefronts (W = 4 for the large batches: one per SIMD of a CU, sharing one model image; W = 1 spreads small batches
 // over the CUs). stats[0]: candidates handed to the fallback kernel, stats[1 + log2(flag)]: by reason.
 // RESUME: the wavefront's candidates are entries of a.resume_list (rollout<FEEDBACK, RESUME> of quad_step.h)
-template <bool FEEDBACK, bool RESUME = false>
+// ENVREC: the launch may carry a record per environment (QArgs::rec_stride, resume_groups). The plain kernels are instantiated without it, so
+// that the launches that never prune per environment run the code they ran before there was such a record
+template <bool FEEDBACK, bool RESUME = false, bool ENVREC = false>
 __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ gm0, const QuadTables* __restrict__ tab0, const double* __restrict__ blob0,
                                                  const QBlob& bo, const QArgs& a0, const QFeedback& fb, int* __restrict__ stats) {
   // the workgroup's environment (env_select.h; 0 of one unless a0.env_n is set), from its first candidate: that environment's blob, node
   // times, nominal spline and noise stream. What the workgroup shares below (static_pose from the mocap pose) is then the environment's.
-  const int env = env_of(a0, (int)((blockIdx.x * blockDim.x) >> 6) * (a0.cpw > 0 ? a0.cpw : 16));
+  // The resume launch of a pruned batched launch has no such candidate to go by: its workgroup's environment, the first slot it serves of
+  // that environment's resume list and the list's length come from the host's table (resume_table.h), one entry per workgroup.
+  const bool grouped = RESUME && ENVREC && a0.resume_groups != nullptr;
+  int env, group_first = 0, group_count = 0;
+  if (grouped) {
+    const ResumeGroup g = a0.resume_groups[blockIdx.x];
+    env = __builtin_amdgcn_readfirstlane(g.env); group_first = __builtin_amdgcn_readfirstlane(g.first); group_count = __builtin_amdgcn_readfirstlane(g.count);
+  } else env = env_of(a0, (int)((blockIdx.x * blockDim.x) >> 6) * (a0.cpw > 0 ? a0.cpw : 16));
   const double* __restrict__ blob = env_ptr(blob0, env, a0.env_stride);
   // and that environment's model and pair tables (mjpcx_set_models_batched; strides of 0: the one model): scalar adds, once, before the step loop
   const QuadModel* __restrict__ gm = env_ptr(gm0, env, a0.model_stride);
@@ -233,6 +242,14 @@ __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ g
   env_rebase(a, env);
   a.param_variance = env_ptr(a.param_variance, env, a0.env_stride);  // (CE: the environment's own variance row)
   a.seed += (uint64_t)env; a.candidate_offset -= env * a0.env_n;
+  // a bound per environment (mjpcx_set_pruning_batched; a stride of 0: the one record of a plain launch): the bound word and the counters
+  // are the environment's, and so is the park hint, which sits in the record -- scalar adds and one scalar load, once, before the step loop.
+  // Nothing of another environment is compared with, lowered or counted from here on.
+  if (ENVREC && a0.rec_stride) {
+    a.prune_bound = const_cast<unsigned long long*>(env_ptr(a0.prune_bound, env, a0.rec_stride));
+    a.prune_stats = const_cast<int*>(env_ptr(a0.prune_stats, env, a0.rec_stride));
+    if (!RESUME) a.park_hint = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.prune_bound) + kQEnvRecHint);  // (a resumed candidate is never parked again)
+  }
   __shared__ QuadModel sm;
   __shared__ QStaticPose sp[kQStatic];
   extern __shared__ __attribute__((aligned(16))) double con_lds[];
@@ -249,9 +266,11 @@ __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ g
   // its first lanes), so that its lock-step is over fewer candidates and it still uses every SIMD
   const int cpw = a.cpw > 0 ? a.cpw : 16;
   const int quad = (threadIdx.x & 63) >> 2, leg = threadIdx.x & 3;
-  const int slot = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * cpw + quad;
-  if (quad >= cpw || slot >= (RESUME ? a.resume_n : a.N)) return;  // (whole quads leave together)
-  const int cand = RESUME ? a.resume_list[slot] : slot;
+  // (grouped: the workgroup's wavefronts share out the slots from group_first on; the environment's segment of the list starts env_n entries
+  // after the one before and holds group_count <= env_n indices, global ones)
+  const int slot = grouped ? group_first + (int)(threadIdx.x >> 6) * cpw + quad : ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * cpw + quad;
+  if (quad >= cpw || slot >= (grouped ? group_count : RESUME ? a.resume_n : a.N)) return;  // (whole quads leave together)
+  const int cand = RESUME ? a.resume_list[(grouped ? (size_t)env * a0.env_n : (size_t)0) + slot] : slot;
   QTask tk;
   tk.mocap = blob + bo.off_mocap; tk.weight = blob + bo.off_weight; tk.norm_p = blob + bo.off_normp; tk.norm_q = blob + bo.off_normq;
   tk.param = blob + bo.off_param; tk.re = blob + bo.off_rreal; tk.ri = reinterpret_cast<const int*>(blob + bo.off_rint); tk.risk = blob[bo.off_risk];
@@ -278,11 +297,16 @@ __global__ __launch_bounds__(256) void rollout_quad_kernel(const QuadModel* __re
                                                            const QBlob bo, const QArgs a, int* __restrict__ stats) {
   quad_kernel_body<false>(gm, tab, blob, bo, a, QFeedback{}, stats);
 }
+// rollout_quad_kernel for a launch with a bound, a hint and a set of counters per environment (QArgs::rec_stride != 0: mjpcx_set_pruning_batched)
+__global__ __launch_bounds__(256) void rollout_quad_env_kernel(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob,
+                                                               const QBlob bo, const QArgs a, int* __restrict__ stats) {
+  quad_kernel_body<false, false, true>(gm, tab, blob, bo, a, QFeedback{}, stats);
+}
 // The candidates a launch with QArgs::park_hint set aside and its settling pass (park_settle.h) could not retire: a.resume_n of them, a.cpw per
 // wavefront, each from its record. Same outputs, flags and hand-on counters as rollout_quad_kernel
 __global__ __launch_bounds__(256) void rollout_quad_resume_kernel(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob,
                                                                   const QBlob bo, const QArgs a, int* __restrict__ stats) {
-  quad_kernel_body<false, true>(gm, tab, blob, bo, a, QFeedback{}, stats);
+  quad_kernel_body<false, true, true>(gm, tab, blob, bo, a, QFeedback{}, stats);
 }
 // The iLQG rollouts (the nominal under iLQGPolicy::Action, the line search's under the index policy) on the same step function: one or ten
 // candidates, ONE per wavefront (QArgs::cpw = 1) -- pure per-step latency, and the quad form's step is the shortest of the kernels' (0.145 ms

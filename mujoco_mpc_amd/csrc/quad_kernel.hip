@@ -45,28 +45,42 @@ hipError_t launch_rollout_quad(const void* model_, const void* tables_, const do
   const int W = waves >= 4 * 256 ? 4 : 1;
   const size_t lds = W * kQWaveLds;
   // (the opt-in to more than 64 KB of dynamic LDS is per device and costs nothing next to a 60 ms launch: set on every launch, like the other launchers)
-  hipError_t e = hipFuncSetAttribute((const void*)rollout_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kQWaveLds));
+  // (a launch with a record per environment has an instantiation of its own: the plain one stays as it was)
+  const auto kern = q.rec_stride ? rollout_quad_env_kernel : rollout_quad_kernel;
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kQWaveLds));
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(rollout_quad_kernel, dim3((waves + W - 1) / W), dim3(64 * W), lds, stream, model, tables, blob, bo, q, stats);
+  hipLaunchKernelGGL(kern, dim3((waves + W - 1) / W), dim3(64 * W), lds, stream, model, tables, blob, bo, q, stats);
   return hipGetLastError();
 }
 hipError_t launch_resume_quad(const void* model_, const void* tables_, const double* blob, const QBlob& bo, const QArgs& a, int* stats, hipStream_t stream) {
   const QuadModel* model = static_cast<const QuadModel*>(model_);
   const QuadTables* tables = static_cast<const QuadTables*>(tables_);
   if (a.resume_n <= 0) return hipSuccess;
-  // candidates per wavefront from the list's length, as pick_cpw does, but down to ONE: the list is what is left of a launch, the machine is
-  // otherwise empty, and the candidates of a resumed wavefront are at different steps -- up to 1024 of them get a wavefront (and a SIMD) each.
-  // Never more wavefronts than the 1024 SIMDs: a second round of wavefronts would cost more than a wider lock-step. (The choice between 2 and 4
-  // per wavefront for lists of 1025 .. 4096 has not been measured on this path; pick_cpw's figures are for a main launch of gait steps.)
+  // candidates per wavefront from the list's length, as pick_cpw does, but down to ONE (resume_cpw of resume_table.h): up to 1024 resumed
+  // candidates get a wavefront (and a SIMD) each. Never more wavefronts than the 1024 SIMDs: a second round of wavefronts would cost more than
+  // a wider lock-step. (pick_cpw's figures are for a main launch of gait steps.)
   QArgs q = a;
-  q.cpw = 16;
-  while (q.cpw > 1 && (a.resume_n + q.cpw / 2 - 1) / (q.cpw / 2) <= 1024) q.cpw >>= 1;
+  q.cpw = resume_cpw(a.resume_n);
+  q.resume_groups = nullptr;
   q.stamps = nullptr; q.wave_times = nullptr; q.wave_class = nullptr;  // (the tuning aids index by the main launch's wavefronts)
   const int waves = (a.resume_n + q.cpw - 1) / q.cpw;
-  const int W = waves >= 4 * 256 ? 4 : 1;
+  const int W = resume_wpg(waves);
   hipError_t e = hipFuncSetAttribute((const void*)rollout_quad_resume_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kQWaveLds));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(rollout_quad_resume_kernel, dim3((waves + W - 1) / W), dim3(64 * W), W * kQWaveLds, stream, model, tables, blob, bo, q, stats);
+  return hipGetLastError();
+}
+hipError_t launch_resume_quad_groups(const void* model_, const void* tables_, const double* blob, const QBlob& bo, const QArgs& a, int W, int grid, int* stats,
+                                     hipStream_t stream) {
+  const QuadModel* model = static_cast<const QuadModel*>(model_);
+  const QuadTables* tables = static_cast<const QuadTables*>(tables_);
+  if (grid <= 0) return hipSuccess;
+  if (!a.resume_groups || !a.rec_stride || a.cpw < 1 || (W != 1 && W != 4)) return hipErrorInvalidValue;
+  QArgs q = a;
+  q.stamps = nullptr; q.wave_times = nullptr; q.wave_class = nullptr;
+  hipError_t e = hipFuncSetAttribute((const void*)rollout_quad_resume_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kQWaveLds));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(rollout_quad_resume_kernel, dim3(grid), dim3(64 * W), W * kQWaveLds, stream, model, tables, blob, bo, q, stats);
   return hipGetLastError();
 }
 } }

@@ -24,4 +24,8 @@ hipError_t launch_feedback_quad(const void* model, const void* tables, const dou
 hipError_t launch_rollout_quad(const void* model, const void* tables, const double* blob, const QBlob& bo, const QArgs& a, int* stats, hipStream_t stream);
 // the candidates of a.resume_list (device memory, a.resume_n entries, known to the host) from their park records; outputs, flags and hand-on as launch_rollout_quad
 hipError_t launch_resume_quad(const void* model, const void* tables, const double* blob, const QBlob& bo, const QArgs& a, int* stats, hipStream_t stream);
+// the same for a launch with a record per environment (a.rec_stride): ONE launch over the environments' lists, `grid` workgroups of W wavefronts of a.cpw candidates,
+// workgroup b serving a.resume_groups[b] (device memory, `grid` entries, built by resume_table_build of resume_table.h with the same cpw and W)
+hipError_t launch_resume_quad_groups(const void* model, const void* tables, const double* blob, const QBlob& bo, const QArgs& a, int W, int grid, int* stats,
+                                     hipStream_t stream);
 } }

@@ -92,7 +92,9 @@ __global__ __launch_bounds__(TREE_KERNEL_THREADS) void rollout_tree_kernel(const
       WSYNC();
     }
     if constexpr (BIG) {
-      if (a.failure[cand] & (32 << 8))  // wave-uniform
+      // (a candidate the quad kernel retired carries kQPruned | (retire step << 8): a retire step with bit 5 set is no overflow of the first
+      // pass. Without this test every hand-on of a pruned launch had those candidates rolled out again here, a wavefront each)
+      if ((a.failure[cand] & (32 << 8)) && !(a.failure[cand] & kQPruned))  // wave-uniform
         wave_rollout_body<C::NMAX, true, kTreeMaxSimpleBig, kTreeMaxConeBig>(m, tk, ae, arena, cand, lane);
     } else {
       if (!(mode & 32) || (a.failure[cand] & kQFallback))  // wave-uniform

@@ -19,7 +19,7 @@ import numpy as np
 from . import capi
 from .cstructs import PackedModel
 from .spline import CUBIC, LINEAR, ZERO, TimeSpline
-from .task import Task
+from .task import NORM_L2, NORM_POWER_LOSS, NORM_QUADRATIC, NORM_RECTIFY, NORM_SMOOTH_ABS, Task
 
 K_MAX_TRAJECTORY_HORIZON = 512  # mjpc/trajectory.h:27
 
@@ -472,9 +472,21 @@ class GpuBatchSamplingPlanner(_FleetTasks):
         self.differentiable = False  # plan on the differentiable model copy (GpuSamplingPlanner's): on in GpuBatchILQSPlanner
         # the members never roll out themselves: they are handed the shared context instead of creating their own
         self.envs = [GpuSamplingPlanner(device, precision, seed + e, backend_factory=lambda task: self.ctx) for e in range(self.num_envs)]
+        # optimize_policy reads nothing of a launch but each robot's argmin, its nominal's return and the winner's spline -- what a pruned launch
+        # keeps exact. pruning: the plan launch retires, per robot, the candidates that can no longer win (set_pruning_batched) and parks the ones
+        # the robot's previous best return x (1 + park_slack) condemns (GpuSamplingPlanner::OptimizePolicy of gpu_sampling/planner.cc, per robot).
+        # Off by default; the planners built on this one (Robust's delegate, iLQS's sampling half) rank every return and leave it off.
+        self.pruning = False
+        self.park_slack = DEFAULT_PARK_SLACK   # "sampling_park_slack" in the model; <= -1: no hints
+        self.prune_stats = self.park_stats = None   # of the last plan, per robot (capi.Context.prune_stats_batched); None unless it was pruned
+        self.park_hints_used = None                 # the hints the last plan's launch ran on (E; +inf: none), None unless it was pruned
+        self.pruned_launch_repeated = False         # the last plan's pruned launch was refused (MJPCX_ESTATE) and repeated unpruned
+        self._hint = [None] * self.num_envs         # per robot: (previous best return, task signature), or None -- no hint for the next plan
 
     def initialize(self, model, task: Task):
         self.model, self.task = model, task
+        self.park_slack = float(model.get_number("sampling_park_slack", DEFAULT_PARK_SLACK))
+        self._hint = [None] * self.num_envs
         for p in self.envs:
             p.initialize(model, task)
 
@@ -505,6 +517,7 @@ class GpuBatchSamplingPlanner(_FleetTasks):
         for p in self.envs:
             p.reset(horizon, initial_repeated_action)
         self._last = None
+        self._hint = [None] * self.num_envs
 
     def set_states(self, states):
         """one State per environment (Planner::SetState for each)"""
@@ -520,7 +533,18 @@ class GpuBatchSamplingPlanner(_FleetTasks):
                             np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
         self._push_task_rows()
 
-    def _launch(self, horizon):
+    def _park_hints(self):
+        """Robot e's park hint for the next launch: its previous best return x (1 + park_slack); +inf when it has no previous plan, when
+        that plan's best was not finite or was negative or it resumed more than a quarter of its candidates (_hint[e] is None then), or
+        when the robot's task row has changed since"""
+        hints = np.full(self.num_envs, np.inf)
+        if self.park_slack > -1.0:
+            for e, p in enumerate(self.envs):
+                if self._hint[e] is not None and self._hint[e][1] == task_signature(p.task):
+                    hints[e] = self._hint[e][0] * (1.0 + self.park_slack)
+        return hints
+
+    def _launch(self, horizon, prune=False):
         """First half of a plan step: every environment's nominal resampled, states and task rows pushed, the E x n candidates
         enqueued in one launch -- nothing read back, no sync. Returns when the rollouts' clock started (rollouts_compute_time)."""
         n = self.num_trajectory_
@@ -529,16 +553,31 @@ class GpuBatchSamplingPlanner(_FleetTasks):
             p.update_nominal_policy(horizon)
             p.policy.plan.set_interpolation(p.interpolation_)
         t0 = _time.perf_counter()
+        self._enqueue(horizon, prune)
+        return t0
+
+    def _enqueue(self, horizon, prune):
+        """the launch of _launch, with the members' nominals as they stand: optimize_policy repeats it unpruned, same seed and iteration,
+        when the context refuses the pruned one's argmin"""
+        n = self.num_trajectory_
         plans = [p.policy.plan for p in self.envs]
         exploration = self.envs[0].noise_exploration
         ns = capi.make_noise_spec(seed=self.seed, iteration=self.iteration, mode=capi.NOISE_SAMPLING, candidate_offset=0,
                                   nominal_candidate=0, std0=exploration[0], std1=exploration[1])
         self._push_states()
-        self.ctx.rollout_noise_batched(n, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
-                                       np.stack([pl.values() for pl in plans]), ns, num_envs=self.num_envs)
+        # (a cost that can be negative in any robot's task row: no pruning for the launch -- partial returns would be no lower bounds there)
+        self._pruned = bool(prune) and all(cost_is_non_negative(p.task) for p in self.envs)
+        self.park_hints_used = self._park_hints() if self._pruned else None
+        if self._pruned:
+            self.ctx.set_pruning_batched(True, self.num_envs, None, self.park_hints_used)
+        try:
+            self.ctx.rollout_noise_batched(n, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
+                                           np.stack([pl.values() for pl in plans]), ns, num_envs=self.num_envs)
+        finally:
+            if self._pruned:   # (the switch is sticky and the context is shared with the planners built on this one: on for this launch alone)
+                self.ctx.set_pruning_batched(False)
         self._last = "plan"
         self._n = n
-        return t0
 
     def _finish(self, t0, ranked):
         """Second half: `ranked` yields, per environment, (trajectory_order, scores, winner's place in them, winner's spline values) of
@@ -554,12 +593,32 @@ class GpuBatchSamplingPlanner(_FleetTasks):
         self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
 
     def optimize_policy(self, horizon, pool=None):
-        t0 = self._launch(horizon)
-        idx, best_ret, nominal_ret, values = self.ctx.best_batched(self.num_envs, 0)
+        t0 = self._launch(horizon, prune=self.pruning)
+        pruned = self._pruned
+        self.prune_stats = self.park_stats = None
+        self.pruned_launch_repeated = False
+        if pruned:
+            st = self.ctx.prune_stats_batched(self.num_envs)
+            self.prune_stats = {k: st[k] for k in ("retired", "retire_step_sum", "negative_cost", "wavefronts_ended_early", "final_bound")}
+            self.park_stats = {k: st[k] for k in ("parked", "settled_retired", "resumed")}
+        try:
+            idx, best_ret, nominal_ret, values = self.ctx.best_batched(self.num_envs, 0)
+        except capi.MjpcxError as err:
+            if not pruned or err.code != MJPCX_ESTATE:
+                raise
+            # some robot's pruned argmin is not proven (a negative step cost; with +inf as the initial bound nothing else leads here): the
+            # same candidates again, all to the horizon -- the policy stays exact
+            self.pruned_launch_repeated = True
+            self._enqueue(horizon, False)
+            idx, best_ret, nominal_ret, values = self.ctx.best_batched(self.num_envs, 0)
         self._finish(t0, [([idx[e]], [best_ret[e]], 0, values[e]) for e in range(self.num_envs)])
         for e, p in enumerate(self.envs):
             p.best_return, p.nominal_return = float(best_ret[e]), float(nominal_ret[e])
             p.improvement = max(float(nominal_ret[e] - best_ret[e]), 0.0)
+            # the next plan's hint, unless this plan's resume launch shows that the estimate it ran on was stale
+            best = float(best_ret[e])
+            stale = pruned and float(self.park_stats["resumed"][e]) > K_PARK_MAX_RESUME_SHARE * max(self._n, 1)
+            self._hint[e] = (best, task_signature(p.task)) if pruned and np.isfinite(best) and best >= 0 and not stale else None
 
     @property
     def winners(self):
@@ -595,6 +654,26 @@ class GpuBatchSamplingPlanner(_FleetTasks):
 
     def num_parameters(self):
         return self.envs[0].num_parameters()
+
+
+MJPCX_ESTATE = -5              # include/mjpcx.h
+DEFAULT_PARK_SLACK = 0.05      # kDefaultParkSlack of gpu_sampling/planner.h
+K_PARK_MAX_RESUME_SHARE = 0.25  # kParkMaxResumeShare: a plan that resumed more of a robot's candidates ran on a stale hint
+
+
+def task_signature(task):
+    """GpuSamplingPlanner::TaskSignature: what a robot's park hint is tied to -- weights, parameters, norm kinds and parameters, risk"""
+    return ([float(x) for x in task.weight] + [float(x) for x in task.parameters] + [float(int(k)) for k in task.norm] +
+            [float(x) for x in task.norm_parameter] + [float(task.risk)])
+
+
+def cost_is_non_negative(task):
+    """GpuSamplingPlanner::CostIsNonNegative: pruning needs every step's cost >= 0 in floating point -- weights >= 0, no risk transform, and
+    the norm kinds whose computed value is shown to be >= 0"""
+    if not abs(float(task.risk)) < 1.0e-6:
+        return False
+    ok = (NORM_QUADRATIC, NORM_L2, NORM_POWER_LOSS, NORM_SMOOTH_ABS, NORM_RECTIFY)
+    return all(float(w) >= 0 for w in task.weight) and all(int(k) in ok for k in task.norm)
 
 
 def _fleet_setting(name):

@@ -508,7 +508,7 @@ def sweep_ilqs(name, precision, H, shapes, steps, warmup, out, device_chain=None
         c.close()
 
 
-def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mixed=False, models=False):
+def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mixed=False, models=False, prune=False, park=True):
     task = load_task(name)
     m = task.model
     rng = np.random.default_rng(1)
@@ -552,10 +552,23 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
                 ctx.rollout_noise(n, H, interp, times[e], nominal[e], capi.make_noise_spec(seed=7 + e, iteration=it[0], std0=std))
                 ctx.best(0)
 
+        # --prune: the batched side retires and parks per environment (set_pruning_batched), as GpuBatchSamplingPlanner(pruning=True) does:
+        # on for the launch alone, every robot's hint its previous best return x 1.05 (--no-park: no hints)
+        last_best, counts = [None], []
+
         def batched():
             fleet_states()
-            ctx.rollout_noise_batched(n, H, interp, times, nominal, capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_envs=E)
-            ctx.best_batched(E, 0)
+            if prune:
+                hints = None if not park or last_best[0] is None else 1.05 * last_best[0]
+                ctx.set_pruning_batched(True, E, None, hints)
+            try:
+                ctx.rollout_noise_batched(n, H, interp, times, nominal, capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_envs=E)
+            finally:
+                if prune:
+                    ctx.set_pruning_batched(False)
+            if prune:
+                counts.append(ctx.prune_stats_batched(E))
+            last_best[0] = ctx.best_batched(E, 0)[1]
 
         ce = planner == "cross_entropy"
         n_elite = max(n // 10, 2)
@@ -601,6 +614,10 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
                "batched_ms": {"median": float(np.median(tb)), "min": float(np.min(tb)), "max": float(np.max(tb))},
                "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)),
                "beyond_spread": bool(np.max(tb) < np.min(ts))}
+        if prune and not ce:   # per environment, summed over the timed steps: how much of the fleet left early, and how
+            timed = counts[-steps:]
+            rec.update(prune=True, park=bool(park), candidates_per_env=int(n) * steps,
+                       **{k: [int(sum(c[k][e] for c in timed)) for e in range(E)] for k in ("retired", "retire_step_sum", "parked", "settled_retired", "resumed")})
         if ce:
             tr, tu = [], []
             for _ in range(steps):
@@ -632,6 +649,8 @@ def main():
     ap.add_argument("--mixed-models", action="store_true", help="sampling, cross_entropy: every environment its own model (payload, friction, actuator strength)")
     ap.add_argument("--robust", default="16x4", help="--planner robust: candidates x repetitions")
     ap.add_argument("--gradient-candidates", type=int, default=32, help="--planner sample_gradient: gradient candidates per environment")
+    ap.add_argument("--prune", action="store_true", help="--planner sampling: the batched side prunes and parks per environment (set_pruning_batched)")
+    ap.add_argument("--no-park", action="store_true", help="with --prune: no park hints")
     ap.add_argument("--no-device-chain", action="store_true", help="--planner ilqg, ilqs: the sequential middle (the A/B of ilqg_step_batched[_from])")
     a = ap.parse_args()
     if a.out is None:
@@ -644,6 +663,8 @@ def main():
         for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES, "ilqs": ILQS_SHAPES, "robust": ROBUST_SHAPES,
                                              "sample_gradient": SAMPLE_GRADIENT_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
+            if keep is not None and a.only == name and a.planner == "sampling":   # (--only with --shapes: also shapes outside the default list, e.g. 16x1024)
+                shapes += [sh for sh in sorted(keep) if sh not in shapes]
             if shapes and (a.only is None or a.only == name):
                 if a.mixed_models and (a.planner not in ("sampling", "cross_entropy") or name == "Cartpole"):
                     if a.planner not in ("sampling", "cross_entropy"):
@@ -663,7 +684,9 @@ def main():
                 elif a.planner == "ilqg":
                     sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out, False if a.no_device_chain else None, a.mixed_params)
                 else:
-                    sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner, a.mixed_params, a.mixed_models)
+                    if a.prune and a.planner != "sampling":
+                        raise SystemExit("batch_sweep.py: --prune is for --planner sampling")
+                    sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner, a.mixed_params, a.mixed_models, a.prune, not a.no_park)
 
 
 if __name__ == "__main__":
