@@ -101,7 +101,27 @@ class SamplingPolicy:
         self.num_spline_points = policy.num_spline_points
 
 
-class GpuSamplingPlanner:
+def _agent_differentiable(model):
+    """the gradient-based planners plan on the differentiable model copy unless agent_differentiable says otherwise (agent.cc:156-164)"""
+    return bool(int(model.get_number("agent_differentiable", 1)))
+
+
+class _ContextOwner:
+    """what every planner with a context of its own shares, single or fleet: `device`, `precision`, `_backend_factory`, `model` and
+    `task` are the planner's"""
+
+    def _create_context(self, differentiable=False):
+        """the one place a context is made: `backend_factory(task)` where the planner was given one (a fleet's member is handed the
+        shared context; test backends: see tests/oracle_backend.py), else a device context on the task's planning model"""
+        if self._backend_factory is not None:
+            return self._backend_factory(self.task)
+        return capi.Context(self.task.packed_model(differentiable=differentiable), self.task.packed(), self.device, self.precision)
+
+    def _timestep(self):
+        return self.model.get_number("agent_timestep", self.model.timestep)
+
+
+class GpuSamplingPlanner(_ContextOwner):
     """mjpc::SamplingPlanner with the candidate fan-out on the GPU.
 
     `group`: optional rank group (see distributed.py) sharding the candidates over
@@ -153,11 +173,7 @@ class GpuSamplingPlanner:
         self.winner_policy.allocate(m, self.task, K_MAX_TRAJECTORY_HORIZON)
         self.plan_scratch = TimeSpline(m.nu)
         self._best = None
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            self.ctx = capi.Context(self.task.packed_model(differentiable=self.differentiable), self.task.packed(), self.device,
-                                    self.precision)
+        self.ctx = self._create_context(self.differentiable)
 
     # ---- Planner::Reset, planner.cc:110-147
     def reset(self, horizon, initial_repeated_action=None):
@@ -213,9 +229,6 @@ class GpuSamplingPlanner:
                 nominal_time += time_shift
             with self.mtx_:
                 self.policy.plan = self.plan_scratch.copy()
-
-    def _timestep(self):
-        return self.model.get_number("agent_timestep", self.model.timestep)
 
     # ---- Rollouts, planner.cc:355-393: the device fan-out
     def rollouts(self, num_trajectory, horizon):
@@ -356,8 +369,97 @@ class GpuSamplingPlanner:
         self._set_winner(self.trajectory_order[candidate], p.plan.values())
 
 
-class _FleetTasks:
-    """`set_tasks` of the fleet planners: one Task per environment instead of the one the fleet was initialised with."""
+MJPCX_ESTATE = -5              # include/mjpcx.h
+DEFAULT_PARK_SLACK = 0.05      # kDefaultParkSlack of gpu_sampling/planner.h
+K_PARK_MAX_RESUME_SHARE = 0.25  # kParkMaxResumeShare: a plan that resumed more of a robot's candidates ran on a stale hint
+
+
+class _Fleet(_ContextOwner):
+    """The fleet ("batched") planners' base: `num_envs` members in `envs`, one per environment and each the single planner of its
+    kind, on ONE shared context. Here is everything per environment that does not depend on the kind of planner: the members'
+    states, tasks and models and their way to the context, the pass-throughs to the members, and the two fetches of trajectories
+    from a batched launch. A fleet planner supplies its members (`envs`, which are handed the shared context through their
+    backend_factory), its launch and its selection (`optimize_policy`, and `nominal_trajectory` / `best_trajectory` where it has
+    them), and `_reset_own` for what a reset clears beside the members."""
+    derivative_chain = False     # Gradient, iLQG: the batched derivative calls use the context's one model, so no set_models
+    differentiable = False       # plan on the differentiable model copy: GpuBatchILQSPlanner turns it on in its sampling half (a planner
+                                 # with a derivative chain asks agent_differentiable instead)
+    _n_advice = "set sampling_trajectories / num_trajectory_ accordingly"   # _check_n's last sentence: the setting behind n
+    _last, _n = None, 0          # what the context's last rollout was: "plan" (_n candidates per environment) or "nominal" (64)
+
+    def __init__(self, num_envs, device, precision, backend_factory):
+        if int(num_envs) < 1:
+            raise ValueError(f"{type(self).__name__} needs at least one environment")
+        self.num_envs, self.device, self.precision = int(num_envs), device, precision
+        self._backend_factory = backend_factory
+        self.model = self.task = self.ctx = None
+
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
+        for p in self.envs:
+            p.initialize(model, task)
+
+    def allocate(self):
+        self.ctx = self._create_context(_agent_differentiable(self.model) if self.derivative_chain else self.differentiable)
+        for p in self.envs:
+            p.allocate()
+        self._push_models()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        for p in self.envs:
+            p.reset(horizon, initial_repeated_action)
+        self._reset_own()
+
+    def _reset_own(self):
+        """what a reset clears in the fleet planner itself"""
+
+    def _check_n(self, n):
+        if n < 64 or n % 64 != 0:
+            raise ValueError(f"{type(self).__name__}: {n} candidates per environment; a batched launch needs a positive multiple "
+                             f"of 64 (every wavefront serves one environment) -- {self._n_advice}")
+
+    def set_states(self, states):
+        """one State per environment (Planner::SetState for each)"""
+        if len(states) != self.num_envs:
+            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
+        for p, st in zip(self.envs, states):
+            p.set_state(st)
+
+    def _push_states(self, members=None):
+        """before every batched launch: the fleet's task, the members' states (another fleet's members for Robust, whose members sit
+        on its delegate's), the task rows"""
+        members = self.envs if members is None else members
+        sync_task(self.ctx, self.task)
+        self.ctx.set_states(np.stack([p.state for p in members]), np.array([p.time for p in members]),
+                            np.stack([p.mocap for p in members]) if self.model.nmocap else None,
+                            np.stack([p.userdata for p in members]) if self.model.nuserdata else None)
+        self._push_task_rows()
+
+    def _nominal_launch(self, horizon, interpolation, times, values, fetch=True):
+        """NominalTrajectory of every environment in one launch: 64 candidates per environment, each carrying the environment's policy
+        (`values` E x P x nu, so candidate 0 does); -> the E trajectories, unless the caller reads the rollout on the device instead"""
+        self._push_states()
+        values = np.stack([np.broadcast_to(v[None], (64,) + v.shape) for v in values])
+        self.ctx.rollout_splines_batched(horizon, interpolation, times, values, num_envs=self.num_envs, n_per_env=64)
+        self._last = "nominal"
+        return [self.ctx.fetch_trajectory(64 * e) for e in range(self.num_envs)] if fetch else None
+
+    def _fetch_planned(self, env, index):
+        """candidate `index` of environment `env` in the plan launch (global candidate env * n + index), for a lazy best_trajectory;
+        None once the context's last rollout is no longer that launch"""
+        return self.ctx.fetch_trajectory(env * self._n + index) if self._last == "plan" else None
+
+    @property
+    def winners(self):
+        return [p.winner for p in self.envs]
+
+    def action_from_policy(self, env, action, state, time, use_previous=False):
+        return self.envs[env].action_from_policy(action, state, time, use_previous)
+
+    def num_parameters(self):
+        return self.envs[0].num_parameters()
+
+    # ---- a task per environment
     _tasks = None
     _rows_pushed = False
 
@@ -400,6 +502,8 @@ class _FleetTasks:
         flag) and handed to the context (`set_models_batched`, a setup call: not for a plan loop). Member e then plans exactly like the
         single planner of its kind created on models[e]. After `allocate`; the models are pushed again when `allocate` re-creates the
         context. None: the fleet's one model for every environment again. Composes with `set_tasks`."""
+        if self.derivative_chain:
+            raise NotImplementedError(self._MODELS_FOLLOW_UP)
         previous = self._models
         if models is None:
             self._models = None
@@ -433,7 +537,7 @@ class _FleetTasks:
         ref = self.task.model
         ts = ref.get_number("agent_timestep", ref.timestep)
         integ = int(ref.get_number("agent_integrator", ref.integrator))
-        self.ctx.set_models_batched([PackedModel(m, timestep=ts, integrator=integ, differentiable=bool(getattr(self, "differentiable", False)))
+        self.ctx.set_models_batched([PackedModel(m, timestep=ts, integrator=integ, differentiable=bool(self.differentiable))
                                      for m in self._models])
         self._models_on = (self.ctx, self._models)
 
@@ -453,7 +557,7 @@ class _FleetTasks:
                                          rows("residual_real") if ts[0].residual_real else None)
 
 
-class GpuBatchSamplingPlanner(_FleetTasks):
+class GpuBatchSamplingPlanner(_Fleet):
     """Predictive Sampling for `num_envs` environments (robots) on ONE context: every plan step is one `set_states`, one
     `rollout_noise_batched` over all E x n candidates, one `best_batched` and one sync, instead of E plan steps one after the
     other. The environments share the model and the task (weights, parameters) unless `set_tasks` gives each its own; each has its own
@@ -461,15 +565,10 @@ class GpuBatchSamplingPlanner(_FleetTasks):
     logic (nominal resampling, policy copy, ActionFromPolicy) IS that planner's, one member per environment."""
 
     def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
-        if int(num_envs) < 1:
-            raise ValueError("GpuBatchSamplingPlanner needs at least one environment")
-        self.num_envs, self.device, self.precision, self.seed = int(num_envs), device, precision, seed
-        self._backend_factory = backend_factory
-        self.model = self.task = self.ctx = None
+        super().__init__(num_envs, device, precision, backend_factory)
+        self.seed = seed
         self.iteration = 0
         self.rollouts_compute_time = self.policy_update_compute_time = 0.0
-        self._last = None  # what the context's last rollout was: "plan" (n candidates per environment) or "nominal"
-        self.differentiable = False  # plan on the differentiable model copy (GpuSamplingPlanner's): on in GpuBatchILQSPlanner
         # the members never roll out themselves: they are handed the shared context instead of creating their own
         self.envs = [GpuSamplingPlanner(device, precision, seed + e, backend_factory=lambda task: self.ctx) for e in range(self.num_envs)]
         # optimize_policy reads nothing of a launch but each robot's argmin, its nominal's return and the winner's spline -- what a pruned launch
@@ -484,11 +583,9 @@ class GpuBatchSamplingPlanner(_FleetTasks):
         self._hint = [None] * self.num_envs         # per robot: (previous best return, task signature), or None -- no hint for the next plan
 
     def initialize(self, model, task: Task):
-        self.model, self.task = model, task
+        super().initialize(model, task)
         self.park_slack = float(model.get_number("sampling_park_slack", DEFAULT_PARK_SLACK))
         self._hint = [None] * self.num_envs
-        for p in self.envs:
-            p.initialize(model, task)
 
     @property
     def num_trajectory_(self):
@@ -499,39 +596,9 @@ class GpuBatchSamplingPlanner(_FleetTasks):
         for p in self.envs:
             p.num_trajectory_ = int(n)
 
-    def _check_n(self, n):
-        if n < 64 or n % 64 != 0:
-            raise ValueError(f"GpuBatchSamplingPlanner: {n} candidates per environment; a batched launch needs a positive multiple "
-                             "of 64 (every wavefront serves one environment) -- set sampling_trajectories / num_trajectory_ accordingly")
-
-    def allocate(self):
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            self.ctx = capi.Context(self.task.packed_model(differentiable=self.differentiable), self.task.packed(), self.device, self.precision)
-        for p in self.envs:
-            p.allocate()
-        self._push_models()
-
-    def reset(self, horizon, initial_repeated_action=None):
-        for p in self.envs:
-            p.reset(horizon, initial_repeated_action)
+    def _reset_own(self):
         self._last = None
         self._hint = [None] * self.num_envs
-
-    def set_states(self, states):
-        """one State per environment (Planner::SetState for each)"""
-        if len(states) != self.num_envs:
-            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
-        for p, st in zip(self.envs, states):
-            p.set_state(st)
-
-    def _push_states(self):
-        sync_task(self.ctx, self.task)
-        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
-                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
-                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
-        self._push_task_rows()
 
     def _park_hints(self):
         """Robot e's park hint for the next launch: its previous best return x (1 + park_slack); +inf when it has no previous plan, when
@@ -620,45 +687,26 @@ class GpuBatchSamplingPlanner(_FleetTasks):
             stale = pruned and float(self.park_stats["resumed"][e]) > K_PARK_MAX_RESUME_SHARE * max(self._n, 1)
             self._hint[e] = (best, task_signature(p.task)) if pruned and np.isfinite(best) and best >= 0 and not stale else None
 
-    @property
-    def winners(self):
-        return [p.winner for p in self.envs]
-
     def nominal_trajectory(self, horizon, pool=None):
-        """NominalTrajectory of every environment in one launch: 64 candidates per environment, candidate 0 carrying the policy"""
         plans = [(p.winner_policy.plan if p.winner_policy.plan.size() else p.policy.plan) for p in self.envs]
         if any(pl.size() != plans[0].size() for pl in plans):
             raise ValueError("the environments' policies have different numbers of spline nodes")
-        self._push_states()
         if plans[0].size() == 0:
             times = np.array([[p.time] for p in self.envs])
-            values = np.zeros((self.num_envs, 64, 1, self.model.nu))
+            values = np.zeros((self.num_envs, 1, self.model.nu))
         else:
             times = np.stack([pl.times() for pl in plans])
-            values = np.stack([np.broadcast_to(pl.values()[None], (64,) + pl.values().shape) for pl in plans])
-        self.ctx.rollout_splines_batched(horizon, plans[0].interpolation(), times, values, num_envs=self.num_envs, n_per_env=64)
-        self._last = "nominal"
-        out = [self.ctx.fetch_trajectory(64 * e) for e in range(self.num_envs)]
+            values = [pl.values() for pl in plans]
+        out = self._nominal_launch(horizon, plans[0].interpolation(), times, values)
         for p, tr in zip(self.envs, out):
             p._best = tr
         return out
 
-    def action_from_policy(self, env, action, state, time, use_previous=False):
-        return self.envs[env].action_from_policy(action, state, time, use_previous)
-
     def best_trajectory(self, env):
         p = self.envs[env]
-        if p._best is None and self._last == "plan":
-            p._best = self.ctx.fetch_trajectory(env * self._n + p.winner)
+        if p._best is None:
+            p._best = self._fetch_planned(env, p.winner)
         return p._best
-
-    def num_parameters(self):
-        return self.envs[0].num_parameters()
-
-
-MJPCX_ESTATE = -5              # include/mjpcx.h
-DEFAULT_PARK_SLACK = 0.05      # kDefaultParkSlack of gpu_sampling/planner.h
-K_PARK_MAX_RESUME_SHARE = 0.25  # kParkMaxResumeShare: a plan that resumed more of a robot's candidates ran on a stale hint
 
 
 def task_signature(task):
@@ -706,7 +754,7 @@ def robust_scores(scores, returns, failure, repetitions):
     return perturbed, valid, best
 
 
-class GpuRobustPlanner:
+class GpuRobustPlanner(_ContextOwner):
     """mjpc::RobustPlanner (mjpc/planners/robust/robust_planner.{h,cc}) with both fan-outs on the device, the mirror of the C++
     GpuRobustPlanner for one rank: the delegate (a GpuSamplingPlanner) ranks its candidates, the `robust_candidates` best are rolled
     out `robust_repetitions` times each under Ornstein-Uhlenbeck force noise in ONE launch on a second context (the delegate's
@@ -736,10 +784,7 @@ class GpuRobustPlanner:
 
     def allocate(self):
         self.delegate.allocate()
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+        self.ctx = self._create_context()
 
     def reset(self, horizon, initial_repeated_action=None):
         self.delegate.reset(horizon, initial_repeated_action)
@@ -788,7 +833,7 @@ class GpuRobustPlanner:
         return self.delegate.num_parameters()
 
 
-class GpuBatchRobustPlanner(_FleetTasks):
+class GpuBatchRobustPlanner(_Fleet):
     """The Robust planner for `num_envs` robots on two contexts of one model: a plan step is the delegate fleet's launch
     (GpuBatchSamplingPlanner: states and task rows pushed, E x n candidates rolled out, nothing read back) and one
     `robust_step_batched` on the second context -- per environment the k best candidates selected, replicated R times, rolled out
@@ -802,18 +847,15 @@ class GpuBatchRobustPlanner(_FleetTasks):
 
     def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
         self.delegate = GpuBatchSamplingPlanner(num_envs, device, precision, seed, backend_factory)
-        self.num_envs, self.device, self.precision, self.seed = self.delegate.num_envs, device, precision, seed
-        self._backend_factory = backend_factory
-        self.model = self.task = self.ctx = None
+        super().__init__(num_envs, device, precision, backend_factory)
+        self.seed = seed
         self.iteration = 0
         # the members never roll out themselves: each sits on the delegate fleet's member and is handed the second context
         self.envs = [GpuRobustPlanner(p, device, precision, seed + e, backend_factory=lambda task: self.ctx) for e, p in enumerate(self.delegate.envs)]
 
     def initialize(self, model, task: Task):
-        self.model, self.task = model, task
         self.delegate.initialize(model, task)
-        for p in self.envs:
-            p.initialize(model, task)   # (its delegate, the delegate fleet's member, once more: the same values)
+        super().initialize(model, task)   # (a member initialises its delegate, the delegate fleet's member, once more: the same values)
 
     @property
     def num_trajectory_(self):
@@ -829,10 +871,7 @@ class GpuBatchRobustPlanner(_FleetTasks):
 
     def allocate(self):
         self.delegate.allocate()
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+        self.ctx = self._create_context()
         for p in self.envs:
             p.ctx = self.ctx
         self._push_models()
@@ -857,12 +896,7 @@ class GpuBatchRobustPlanner(_FleetTasks):
 
     def _push_states(self):
         """the delegate fleet's states and task rows, to the second context"""
-        d = self.delegate.envs
-        sync_task(self.ctx, self.task)
-        self.ctx.set_states(np.stack([p.state for p in d]), np.array([p.time for p in d]),
-                            np.stack([p.mocap for p in d]) if self.model.nmocap else None,
-                            np.stack([p.userdata for p in d]) if self.model.nuserdata else None)
-        self._push_task_rows()
+        super()._push_states(self.delegate.envs)
 
     def optimize_policy(self, horizon, pool=None):
         d = self.delegate
@@ -901,12 +935,6 @@ class GpuBatchRobustPlanner(_FleetTasks):
 
     def num_parameters(self):
         return self.delegate.num_parameters()
-
-
-def log_scale(max_value, min_value, steps):
-    """LogScale, mjpc/utilities.cc:819-826: log-spaced values from min_value up to max_value"""
-    step = (math.log(max_value) - math.log(min_value)) / (steps - 1 if steps > 1 else 1)
-    return np.array([math.exp(math.log(min_value) + i * step) for i in range(steps)])
 
 
 def strided_tree_sum(terms):
@@ -987,8 +1015,42 @@ class _SampleGradientMember:
         self.gradient = np.zeros(0)
         self._best = None
 
+    def initialize(self, model, task: Task):
+        self.model, self.task = model, task
 
-class GpuBatchSampleGradientPlanner(_FleetTasks):
+    # ---- Allocate, planner.cc:73-112
+    def allocate(self):
+        m = self.model
+        self.state, self.mocap, self.userdata, self.time = np.zeros(m.nq + m.nv + m.na), np.zeros(7 * m.nmocap), np.zeros(m.nuserdata), 0.0
+        self.policy, self.previous_policy = SamplingPolicy(), SamplingPolicy()
+        self.policy.allocate(m, self.task, K_MAX_TRAJECTORY_HORIZON)
+        self.previous_policy.allocate(m, self.task, K_MAX_TRAJECTORY_HORIZON)
+        self.gradient = np.zeros(self.policy.num_spline_points * m.nu)
+
+    # ---- Reset, planner.cc:115-163: the gradient is zeroed
+    def reset(self, horizon, initial_repeated_action=None):
+        self.state[:] = 0
+        self.mocap[:] = 0
+        self.userdata[:] = 0
+        self.time = 0.0
+        with self.mtx_:
+            self.policy.reset(horizon, initial_repeated_action)
+            self.previous_policy.reset(horizon, initial_repeated_action)
+        self.improvement, self.winner, self._best = 0.0, 0, None
+        self.gradient = np.zeros_like(self.gradient)
+
+    def set_state(self, state: State):
+        self.state, self.mocap, self.userdata, self.time = state.copy_to()
+
+    def action_from_policy(self, action, state, time, use_previous=False):
+        with self.mtx_:
+            return (self.previous_policy if use_previous else self.policy).action(action, state, time)
+
+    def num_parameters(self):
+        return self.policy.num_spline_points * self.model.nu
+
+
+class GpuBatchSampleGradientPlanner(_Fleet):
     """mjpc::SampleGradientPlanner (mjpc/planners/sample_gradient/planner.{h,cc}) for `num_envs` robots on ONE context, the candidates,
     the sort, the fitness-shaped gradient estimate and the gradient-step candidates on the device: a plan step is the host resample of
     every nominal, one `set_states`, one `rollout_sample_gradient_batched`, one `sample_gradient_update_batched` and ONE sync. The
@@ -999,74 +1061,32 @@ class GpuBatchSampleGradientPlanner(_FleetTasks):
     of num_gradient_ or of the number of spline points starts the gradient candidates again from the zero spline, as a reset does."""
 
     def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
-        if int(num_envs) < 1:
-            raise ValueError("GpuBatchSampleGradientPlanner needs at least one environment")
-        self.num_envs, self.device, self.precision, self.seed = int(num_envs), device, precision, seed
-        self._backend_factory = backend_factory
-        self.model = self.task = self.ctx = None
+        super().__init__(num_envs, device, precision, backend_factory)
+        self.seed = seed
         self.iteration = 0
         self.rollouts_compute_time = self.policy_update_compute_time = 0.0
         self.gradient_max_step_size, self.gradient_min_step_size = 2.0, 1.0e-3   # planner.h
         self.envs = [_SampleGradientMember(seed + e) for e in range(self.num_envs)]
-        self._n = 0
         self._weights_for = None      # num_noisy the context's shaping weights were computed for (return_weight_.size())
         self._zero_gradient = True    # the context's gradient is to be taken as zero (Allocate / Reset)
         self._candidates_for = None   # (num_gradient, spline points) of the gradient candidates on the device; None: upload the zero spline
 
     # ---- Initialize, planner.cc:41-70
     def initialize(self, model, task: Task):
-        self.model, self.task = model, task
+        super().initialize(model, task)
         self.noise_exploration = model.get_number("sampling_exploration", 0.1)
         self.num_trajectory_ = int(model.get_number("sampling_trajectories", 10))
         self.interpolation_ = int(model.get_number("sampling_representation", CUBIC))
         self.num_gradient_ = int(model.get_number("sample_gradient_trajectories", 0))
         self.gradient_filter_ = model.get_number("sample_gradient_filter", 1.0)
-        for p in self.envs:
-            p.task = task
 
-    # ---- Allocate, planner.cc:73-112
     def allocate(self):
-        m = self.model
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
-        for p in self.envs:
-            p.state, p.mocap, p.userdata, p.time = np.zeros(m.nq + m.nv + m.na), np.zeros(7 * m.nmocap), np.zeros(m.nuserdata), 0.0
-            p.policy, p.previous_policy = SamplingPolicy(), SamplingPolicy()
-            p.policy.allocate(m, self.task, K_MAX_TRAJECTORY_HORIZON)
-            p.previous_policy.allocate(m, self.task, K_MAX_TRAJECTORY_HORIZON)
-            p.gradient = np.zeros(p.policy.num_spline_points * m.nu)
+        super().allocate()
+        self._reset_own()
+
+    def _reset_own(self):
+        """the context's gradient and gradient candidates start again; its shaping weights are kept (planner.cc:115-163)"""
         self._zero_gradient, self._candidates_for = True, None
-        self._push_models()
-
-    # ---- Reset, planner.cc:115-163: the gradient is zeroed, the shaping weights are kept
-    def reset(self, horizon, initial_repeated_action=None):
-        for p in self.envs:
-            p.state[:] = 0
-            p.mocap[:] = 0
-            p.userdata[:] = 0
-            p.time = 0.0
-            with p.mtx_:
-                p.policy.reset(horizon, initial_repeated_action)
-                p.previous_policy.reset(horizon, initial_repeated_action)
-            p.improvement, p.winner, p._best = 0.0, 0, None
-            p.gradient = np.zeros_like(p.gradient)
-        self._zero_gradient, self._candidates_for = True, None
-
-    def set_states(self, states):
-        """one State per environment (Planner::SetState for each)"""
-        if len(states) != self.num_envs:
-            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
-        for p, st in zip(self.envs, states):
-            p.state, p.mocap, p.userdata, p.time = st.copy_to()
-
-    def _push_states(self):
-        sync_task(self.ctx, self.task)
-        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
-                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
-                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
-        self._push_task_rows()
 
     # ---- ResamplePolicy, planner.cc:290-318
     def _resample(self, p, horizon):
@@ -1089,9 +1109,7 @@ class GpuBatchSampleGradientPlanner(_FleetTasks):
     # ---- OptimizePolicy, planner.cc:166-264
     def optimize_policy(self, horizon, pool=None):
         n = int(self.num_trajectory_)
-        if n < 64 or n % 64 != 0:
-            raise ValueError(f"{type(self).__name__}: {n} candidates per environment; a batched launch needs a positive multiple of 64 "
-                             "(every wavefront serves one environment) -- set sampling_trajectories / num_trajectory_ accordingly")
+        self._check_n(n)
         self.num_gradient_ = G = min(int(self.num_gradient_), n - 1)
         E, nu = self.num_envs, self.model.nu
         for p in self.envs:
@@ -1119,7 +1137,7 @@ class GpuBatchSampleGradientPlanner(_FleetTasks):
         if G > 0:
             self._weights_for, self._candidates_for = n - G, (G, P)
         self._zero_gradient = False
-        self._n = n
+        self._last, self._n = "plan", n
         self.iteration += 1
         for e, p in enumerate(self.envs):
             p.winner, p.winner_type_ = int(out["index"][e]), int(out["winner_type"][e])
@@ -1136,24 +1154,12 @@ class GpuBatchSampleGradientPlanner(_FleetTasks):
             p._best = None
         self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
 
-    @property
-    def winners(self):
-        return [p.winner for p in self.envs]
-
-    def action_from_policy(self, env, action, state, time, use_previous=False):
-        p = self.envs[env]
-        with p.mtx_:
-            return (p.previous_policy if use_previous else p.policy).action(action, state, time)
-
     def best_trajectory(self, env):
-        """the winner's trajectory, fetched lazily from the context (global candidate env * n + winner)"""
+        """the winner's trajectory, fetched lazily from the context"""
         p = self.envs[env]
-        if p._best is None and self._n:
-            p._best = self.ctx.fetch_trajectory(env * self._n + p.winner)
+        if p._best is None:
+            p._best = self._fetch_planned(env, p.winner)
         return p._best
-
-    def num_parameters(self):
-        return self.envs[0].policy.num_spline_points * self.model.nu
 
 
 def _member_attr(name):
@@ -1212,7 +1218,7 @@ class GpuSampleGradientPlanner:
         return self.fleet.num_parameters()
 
 
-class GpuCrossEntropyPlanner:
+class GpuCrossEntropyPlanner(_ContextOwner):
     """mjpc::CrossEntropyPlanner (mjpc/planners/cross_entropy/planner.{h,cc}) with the candidate
     fan-out, the sort and the elite statistics on the GPU. Differences forced by SURVEY F4/F5 as for
     the sampling planner; the extra nominal rollout (planner.cc:435) rides along as one more candidate."""
@@ -1251,10 +1257,7 @@ class GpuCrossEntropyPlanner:
         self.times_scratch = np.zeros(K_MAX_TRAJECTORY_HORIZON)
         self.parameters_scratch = np.zeros(m.nu * K_MAX_TRAJECTORY_HORIZON)
         self._nominal = None
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
+        self.ctx = self._create_context()
 
     # ---- Reset, planner.cc:122-160
     def reset(self, horizon, initial_repeated_action=None):
@@ -1270,9 +1273,6 @@ class GpuCrossEntropyPlanner:
 
     def set_state(self, state: State):
         self.state, self.mocap, self.userdata, self.time = state.copy_to()
-
-    def _timestep(self):
-        return self.model.get_number("agent_timestep", self.model.timestep)
 
     # ---- ResamplePolicy, planner.cc:322-348
     def resample_policy(self, horizon):
@@ -1384,7 +1384,7 @@ class GpuCrossEntropyPlanner:
         return self.policy.num_spline_points * self.model.nu
 
 
-class GpuBatchCrossEntropyPlanner(_FleetTasks):
+class GpuBatchCrossEntropyPlanner(_Fleet):
     """Cross-Entropy for `num_envs` environments (robots) on ONE context: every plan step is one `set_states`, one
     `rollout_noise_batched_ce` over all E x (n + 1) candidates with a variance row per environment, one `ce_update_batched`
     (selection of the elites, their mean, variance and mean return, on the device) and one sync -- instead of E plan steps of
@@ -1395,61 +1395,23 @@ class GpuBatchCrossEntropyPlanner(_FleetTasks):
     num_trajectory_ + 1 must be a positive multiple of 64."""
 
     def __init__(self, num_envs, device=0, precision=64, seed=0, backend_factory=None):
-        if int(num_envs) < 1:
-            raise ValueError("GpuBatchCrossEntropyPlanner needs at least one environment")
-        self.num_envs, self.device, self.precision, self.seed = int(num_envs), device, precision, seed
-        self._backend_factory = backend_factory
-        self.model = self.task = self.ctx = None
+        super().__init__(num_envs, device, precision, backend_factory)
+        self.seed = seed
         self.iteration = 0
         self.rollouts_compute_time = self.policy_update_compute_time = 0.0
-        self._last = None  # what the context's last rollout was: "plan" (n + 1 candidates per environment) or "nominal"
         # the members never roll out themselves: they are handed the shared context instead of creating their own
         self.envs = [GpuCrossEntropyPlanner(device, precision, seed + e, backend_factory=lambda task: self.ctx) for e in range(self.num_envs)]
-
-    def initialize(self, model, task: Task):
-        self.model, self.task = model, task
-        for p in self.envs:
-            p.initialize(model, task)
 
     num_trajectory_ = _fleet_setting("num_trajectory_")
     n_elite_ = _fleet_setting("n_elite_")
     std_initial_ = _fleet_setting("std_initial_")
     std_min_ = _fleet_setting("std_min_")
     explore_fraction_ = _fleet_setting("explore_fraction_")
+    _n_advice = ("with the nominal rollout every environment launches num_trajectory_ + 1 candidates: set sampling_trajectories / "
+                 "num_trajectory_ to 63, 127, ..., 2047, ...")
 
-    def _check_n(self, n):
-        if n < 64 or n % 64 != 0:
-            raise ValueError(f"GpuBatchCrossEntropyPlanner: num_trajectory_ = {n - 1}; with the nominal rollout every environment launches "
-                             "num_trajectory_ + 1 candidates, and a batched launch needs a positive multiple of 64 (every wavefront "
-                             "serves one environment) -- set sampling_trajectories / num_trajectory_ to 63, 127, ..., 2047, ...")
-
-    def allocate(self):
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            self.ctx = capi.Context(self.task.packed_model(), self.task.packed(), self.device, self.precision)
-        for p in self.envs:
-            p.allocate()
-        self._push_models()
-
-    def reset(self, horizon, initial_repeated_action=None):
-        for p in self.envs:
-            p.reset(horizon, initial_repeated_action)
+    def _reset_own(self):
         self._last = None
-
-    def set_states(self, states):
-        """one State per environment (Planner::SetState for each)"""
-        if len(states) != self.num_envs:
-            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
-        for p, st in zip(self.envs, states):
-            p.set_state(st)
-
-    def _push_states(self):
-        sync_task(self.ctx, self.task)
-        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
-                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
-                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
-        self._push_task_rows()
 
     # ---- OptimizePolicy, cross_entropy/planner.cc:168-291, for every environment
     def optimize_policy(self, horizon, pool=None):
@@ -1502,33 +1464,21 @@ class GpuBatchCrossEntropyPlanner(_FleetTasks):
         self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
 
     def nominal_trajectory(self, horizon, pool=None):
-        """NominalTrajectory of every environment in one launch: 64 candidates per environment, candidate 0 carrying the policy"""
         plans = [p.resampled_policy.plan for p in self.envs]
         if any(pl.size() != plans[0].size() for pl in plans):
             raise ValueError("the environments' policies have different numbers of spline nodes")
-        self._push_states()
-        times = np.stack([pl.times() for pl in plans])
-        values = np.stack([np.broadcast_to(pl.values()[None], (64,) + pl.values().shape) for pl in plans])
-        self.ctx.rollout_splines_batched(horizon, plans[0].interpolation(), times, values, num_envs=self.num_envs, n_per_env=64)
-        self._last = "nominal"
-        out = [self.ctx.fetch_trajectory(64 * e) for e in range(self.num_envs)]
+        out = self._nominal_launch(horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]), [pl.values() for pl in plans])
         for p, tr in zip(self.envs, out):
             p._nominal = tr
             p._n_local = 0
         return out
 
-    def action_from_policy(self, env, action, state, time, use_previous=False):
-        return self.envs[env].action_from_policy(action, state, time, use_previous)
-
     # ---- BestTrajectory, planner.cc:446-448: the NOMINAL rollout, the environment's last candidate
     def best_trajectory(self, env):
         p = self.envs[env]
-        if p._nominal is None and self._last == "plan":
-            p._nominal = self.ctx.fetch_trajectory(env * self._n + self._n - 1)
+        if p._nominal is None:
+            p._nominal = self._fetch_planned(env, self._n - 1)
         return p._nominal
-
-    def num_parameters(self):
-        return self.envs[0].num_parameters()
 
 
 # ====================================================================================== iLQG
@@ -1694,7 +1644,7 @@ class ILQGPolicy:
         return clamp(action, self.model.actuator_ctrlrange)
 
 
-class GpuILQGPlanner:
+class GpuILQGPlanner(_ContextOwner):
     """mjpc::iLQGPlanner (mjpc/planners/ilqg/planner.{h,cc}) with every data-parallel piece on the GPU:
     feedback / line-search rollouts (mjpcx_rollout_feedback), finite-difference model derivatives
     (mjpcx_transition_fd), cost derivatives (mjpcx_cost_derivatives) and the Riccati sweep on the matrix
@@ -1725,11 +1675,8 @@ class GpuILQGPlanner:
         self.policy = ILQGPolicy(m, self.task)
         self.previous_policy = ILQGPolicy(m, self.task)
         self.candidate0 = ILQGPolicy(m, self.task)          # candidate_policy[0]
-        # gradient-based planners plan on the differentiable model copy unless agent_differentiable says otherwise
-        self.differentiable_ = bool(int(m.get_number("agent_differentiable", 1)))
-        self.ctx = (self._backend_factory(self.task) if self._backend_factory   # test backends: see tests/oracle_backend.py
-                    else capi.Context(self.task.packed_model(differentiable=self.differentiable_), self.task.packed(), self.device,
-                                      self.precision))
+        self.differentiable_ = _agent_differentiable(m)
+        self.ctx = self._create_context(self.differentiable_)
 
     def reset(self, horizon, initial_repeated_action=None):
         self.state[:] = 0; self.mocap[:] = 0; self.userdata[:] = 0
@@ -1941,7 +1888,7 @@ class GpuILQGPlanner:
         return self.dim_action * K_MAX_TRAJECTORY_HORIZON
 
 
-class GpuBatchILQGPlanner(_FleetTasks):
+class GpuBatchILQGPlanner(_Fleet):
     """iLQG for `num_envs` environments (robots) on ONE context. The two feedback-rollout phases of a plan step -- the nominal
     under iLQGPolicy::Action and the line search under the index policy, three quarters of an iteration and pure per-step latency --
     are one `rollout_feedback_batched` launch each for the whole fleet (any number of rollouts per environment: iLQG's ten). Between
@@ -1960,11 +1907,7 @@ class GpuBatchILQGPlanner(_FleetTasks):
     other two are 0 (plus whatever a member that fell back to the sequential chain spent)."""
 
     def __init__(self, num_envs, device=0, precision=64, backend_factory=None):
-        if int(num_envs) < 1:
-            raise ValueError("GpuBatchILQGPlanner needs at least one environment")
-        self.num_envs, self.device, self.precision = int(num_envs), device, precision
-        self._backend_factory = backend_factory
-        self.model = self.task = self.ctx = None
+        super().__init__(num_envs, device, precision, backend_factory)
         self.timers = {}
         self.device_chain = None    # None: ilqg_step_batched whenever the context has it; False: the sequential middle (the tests' comparison)
         self.used_device_chain = False   # which middle the last optimize_policy ran
@@ -1973,46 +1916,13 @@ class GpuBatchILQGPlanner(_FleetTasks):
         for p in self.envs:
             p.settings = self.envs[0].settings      # one ILQGSettings for the fleet
 
-    def initialize(self, model, task: Task):
-        self.model, self.task = model, task
-        for p in self.envs:
-            p.initialize(model, task)
-
+    derivative_chain = True
     num_rollouts_gui_ = _fleet_setting("num_rollouts_gui_")
     derivative_skip_ = _fleet_setting("derivative_skip_")
     settings = _fleet_setting("settings")
 
-    def set_models(self, models):
-        """not for a planner with a derivative chain: the batched derivative calls use the context's one model"""
-        raise NotImplementedError(_FleetTasks._MODELS_FOLLOW_UP)
-
-    def allocate(self):
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            differentiable = bool(int(self.model.get_number("agent_differentiable", 1)))
-            self.ctx = capi.Context(self.task.packed_model(differentiable=differentiable), self.task.packed(), self.device, self.precision)
-        for p in self.envs:
-            p.allocate()
-
-    def reset(self, horizon, initial_repeated_action=None):
-        for p in self.envs:
-            p.reset(horizon, initial_repeated_action)
+    def _reset_own(self):
         self.timers = {}
-
-    def set_states(self, states):
-        """one State per environment (Planner::SetState for each)"""
-        if len(states) != self.num_envs:
-            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
-        for p, st in zip(self.envs, states):
-            p.set_state(st)
-
-    def _push_states(self):
-        sync_task(self.ctx, self.task)
-        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
-                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
-                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
-        self._push_task_rows()
 
     def _rollout(self, horizon, mode, representation, use_state, requests):
         """one batched launch of every environment's request; each member's share of the returns"""
@@ -2137,14 +2047,8 @@ class GpuBatchILQGPlanner(_FleetTasks):
                 p._iteration_after_rollouts(horizon, ret, fail)
         self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
 
-    def action_from_policy(self, env, action, state, time, use_previous=False):
-        return self.envs[env].action_from_policy(action, state, time, use_previous)
-
     def best_trajectory(self, env):
         return self.envs[env].best_trajectory()
-
-    def num_parameters(self):
-        return self.envs[0].num_parameters()
 
     winner = property(lambda self: [p.winner for p in self.envs])
     action_step = property(lambda self: [p.action_step for p in self.envs])
@@ -2227,7 +2131,7 @@ class GradientPolicy:
         return clamp(action, self.model.actuator_ctrlrange)
 
 
-class GpuGradientPlanner:
+class GpuGradientPlanner(_ContextOwner):
     """mjpc::GradientPlanner (mjpc/planners/gradient/planner.{h,cc}, max_rollout = 1) with its device work on the GPU: the
     nominal and line-search rollouts (mjpcx_rollout_splines), finite-difference model derivatives (mjpcx_transition_fd), cost
     derivatives (mjpcx_cost_derivatives), and the adjoint sweep with its spline-mapping projection (mjpcx_gradient_pass).
@@ -2257,10 +2161,8 @@ class GpuGradientPlanner:
         self.previous_policy = GradientPolicy(m, self.task)
         self.candidate0 = GradientPolicy(m, self.task)      # candidate_policy[0]
         self.trajectory0 = None                             # trajectory[0]
-        self.differentiable_ = bool(int(m.get_number("agent_differentiable", 1)))
-        self.ctx = (self._backend_factory(self.task) if self._backend_factory   # test backends: see tests/oracle_backend.py
-                    else capi.Context(self.task.packed_model(differentiable=self.differentiable_), self.task.packed(), self.device,
-                                      self.precision))
+        self.differentiable_ = _agent_differentiable(m)
+        self.ctx = self._create_context(self.differentiable_)
 
     def reset(self, horizon, initial_repeated_action=None):
         self.state[:] = 0; self.mocap[:] = 0; self.userdata[:] = 0
@@ -2282,8 +2184,7 @@ class GpuGradientPlanner:
     def resample_policy(self, horizon):
         c0 = self.candidate0
         P, nu = c0.num_spline_points, self.model.nu
-        timestep = self.model.get_number("agent_timestep", self.model.timestep)   # the planning model's opt.timestep
-        time_shift = max((horizon - 1) * timestep / (P - 1), 1.0e-5) if P > 1 else 0.0
+        time_shift = max((horizon - 1) * self._timestep() / (P - 1), 1.0e-5) if P > 1 else 0.0   # (the planning model's opt.timestep)
         params = np.zeros((P, nu))
         nominal_time = self.time
         for t in range(P):
@@ -2394,7 +2295,7 @@ def derivative_steps(T, derivative_skip):
     return sorted(set(e for e in evaluate if 0 <= e < T))
 
 
-class GpuBatchGradientPlanner(_FleetTasks):
+class GpuBatchGradientPlanner(_Fleet):
     """The Gradient planner for `num_envs` environments (robots) on ONE context: a plan step is one `set_states`, one
     `rollout_splines_batched` of the resampled policies (64 candidates per environment, candidate 0 the nominal), one
     `gradient_step_batched` -- model derivatives, cost derivatives and the adjoint sweep of every environment chained on the device,
@@ -2405,77 +2306,30 @@ class GpuBatchGradientPlanner(_FleetTasks):
     per environment. gradient_num_trajectory must be a positive multiple of 64."""
 
     def __init__(self, num_envs, device=0, precision=64, backend_factory=None):
-        if int(num_envs) < 1:
-            raise ValueError("GpuBatchGradientPlanner needs at least one environment")
-        self.num_envs, self.device, self.precision = int(num_envs), device, precision
-        self._backend_factory = backend_factory
-        self.model = self.task = self.ctx = None
+        super().__init__(num_envs, device, precision, backend_factory)
         self.timers = {}
-        self._last = None  # what the context's last rollout was: "plan" (the line search) or "nominal"
         # the members never roll out themselves: they are handed the shared context instead of creating their own
         self.envs = [GpuGradientPlanner(device, precision, backend_factory=lambda task: self.ctx) for _ in range(self.num_envs)]
         for p in self.envs:
             p.settings = self.envs[0].settings      # one GradientSettings for the fleet
 
-    def initialize(self, model, task: Task):
-        self.model, self.task = model, task
-        for p in self.envs:
-            p.initialize(model, task)
-
+    derivative_chain = True
     num_trajectory = _fleet_setting("num_trajectory")
     derivative_skip_ = _fleet_setting("derivative_skip_")
     settings = _fleet_setting("settings")
+    _n_advice = "set gradient_num_trajectory / num_trajectory accordingly"
 
-    def _check_n(self, n):
-        if n < 64 or n % 64 != 0:
-            raise ValueError(f"GpuBatchGradientPlanner: {n} candidates per environment; a batched launch needs a positive multiple "
-                             "of 64 (every wavefront serves one environment) -- set gradient_num_trajectory / num_trajectory accordingly")
-
-    def set_models(self, models):
-        """not for a planner with a derivative chain: the batched derivative calls use the context's one model"""
-        raise NotImplementedError(_FleetTasks._MODELS_FOLLOW_UP)
-
-    def allocate(self):
-        if self._backend_factory is not None:
-            self.ctx = self._backend_factory(self.task)
-        else:
-            differentiable = bool(int(self.model.get_number("agent_differentiable", 1)))
-            self.ctx = capi.Context(self.task.packed_model(differentiable=differentiable), self.task.packed(), self.device, self.precision)
-        for p in self.envs:
-            p.allocate()
-
-    def reset(self, horizon, initial_repeated_action=None):
-        for p in self.envs:
-            p.reset(horizon, initial_repeated_action)
+    def _reset_own(self):
         self._last = None
         self.timers = {}
 
-    def set_states(self, states):
-        """one State per environment (Planner::SetState for each)"""
-        if len(states) != self.num_envs:
-            raise ValueError(f"{len(states)} states for {self.num_envs} environments")
-        for p, st in zip(self.envs, states):
-            p.set_state(st)
-
-    def _push_states(self):
-        sync_task(self.ctx, self.task)
-        self.ctx.set_states(np.stack([p.state for p in self.envs]), np.array([p.time for p in self.envs]),
-                            np.stack([p.mocap for p in self.envs]) if self.model.nmocap else None,
-                            np.stack([p.userdata for p in self.envs]) if self.model.nuserdata else None)
-        self._push_task_rows()
-
-    def _rollout_nominal(self, horizon):
-        """candidate0 of every environment in one launch: 64 candidates per environment, candidate 0 carrying the policy"""
+    def _nominal_splines(self):
+        """candidate0 of every environment, as _nominal_launch takes them: (representation, node times, node values)"""
         c0s = [p.candidate0 for p in self.envs]
         P = c0s[0].num_spline_points
         if any(c.num_spline_points != P or c.representation != c0s[0].representation for c in c0s):
             raise ValueError("the environments' policies have different spline shapes")
-        self._push_states()
-        times = np.stack([c.times[:P] for c in c0s])
-        values = np.stack([np.broadcast_to(c.parameters[:P][None], (64, P, self.model.nu)) for c in c0s])
-        self.ctx.rollout_splines_batched(horizon, c0s[0].representation, times, values, num_envs=self.num_envs, n_per_env=64)
-        self._last = "nominal"
-        return times
+        return c0s[0].representation, np.stack([c.times[:P] for c in c0s]), [c.parameters[:P] for c in c0s]
 
     # ---- OptimizePolicy, gradient/planner.cc:159-327, for every environment
     def optimize_policy(self, horizon, pool=None):
@@ -2487,7 +2341,8 @@ class GpuBatchGradientPlanner(_FleetTasks):
             with p.mtx_:
                 p.candidate0.copy_from(p.policy)
             p.resample_policy(horizon)
-        times = self._rollout_nominal(horizon)
+        rep, times, values = self._nominal_splines()
+        self._nominal_launch(horizon, rep, times, values, fetch=False)    # gradient_step_batched reads the nominals on the device
         self.timers["nominal"] = (_time.perf_counter() - t0) * 1e6
         t0 = _time.perf_counter()
         first = self.envs[0]
@@ -2514,24 +2369,16 @@ class GpuBatchGradientPlanner(_FleetTasks):
         self.timers["rollouts"] = (_time.perf_counter() - t0) * 1e6
 
     def nominal_trajectory(self, horizon, pool=None):
-        """NominalTrajectory of every environment in one launch"""
-        self._rollout_nominal(horizon)
-        out = [self.ctx.fetch_trajectory(64 * e) for e in range(self.num_envs)]
+        out = self._nominal_launch(horizon, *self._nominal_splines())
         for p, tr in zip(self.envs, out):
             p.trajectory0 = tr
         return out
 
-    def action_from_policy(self, env, action, state, time, use_previous=False):
-        return self.envs[env].action_from_policy(action, state, time, use_previous)
-
     def best_trajectory(self, env):
         p = self.envs[env]
-        if p.trajectory0 is None and self._last == "plan":
-            p.trajectory0 = self.ctx.fetch_trajectory(env * self._n + p.winner)
+        if p.trajectory0 is None:
+            p.trajectory0 = self._fetch_planned(env, p.winner)
         return p.trajectory0
-
-    def num_parameters(self):
-        return self.envs[0].num_parameters()
 
     winner = property(lambda self: [p.winner for p in self.envs])
     dV = property(lambda self: [p.dV for p in self.envs])
@@ -2594,7 +2441,7 @@ class GpuILQSPlanner:
 
     def allocate(self):
         # the iLQG mirror reads agent_differentiable (default 1) itself; the sampling half is told the same
-        self.sampling.differentiable = bool(int(self.model.get_number("agent_differentiable", 1)))
+        self.sampling.differentiable = _agent_differentiable(self.model)
         self.sampling.allocate()
         self.ilqg.allocate()
 
@@ -2762,7 +2609,7 @@ class GpuBatchILQSPlanner:
             m.model, m.task = model, task
 
     def set_tasks(self, tasks):
-        """one Task per environment, for both halves (_FleetTasks.set_tasks)"""
+        """one Task per environment, for both halves (_Fleet.set_tasks)"""
         self.sampling.set_tasks(tasks)
         self.ilqg.set_tasks(tasks)
         for e, m in enumerate(self.envs):
@@ -2770,11 +2617,11 @@ class GpuBatchILQSPlanner:
 
     def set_models(self, models):
         """not for a planner with a derivative chain: the batched derivative calls use the context's one model"""
-        raise NotImplementedError(_FleetTasks._MODELS_FOLLOW_UP)
+        raise NotImplementedError(_Fleet._MODELS_FOLLOW_UP)
 
     def allocate(self):
         # the iLQG half reads agent_differentiable (default 1) itself; the sampling half is told the same
-        self.sampling.differentiable = bool(int(self.model.get_number("agent_differentiable", 1)))
+        self.sampling.differentiable = _agent_differentiable(self.model)
         self.sampling.allocate()
         self.ilqg.allocate()
 
