@@ -751,7 +751,8 @@ int mjpcx_quad_stats(mjpcx_ctx* ctx, int32_t* handed_on /* 8 */);
  *     it (the last step is not checked). Otherwise every retired candidate is strictly above the winner. Roll out again
  *     with pruning off after MJPCX_ESTATE.
  *   - mjpcx_topk with k > 1, mjpcx_elite_moments and mjpcx_merge_topk return MJPCX_ESTATE: their answers would depend on
- *     timing. mjpcx_get_returns, mjpcx_fetch_trajectory and mjpcx_fetch_spline stay usable. */
+ *     timing (mjpcx_set_prune_rank below gives a launch whose first K returns are exact). mjpcx_get_returns,
+ *     mjpcx_fetch_trajectory and mjpcx_fetch_spline stay usable. */
 #define MJPCX_FAILURE_PRUNED 0x20000000
 int mjpcx_set_pruning(mjpcx_ctx* ctx, int enabled, double initial_bound);
 /* Of the last rollout (zeros unless it was pruned): [0] candidates retired, [1] the sum of their retire steps, [2] != 0 if a
@@ -815,7 +816,7 @@ int mjpcx_park_resumed(mjpcx_ctx* ctx, int32_t* index, int32_t* step, int cap);
  * makes it ignore the hints.
  *
  * Launches that ignore the switch and roll everything out: mjpcx_rollout_splines_batched,
- * mjpcx_rollout_noise_batched_ce, the noisy, sample-gradient and feedback launches, and any launch that does not reach
+ * mjpcx_rollout_noise_batched_ce (at rank 1; in rank mode, mjpcx_set_prune_rank below, it obeys the switch), the noisy, sample-gradient and feedback launches, and any launch that does not reach
  * rollout_quad_kernel (a total below MJPCX_QUAD_MIN_N, a limb, tree or lane context, MJPCX_QUAD_NO_FALLBACK). The plain
  * launches ignore it too, as the batched ones keep ignoring mjpcx_set_pruning and mjpcx_set_park_hint. */
 int mjpcx_set_pruning_batched(mjpcx_ctx* ctx, int enabled, int num_envs, const double* initial_bound /* E, or NULL */,
@@ -825,6 +826,46 @@ int mjpcx_set_pruning_batched(mjpcx_ctx* ctx, int enabled, int num_envs, const d
  * NULL). No synchronisation. */
 int mjpcx_prune_stats_batched(mjpcx_ctx* ctx, int num_envs, int64_t* prune /* E x 4 */, int64_t* park /* E x 3 */,
                               double* final_bound /* E */);
+
+/* ---- rank mode: the bound of the K best, for planners that read more than the argmin -----------------------------------
+ * Pruning's bound is the least completed return: "cannot be the argmin" says nothing about "cannot be an elite", which is why
+ * the ranking entry points refuse a pruned launch. With rank K > 1 the bound is T, the K-th smallest return among the
+ * candidates that have completed, and the launch runs in four stages on the stream:
+ *   1. the main launch. The bound word starts at +inf and completed rollouts do NOT lower it, so nothing is retired here. A
+ *      candidate other than the nominal whose partial return strictly exceeds the park hint is parked, as ever.
+ *   2. rank_bound_kernel (csrc/rank_bound.h), one workgroup per environment: C = the candidates whose failure word is 0 and
+ *      whose return is finite and >= 0 (-0.0 counts as 0; handed-on candidates have not completed: not in C). T = the K-th
+ *      smallest return of C, +inf if C has fewer than K members; T goes into the environment's bound word.
+ *   3. the settling pass, unchanged: parked with partial return > T: retired (MJPCX_FAILURE_PRUNED); otherwise resumed.
+ *   4. the resume launch, unchanged but for leaving the word alone: it prunes against T.
+ * Exact: a retired candidate's return >= its stored partial return > T, and K candidates hold returns <= T, stored and true
+ * alike. So in the order of mjpcx_topk (ascending, ties to the lower index, NaN last) the first K of the stored returns are the
+ * first K of the unpruned launch's, bit for bit. T is the K-th smallest of a subset of the launch, so it is >= the final K-th
+ * smallest: candidates that complete later (hand-ons, resumed ones) only move the true K-th down. With several ranks each
+ * settles on its own K-th, again >= the global one, so the K that mjpcx_merge_topk takes from each stay exact.
+ * A completed candidate other than the nominal stayed at or below the hint up to its last check, so when C has K members T
+ * lies at or close above the hint (the last step is not checked, and the nominal is exempt) and the settling pass retires the
+ * parked candidates; one whose partial return lies between the hint and T is resumed and pruned against T. When the hint was
+ * too low fewer than K complete, T = +inf and every parked candidate is resumed unpruned. A bad hint costs the parked
+ * candidates' remaining work, never a second rollout and never a wrong answer. Without a hint nothing is parked and nothing
+ * is saved.
+ *
+ * Sticky. rank < 1: MJPCX_EINVAL. rank == 1 (the default): everything behaves as described above. rank == K > 1 applies to
+ * the launches mjpcx_set_pruning + mjpcx_set_park_hint apply to, to those mjpcx_set_pruning_batched applies to, and to
+ * mjpcx_rollout_noise_batched_ce under mjpcx_set_pruning_batched (which at rank 1 keeps ignoring that switch). In rank mode a
+ * finite initial_bound is MJPCX_EINVAL, here and in the two setters: nobody can vouch for a K-th return. MJPCX_PRUNE=0 and
+ * MJPCX_PARK=0 keep their meaning.
+ *
+ * After a launch at rank K, bit-identical to the unpruned launch: mjpcx_topk(k <= K); mjpcx_merge_topk(k <= K);
+ * mjpcx_elite_moments of at most K candidates none of which was retired (the first K never are); mjpcx_best /
+ * mjpcx_best_batched; mjpcx_ce_update_batched with n_elite + (skip_candidate >= 0) <= K. A larger k or n_elite, the Robust
+ * and Sample-Gradient updates and a negative step cost return MJPCX_ESTATE as before. mjpcx_prune_stats_batched's
+ * final_bound reports T. */
+int mjpcx_set_prune_rank(mjpcx_ctx* ctx, int rank);
+/* For tests and tools: rank_bound_kernel over the last rollout's returns and failure words, taken as num_envs equal
+ * environments. bound[e] = T of environment e at this rank (+inf: fewer than `rank` qualify). Synchronises; touches no state
+ * of the last rollout, its bound words included. */
+int mjpcx_rank_bound_batched(mjpcx_ctx* ctx, int num_envs, int rank, double* bound /* E */);
 
 /* Algorithmic bytes of one candidate rollout:
  * w*[H*(dim_state+nu+1+nr+3*ntrace+1) + P*nu + P + 2]. */

@@ -36,6 +36,7 @@ EXPORTS = [
     "mjpcx_set_models_batched", "mjpcx_set_pruning", "mjpcx_prune_stats",
     "mjpcx_set_park_hint", "mjpcx_park_stats", "mjpcx_park_resumed",
     "mjpcx_set_pruning_batched", "mjpcx_prune_stats_batched",
+    "mjpcx_set_prune_rank", "mjpcx_rank_bound_batched",
 ]
 
 SG_COMPUTE_WEIGHTS, SG_ZERO_GRADIENT = 1, 2   # MJPCX_SG_* flags of mjpcx_sample_gradient_update_batched
@@ -122,6 +123,8 @@ def lib():
         L.mjpcx_park_resumed.argtypes = [vp, c_i32p, c_i32p, C.c_int]
         L.mjpcx_set_pruning_batched.argtypes = [vp, C.c_int, C.c_int, c_f64p, c_f64p]
         L.mjpcx_prune_stats_batched.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f64p]
+        L.mjpcx_set_prune_rank.argtypes = [vp, C.c_int]
+        L.mjpcx_rank_bound_batched.argtypes = [vp, C.c_int, C.c_int, c_f64p]
         L.mjpcx_algorithmic_bytes.restype = C.c_int64
         L.mjpcx_algorithmic_bytes.argtypes = [vp, C.c_int, C.c_int]
         L.mjpcx_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -720,6 +723,18 @@ class Context:
         pr, pk = np.array(pr[:], np.int64).reshape(E, 4), np.array(pk[:], np.int64).reshape(E, 3)
         return dict(retired=pr[:, 0].copy(), retire_step_sum=pr[:, 1].copy(), negative_cost=pr[:, 2] != 0, wavefronts_ended_early=pr[:, 3].copy(),
                     parked=pk[:, 0].copy(), settled_retired=pk[:, 1].copy(), resumed=pk[:, 2].copy(), final_bound=fb)
+
+    def set_prune_rank(self, rank=1):
+        """mjpcx_set_prune_rank: the following pruned launches settle on the rank-th smallest completed return, so that their first `rank`
+        stored returns are exact (sticky; 1: the bound of the argmin, the default)"""
+        self._chk(lib().mjpcx_set_prune_rank(self.handle, int(rank)))
+
+    def rank_bound_batched(self, num_envs, rank):
+        """mjpcx_rank_bound_batched: rank_bound_kernel over the last rollout's returns and failure words as num_envs equal environments:
+        per environment the rank-th smallest qualifying return (+inf: fewer qualify). For tests and tools"""
+        out = np.zeros(int(num_envs), np.float64)
+        self._chk(lib().mjpcx_rank_bound_batched(self.handle, int(num_envs), int(rank), as_f64p(out)))
+        return out
 
     def algorithmic_bytes(self, horizon, num_nodes):
         return lib().mjpcx_algorithmic_bytes(self.handle, int(horizon), int(num_nodes))

@@ -24,6 +24,7 @@
 #include "rollout_wave.h"
 #include "quad_launch.h"
 #include "park_settle.h"
+#include "rank_bound.h"
 #include "limb_launch.h"
 #include "wave32_launch.h"
 #include <type_traits>
@@ -937,6 +938,9 @@ struct mjpcx_ctx {
   bool last_pruned = false;       // the last rollout was launched with a bound: its returns hold lower bounds, only the argmin is exact
   int prune_h[4] = {0, 0, 0, 0};  // ... and its counters, read back with the hand-on count
   double prune_final = 0;         // ... and the bound word after the launch: min(initial bound, the returns completed inside the launch)
+  // rank mode (mjpcx_set_prune_rank): the bound of a pruned launch is the K-th smallest completed return (rank_bound.h), not the least
+  int prune_rank = 1;             // K; 1: the bound of the argmin, as ever
+  int last_prune_rank = 1;        // the K the last pruned rollout was launched with: its first K stored returns are exact (1: only the argmin)
   // parking on an unproven estimate of the launch's best return (mjpcx_set_park_hint; pruned launches only): the candidates the estimate
   // condemns are set aside with their state, settled against the final bound (park_settle.h) and, if not retired, resumed in a second launch
   bool park_allowed = true;       // MJPCX_PARK=0 at creation: mjpcx_set_park_hint does nothing
@@ -1413,6 +1417,11 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
     if (a.noise.mode < 0) q.nominal_candidate = -1;  // (given splines have no nominal: no candidate is exempt)
   }
   c->last_pruned = pruned; c->last_pruned_batched = bpruned;
+  // (mjpcx_set_prune_rank: completions leave the word at +inf -- the setters refuse a finite initial bound in rank mode -- and rank_bound_kernel
+  // writes the K-th smallest completed return into it behind the main launch)
+  const bool ranked = pruned && c->prune_rank > 1;
+  q.keep_bound = ranked;
+  c->last_prune_rank = ranked ? c->prune_rank : 1;
   // (mjpcx_set_park_hint: a pruned launch only -- the settling pass needs its bound word. A batched one parks on its environments' own hints)
   const bool parking = bpruned ? bparking : pruned && c->park_allowed && c->park_hint < HUGE_VAL;
   c->park_h[0] = c->park_h[1] = c->park_h[2] = 0; c->park_resume_ms = 0;
@@ -1461,6 +1470,12 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
                      tot[2 * k] ? (double)tot[2 * k + 1] / tot[2 * k] : 0.0);
   }
   if (c->timing && c->cur_main) { if ((e = hipEventRecord(c->cur_main, c->stream)) != hipSuccess) return e; c->cur_main = nullptr; }
+  // rank mode: every environment's bound word becomes the K-th smallest return its candidates have completed with (+inf: fewer than K have)
+  if (ranked) {
+    hipLaunchKernelGGL(rank_bound_kernel, dim3(bpruned ? bE : 1), dim3(kRankBoundThreads), 0, c->stream, (const double*)a.total_return, (const int*)a.failure,
+                       bpruned ? bn : N, c->prune_rank, q.prune_bound, q.rec_stride);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
   // the settling pass: parked candidates against the launch's final bound; its two counts ride on the readback below (words 14 and 15)
   if (parking) {
     hipLaunchKernelGGL(park_settle_kernel, dim3((N + 255) / 256), dim3(256), 0, c->stream, N, (const double*)a.total_return, a.failure,
@@ -2516,6 +2531,12 @@ int check_batched_args(mjpcx_ctx* c, int E, int n, int H, int P, int interp, con
 }
 // which candidates a pruned launch (mjpcx_set_pruning, mjpcx_set_pruning_batched) retires, and when, depends on the order its wavefronts finish in: only the argmin is exact
 const char* const kPrunedRanking = "the last rollout was pruned (mjpcx_set_pruning): beyond the argmin its returns are lower bounds that depend on timing";
+// ... and in rank mode (mjpcx_set_prune_rank) beyond the first K
+int fail_ranking(mjpcx_ctx* c, const std::string& who = "") {
+  if (c->last_prune_rank <= 1) return fail(c, MJPCX_ESTATE, who + kPrunedRanking);
+  return fail(c, MJPCX_ESTATE, who + "the last rollout was pruned at rank " + std::to_string(c->last_prune_rank) + " (mjpcx_set_prune_rank): beyond its first " +
+                                   std::to_string(c->last_prune_rank) + " its returns are lower bounds");
+}
 }  // namespace
 
 int mjpcx_rollout_splines_batched(mjpcx_ctx* c, int E, int n, int H, int P, int interp, const double* node_times, const double* node_values) {
@@ -2562,6 +2583,12 @@ int mjpcx_rollout_noise_batched_ce(mjpcx_ctx* c, int E, int n, int H, int P, int
   if (ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "mjpcx_rollout_noise_batched_ce: the noise mode must be MJPCX_NOISE_CROSS_ENTROPY");
   RolloutRequest r{E * n, H, P, interp, node_times, E};
   r.nominal = nominal; r.noise = ns; r.variance_rows = variance;
+  // (rank mode only: with the bound of the argmin a pruned launch could not feed mjpcx_ce_update_batched, so at rank 1 the switch stays ignored)
+  if (c->prune_rank > 1) {
+    if (c->bprune_on && c->bprune_E != E)
+      return fail(c, MJPCX_EINVAL, "batched rollout of " + std::to_string(E) + " environments while mjpcx_set_pruning_batched is set for " + std::to_string(c->bprune_E));
+    r.prune_batched = true;
+  }
   return rollout(c, r);
 }
 
@@ -2575,7 +2602,15 @@ int mjpcx_ce_update_batched(mjpcx_ctx* c, int E, int n_elite, int skip_candidate
   if (n_elite < 1 || n_elite > left)
     return fail(c, MJPCX_EINVAL, "mjpcx_ce_update_batched: n_elite = " + std::to_string(n_elite) + " outside 1.." + std::to_string(left) +
                                  " (the candidates of an environment without the skipped one)");
-  if (c->last_pruned) return fail(c, MJPCX_ESTATE, kPrunedRanking);
+  // (after a launch in rank mode the first K of every environment's stored order are exact: the elites and the skipped candidate must fit in them)
+  if (c->last_pruned && !(c->last_pruned_batched && c->last_prune_rank > 1 && n_elite + (skip_candidate >= 0 ? 1 : 0) <= c->last_prune_rank)) return fail_ranking(c);
+  if (c->last_pruned) {
+    std::string named;
+    for (int e = 0; e < E && (size_t)e * 4 + 2 < c->env_prune_h.size(); e++) if (c->env_prune_h[4 * (size_t)e + 2]) named += (named.empty() ? "" : ", ") + std::to_string(e);
+    if (!named.empty())
+      return fail(c, MJPCX_ESTATE, "pruned batched rollout: a step's cost was negative in environment(s) " + named +
+                                       ", so partial returns are no lower bounds there (roll out again with pruning off)");
+  }
   HIPCHK(c, hipSetDevice(c->device));
   const int np = c->P * c->nu;
   CeRecord rec;
@@ -2937,7 +2972,7 @@ int mjpcx_topk(mjpcx_ctx* c, int k, int32_t* index, double* total_return) {
   if (!c || !index) return fail(c, MJPCX_EINVAL, "null argument");
   if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
   if (k < 1 || k > c->N) return fail(c, MJPCX_EINVAL, "k out of range");
-  if ((k > 1 && c->last_pruned) || c->last_pruned_batched) return fail(c, MJPCX_ESTATE, kPrunedRanking);
+  if ((c->last_pruned && k > c->last_prune_rank) || c->last_pruned_batched) return fail_ranking(c);  // (rank 1: only the argmin is exact)
   int rc;
   if ((rc = pruned_launch_valid(c)) != MJPCX_OK) return rc;  // (k = 1 is the argmin: mjpcx_best's checks)
   HIPCHK(c, hipSetDevice(c->device));
@@ -2968,8 +3003,19 @@ int mjpcx_elite_moments(mjpcx_ctx* c, int n, const int32_t* candidates, const do
   if (n < 0) return fail(c, MJPCX_EINVAL, "negative count");
   for (int i = 0; i < n; i++)
     if (candidates[i] < 0 || candidates[i] >= c->N) return fail(c, MJPCX_EINVAL, "candidate out of range");
-  if (c->last_pruned) return fail(c, MJPCX_ESTATE, kPrunedRanking);
+  // (after a plain launch in rank mode: at most K candidates, none of them retired -- what is not retired equals the unpruned launch's, and
+  // the first K of the stored order, mjpcx_topk's, never are)
+  if (c->last_pruned && (c->last_pruned_batched || c->last_prune_rank <= 1 || n > c->last_prune_rank)) return fail_ranking(c);
+  int rc;
+  if ((rc = pruned_launch_valid(c)) != MJPCX_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
+  if (c->last_pruned && n > 0) {
+    std::vector<int> f(c->N);  // (one copy of the launch's failure words: a copy per candidate costs 10 us each, and a planner passes a tenth of the batch)
+    HIPCHK(c, hipMemcpyAsync(f.data(), c->d_fail.p, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; i++)
+      if (f[candidates[i]] & kQPruned) return fail(c, MJPCX_ESTATE, "candidate " + std::to_string(candidates[i]) + " was retired: it is not among the first " + std::to_string(c->last_prune_rank));
+  }
   const int np = c->P * c->nu;
   // staging: [cand (n i32) | mean (np f64) | out (np+1 f64)]
   const size_t off_mean = (((size_t)n * 4) + 15) & ~(size_t)15;
@@ -3093,11 +3139,42 @@ int mjpcx_timing_read_main(mjpcx_ctx* c, double* main_kernel_ms, int64_t* launch
   return MJPCX_OK;
 }
 
+// rank mode (mjpcx_set_prune_rank): the bound is the K-th smallest completed return, which no caller can know ahead of the launch
+static const char* const kRankInitialBound = "in rank mode (mjpcx_set_prune_rank > 1) the initial bound must be +inf: nobody can vouch for a K-th return";
+
 int mjpcx_set_pruning(mjpcx_ctx* c, int enabled, double initial_bound) {
   if (!c) return MJPCX_EINVAL;
   if (enabled && !(initial_bound >= 0)) return fail(c, MJPCX_EINVAL, "the initial bound is a return: >= 0 (+inf for none)");
+  if (enabled && c->prune_allowed && c->prune_rank > 1 && initial_bound < HUGE_VAL) return fail(c, MJPCX_EINVAL, kRankInitialBound);
   c->prune_on = enabled != 0 && c->prune_allowed;
   c->prune_initial = initial_bound;
+  return MJPCX_OK;
+}
+
+int mjpcx_set_prune_rank(mjpcx_ctx* c, int rank) {
+  if (!c) return MJPCX_EINVAL;
+  if (rank < 1) return fail(c, MJPCX_EINVAL, "the rank is a count of candidates: >= 1");
+  if (rank > 1) {
+    bool vouched = c->prune_on && c->prune_initial < HUGE_VAL;
+    for (double b : c->bprune_initial) vouched = vouched || b < HUGE_VAL;
+    if (vouched) return fail(c, MJPCX_EINVAL, kRankInitialBound);
+  }
+  c->prune_rank = rank;
+  return MJPCX_OK;
+}
+
+int mjpcx_rank_bound_batched(mjpcx_ctx* c, int num_envs, int rank, double* bound) {
+  if (!c || !bound) return fail(c, MJPCX_EINVAL, "null argument");
+  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (num_envs < 1 || rank < 1 || c->N % num_envs != 0)
+    return fail(c, MJPCX_EINVAL, "mjpcx_rank_bound_batched: rank < 1, or the last rollout's " + std::to_string(c->N) + " candidates are not " + std::to_string(num_envs) + " equal environments");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, c->result.reserve((size_t)num_envs * 8));
+  hipLaunchKernelGGL(rank_bound_kernel, dim3(num_envs), dim3(kRankBoundThreads), 0, c->stream, (const double*)c->d_ret.p, (const int*)c->d_fail.p, c->N / num_envs, rank,
+                     (unsigned long long*)c->result.dev, 8u);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::memcpy(bound, c->result.p, (size_t)num_envs * 8);
   return MJPCX_OK;
 }
 
@@ -3108,6 +3185,7 @@ int mjpcx_set_pruning_batched(mjpcx_ctx* c, int enabled, int num_envs, const dou
   for (int e = 0; e < num_envs; e++) {
     if (initial_bound && !(initial_bound[e] >= 0)) return fail(c, MJPCX_EINVAL, "environment " + std::to_string(e) + ": the initial bound is a return: >= 0 (+inf for none)");
     if (park_hint && !(park_hint[e] >= 0)) return fail(c, MJPCX_EINVAL, "environment " + std::to_string(e) + ": the park hint is an estimate of a return: >= 0 (+inf for none)");
+    if (initial_bound && c->prune_allowed && c->prune_rank > 1 && initial_bound[e] < HUGE_VAL) return fail(c, MJPCX_EINVAL, "environment " + std::to_string(e) + ": " + kRankInitialBound);
   }
   if (!c->prune_allowed) return MJPCX_OK;  // (MJPCX_PRUNE=0: the call does nothing)
   c->bprune_on = true; c->bprune_E = num_envs;
@@ -4136,7 +4214,7 @@ int mjpcx_exchange_best(mjpcx_ctx* c, int32_t* index, double* best_return, doubl
 
 int mjpcx_merge_topk(mjpcx_ctx* c, int k, int64_t* index, double* total_return) {
   if (!c || k < 1 || !index || !total_return) return fail(c, MJPCX_EINVAL, "null argument");
-  if (c->last_pruned) return fail(c, MJPCX_ESTATE, kPrunedRanking);
+  if (c->last_pruned && (c->last_prune_rank <= 1 || k > c->last_prune_rank)) return fail_ranking(c);  // (each rank's first K are exact: so are the merged first k <= K)
   if (!c->comm) return c->comm_world == 1 ? MJPCX_OK : fail(c, MJPCX_ESTATE, "mjpcx_comm_init has not been called");
   std::vector<double> mine(2 * (size_t)k);
   for (int i = 0; i < k; i++) {

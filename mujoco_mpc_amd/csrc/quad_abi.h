@@ -58,6 +58,9 @@ struct QArgs {
                             // 0: the one record of a plain launch, park_hint as given above
   const ResumeGroup* resume_groups = nullptr;  // rollout_quad_resume_kernel of such a launch: one entry per workgroup (resume_table.h); resume_list then holds a segment of
                                                // env_n entries per environment and resume_n is not read. nullptr: the one list of resume_n entries
+  bool keep_bound = false;  // rank mode (mjpcx_set_prune_rank): a completed rollout leaves the bound word alone. The word then stays where the host put it (+inf: nothing is
+                            // retired in the main launch) until rank_bound_kernel (rank_bound.h) writes the K-th smallest completed return into it; the resume launch prunes
+                            // against that and leaves it alone too. false: a completed rollout lowers the word to its return (the bound of the argmin)
 };
 // an environment's record of a pruned batched launch, byte offsets: the bound word; prune_stats' four ints; the settling pass's two counts (candidates parked, candidates
 // to resume); the environment's park hint. The first 32 bytes are what a plain launch keeps behind its hand-on counters, in the same order

@@ -2738,8 +2738,9 @@ QD int rollout(const QuadModel& m, const QuadTables& tab, const QStaticPose* sp,
     if (leg == 0) {
       if (pruned) {
         if (a.prune_stats) { q_count_add(a.prune_stats, 1); q_count_add(a.prune_stats + 1, flag_step); }
-      } else if (!flags && !parked) {
-        // a completed rollout's return is one the argmin can take: it lowers the bound (NaN and negative totals never do)
+      } else if (!flags && !parked && !a.keep_bound) {
+        // a completed rollout's return is one the argmin can take: it lowers the bound (NaN and negative totals never do). Not in rank mode
+        // (QArgs::keep_bound): the minimum would retire candidates that are among the K best
         const double ret = total / (double)(H > 1 ? H : 1);
         if (ret >= 0 && ret <= 1.79769313486231570815e308) q_bound_min(a.prune_bound, q_bits(ret));
       }

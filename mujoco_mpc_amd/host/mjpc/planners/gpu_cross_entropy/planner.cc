@@ -2,6 +2,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <limits>
 #include <mutex>
 
 #include "../../utilities.h"
@@ -19,6 +21,9 @@ void GpuCrossEntropyPlanner::Initialize(mjModel* m, const Task& t) {
   explore_fraction_ = GetNumberOrDefault(0.0, m, "explore_fraction");
   num_trajectory_ = GetNumberOrDefault(10, m, "sampling_trajectories");
   n_elite_ = GetNumberOrDefault(std::max(num_trajectory_ / 10, 2), m, "n_elite");
+  pruning = GetNumberOrDefault(0, m, "cross_entropy_prune") != 0;
+  park_slack = GetNumberOrDefault(kDefaultParkSlack, m, "cross_entropy_park_slack");
+  hint_valid_ = false;
 }
 
 // cross_entropy/planner.cc:77-119
@@ -53,6 +58,48 @@ void GpuCrossEntropyPlanner::Reset(int horizon, const double* initial_repeated_a
   nominal_.Reset(kMaxTrajectoryHorizon);
   nominal_valid_ = false;
   improvement = 0.0;
+  hint_valid_ = false;
+}
+
+// GpuSamplingPlanner::TaskSignature / CostIsNonNegative: what a hint is tied to, and when a partial return is a lower bound of the return
+std::vector<double> GpuCrossEntropyPlanner::TaskSignature() const {
+  std::vector<double> s(task->weight);
+  s.insert(s.end(), task->parameters.begin(), task->parameters.end());
+  for (NormType k : task->norm) s.push_back((double)(int)k);
+  s.insert(s.end(), task->norm_parameter.begin(), task->norm_parameter.end());
+  s.push_back(task->risk);
+  return s;
+}
+
+bool GpuCrossEntropyPlanner::CostIsNonNegative() const {
+  if (!(std::fabs(task->risk) < 1.0e-6)) return false;
+  for (size_t k = 0; k < task->weight.size(); k++) {
+    if (!(task->weight[k] >= 0)) return false;
+    switch (task->norm[k]) {
+      case kQuadratic: case kL2: case kPowerLoss: case kSmoothAbsLoss: case kRectifyLoss: break;
+      default: return false;
+    }
+  }
+  return true;
+}
+
+// the plan launch; prune: at rank `rank`, parked on park_hint (the switches are sticky: on for this launch alone). Returns whether the
+// launch was asked to prune
+bool GpuCrossEntropyPlanner::Rollouts(int horizon, const mjpcx_noise_spec& ns, bool prune, int rank, double park_hint) {
+  const double inf = std::numeric_limits<double>::infinity();
+  const TimeSpline& plan = resampled_policy.plan;
+  const bool pruned = prune && world_ <= 1 && CostIsNonNegative();
+  if (pruned) {
+    ctx_->Check(mjpcx_set_pruning(ctx_->handle(), 0, inf));
+    ctx_->Check(mjpcx_set_prune_rank(ctx_->handle(), rank));
+    ctx_->Check(mjpcx_set_pruning(ctx_->handle(), 1, inf));
+    ctx_->Check(mjpcx_set_park_hint(ctx_->handle(), park_hint >= 0 ? park_hint : inf));
+  }
+  const int rc = mjpcx_rollout_noise(ctx_->handle(), n_local_, horizon, (int)plan.Size(), (int)plan.Interpolation(), plan.times().data(),
+                                     plan.values().data(), &ns);
+  if (pruned) { (void)mjpcx_set_pruning(ctx_->handle(), 0, inf); (void)mjpcx_set_park_hint(ctx_->handle(), inf); (void)mjpcx_set_prune_rank(ctx_->handle(), 1); }
+  ctx_->Check(rc);
+  return pruned;
 }
 
 double GpuCrossEntropyPlanner::PlanningTimestep() const {
@@ -120,17 +167,32 @@ void GpuCrossEntropyPlanner::OptimizePolicy(int horizon, ThreadPool& pool) {
   ns.std0 = std_initial_;
   ns.std1 = std_min_;
   ns.param_variance = variance.data();
-  const TimeSpline& plan = resampled_policy.plan;
   ctx_->SyncTask(*task);  // the per-plan frozen ResidualFn copy (agent.cc:319)
   ctx_->Check(mjpcx_set_state(ctx_->handle(), state.data(), time, mocap.data(), userdata.data()));
-  ctx_->Check(mjpcx_rollout_noise(ctx_->handle(), n_local_, horizon, (int)plan.Size(), (int)plan.Interpolation(),
-                                  plan.times().data(), plan.values().data(), &ns));
+  // the park hint: the previous plan's worst elite return x (1 + park_slack), if it was taken under this task row (mjpcx_set_park_hint: no
+  // result depends on it)
+  const std::vector<double> signature = TaskSignature();
+  double hint = std::numeric_limits<double>::infinity();
+  if (hint_valid_ && park_slack > -1.0 && signature == hint_task_) hint = hint_worst_ * (1.0 + park_slack);
+  const bool pruned = Rollouts(horizon, ns, pruning, n_elite + 1, hint);
+  park_hint_used = pruned ? hint : std::numeric_limits<double>::infinity();
+  pruned_launch_repeated = false;
+  ctx_->Check(mjpcx_prune_stats(ctx_->handle(), prune_counts));
+  ctx_->Check(mjpcx_park_stats(ctx_->handle(), park_counts, nullptr));
 
   // ---- the reference sorts all N returns (:206-211); only the n_elite best (+1 for the nominal) matter
   int k = std::min(n_elite + 1, n_local_);
   std::vector<std::int32_t> idx32(k);
   std::vector<double> ret(k);
-  ctx_->Check(mjpcx_topk(ctx_->handle(), k, idx32.data(), ret.data()));
+  int rc = mjpcx_topk(ctx_->handle(), k, idx32.data(), ret.data());
+  if (rc == MJPCX_ESTATE && pruned) {
+    // the pruned launch reported a negative step cost: its partial returns were no lower bounds. The same candidates again (same seed and
+    // iteration), all to the horizon: the policy stays exact
+    pruned_launch_repeated = true;
+    Rollouts(horizon, ns, /*prune=*/false, 1, hint);
+    rc = mjpcx_topk(ctx_->handle(), k, idx32.data(), ret.data());
+  }
+  ctx_->Check(rc);
   std::vector<std::int64_t> idx(n_elite + 1, -1);
   ret.resize(n_elite + 1, 1.0e300);
   for (int i = 0; i < k; i++) idx[i] = (std::int64_t)idx32[i] + offset_;
@@ -144,13 +206,18 @@ void GpuCrossEntropyPlanner::OptimizePolicy(int horizon, ThreadPool& pool) {
     }
   }
   trajectory_order.clear();
-  double best_return = 0;
+  double best_return = 0, worst_elite = std::numeric_limits<double>::quiet_NaN();
   bool have_best = false;
   for (int i = 0; i < n_elite + 1 && (int)trajectory_order.size() < n_elite; i++) {
     if (idx[i] < 0 || idx[i] == num_trajectory) continue;  // the nominal rollout is not a candidate
     if (!have_best) { best_return = ret[i]; have_best = true; }
     trajectory_order.push_back((int)idx[i]);
+    if ((int)trajectory_order.size() == n_elite) worst_elite = ret[i];
   }
+  // the next plan's hint, unless this plan's resume launch shows that the estimate it ran on was stale
+  hint_worst_ = worst_elite;
+  hint_task_ = signature;
+  hint_valid_ = pruned && std::isfinite(worst_elite) && worst_elite >= 0 && !((double)park_counts[2] > kParkMaxResumeShare * (double)std::max(n_local_, 1));
   rollouts_compute_time = GetDuration(start);
 
   // ---- elite mean / variance (:216-270): partial sums over this rank's elites, all-reduced when sharded

@@ -72,9 +72,28 @@ class GpuCrossEntropyPlanner : public Planner {
   int num_trajectory_ = 0;
   std::uint32_t iteration = 0;
   mutable std::shared_mutex mtx_;
+  // OptimizePolicy reads nothing of a launch but its n_elite best candidates, their splines and the nominal rollout: what a pruned launch
+  // at rank n_elite + 1 keeps exact (mjpcx_set_prune_rank; the nominal completes and may sit among the first n_elite + 1). pruning: the plan
+  // launch parks the candidates that the previous plan's worst elite return x (1 + park_slack) condemns and retires those above the K-th
+  // completed return, as GpuSamplingPlanner::OptimizePolicy does with the bound of the argmin. Off by default ("cross_entropy_prune" in the
+  // model), and off on a sharded planner (world > 1).
+  bool pruning = false;
+  double park_slack = kDefaultParkSlack;   // "cross_entropy_park_slack" in the model; <= -1: no hints
+  static constexpr double kDefaultParkSlack = 0.05;
+  static constexpr double kParkMaxResumeShare = 0.25;  // a plan that resumed more of its candidates ran on a stale hint: no hint for the next
+  // of the last OptimizePolicy (zeros / +inf / false unless it pruned)
+  std::int64_t prune_counts[4] = {0, 0, 0, 0}, park_counts[3] = {0, 0, 0};
+  double park_hint_used = 0;
+  bool pruned_launch_repeated = false;
 
  private:
   double PlanningTimestep() const;
+  bool CostIsNonNegative() const;
+  std::vector<double> TaskSignature() const;
+  bool Rollouts(int horizon, const mjpcx_noise_spec& ns, bool prune, int rank, double park_hint);
+  double hint_worst_ = 0;
+  std::vector<double> hint_task_;
+  bool hint_valid_ = false;
   int device_, precision_;
   std::uint64_t seed_;
   int rank_ = 0, world_ = 1, offset_ = 0, n_local_ = 0;

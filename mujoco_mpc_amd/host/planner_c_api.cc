@@ -483,6 +483,25 @@ int mjpc_planner_park_info(void* h, double* out) {
   out[3] = H->ps->park_hint_used;
   return 0;
 }
+// the Cross-Entropy planner's switch (GpuCrossEntropyPlanner::pruning, park_slack; slack <= -1: no hint). Returns -1 for the other planners
+int mjpc_planner_prune_set(void* h, int enabled, double slack) {
+  Handle* H = static_cast<Handle*>(h);
+  if (!H->ce) return -1;
+  H->ce->pruning = enabled != 0;
+  H->ce->park_slack = slack;
+  return 0;
+}
+// of its last OptimizePolicy: out[0..2] candidates parked, retired by the settling pass, resumed; out[3] the hint it used (+inf: none);
+// out[4] candidates retired in all; out[5] != 0 if the pruned launch was refused and repeated unpruned
+int mjpc_planner_prune_info(void* h, double* out) {
+  Handle* H = static_cast<Handle*>(h);
+  if (!H->ce) return -1;
+  for (int k = 0; k < 3; k++) out[k] = (double)H->ce->park_counts[k];
+  out[3] = H->ce->park_hint_used;
+  out[4] = (double)H->ce->prune_counts[0];
+  out[5] = H->ce->pruned_launch_repeated ? 1.0 : 0.0;
+  return 0;
+}
 // the underlying mjpcx context (timing, algorithmic bytes, kernel name)
 mjpcx_ctx* mjpc_planner_ctx(void* h) { return static_cast<Handle*>(h)->context()->handle(); }
 

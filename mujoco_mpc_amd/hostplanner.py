@@ -86,6 +86,8 @@ def lib():
         L.mjpc_planner_policy.argtypes = [vp, c_f64p, c_f64p, C.c_int]
         L.mjpc_planner_park_set.argtypes = [vp, C.c_double]
         L.mjpc_planner_park_info.argtypes = [vp, c_f64p]
+        L.mjpc_planner_prune_set.argtypes = [vp, C.c_int, C.c_double]
+        L.mjpc_planner_prune_info.argtypes = [vp, c_f64p]
         L.mjpc_planner_ctx.restype = vp
         L.mjpc_planner_ctx.argtypes = [vp]
         _LIB = L
@@ -428,6 +430,18 @@ class HostPlanner:
         h = np.zeros(4)
         self._chk(lib().mjpc_planner_park_info(self.h, as_f64p(h)))
         return dict(parked=int(h[0]), settled_retired=int(h[1]), resumed=int(h[2]), hint=float(h[3]))
+
+    def prune_set(self, enabled, slack=0.05):
+        """the Cross-Entropy planner's pruning: the plan launch at rank n_elite + 1 (mjpcx_set_prune_rank), parked on the previous plan's worst
+        elite return x (1 + slack); slack <= -1: no hint. Off by default"""
+        self._chk(lib().mjpc_planner_prune_set(self.h, int(bool(enabled)), float(slack)))
+
+    def prune_info(self):
+        """of the Cross-Entropy planner's last optimize_policy: candidates parked, retired by the settling pass, resumed, the hint it used
+        (inf: none), candidates retired in all, and whether the pruned launch was refused and repeated unpruned"""
+        h = np.zeros(6)
+        self._chk(lib().mjpc_planner_prune_info(self.h, as_f64p(h)))
+        return dict(parked=int(h[0]), settled_retired=int(h[1]), resumed=int(h[2]), hint=float(h[3]), retired=int(h[4]), repeated=bool(h[5]))
 
     def algorithmic_bytes(self, horizon, num_nodes):
         return capi.lib().mjpcx_algorithmic_bytes(self._ctx(), horizon, num_nodes)

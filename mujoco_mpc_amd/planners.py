@@ -715,6 +715,14 @@ def task_signature(task):
             [float(x) for x in task.norm_parameter] + [float(task.risk)])
 
 
+def _park_hint(hint, task, slack):
+    """the park hint of the next launch from a planner's (previous return, task signature) record: the return x (1 + slack); +inf when there
+    is no record, when slack <= -1, or when the task row has changed since"""
+    if hint is None or not slack > -1.0 or hint[1] != task_signature(task):
+        return np.inf
+    return hint[0] * (1.0 + slack)
+
+
 def cost_is_non_negative(task):
     """GpuSamplingPlanner::CostIsNonNegative: pruning needs every step's cost >= 0 in floating point -- weights >= 0, no risk transform, and
     the norm kinds whose computed value is shown to be >= 0"""
@@ -1233,10 +1241,22 @@ class GpuCrossEntropyPlanner(_ContextOwner):
         self.noise_compute_time = self.rollouts_compute_time = self.policy_update_compute_time = 0.0
         self.trajectory_order = []
         self.interpolation_ = ZERO  # member default kZeroSpline, planner.h:141-142 (CE never reads sampling_representation)
+        # optimize_policy reads nothing of a launch but its n_elite best candidates, their splines and the nominal rollout -- what a pruned launch
+        # at rank n_elite + 1 keeps exact (set_prune_rank: the nominal completes and may sit among the first n_elite + 1). pruning: the plan
+        # launch parks the candidates that the previous plan's worst elite return x (1 + park_slack) condemns and retires those above the
+        # K-th completed return. Off by default, and off on a planner with a group (world > 1).
+        self.pruning = False
+        self.park_slack = DEFAULT_PARK_SLACK   # "cross_entropy_park_slack" in the model; <= -1: no hints
+        self.prune_stats = self.park_stats = None   # of the last plan (capi.Context.prune_stats / park_stats); None unless it was pruned
+        self.park_hint_used = None                  # the hint the last plan's launch ran on (+inf: none), None unless it was pruned
+        self.pruned_launch_repeated = False         # the last plan's pruned launch was refused (MJPCX_ESTATE) and repeated unpruned
+        self._hint = None                           # (previous worst elite return, task signature), or None -- no hint for the next plan
 
     # ---- Initialize, planner.cc:41-74
     def initialize(self, model, task: Task):
         self.model, self.task = model, task
+        self.park_slack = float(model.get_number("cross_entropy_park_slack", DEFAULT_PARK_SLACK))
+        self._hint = None
         self.std_initial_ = model.get_number("sampling_exploration", 0.1)
         self.std_min_ = model.get_number("std_min", 0.01)
         self.explore_fraction_ = model.get_number("explore_fraction", 0.0)
@@ -1270,9 +1290,29 @@ class GpuCrossEntropyPlanner(_ContextOwner):
         self.variance[:] = self.std_initial_ ** 2
         self.improvement = 0.0
         self._nominal = None
+        self._hint = None
 
     def set_state(self, state: State):
         self.state, self.mocap, self.userdata, self.time = state.copy_to()
+
+    def _rollouts(self, n_local, horizon, plan, ns, prune, rank):
+        """the plan launch; prune: at rank `rank`, parked on the hint (the switches are sticky and the context may be shared: on for this
+        launch alone). Returns whether the launch was asked to prune"""
+        pruned = bool(prune) and cost_is_non_negative(self.task)
+        self.park_hint_used = _park_hint(self._hint, self.task, self.park_slack) if pruned else None
+        if pruned:
+            self.ctx.set_pruning(False)
+            self.ctx.set_prune_rank(rank)
+            self.ctx.set_pruning(True)
+            self.ctx.set_park_hint(self.park_hint_used)
+        try:
+            self.ctx.rollout_noise(n_local, horizon, plan.interpolation(), plan.times(), plan.values(), ns)
+        finally:
+            if pruned:
+                self.ctx.set_pruning(False)
+                self.ctx.set_park_hint(np.inf)
+                self.ctx.set_prune_rank(1)
+        return pruned
 
     # ---- ResamplePolicy, planner.cc:322-348
     def resample_policy(self, horizon):
@@ -1318,11 +1358,23 @@ class GpuCrossEntropyPlanner(_ContextOwner):
         plan = self.resampled_policy.plan
         sync_task(self.ctx, self.task)
         self.ctx.set_state(self.state, self.time, self.mocap, self.userdata)
-        self.ctx.rollout_noise(n_local, horizon, plan.interpolation(), plan.times(), plan.values(), ns)
+        pruned = self._rollouts(n_local, horizon, plan, ns, self.pruning and world == 1, n_elite + 1)
         self._offset, self._n_local = offset, n_local
+        self.prune_stats = self.park_stats = None
+        self.pruned_launch_repeated = False
+        if pruned:
+            self.prune_stats, self.park_stats = self.ctx.prune_stats(), self.ctx.park_stats()
         # ---- full sort in the reference (planner.cc:206-211); only the elites matter downstream
         k = min(n_elite + 1, n_local)
-        idx, ret = self.ctx.topk(k)
+        try:
+            idx, ret = self.ctx.topk(k)
+        except capi.MjpcxError as err:
+            if not pruned or err.code != MJPCX_ESTATE:
+                raise
+            # the pruned launch's ranking is not proven (a negative step cost): the same candidates again, all to the horizon
+            self.pruned_launch_repeated = True
+            self._rollouts(n_local, horizon, plan, ns, False, 1)
+            idx, ret = self.ctx.topk(k)
         idx = idx.astype(np.int64) + offset
         if world > 1:
             idx, ret = self.group.merge_topk(idx, ret, n_elite + 1)
@@ -1354,6 +1406,10 @@ class GpuCrossEntropyPlanner(_ContextOwner):
             for t in range(P):
                 self.policy.plan.add_node(self.times_scratch[t], mean[t])
         self.improvement = max(avg_return - float(ret[0]), 0.0)
+        # the next plan's hint: this plan's worst elite return, unless its resume launch shows that the estimate it ran on was stale
+        worst = float(ret[n_elite - 1]) if len(ret) >= n_elite else np.nan
+        stale = pruned and float(self.park_stats["resumed"]) > K_PARK_MAX_RESUME_SHARE * max(n_local, 1)
+        self._hint = (worst, task_signature(self.task)) if pruned and np.isfinite(worst) and worst >= 0 and not stale else None
         self._nominal = None
         self.iteration += 1
         self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
@@ -1401,6 +1457,20 @@ class GpuBatchCrossEntropyPlanner(_Fleet):
         self.rollouts_compute_time = self.policy_update_compute_time = 0.0
         # the members never roll out themselves: they are handed the shared context instead of creating their own
         self.envs = [GpuCrossEntropyPlanner(device, precision, seed + e, backend_factory=lambda task: self.ctx) for e in range(self.num_envs)]
+        # pruning: the plan launch runs at rank n_elite + 1 with a bound per robot (set_prune_rank + set_pruning_batched): it parks, per robot,
+        # the candidates that the robot's previous worst elite return x (1 + park_slack) condemns and retires those above the robot's K-th
+        # completed return. ce_update_batched reads the n_elite best without the nominal: what such a launch keeps exact. Off by default.
+        self.pruning = False
+        self.park_slack = DEFAULT_PARK_SLACK   # "cross_entropy_park_slack" in the model; <= -1: no hints
+        self.prune_stats = self.park_stats = None   # of the last plan, per robot (capi.Context.prune_stats_batched); None unless it was pruned
+        self.park_hints_used = None                 # the hints the last plan's launch ran on (E; +inf: none), None unless it was pruned
+        self.pruned_launch_repeated = False         # the last plan's pruned launch was refused (MJPCX_ESTATE) and repeated unpruned
+        self._hint = [None] * self.num_envs         # per robot: (previous worst elite return, task signature), or None
+
+    def initialize(self, model, task: Task):
+        super().initialize(model, task)
+        self.park_slack = float(model.get_number("cross_entropy_park_slack", DEFAULT_PARK_SLACK))
+        self._hint = [None] * self.num_envs
 
     num_trajectory_ = _fleet_setting("num_trajectory_")
     n_elite_ = _fleet_setting("n_elite_")
@@ -1412,6 +1482,28 @@ class GpuBatchCrossEntropyPlanner(_Fleet):
 
     def _reset_own(self):
         self._last = None
+        self._hint = [None] * self.num_envs
+
+    def _enqueue(self, n, horizon, ns, prune, rank):
+        """the plan launch, with the members' resampled policies and variances as they stand: optimize_policy repeats it unpruned, same
+        seed and iteration, when the context refuses the pruned one's ranking. Returns whether the launch was asked to prune"""
+        plans = [p.resampled_policy.plan for p in self.envs]
+        np_ = self.envs[0].resampled_policy.num_spline_points * self.model.nu
+        # (a cost that can be negative in any robot's task row: no pruning for the launch -- partial returns would be no lower bounds there)
+        pruned = bool(prune) and all(cost_is_non_negative(p.task) for p in self.envs)
+        self.park_hints_used = np.array([_park_hint(h, p.task, self.park_slack) for h, p in zip(self._hint, self.envs)]) if pruned else None
+        if pruned:
+            self.ctx.set_prune_rank(rank)
+            self.ctx.set_pruning_batched(True, self.num_envs, None, self.park_hints_used)
+        try:
+            self.ctx.rollout_noise_batched_ce(n, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
+                                              np.stack([pl.values() for pl in plans]), np.stack([p.variance[:np_] for p in self.envs]),
+                                              ns, num_envs=self.num_envs)
+        finally:
+            if pruned:   # (the switches are sticky: on for this launch alone)
+                self.ctx.set_pruning_batched(False)
+                self.ctx.set_prune_rank(1)
+        return pruned
 
     # ---- OptimizePolicy, cross_entropy/planner.cc:168-291, for every environment
     def optimize_policy(self, horizon, pool=None):
@@ -1433,12 +1525,23 @@ class GpuBatchCrossEntropyPlanner(_Fleet):
         ns = capi.make_noise_spec(seed=self.seed, iteration=self.iteration, mode=capi.NOISE_CROSS_ENTROPY, candidate_offset=0,
                                   nominal_candidate=num_trajectory, explore_count=explore_count, std0=self.std_initial_,
                                   std1=self.std_min_)
-        plans = [p.resampled_policy.plan for p in self.envs]
         self._push_states()
-        self.ctx.rollout_noise_batched_ce(n, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
-                                          np.stack([pl.values() for pl in plans]), np.stack([p.variance[:np_] for p in self.envs]),
-                                          ns, num_envs=self.num_envs)
-        idx, ret, mean, var, avg = self.ctx.ce_update_batched(self.num_envs, n_elite, num_trajectory)
+        pruned = self._enqueue(n, horizon, ns, self.pruning, n_elite + 1)
+        self.prune_stats = self.park_stats = None
+        self.pruned_launch_repeated = False
+        if pruned:
+            st = self.ctx.prune_stats_batched(self.num_envs)
+            self.prune_stats = {k: st[k] for k in ("retired", "retire_step_sum", "negative_cost", "wavefronts_ended_early", "final_bound")}
+            self.park_stats = {k: st[k] for k in ("parked", "settled_retired", "resumed")}
+        try:
+            idx, ret, mean, var, avg = self.ctx.ce_update_batched(self.num_envs, n_elite, num_trajectory)
+        except capi.MjpcxError as err:
+            if not pruned or err.code != MJPCX_ESTATE:
+                raise
+            # some robot's pruned ranking is not proven (a negative step cost): the same candidates again, all to the horizon
+            self.pruned_launch_repeated = True
+            self._enqueue(n, horizon, ns, False, 1)
+            idx, ret, mean, var, avg = self.ctx.ce_update_batched(self.num_envs, n_elite, num_trajectory)
         self._last = "plan"
         self._n = n
         self.rollouts_compute_time = (_time.perf_counter() - t0) * 1e6
@@ -1461,6 +1564,10 @@ class GpuBatchCrossEntropyPlanner(_Fleet):
             p.improvement = max(float(avg[e]) - float(ret[e][0]), 0.0)
             p._nominal = None
             p.iteration = self.iteration
+            # the next plan's hint: the robot's worst elite return, unless its resume launch shows that the estimate it ran on was stale
+            worst = float(ret[e][n_elite - 1])
+            stale = pruned and float(self.park_stats["resumed"][e]) > K_PARK_MAX_RESUME_SHARE * max(n, 1)
+            self._hint[e] = (worst, task_signature(p.task)) if pruned and np.isfinite(worst) and worst >= 0 and not stale else None
         self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
 
     def nominal_trajectory(self, horizon, pool=None):

@@ -590,13 +590,28 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
                 s, _ = ctx.elite_moments(idx)
                 ctx.elite_moments(idx, s / n_elite)
 
+        # --prune: the batched side runs at rank n_elite + 1 (set_prune_rank) with a bound per environment, as
+        # GpuBatchCrossEntropyPlanner(pruning=True) does: on for the launch alone, every robot's hint its previous worst elite return x 1.05
+        # (--no-park: no hints)
+        last_worst = [None]
+
         def ce_rollout():
             fleet_states()
-            ctx.rollout_noise_batched_ce(n, H, interp, times, nominal, variance, ce_spec(0, None), num_envs=E)
+            if prune:
+                ctx.set_prune_rank(n_elite + 1)
+                ctx.set_pruning_batched(True, E, None, None if not park or last_worst[0] is None else 1.05 * last_worst[0])
+            try:
+                ctx.rollout_noise_batched_ce(n, H, interp, times, nominal, variance, ce_spec(0, None), num_envs=E)
+            finally:
+                if prune:
+                    ctx.set_pruning_batched(False)
+                    ctx.set_prune_rank(1)
+            if prune:
+                counts.append(ctx.prune_stats_batched(E))
 
         def ce_batched():      # GpuBatchCrossEntropyPlanner.optimize_policy's calls
             ce_rollout()
-            ctx.ce_update_batched(E, n_elite, n - 1)
+            last_worst[0] = ctx.ce_update_batched(E, n_elite, n - 1)[1][:, n_elite - 1].copy()
 
         if ce:
             sequential, batched = ce_sequential, ce_batched
@@ -614,7 +629,7 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
                "batched_ms": {"median": float(np.median(tb)), "min": float(np.min(tb)), "max": float(np.max(tb))},
                "ratio_sequential_over_batched": float(np.median(ts) / np.median(tb)),
                "beyond_spread": bool(np.max(tb) < np.min(ts))}
-        if prune and not ce:   # per environment, summed over the timed steps: how much of the fleet left early, and how
+        if prune:   # per environment, summed over the timed steps: how much of the fleet left early, and how
             timed = counts[-steps:]
             rec.update(prune=True, park=bool(park), candidates_per_env=int(n) * steps,
                        **{k: [int(sum(c[k][e] for c in timed)) for e in range(E)] for k in ("retired", "retire_step_sum", "parked", "settled_retired", "resumed")})
@@ -622,7 +637,7 @@ def sweep(name, precision, H, shapes, steps, warmup, out, planner="sampling", mi
             tr, tu = [], []
             for _ in range(steps):
                 t0 = time.perf_counter(); ce_rollout(); ctx.sync(); t1 = time.perf_counter()
-                ctx.ce_update_batched(E, n_elite, n - 1); t2 = time.perf_counter()
+                last_worst[0] = ctx.ce_update_batched(E, n_elite, n - 1)[1][:, n_elite - 1].copy(); t2 = time.perf_counter()
                 tr.append((t1 - t0) * 1e3)
                 tu.append((t2 - t1) * 1e3)
             rec.update(planner="cross_entropy", n_elite=n_elite,
@@ -649,7 +664,8 @@ def main():
     ap.add_argument("--mixed-models", action="store_true", help="sampling, cross_entropy: every environment its own model (payload, friction, actuator strength)")
     ap.add_argument("--robust", default="16x4", help="--planner robust: candidates x repetitions")
     ap.add_argument("--gradient-candidates", type=int, default=32, help="--planner sample_gradient: gradient candidates per environment")
-    ap.add_argument("--prune", action="store_true", help="--planner sampling: the batched side prunes and parks per environment (set_pruning_batched)")
+    ap.add_argument("--prune", action="store_true", help="--planner sampling, cross_entropy: the batched side prunes and parks per environment (set_pruning_batched; "
+                    "cross_entropy: at rank n_elite + 1, set_prune_rank)")
     ap.add_argument("--no-park", action="store_true", help="with --prune: no park hints")
     ap.add_argument("--no-device-chain", action="store_true", help="--planner ilqg, ilqs: the sequential middle (the A/B of ilqg_step_batched[_from])")
     a = ap.parse_args()
@@ -663,7 +679,7 @@ def main():
         for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES, "ilqs": ILQS_SHAPES, "robust": ROBUST_SHAPES,
                                              "sample_gradient": SAMPLE_GRADIENT_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
-            if keep is not None and a.only == name and a.planner == "sampling":   # (--only with --shapes: also shapes outside the default list, e.g. 16x1024)
+            if keep is not None and a.only == name and a.planner in ("sampling", "cross_entropy"):   # (--only with --shapes: also shapes outside the default list, e.g. 16x1024)
                 shapes += [sh for sh in sorted(keep) if sh not in shapes]
             if shapes and (a.only is None or a.only == name):
                 if a.mixed_models and (a.planner not in ("sampling", "cross_entropy") or name == "Cartpole"):
@@ -684,8 +700,8 @@ def main():
                 elif a.planner == "ilqg":
                     sweep_ilqg(name, precision, H, shapes, a.steps, a.warmup, out, False if a.no_device_chain else None, a.mixed_params)
                 else:
-                    if a.prune and a.planner != "sampling":
-                        raise SystemExit("batch_sweep.py: --prune is for --planner sampling")
+                    if a.prune and a.planner not in ("sampling", "cross_entropy"):
+                        raise SystemExit("batch_sweep.py: --prune is for --planner sampling and --planner cross_entropy")
                     sweep(name, precision, H, shapes, a.steps, a.warmup, out, a.planner, a.mixed_params, a.mixed_models, a.prune, not a.no_park)
 
 
