@@ -445,6 +445,38 @@ int mjpcx_ce_update_batched(mjpcx_ctx* ctx, int num_envs, int n_elite, int skip_
 int mjpcx_best_batched(mjpcx_ctx* ctx, int num_envs, int ref_candidate, int32_t* index, double* best_return,
                        double* ref_return, double* spline_values);
 
+/* An ensemble: ONE set of n candidates rolled out under M hypotheses about one robot, in the batched launch of M environments.
+ * Hypothesis h is environment h of the preceding mjpcx_set_states(M, ...): its state, its task row if mjpcx_set_task_params_batched
+ * gave one, its residual state, and its model if mjpcx_set_models_batched(M, ...) gave one. The hypotheses share node_times (P),
+ * nominal_values (P x nu) and the noise stream: local candidate i of every hypothesis is the same spline. Hypothesis h behaves
+ * exactly like mjpcx_rollout_noise with noise->seed (NOT + h) on a context created on models[h], after mjpcx_set_state(state h) and
+ * mjpcx_set_task_params(row h): equal bits in the returns, the failure words and all six Trajectory buffers.
+ *   - Afterwards the context's last rollout is a batched one of M x n, hypothesis-major (candidate h * n + i): every getter,
+ *     mjpcx_best_batched (the argmin per hypothesis) and mjpcx_ensemble_best work on it.
+ *   - Validation and error codes as mjpcx_rollout_noise_batched: n a positive multiple of 64, mjpcx_set_states with the same M first,
+ *     M models if any are set (MJPCX_EINVAL; the context keeps its last rollout), MJPCX_EUNSUPPORTED on a sharded context. Both noise
+ *     modes; noise->param_variance (CE) is shared.
+ *   - mjpcx_set_pruning_batched is ignored: everything is rolled out to the horizon (the score needs every return). */
+int mjpcx_rollout_noise_ensemble(mjpcx_ctx* ctx, int num_hypotheses, int n, int horizon, int num_nodes, int interpolation,
+                                 const double* node_times, const double* nominal_values, const mjpcx_noise_spec* noise);
+
+/* The selection of an ensemble, one launch and one sync, over the M x n stored returns R[h][i] (candidate h * n + i) of the last
+ * batched rollout. The failure words are not consulted, as in mjpcx_best: a failed rollout's 1e6 makes the candidate lose.
+ *   score[i] = the mean of the `tail` largest of R[0][i] .. R[M-1][i], 1 <= tail <= M: the M values ordered descending, equal values
+ *     with the lower h first, the first `tail` summed in that order in fp64 with plain adds (starting at the first) and divided by
+ *     tail; NaN if any of the M values is NaN. tail = M: the mean over the hypotheses; tail = 1: the worst case; in between the
+ *     tail mean (CVaR).
+ *   index: the argmin of the scores in mjpcx_topk's order (ascending, ties to the lower index, NaN last) -> best_score;
+ *   member_returns (M): the winner's returns R[h][index]; ref_score: the score of ref_candidate (-1: skipped, NaN);
+ *   spline_values (P x nu): the winner's spline, hypothesis 0's copy; scores (n, may be NULL): every candidate's score.
+ * Any output but index may be NULL. Deterministic: two calls give the same bits. MJPCX_EINVAL when the last rollout was not a
+ * batched one of num_hypotheses environments, tail is outside 1..M or ref_candidate outside -1..n-1; MJPCX_EUNSUPPORTED for
+ * M > MJPCX_MAX_HYPOTHESES; MJPCX_ESTATE when the last rollout was pruned (stored partial returns are no returns: the rule of
+ * mjpcx_ce_update_batched). */
+#define MJPCX_MAX_HYPOTHESES 32
+int mjpcx_ensemble_best(mjpcx_ctx* ctx, int num_hypotheses, int tail, int ref_candidate, int32_t* index, double* best_score,
+                        double* ref_score, double* member_returns, double* spline_values, double* scores);
+
 /* The Robust planner's plan step (RobustPlanner::OptimizePolicy after the delegate's rollout) for E environments: select, replicate,
  * roll out under force noise and score, enqueued on ctx's stream behind source's (an event; nothing goes through the host), ONE sync.
  * `source` is the context of the delegate's rollout -- the same model, device and precision; its last rollout a batched one of num_envs

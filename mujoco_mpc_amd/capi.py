@@ -37,8 +37,10 @@ EXPORTS = [
     "mjpcx_set_park_hint", "mjpcx_park_stats", "mjpcx_park_resumed",
     "mjpcx_set_pruning_batched", "mjpcx_prune_stats_batched",
     "mjpcx_set_prune_rank", "mjpcx_rank_bound_batched",
+    "mjpcx_rollout_noise_ensemble", "mjpcx_ensemble_best",
 ]
 
+MAX_HYPOTHESES = 32                           # MJPCX_MAX_HYPOTHESES of mjpcx_ensemble_best
 SG_COMPUTE_WEIGHTS, SG_ZERO_GRADIENT = 1, 2   # MJPCX_SG_* flags of mjpcx_sample_gradient_update_batched
 
 _LIB = None
@@ -90,6 +92,8 @@ def lib():
         L.mjpcx_rollout_sample_gradient_batched.argtypes = [vp] + [C.c_int] * 6 + [c_f64p, c_f64p, C.c_double, C.c_uint64, C.c_int, c_f64p, c_f64p]
         L.mjpcx_sample_gradient_update_batched.argtypes = ([vp] + [C.c_int] * 3 + [C.c_double] * 4 + [c_i32p, c_i32p] + [c_f64p] * 5)
         L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
+        L.mjpcx_rollout_noise_ensemble.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
+        L.mjpcx_ensemble_best.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_i32p] + [C.POINTER(C.c_double)] * 2 + [c_f64p] * 3
         L.mjpcx_rollout_noise_batched_ce.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_ce_update_batched.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_gradient_step_batched.argtypes = ([vp] + [C.c_int] * 4 + [c_i32p, C.c_double] + [C.c_int] * 3 + [c_f64p] * 9)
@@ -461,6 +465,30 @@ class Context:
         self._chk(lib().mjpcx_best_batched(self.handle, E, int(ref_candidate), as_i32p(idx), as_f64p(br), as_f64p(rr),
                                            as_f64p(sp) if with_spline else None))
         return idx, br, rr, sp
+
+    def rollout_noise_ensemble(self, n, horizon, interp, node_times, nominal, noise_spec, num_hypotheses):
+        """ONE set of n candidates under num_hypotheses hypotheses (the environments of the preceding set_states, with their task rows and
+        models): node_times P, nominal P x nu and the noise stream of noise_spec.seed are shared, so candidate h * n + i is the same spline
+        for every h. The context's last rollout is then a batched one of M x n."""
+        nt, nom = _f(node_times).reshape(-1), _f(nominal)
+        M, P = int(num_hypotheses), nt.size
+        assert nom.size == P * self.nu
+        self._chk(lib().mjpcx_rollout_noise_ensemble(self.handle, M, int(n), int(horizon), P, int(interp), as_f64p(nt), as_f64p(nom),
+                                                     C.byref(noise_spec)))
+        self.N, self.H, self.P, self.n_per_env = M * int(n), int(horizon), P, int(n)
+
+    def ensemble_best(self, num_hypotheses, tail, ref_candidate=0, with_scores=False):
+        """the ensemble's selection in one launch / one sync (mjpcx_ensemble_best): a candidate's score is the mean of the `tail` largest
+        of its num_hypotheses returns (tail = M: the mean, 1: the worst case). -> the argmin, its score, the score of ref_candidate
+        (-1: NaN), the winner's M returns, its spline (P x nu) and, with_scores, the n scores (else None)."""
+        M = int(num_hypotheses)
+        idx = np.zeros(1, np.int32)
+        bs, rs = C.c_double(), C.c_double()
+        members, sp = np.zeros(max(M, 1)), np.zeros((self.P, self.nu))
+        scores = np.zeros(max(self.N // max(M, 1), 1)) if with_scores else None
+        self._chk(lib().mjpcx_ensemble_best(self.handle, M, int(tail), int(ref_candidate), as_i32p(idx), C.byref(bs), C.byref(rs),
+                                            as_f64p(members), as_f64p(sp), as_f64p(scores) if with_scores else None))
+        return int(idx[0]), bs.value, rs.value, members, sp, scores
 
     def sync(self):
         self._chk(lib().mjpcx_sync(self.handle))

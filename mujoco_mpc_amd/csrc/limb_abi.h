@@ -24,6 +24,7 @@ template <typename R> struct LArgs {
   int* iters;           // nullptr, or [N]: Newton iterations summed over the steps (tuning aid)
   int env_n;            // several environments in one launch (env_select.h): candidates per environment, a multiple of 64 (0: one environment) ...
   unsigned env_stride;  // ... and the bytes between the plan records of consecutive environments (node_times, nominal and the blob are environment 0's)
+  int seed_shared;      // mjpcx_rollout_noise_ensemble: every environment draws the noise stream of `seed` itself (0: environment e that of seed + e)
 };
 constexpr int kLFallback = 0x40000000;  // failure[] marker of a candidate handed on (= kQFallback of quad_abi.h: tree_kernel.h's mode bit 32 reads it)
 // offsets into the per-plan blob (WaveTaskT: wave_model.h), in elements of the working precision

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void rollout_limb_kernel(const LimbModelT<R>* 
   LArgs<R> a = a0;
   env_rebase(a, env);
   a.param_variance = env_ptr(a.param_variance, env, a0.env_stride);  // (CE: the environment's own variance row)
-  a.seed += (uint64_t)env; a.candidate_offset -= env * a0.env_n;
+  a.seed += a0.seed_shared ? 0 : (uint64_t)env; a.candidate_offset -= env * a0.env_n;  // (an ensemble's hypotheses share the candidates)
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   LimbModelT<R>& sm = *reinterpret_cast<LimbModelT<R>*>(lds_raw);
   {

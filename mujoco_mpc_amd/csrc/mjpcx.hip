@@ -25,6 +25,8 @@
 #include "quad_launch.h"
 #include "park_settle.h"
 #include "rank_bound.h"
+#include "wave_argmin.h"
+#include "ensemble_best.h"
 #include "limb_launch.h"
 #include "wave32_launch.h"
 #include <type_traits>
@@ -126,14 +128,7 @@ const KernelEntry kWaveEntry = {"rollout_wave_kernel (wavefront per candidate, m
 // ===================================================================== small kernels
 // argmin / top-k over total_return: replaces std::partial_sort (sampling/planner.cc:184-188).
 // Keys are (return, index) with ties broken by index, so the result is deterministic.
-struct RetIdx { double r; int i; };
-__device__ __forceinline__ bool less_ri(const RetIdx& a, const RetIdx& b) {
-  // NaN returns sort last (the reference's operator< would make the order unspecified)
-  const bool an = a.r != a.r, bn = b.r != b.r;
-  if (an != bn) return bn;
-  if (a.r != b.r && !an) return a.r < b.r;
-  return a.i < b.i;
-}
+// (RetIdx, less_ri: wave_argmin.h)
 __global__ __launch_bounds__(1024) void argmin_kernel(const double* __restrict__ ret, int n, RetIdx* out) {
   __shared__ RetIdx sm[16];
   RetIdx best{INFINITY, 0x7fffffff};
@@ -221,32 +216,7 @@ __global__ __launch_bounds__(1024) void best_kernel(const double* __restrict__ r
 }
 
 // The same reads for E environments in one launch (mjpcx_best_batched): one workgroup per environment over its n_env returns,
-// environment-major. The wavefront reduction is a butterfly of (return, index) minima: the steps inside a row of 16 lanes are DPP
-// moves (no LDS traffic) -- quad_perm [1,0,3,2] and [2,3,0,1] leave a quad's minimum in its four lanes, row_half_mirror and row_mirror
-// then pair whole quads and whole halves -- and the two steps across rows go through the LDS crossbar. less_ri is a total order
-// (NaN last, ties to the lower index), so every lane ends with the same minimum whatever the pairing.
-template <int CTRL> __device__ __forceinline__ RetIdx dpp_ri(const RetIdx& v) {
-  RetIdx o;
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v.r), CTRL, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v.r), CTRL, 0xf, 0xf, true);
-  o.r = __hiloint2double(hi, lo);
-  o.i = __builtin_amdgcn_update_dpp(0, v.i, CTRL, 0xf, 0xf, true);
-  return o;
-}
-__device__ __forceinline__ RetIdx wave_argmin(RetIdx best) {  // every lane of the wavefront active
-  RetIdx o;
-  o = dpp_ri<0xB1>(best); if (less_ri(o, best)) best = o;   // quad_perm:[1,0,3,2]
-  o = dpp_ri<0x4E>(best); if (less_ri(o, best)) best = o;   // quad_perm:[2,3,0,1]
-  o = dpp_ri<0x141>(best); if (less_ri(o, best)) best = o;  // row_half_mirror
-  o = dpp_ri<0x140>(best); if (less_ri(o, best)) best = o;  // row_mirror
-#pragma unroll
-  for (int off = 16; off <= 32; off <<= 1) {
-    o.r = __shfl_xor(best.r, off, 64);
-    o.i = __shfl_xor(best.i, off, 64);
-    if (less_ri(o, best)) best = o;
-  }
-  return best;
-}
+// environment-major, reduced with wave_argmin (wave_argmin.h).
 constexpr size_t kBestHeader = 24;  // bytes of a BestRecord before its spline values
 template <typename T>
 __global__ __launch_bounds__(256) void best_segmented_kernel(const double* __restrict__ ret, const int* __restrict__ fail, const T* __restrict__ nodes,
@@ -1370,7 +1340,7 @@ hipError_t launch_quad(mjpcx_ctx* c, const WaveModel& wm, const WaveTask& wt, co
   q.param_variance = a.noise.param_variance;
   q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
   q.total_return = a.total_return; q.failure = a.failure; q.con_cap = c->quad_con_cap; q.cpw = c->quad_cpw;
-  q.env_n = a.env_n; q.env_stride = a.env_stride;
+  q.env_n = a.env_n; q.env_stride = a.env_stride; q.seed_shared = a.seed_shared;
   q.model_stride = mr.qmodel_stride; q.tables_stride = mr.qtab_stride;  // (a model per environment; 0: the one model)
   const quad::QBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
   hipError_t e;
@@ -1610,7 +1580,7 @@ hipError_t launch_limb(mjpcx_ctx* c, const WaveModelT<T>& wm, const WaveTaskT<T>
   q.param_variance = a.noise.param_variance;
   q.states = a.states; q.actions = a.actions; q.times = a.times; q.residual = a.residual; q.costs = a.costs; q.trace = a.trace;
   q.total_return = a.total_return; q.failure = a.failure; q.cpw = c->limb_cpw;
-  q.env_n = a.env_n; q.env_stride = a.env_stride;
+  q.env_n = a.env_n; q.env_stride = a.env_stride; q.seed_shared = a.seed_shared;
   const limb::LBlob bo{wt.off_time, wt.off_mocap, wt.off_weight, wt.off_normp, wt.off_normq, wt.off_param, wt.off_risk, wt.off_rreal, wt.off_rint};
   hipError_t e;
   if ((e = hipMemsetAsync(c->d_qstats.p, 0, 32, c->stream)) != hipSuccess) return e;  // (how many candidates are handed on, by reason: mjpcx_quad_stats)
@@ -1847,6 +1817,8 @@ struct RolloutRequest {
   double xfrc_std = 0, xfrc_rate = 1; uint64_t xfrc_seed = 0; int xfrc_offset = 0;
   // (mjpcx_rollout_noise_batched) the one batched launch mjpcx_set_pruning_batched applies to
   bool prune_batched = false;
+  // (mjpcx_rollout_noise_ensemble) every environment draws the noise stream of noise->seed itself: the environments roll out the same candidates
+  bool seed_shared = false;
 };
 
 template <typename T>
@@ -1867,6 +1839,7 @@ int do_rollout(mjpcx_ctx* c, const RolloutRequest& r) {
   if (mr.per_env) { a.model_stride = c->em.cold_stride; a.image_stride = c->em.image_stride; }
   a.nodes = (T*)c->d_nodes.p;
   a.noise.mode = -1;
+  a.seed_shared = r.seed_shared ? 1 : 0;
   const double* d_var = nullptr;
   mjpcx_ctx::Slot* slot = nullptr;
   const bool ce = ns && ns->mode == MJPCX_NOISE_CROSS_ENTROPY;
@@ -2682,6 +2655,61 @@ int mjpcx_best_batched(mjpcx_ctx* c, int E, int ref_candidate, int32_t* index, d
     if (ref_return) ref_return[e] = r->ref_return;
     if (spline_values) std::memcpy(spline_values + (size_t)e * np, r->spline, (size_t)np * 8);
   }
+  return MJPCX_OK;
+}
+
+int mjpcx_rollout_noise_ensemble(mjpcx_ctx* c, int M, int n, int H, int P, int interp, const double* node_times, const double* nominal,
+                                 const mjpcx_noise_spec* ns) {
+  if (!c || !node_times) return fail(c, MJPCX_EINVAL, "null argument");
+  if (M < 1) return fail(c, MJPCX_EINVAL, "mjpcx_rollout_noise_ensemble: the number of hypotheses must be >= 1");
+  if (P < 1) return check_rollout_args(c, n, H, P, interp, node_times);
+  // the one row of node times and the one nominal, as every hypothesis's row of the batched launch
+  const size_t np = (size_t)P * c->nu;
+  std::vector<double> times((size_t)M * P), nom;
+  for (int h = 0; h < M; h++) std::memcpy(times.data() + (size_t)h * P, node_times, (size_t)P * 8);
+  int rc = check_batched_args(c, M, n, H, P, interp, times.data());
+  if (rc != MJPCX_OK) return rc;
+  if (!nominal || !ns) return fail(c, MJPCX_EINVAL, "null argument");
+  if (ns->mode != MJPCX_NOISE_SAMPLING && ns->mode != MJPCX_NOISE_CROSS_ENTROPY) return fail(c, MJPCX_EINVAL, "unknown noise mode");
+  nom.resize((size_t)M * np);
+  for (int h = 0; h < M; h++) std::memcpy(nom.data() + (size_t)h * np, nominal, np * 8);
+  RolloutRequest r{M * n, H, P, interp, times.data(), M};
+  r.nominal = nom.data(); r.noise = ns;
+  r.seed_shared = true;  // (and no prune_batched: the score needs every return, so mjpcx_set_pruning_batched is ignored)
+  return rollout(c, r);
+}
+
+int mjpcx_ensemble_best(mjpcx_ctx* c, int M, int tail, int ref_candidate, int32_t* index, double* best_score, double* ref_score,
+                        double* member_returns, double* spline_values, double* scores) {
+  const std::string who = "mjpcx_ensemble_best: ";
+  if (!c || !index) return fail(c, MJPCX_EINVAL, who + "null argument");
+  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (M > MJPCX_MAX_HYPOTHESES) return fail(c, MJPCX_EUNSUPPORTED, who + std::to_string(M) + " hypotheses; at most " + std::to_string(MJPCX_MAX_HYPOTHESES));
+  if (M < 1 || c->env_n < 1 || (long long)M * c->env_n != c->N)
+    return fail(c, MJPCX_EINVAL, who + "the last rollout was not a batched one of " + std::to_string(M) + " environments");
+  const int n = c->env_n;
+  if (tail < 1 || tail > M) return fail(c, MJPCX_EINVAL, who + "tail = " + std::to_string(tail) + " outside 1.." + std::to_string(M));
+  if (ref_candidate < -1 || ref_candidate >= n)
+    return fail(c, MJPCX_EINVAL, who + "ref_candidate = " + std::to_string(ref_candidate) + " outside -1.." + std::to_string(n - 1));
+  if (c->last_pruned) return fail(c, MJPCX_ESTATE, who + kPrunedRanking);  // (stored partial returns are no returns: the rule of mjpcx_ce_update_batched)
+  static_assert(kEnsembleMaxHypotheses == MJPCX_MAX_HYPOTHESES && offsetof(EnsembleRecord, rest) == kEnsembleHeader, "the record of ensemble_best_kernel");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int np = c->P * c->nu;
+  HIPCHK(c, c->result.reserve(kEnsembleHeader + ((size_t)np + (scores ? n : 0)) * 8));
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((ensemble_best_kernel<T>), dim3(1), dim3(kEnsembleThreads), (size_t)tail * kEnsembleThreads * 8, c->stream, (const double*)c->d_ret.p,
+                       (const T*)c->d_nodes.p, n, M, tail, np, ref_candidate, scores ? 1 : 0, (unsigned char*)c->result.dev);
+  });
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const EnsembleRecord* r = (const EnsembleRecord*)c->result.p;
+  *index = r->best_index;
+  if (best_score) *best_score = r->best_score;
+  if (ref_score) *ref_score = r->ref_score;
+  if (member_returns) std::memcpy(member_returns, r->member, (size_t)M * 8);
+  if (spline_values) std::memcpy(spline_values, r->rest, (size_t)np * 8);
+  if (scores) std::memcpy(scores, r->rest + np, (size_t)n * 8);
   return MJPCX_OK;
 }
 

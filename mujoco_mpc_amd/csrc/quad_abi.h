@@ -61,6 +61,8 @@ struct QArgs {
   bool keep_bound = false;  // rank mode (mjpcx_set_prune_rank): a completed rollout leaves the bound word alone. The word then stays where the host put it (+inf: nothing is
                             // retired in the main launch) until rank_bound_kernel (rank_bound.h) writes the K-th smallest completed return into it; the resume launch prunes
                             // against that and leaves it alone too. false: a completed rollout lowers the word to its return (the bound of the argmin)
+  int seed_shared = 0;      // mjpcx_rollout_noise_ensemble: every environment draws the noise stream of `seed` itself, so local candidate i is the same spline in all of
+                            // them. 0: environment e draws the stream of seed + e. Read by rollout_quad_env_kernel alone, where the launcher sends such a launch
 };
 // an environment's record of a pruned batched launch, byte offsets: the bound word; prune_stats' four ints; the settling pass's two counts (candidates parked, candidates
 // to resume); the environment's park hint. The first 32 bytes are what a plain launch keeps behind its hand-on counters, in the same order

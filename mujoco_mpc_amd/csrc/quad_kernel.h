@@ -241,7 +241,9 @@ __device__ __forceinline__ void quad_kernel_body(const QuadModel* __restrict__ g
   QArgs a = a0;
   env_rebase(a, env);
   a.param_variance = env_ptr(a.param_variance, env, a0.env_stride);  // (CE: the environment's own variance row)
-  a.seed += (uint64_t)env; a.candidate_offset -= env * a0.env_n;
+  // (an ensemble's hypotheses share the candidates: QArgs::seed_shared, which only the instantiation with ENVREC reads -- the launcher sends
+  // such a launch there, and the plain kernel's code stays what it was)
+  a.seed += ENVREC && a0.seed_shared ? 0 : (uint64_t)env; a.candidate_offset -= env * a0.env_n;
   // a bound per environment (mjpcx_set_pruning_batched; a stride of 0: the one record of a plain launch): the bound word and the counters
   // are the environment's, and so is the park hint, which sits in the record -- scalar adds and one scalar load, once, before the step loop.
   // Nothing of another environment is compared with, lowered or counted from here on.
@@ -297,7 +299,8 @@ __global__ __launch_bounds__(256) void rollout_quad_kernel(const QuadModel* __re
                                                            const QBlob bo, const QArgs a, int* __restrict__ stats) {
   quad_kernel_body<false>(gm, tab, blob, bo, a, QFeedback{}, stats);
 }
-// rollout_quad_kernel for a launch with a bound, a hint and a set of counters per environment (QArgs::rec_stride != 0: mjpcx_set_pruning_batched)
+// rollout_quad_kernel for a launch with a bound, a hint and a set of counters per environment (QArgs::rec_stride != 0: mjpcx_set_pruning_batched),
+// and for an ensemble's launch (QArgs::seed_shared: mjpcx_rollout_noise_ensemble; rec_stride == 0 there: no bound, nothing retired)
 __global__ __launch_bounds__(256) void rollout_quad_env_kernel(const QuadModel* __restrict__ gm, const QuadTables* __restrict__ tab, const double* __restrict__ blob,
                                                                const QBlob bo, const QArgs a, int* __restrict__ stats) {
   quad_kernel_body<false, false, true>(gm, tab, blob, bo, a, QFeedback{}, stats);

@@ -8,6 +8,9 @@ std::string build_images(const mjpcx_model* m, const mjpcx_task* t, std::vector<
   tables.assign(sizeof(QuadTables), 0);
   return quad_build(m, t, reinterpret_cast<QuadModel*>(model.data()), reinterpret_cast<QuadTables*>(tables.data()));
 }
+// QArgs::seed_shared is read by rollout_quad_env_kernel alone, where launch_rollout_quad sends such a request: the other launchers refuse it
+// instead of quietly drawing seed + env
+static bool draws_shared_seed(const QArgs& a) { return a.seed_shared != 0; }
 static int pick_cpw(int N, int cpw) {
   // candidates per wavefront: as many as it takes to give every SIMD of the 256 CUs one wavefront, 16 at most and 4 at least (cpw > 0: the
   // caller's choice). Below four the lock-step no longer shrinks but the wavefronts multiply, and co-resident wavefronts cost each other more
@@ -26,6 +29,7 @@ hipError_t launch_feedback_quad(const void* model_, const void* tables_, const d
                                 hipStream_t stream) {
   const QuadModel* model = static_cast<const QuadModel*>(model_);
   const QuadTables* tables = static_cast<const QuadTables*>(tables_);
+  if (draws_shared_seed(a)) return hipErrorInvalidValue;
   QArgs q = a;
   q.cpw = 1;  // one candidate per wavefront, one wavefront per workgroup: the rollouts of an iLQG iteration are latency, not throughput
   hipError_t e = hipFuncSetAttribute((const void*)rollout_feedback_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kQWaveLds));
@@ -45,8 +49,9 @@ hipError_t launch_rollout_quad(const void* model_, const void* tables_, const do
   const int W = waves >= 4 * 256 ? 4 : 1;
   const size_t lds = W * kQWaveLds;
   // (the opt-in to more than 64 KB of dynamic LDS is per device and costs nothing next to a 60 ms launch: set on every launch, like the other launchers)
-  // (a launch with a record per environment has an instantiation of its own: the plain one stays as it was)
-  const auto kern = q.rec_stride ? rollout_quad_env_kernel : rollout_quad_kernel;
+  // (a launch with a record per environment, or an ensemble's with its shared noise stream, has an instantiation of its own: the plain one
+  // stays as it was)
+  const auto kern = q.rec_stride || q.seed_shared ? rollout_quad_env_kernel : rollout_quad_kernel;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kQWaveLds));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((waves + W - 1) / W), dim3(64 * W), lds, stream, model, tables, blob, bo, q, stats);
@@ -55,6 +60,7 @@ hipError_t launch_rollout_quad(const void* model_, const void* tables_, const do
 hipError_t launch_resume_quad(const void* model_, const void* tables_, const double* blob, const QBlob& bo, const QArgs& a, int* stats, hipStream_t stream) {
   const QuadModel* model = static_cast<const QuadModel*>(model_);
   const QuadTables* tables = static_cast<const QuadTables*>(tables_);
+  if (draws_shared_seed(a)) return hipErrorInvalidValue;
   if (a.resume_n <= 0) return hipSuccess;
   // candidates per wavefront from the list's length, as pick_cpw does, but down to ONE (resume_cpw of resume_table.h): up to 1024 resumed
   // candidates get a wavefront (and a SIMD) each. Never more wavefronts than the 1024 SIMDs: a second round of wavefronts would cost more than
@@ -74,6 +80,7 @@ hipError_t launch_resume_quad_groups(const void* model_, const void* tables_, co
                                      hipStream_t stream) {
   const QuadModel* model = static_cast<const QuadModel*>(model_);
   const QuadTables* tables = static_cast<const QuadTables*>(tables_);
+  if (draws_shared_seed(a)) return hipErrorInvalidValue;
   if (grid <= 0) return hipSuccess;
   if (!a.resume_groups || !a.rec_stride || a.cpw < 1 || (W != 1 && W != 4)) return hipErrorInvalidValue;
   QArgs q = a;

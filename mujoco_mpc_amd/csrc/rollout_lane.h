@@ -144,6 +144,9 @@ struct RolloutArgs {
   // rollout_wave_kernel, the generic kernel, reads its model through the pointers of its kernel arguments (no image to stage): with a model
   // per environment it is launched once per environment, on that environment's model, over env_n workgroups -- workgroup b is candidate cand_base + b
   int cand_base;
+  // mjpcx_rollout_noise_ensemble: every environment draws the noise stream of `noise.seed` itself, so local candidate i is the same spline
+  // in all of them (0: environment e draws the stream of seed + e). Uniform over the launch; the force-noise seed is not affected.
+  int seed_shared;
 };
 
 // NOISE = false: a pass that draws no noise (noise.mode < 0) and so has no use for the variance pointer
@@ -152,7 +155,7 @@ template <bool NOISE = true, typename T> __device__ __forceinline__ RolloutArgs<
   env_rebase(r, env);
   r.init = env_ptr(a.init, env, a.env_stride);
   if constexpr (NOISE) r.noise.param_variance = env_ptr(a.noise.param_variance, env, a.env_stride);  // (CE: the environment's own variance row)
-  r.noise.seed = a.noise.seed + (uint64_t)env;
+  r.noise.seed = a.noise.seed + (a.seed_shared ? 0 : (uint64_t)env);  // (an ensemble's hypotheses share the candidates)
   r.noise.candidate_offset = a.noise.candidate_offset - env * a.env_n;
   r.xfrc_seed = a.xfrc_seed + (uint64_t)env;  // (NoisyRollout: the environment's own force-noise stream, as a plain call with seed + env)
   return r;

@@ -709,6 +709,109 @@ class GpuBatchSamplingPlanner(_Fleet):
         return p._best
 
 
+class GpuEnsembleSamplingPlanner(_Fleet):
+    """Predictive Sampling for ONE robot over `num_hypotheses` hypotheses about it -- its model (`set_models`: a payload, another floor,
+    weaker motors), its task (`set_tasks`) or its state (`set_states`). Every plan step rolls the SAME n candidates out under every
+    hypothesis in one launch (`rollout_noise_ensemble`: the M environments of a fleet's launch, with the noise stream shared) and takes
+    the candidate whose score over the hypotheses is lowest (`ensemble_best`): the mean of the `tail` largest of its M returns -- tail
+    None or M: the mean, 1: the worst case, in between the tail mean (CVaR). One `set_states`, one launch, one selection, one sync.
+
+    The hypotheses are the fleet's members (`envs`), and what is per hypothesis -- state, task, model and their way to the context -- is
+    _Fleet's. The robot has ONE policy, member 0's: nominal resampling, the policy copy and ActionFromPolicy are that GpuSamplingPlanner's
+    own code (`member`); the other members hold a hypothesis's state and task and never plan. With one hypothesis, or M alike, the planner
+    is GpuSamplingPlanner(seed) bit for bit. No pruning: the score needs every return."""
+
+    def __init__(self, num_hypotheses, device=0, precision=64, seed=0, tail=None, backend_factory=None):
+        super().__init__(num_hypotheses, device, precision, backend_factory)
+        if self.num_envs > capi.MAX_HYPOTHESES:
+            raise ValueError(f"{self.num_envs} hypotheses; mjpcx_ensemble_best takes at most {capi.MAX_HYPOTHESES}")
+        self.num_hypotheses, self.seed = self.num_envs, seed
+        self.tail = self.num_envs if tail is None else int(tail)
+        if not 1 <= self.tail <= self.num_envs:
+            raise ValueError(f"tail = {tail} outside 1..{self.num_envs} (the number of hypotheses)")
+        self.envs = [GpuSamplingPlanner(device, precision, seed, backend_factory=lambda task: self.ctx) for _ in range(self.num_envs)]
+        self.member = self.envs[0]
+        self.best_score = self.nominal_score = 0.0      # the last plan's scores of the winner and of candidate 0, the nominal
+        self.member_returns = np.zeros(self.num_envs)   # the winner's return under every hypothesis
+        self.rollouts_compute_time = self.policy_update_compute_time = 0.0
+        self._trajectories = {}
+
+    @property
+    def num_trajectory_(self):
+        return self.member.num_trajectory_
+
+    @num_trajectory_.setter
+    def num_trajectory_(self, n):
+        self.member.num_trajectory_ = int(n)
+
+    @property
+    def noise_exploration(self):
+        return self.member.noise_exploration
+
+    @noise_exploration.setter
+    def noise_exploration(self, value):
+        self.member.noise_exploration = list(value)
+
+    policy = property(lambda self: self.member.policy)
+    winner = property(lambda self: self.member.winner)
+
+    @property
+    def winners(self):
+        """(_Fleet's list of a winner per robot has no meaning here: the members beside member 0 never plan)"""
+        raise AttributeError("GpuEnsembleSamplingPlanner plans for one robot: `winner` is its candidate, `member_returns` its return under every hypothesis")
+    improvement = property(lambda self: self.member.improvement)
+    iteration = property(lambda self: self.member.iteration)
+
+    def _reset_own(self):
+        self._last = None
+        self._trajectories = {}
+
+    def set_state(self, state: State):
+        """the one robot: every hypothesis starts from this state (set_states: a hypothesis each about the state, too)"""
+        self.set_states([state] * self.num_envs)
+
+    def optimize_policy(self, horizon, pool=None):
+        m, M = self.member, self.num_envs
+        n = m.num_trajectory_
+        self._check_n(n)
+        m.update_nominal_policy(horizon)
+        t0 = _time.perf_counter()
+        plan = m.policy.plan
+        plan.set_interpolation(m.interpolation_)
+        ns = capi.make_noise_spec(seed=self.seed, iteration=m.iteration, mode=capi.NOISE_SAMPLING, candidate_offset=0, nominal_candidate=0,
+                                  std0=m.noise_exploration[0], std1=m.noise_exploration[1])
+        self._push_states()
+        self.ctx.rollout_noise_ensemble(n, horizon, plan.interpolation(), plan.times(), plan.values(), ns, num_hypotheses=M)
+        self._last, self._n, self._trajectories = "plan", n, {}
+        idx, best, nominal, members, values, _ = self.ctx.ensemble_best(M, self.tail, 0)
+        self.rollouts_compute_time = (_time.perf_counter() - t0) * 1e6
+        t0 = _time.perf_counter()
+        m._offset, m._n_local = 0, n
+        m.trajectory_order, m._scores = [int(idx)], [float(best)]
+        m.iteration += 1
+        m._set_winner(int(idx), values)
+        self.best_score, self.nominal_score = float(best), float(nominal)
+        self.member_returns = np.array(members[:M], float)
+        m.best_return, m.nominal_return = self.best_score, self.nominal_score
+        m.improvement = max(self.nominal_score - self.best_score, 0.0)
+        self.policy_update_compute_time = (_time.perf_counter() - t0) * 1e6
+
+    def action_from_policy(self, action, state, time, use_previous=False):
+        """the one robot's action (GpuSamplingPlanner's signature, not the fleets': there is no environment to name)"""
+        return self.member.action_from_policy(action, state, time, use_previous)
+
+    def best_trajectory(self, hypothesis=0):
+        """the winner rolled out under `hypothesis` (candidate hypothesis * n + winner of the plan launch)"""
+        if not 0 <= hypothesis < self.num_envs:
+            raise ValueError(f"hypothesis {hypothesis} outside 0..{self.num_envs - 1}")
+        if hypothesis not in self._trajectories:
+            tr = self._fetch_planned(hypothesis, self.member.winner)
+            if tr is None:
+                return None
+            self._trajectories[hypothesis] = tr
+        return self._trajectories[hypothesis]
+
+
 def task_signature(task):
     """GpuSamplingPlanner::TaskSignature: what a robot's park hint is tied to -- weights, parameters, norm kinds and parameters, risk"""
     return ([float(x) for x in task.weight] + [float(x) for x in task.parameters] + [float(int(k)) for k in task.norm] +

@@ -45,6 +45,12 @@ runs without the chain too and (c) is left out. Host logic included on every sid
 nominal phase, went on to iLQG and were gathered from the sampling context, with that step's time and its derivatives_backward (the
 fleet's composition moves while robots migrate to iLQG: --warmup 16 times a settled fleet). Default output profiles/batch_sweep_ilqs.jsonl.
 
+--planner ensemble: the ensemble plan step -- ONE robot, E hypotheses about its model (--mixed-models; without it E copies of one model), n
+shared candidates. Two variants alternating in one session on one context, from the same states and nominal: (a) "sampling", the fleet's plan
+step as above (set_states, rollout_noise_batched, best_batched); (b) "ensemble": set_states, rollout_noise_ensemble, ensemble_best (--tail,
+default E: the mean). The same launch over E x n rollouts with the noise stream shared, and ensemble_best in place of best_batched: the
+expectation is equal times. Default shape 8 x 2048 on the A1, H = 100, fp64; default output profiles/batch_sweep_ensemble.jsonl.
+
 --mixed-params: every environment plans with task weights, norm parameters, residual parameters and risk of its own (sampling and
 cross_entropy: set_task_params_batched after set_states, and the plain set_task_params of the same row before every sequential plan
 step; gradient and ilqg: the fleet planner's set_tasks, and every sequential planner on its own task). The kernels do the same work
@@ -149,6 +155,59 @@ def mixed_models(task, E):
 def task_rows(tasks):
     arr = lambda k: np.array([getattr(t, k) for t in tasks], float).reshape(len(tasks), -1)
     return dict(weight=arr("weight"), norm_parameter=arr("norm_parameter"), parameters=arr("parameters"), risk=np.array([float(t.risk) for t in tasks]))
+
+
+ENSEMBLE_SHAPES = [("QuadrupedFlat", 64, 100, [(8, 2048)])]
+
+
+def sweep_ensemble(name, precision, H, shapes, steps, warmup, out, tail=None, models=False):
+    task = load_task(name)
+    m = task.model
+    rng = np.random.default_rng(1)
+    ctx = capi.Context(task.packed_model(), task.packed(), 0, precision)
+    P = int(m.get_number("sampling_spline_points", 6))
+    interp = int(m.get_number("sampling_representation", capi.SPLINE_CUBIC))
+    std = float(m.get_number("sampling_exploration", 0.1))
+    dt = m.get_number("agent_timestep", m.timestep)
+    times1 = np.arange(P) * ((H - 1) * dt / max(P - 1, 1))
+    for E, n in shapes:
+        raw, clocks, mocap = initial(task, name, 1, rng)
+        states, clocks, mocap = np.repeat(raw, E, axis=0), np.repeat(clocks, E), None if mocap is None else np.repeat(mocap, E, axis=0)   # the one robot
+        times, nominal = np.stack([times1] * E), np.zeros((E, P, m.nu))
+        k = E if tail is None else int(tail)
+        if models:
+            ctx.set_models_batched(mixed_models(task, E))
+        it = [0]
+
+        def sampling():
+            it[0] += 1
+            ctx.set_states(states, clocks, mocap)
+            ctx.rollout_noise_batched(n, H, interp, times, nominal, capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_envs=E)
+            ctx.best_batched(E, 0)
+
+        def ensemble():
+            ctx.set_states(states, clocks, mocap)
+            ctx.rollout_noise_ensemble(n, H, interp, times1, nominal[0], capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_hypotheses=E)
+            ctx.ensemble_best(E, k, 0)
+
+        for _ in range(warmup):
+            sampling()
+            ensemble()
+        ta, tb = [], []
+        for _ in range(steps):   # alternating: both sides see the same clocks and the same neighbours on the machine
+            t0 = time.perf_counter(); sampling(); t1 = time.perf_counter(); ensemble(); t2 = time.perf_counter()
+            ta.append((t1 - t0) * 1e3)
+            tb.append((t2 - t1) * 1e3)
+        rec = {"planner": "ensemble", "task": name, "precision": precision, "horizon": H, "num_hypotheses": E, "n": n, "tail": k, "steps": steps,
+               "warmup": warmup, "mixed_models": bool(models), "kernel": ctx.kernel_name.split(" (")[0], "sampling_ms": stats(ta), "ensemble_ms": stats(tb),
+               "ratio_ensemble_over_sampling": float(np.median(tb) / np.median(ta)),
+               "inside_spread": bool(np.min(ta) <= np.median(tb) <= np.max(ta))}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+        out.flush()
+        if models:
+            ctx.set_models_batched(None)
+    ctx.close()
 
 
 GRADIENT_SHAPES = [("QuadrupedFlat", 64, 36, [(1, 64), (4, 64), (8, 64), (16, 64)]),
@@ -658,10 +717,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "ilqs", "robust", "sample_gradient"], default="sampling")
+    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "ilqs", "robust", "sample_gradient", "ensemble"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
     ap.add_argument("--mixed-params", action="store_true", help="every environment its own task weights, parameters and risk")
-    ap.add_argument("--mixed-models", action="store_true", help="sampling, cross_entropy: every environment its own model (payload, friction, actuator strength)")
+    ap.add_argument("--mixed-models", action="store_true", help="sampling, cross_entropy, ensemble: every environment its own model (payload, friction, actuator strength)")
+    ap.add_argument("--tail", type=int, default=None, help="--planner ensemble: the score is the mean of the `tail` largest returns (default: all, the mean)")
     ap.add_argument("--robust", default="16x4", help="--planner robust: candidates x repetitions")
     ap.add_argument("--gradient-candidates", type=int, default=32, help="--planner sample_gradient: gradient candidates per environment")
     ap.add_argument("--prune", action="store_true", help="--planner sampling, cross_entropy: the batched side prunes and parks per environment (set_pruning_batched; "
@@ -671,17 +731,20 @@ def main():
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl", "ilqs": "batch_sweep_ilqs.jsonl", "robust": "batch_sweep_robust.jsonl",
-                                                       "sample_gradient": "batch_sweep_sample_gradient.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
+                                                       "sample_gradient": "batch_sweep_sample_gradient.jsonl", "ensemble": "batch_sweep_ensemble.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
     keep = None if a.shapes is None else {tuple(int(x) for x in sh.split("x")) for sh in a.shapes.split(",")}
     if a.steps < 10:
         raise SystemExit("batch_sweep.py: at least 10 timed steps")
     with open(a.out, "w") as out:
         for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES, "ilqs": ILQS_SHAPES, "robust": ROBUST_SHAPES,
-                                             "sample_gradient": SAMPLE_GRADIENT_SHAPES}.get(a.planner, SHAPES):
+                                             "sample_gradient": SAMPLE_GRADIENT_SHAPES, "ensemble": ENSEMBLE_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
             if keep is not None and a.only == name and a.planner in ("sampling", "cross_entropy"):   # (--only with --shapes: also shapes outside the default list, e.g. 16x1024)
                 shapes += [sh for sh in sorted(keep) if sh not in shapes]
             if shapes and (a.only is None or a.only == name):
+                if a.planner == "ensemble":
+                    sweep_ensemble(name, precision, H, shapes, a.steps, a.warmup, out, a.tail, a.mixed_models)
+                    continue
                 if a.mixed_models and (a.planner not in ("sampling", "cross_entropy") or name == "Cartpole"):
                     if a.planner not in ("sampling", "cross_entropy"):
                         raise SystemExit("batch_sweep.py: --mixed-models is for --planner sampling and cross_entropy")
