@@ -307,7 +307,21 @@ int mjpcx_rollout_splines(mjpcx_ctx* ctx, int num_candidates, int horizon,
  * 120-140): as mjpcx_rollout_splines, with Ornstein-Uhlenbeck force / torque noise on every body's xfrc_applied,
  * xfrc[i] <- exp(-dt / xfrc_rate) xfrc[i] + N(0, xfrc_std sqrt(1 - exp(-2 dt / xfrc_rate))) before every step (starting
  * from zero). The normals are counter-based, keyed on (seed, candidate_offset + candidate, step, entry) -- the reference's
- * absl::BitGen is unseeded, so there is no stream to reproduce. Both kernel families. */
+ * absl::BitGen is unseeded, so there is no stream to reproduce. Both kernel families. Exactly:
+ *   - xfrc is the model's 6 nbody array, body-major, force then torque; nbody is the MODEL's body count, the world body and
+ *     bodies a kernel leaves out of its own loops (inert trailing mocap bodies) included. A kernel that skips a body skips its
+ *     draws, not their counters.
+ *   - The Philox4x32-10 key is (low, high word of seed); the counter of a pair is
+ *       (candidate_offset + candidate, step * 3 * nbody + j, 0x58465243, 0),   j = 0 .. 3 nbody - 1,
+ *     the words in this order (word 2 is "XFRC", word 3 is 0); uniforms and Box-Muller as in mjpcx_noise_spec. Entry 2 j of
+ *     xfrc takes z0 of pair j, entry 2 j + 1 takes z1.
+ *   - Step t = 0 .. horizon - 2 draws before its mj_step: x[t] = decay x[t - 1] + scale z, x[-1] = 0; nothing is drawn before
+ *     the final mj_forward of row horizon - 1, which sees x[horizon - 2].
+ *   - decay = exp(-dt / xfrc_rate), scale = xfrc_std sqrt(1 - decay^2), both formed in double on the host, dt the timestep of
+ *     the mjpcx_model the context was created with (the planning timestep, agent_timestep where the task defines one -- not the
+ *     XML's option timestep). A 32-bit context rounds decay and scale z to float and runs the recursion in float.
+ *   - Force and torque act at the body's centre of mass (xipos), in the world frame, on every dof the body hangs under
+ *     (mj_xfrcAccumulate). */
 int mjpcx_rollout_splines_noisy(mjpcx_ctx* ctx, int num_candidates, int horizon, int num_nodes, int interpolation,
                                 const double* node_times, const double* node_values, double xfrc_std, double xfrc_rate,
                                 uint64_t seed, int candidate_offset);

@@ -125,12 +125,21 @@ int orollout_batch(const mjpcx_model* m, const mjpcx_task* task, const double* s
                    int num_threads, OBatchOut* out);
 /* Trajectory::NoisyRollout (trajectory.cc:100-210) for N candidate splines: Ornstein-Uhlenbeck xfrc_applied noise
  * (rate = exp(-dt / xfrc_rate), scale = xfrc_std sqrt(1 - rate^2)), counter-based normals keyed on
- * (seed, candidate_offset + i, step, entry) instead of the reference's unseeded absl::BitGen */
+ * (seed, candidate_offset + i, step, entry) instead of the reference's unseeded absl::BitGen. The counter layout is the one
+ * include/mjpcx.h states for mjpcx_rollout_splines_noisy: pair j of step t is Philox counter (candidate_offset + i,
+ * t * 3 * nbody + j, 0x58465243, 0) under the key (seed low, seed high), nbody the model's; entry 2 j takes z0, entry 2 j + 1
+ * takes z1; drawn before each of the first H - 1 steps; dt is m->timestep (the planning timestep). */
 int orollout_batch_noisy(const mjpcx_model* m, const mjpcx_task* task, const double* state,
                          double time, const double* mocap, const double* userdata, int N, int H,
                          int P, int interp, const double* node_times, const double* node_values,
                          double xfrc_std, double xfrc_rate, uint64_t seed, int candidate_offset,
                          int num_threads, OBatchOut* out);
+/* tests only: one such rollout of global candidate `candidate` (node_values P x nu) that hands back what it applied:
+ * xfrc_out H x 6 nbody, the xfrc_applied each of the H - 1 steps and the final mj_forward saw; states_out H x dim_state or NULL.
+ * Returns the failure flag. */
+int orollout_noisy_xfrc(const mjpcx_model* m, const mjpcx_task* task, const double* state, double time, const double* mocap,
+                        int H, int P, int interp, const double* node_times, const double* node_values, double xfrc_std,
+                        double xfrc_rate, uint64_t seed, int candidate, double* states_out, double* xfrc_out);
 
 /* ---------------- iLQG derivatives and feedback rollouts (oracle/ilqg.c) ---------------- */
 /* StateDiff (mjpc/utilities.cc:543-553): (s2 - s1) / h in the tangent space, 2 nv entries */

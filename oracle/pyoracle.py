@@ -147,6 +147,8 @@ def _load(path):
         L.orollout_batch_noisy.argtypes = [C.POINTER(MjpcxModel), C.POINTER(MjpcxTask), c_f64p, C.c_double, c_f64p, c_f64p,
                                            C.c_int, C.c_int, C.c_int, C.c_int, c_f64p, c_f64p, C.c_double, C.c_double,
                                            C.c_uint64, C.c_int, C.c_int, C.POINTER(OBatchOut)]
+        L.orollout_noisy_xfrc.argtypes = [C.POINTER(MjpcxModel), C.POINTER(MjpcxTask), c_f64p, C.c_double, c_f64p, C.c_int, C.c_int,
+                                          C.c_int, c_f64p, c_f64p, C.c_double, C.c_double, C.c_uint64, C.c_int, c_f64p, c_f64p]
         L.otransition_fd.argtypes = [C.POINTER(MjpcxModel), C.POINTER(MjpcxTask), C.c_void_p, c_f64p, C.c_double, c_f64p,
                                      C.c_double, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]
         L.ocost_derivatives.argtypes = [C.POINTER(MjpcxTask), C.c_int, C.c_int, C.c_int] + [c_f64p] * 8
@@ -257,6 +259,12 @@ class Physics:
     def set_ctrl(self, ctrl):
         lib().odata_set_ctrl(self.d, as_f64p(_f(ctrl)))
 
+    def set_xfrc_applied(self, xfrc):
+        """mjData.xfrc_applied: nbody x 6, force then torque per body (it stays until set again)"""
+        x = _f(xfrc).reshape(-1)
+        assert x.size == 6 * self.m.nbody
+        C.memmove(lib().odata_xfrc_applied(self.d), x.ctypes.data, 8 * x.size)
+
     def forward(self):
         lib().o_forward(self.d)
 
@@ -365,6 +373,18 @@ def rollout_batch(pm, pt, state, time, mocap, N, H, P, interp, node_times, node_
                                as_f64p(nt), as_f64p(nvv), float(xfrc_std), float(xfrc_rate), int(seed), int(candidate_offset),
                                int(num_threads), C.byref(o))
     return out
+
+
+def rollout_noisy_xfrc(pm, pt, state, time, mocap, H, interp, node_times, node_values, xfrc_std, xfrc_rate, seed, candidate):
+    """tests only: one NoisyRollout of global candidate `candidate` -> (states [H, dim_state], the xfrc_applied every row saw [H, nbody, 6])"""
+    m = pm.struct
+    nt, nvv = _f(node_times), _f(node_values)
+    states, xfrc = np.zeros((H, m.nq + m.nv + m.na)), np.zeros((H, m.nbody, 6))
+    mc = None if mocap is None else as_f64p(_f(mocap))
+    rc = lib().orollout_noisy_xfrc(pm.ptr, pt.ptr, as_f64p(_f(state)), float(time), mc, int(H), nt.size, int(interp), as_f64p(nt),
+                                   as_f64p(nvv), float(xfrc_std), float(xfrc_rate), int(seed), int(candidate), as_f64p(states), as_f64p(xfrc))
+    assert rc == 0, rc
+    return states, xfrc
 
 
 def noise_candidates(pm, noise_spec: MjpcxNoiseSpec, P, nominal, candidates):

@@ -19,7 +19,7 @@ static int rollout_core(const mjpcx_model* m, const mjpcx_task* task, OData* d, 
                         double time, const double* mocap, const double* userdata, int horizon,
                         void (*policy)(void*, double*, const double*, double), void* user, mjpcx_traj_view* out);
 #define OXFRC_STREAM 0x58465243u /* "XFRC": Philox stream of the force noise */
-typedef struct { double std, rate; uint64_t seed; int candidate; } XfrcNoise;
+typedef struct { double std, rate; uint64_t seed; int candidate; double* record; /* tests: H x 6 nbody, or NULL */ } XfrcNoise;
 
 static int rollout_core_noisy(const mjpcx_model* m, const mjpcx_task* task, OData* d, const double* state,
                               double time, const double* mocap, const double* userdata, int horizon,
@@ -51,6 +51,7 @@ static int rollout_core_noisy(const mjpcx_model* m, const mjpcx_task* task, ODat
         x[j] = rate * x[j] + scale * z[0];
         x[j + 1] = rate * x[j + 1] + scale * z[1];
       }
+      if (noise->record) memcpy(noise->record + (size_t)t * 6 * m->nbody, x, sizeof(double) * 6 * m->nbody);
     }
     /* mj_step; the residual is evaluated inside its forward pass by the
      * mjSTAGE_ACC sensor callback (app.cc:110-126): it sees the pre-integration
@@ -80,7 +81,9 @@ static int rollout_core_noisy(const mjpcx_model* m, const mjpcx_task* task, ODat
     if (horizon > 1) memcpy(out->actions + (horizon - 1) * nu, out->actions + (horizon - 2) * nu, sizeof(double) * nu);
     else memset(out->actions, 0, sizeof(double) * nu);
   }
-  /* final mj_forward with the last control still in data->ctrl */
+  /* final mj_forward with the last control still in data->ctrl (and the last step's xfrc_applied: nothing is drawn for it) */
+  if (noise && noise->record)
+    memcpy(noise->record + (size_t)(horizon - 1) * 6 * m->nbody, odata_xfrc_applied(d), sizeof(double) * 6 * m->nbody);
   o_forward_task(d, task, r);
   if (out->residual) memcpy(out->residual + (horizon - 1) * nr, r, sizeof(double) * nr);
   for (int k = 0; k < ntr && out->trace; k++)
@@ -169,7 +172,7 @@ static void* batch_worker(void* arg) {
     if (o->costs) v.costs = o->costs + (size_t)i * H;
     if (o->trace) v.trace = o->trace + (size_t)i * H * 3 * ntr;
     if (b->xfrc_std > 0) {
-      XfrcNoise nz = {b->xfrc_std, b->xfrc_rate, b->seed, b->candidate_offset + i};
+      XfrcNoise nz = {b->xfrc_std, b->xfrc_rate, b->seed, b->candidate_offset + i, NULL};
       SplinePolicy pol = {&sp, m};
       rollout_core_noisy(m, b->task, d, b->state, b->time, b->mocap, b->userdata, b->H, spline_policy, &pol, &v, &nz);
     } else {
@@ -203,4 +206,25 @@ int orollout_batch_noisy(const mjpcx_model* m, const mjpcx_task* task, const dou
   for (int t = 0; t < num_threads; t++) pthread_join(th[t], NULL);
   free(th);
   return 0;
+}
+
+/* tests only: one NoisyRollout of global candidate `candidate` that also hands back the xfrc_applied every row saw,
+ * xfrc_out H x 6 nbody (oracle.h) */
+int orollout_noisy_xfrc(const mjpcx_model* m, const mjpcx_task* task, const double* state, double time, const double* mocap,
+                        int H, int P, int interp, const double* node_times, const double* node_values, double xfrc_std,
+                        double xfrc_rate, uint64_t seed, int candidate, double* states_out, double* xfrc_out) {
+  OData* d = odata_new(m);
+  if (!d) return -1;
+  OSpline sp;
+  ospline_init(&sp, m->nu, interp);
+  for (int p = 0; p < P; p++) ospline_add_node(&sp, node_times[p], node_values + (size_t)p * m->nu);
+  mjpcx_traj_view v;
+  memset(&v, 0, sizeof v);
+  v.states = states_out;
+  XfrcNoise nz = {xfrc_std, xfrc_rate, seed, candidate, xfrc_out};
+  SplinePolicy pol = {&sp, m};
+  rollout_core_noisy(m, task, d, state, time, mocap, NULL, H, spline_policy, &pol, &v, &nz);
+  ospline_free(&sp);
+  odata_free(d);
+  return v.failure;
 }

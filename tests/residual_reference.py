@@ -1,7 +1,7 @@
 """An independent reference for the task residuals (test infrastructure, CPU only; not a conftest).
 
 Nothing here shares arithmetic with the kernels, the oracle or the emulators:
-- forward kinematics composes homogeneous transforms [R p; 0 1] down the body tree from the model's arrays (free and hinge joints only);
+- forward kinematics composes homogeneous transforms [R p; 0 1] down the body tree from the model's arrays (free, hinge and slide joints);
 - velocities are central differences of POSITIONS along q(eps) = q (+) eps v, eps = 1e-15 in 50-digit arithmetic (no spatial algebra, no cvel);
 - the ground under a point is the closed-form height of each group-0 geom on the vertical line through it: the plane's equation, the
   sphere's z_c +- sqrt(r^2 - dx^2 - dy^2), and for a box the six face planes cut by the line, kept where the cut lies on the face;
@@ -108,8 +108,8 @@ class Kinematics:
         self.jnt_type = [int(v) for v in a["jnt_type"]]
         self.qadr, self.dadr = [int(v) for v in a["jnt_qposadr"]], [int(v) for v in a["jnt_dofadr"]]
         for t in self.jnt_type:
-            if t not in (JOINT_TYPES["free"], JOINT_TYPES["hinge"]):
-                raise NotImplementedError(f"joint type {t}: the reference kinematics knows free and hinge joints")
+            if t not in (JOINT_TYPES["free"], JOINT_TYPES["hinge"], JOINT_TYPES["slide"]):
+                raise NotImplementedError(f"joint type {t}: the reference kinematics knows free, hinge and slide joints")
         self.body_T = [pose(B, B.vec(a["body_pos"][b]), B.vec(a["body_quat"][b])) for b in range(self.nbody)]
         self.body_q = [q_unit(B, B.vec(a["body_quat"][b])) for b in range(self.nbody)]
         self.ipos = [B.vec(v) for v in a["body_ipos"]]
@@ -120,33 +120,44 @@ class Kinematics:
     def name(self, kind, name):
         return self.m.names[kind].index(name)
 
-    def forward(self, qpos, mocap=None):
+    def forward(self, qpos, mocap=None, upto=None):
+        """the pose of every body (of bodies 0 .. upto - 1: enough where only a leading part of the tree is asked for)"""
         B = self.B
         q = B.vec(qpos)
         ident = transform(q_matrix(B.vec([1, 0, 0, 0])), B.vec([0, 0, 0]))
         T, Q = [ident], [B.vec([1, 0, 0, 0])]
-        for b in range(1, self.nbody):
-            if self.mocapid[b] >= 0 and mocap is not None:
-                mc = B.vec(mocap[7 * self.mocapid[b]:7 * self.mocapid[b] + 7])
-                Tb, Qb = pose(B, mc[:3], mc[3:]), q_unit(B, mc[3:])
-            else:
-                Tb, Qb = t_mul(T[self.parent[b]], self.body_T[b]), q_mul(Q[self.parent[b]], self.body_q[b])
-            for j in range(self.jntadr[b], self.jntadr[b] + self.jntnum[b]):
-                adr = self.qadr[j]
-                if self.jnt_type[j] == JOINT_TYPES["free"]:
-                    Qb = q_unit(B, q[adr + 3:adr + 7])
-                    Tb = transform(q_matrix(Qb), q[adr:adr + 3])
-                else:
-                    ax = self.jnt_axis[j]
-                    n = B.sqrt(sum(v * v for v in ax))
-                    qj = q_rotvec(B, [v / n * (q[adr] - self.qpos0[adr]) for v in ax])
-                    zero, anchor = B.vec([0, 0, 0]), self.jnt_pos[j]
-                    Tb = t_mul(t_mul(t_mul(Tb, transform(q_matrix(B.vec([1, 0, 0, 0])), anchor)), transform(q_matrix(qj), zero)),
-                               transform(q_matrix(B.vec([1, 0, 0, 0])), [-v for v in anchor]))
-                    Qb = q_mul(Qb, qj)
+        for b in range(1, self.nbody if upto is None else upto):
+            Tb, Qb = self.body_pose(b, T[self.parent[b]], Q[self.parent[b]], q, mocap)
             T.append(Tb)
             Q.append(Qb)
         return Pose(self, T, Q)
+
+    def body_pose(self, b, T_parent, Q_parent, q, mocap=None):
+        """(transform, quaternion) of body b given its parent's, q a backend vector"""
+        B = self.B
+        if self.mocapid[b] >= 0 and mocap is not None:
+            mc = B.vec(mocap[7 * self.mocapid[b]:7 * self.mocapid[b] + 7])
+            Tb, Qb = pose(B, mc[:3], mc[3:]), q_unit(B, mc[3:])
+        else:
+            Tb, Qb = t_mul(T_parent, self.body_T[b]), q_mul(Q_parent, self.body_q[b])
+        for j in range(self.jntadr[b], self.jntadr[b] + self.jntnum[b]):
+            adr = self.qadr[j]
+            if self.jnt_type[j] == JOINT_TYPES["free"]:
+                Qb = q_unit(B, q[adr + 3:adr + 7])
+                Tb = transform(q_matrix(Qb), q[adr:adr + 3])
+            elif self.jnt_type[j] == JOINT_TYPES["slide"]:
+                ax = self.jnt_axis[j]
+                n = B.sqrt(sum(v * v for v in ax))
+                Tb = t_mul(Tb, transform(q_matrix(B.vec([1, 0, 0, 0])), [v / n * (q[adr] - self.qpos0[adr]) for v in ax]))
+            else:
+                ax = self.jnt_axis[j]
+                n = B.sqrt(sum(v * v for v in ax))
+                qj = q_rotvec(B, [v / n * (q[adr] - self.qpos0[adr]) for v in ax])
+                zero, anchor = B.vec([0, 0, 0]), self.jnt_pos[j]
+                Tb = t_mul(t_mul(t_mul(Tb, transform(q_matrix(B.vec([1, 0, 0, 0])), anchor)), transform(q_matrix(qj), zero)),
+                           transform(q_matrix(B.vec([1, 0, 0, 0])), [-v for v in anchor]))
+                Qb = q_mul(Qb, qj)
+        return Tb, Qb
 
     def displaced(self, qpos, qvel, eps):
         """q (+) eps v: a free joint moves by eps v_lin in the world and turns by eps omega in its own frame, a hinge by eps v"""

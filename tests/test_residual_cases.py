@@ -62,8 +62,22 @@ def test_reference_kinematics_self_checks():
     first_column = [1 - 2 * (y * y + z * z), 2 * (x * y + w * z), 2 * (x * z - w * y)]
     head = kin.forward(q, None).site_xpos(kin.name("site", "head"))
     assert max(abs(h - (mpf(float(p)) + mpf(0.3) * c)) for h, p, c in zip(head, q[:3], first_column)) < 1e-17    # (0.3 as the double the model holds)
-    with pytest.raises(NotImplementedError):
-        rr.Kinematics(rc.task_of("Cartpole").model)      # a slide joint
+    cart = rc.task_of("Cartpole").model                      # a slide joint: the cart sits at body_pos + q axis, its frame unturned
+    ck, ca = rr.Kinematics(cart), cart.arrays
+    j = int(np.flatnonzero(np.asarray(ca["jnt_type"]) == rr.JOINT_TYPES["slide"])[0])
+    b, q = int(ca["jnt_bodyid"][j]), np.array([0.37, -0.8])
+    assert ck.parent[b] == 0 and np.array_equal(ca["body_quat"][b], [1, 0, 0, 0])
+    Pc = ck.forward(q, None)
+    want = [mpf(float(p)) + mpf(float(q[ck.qadr[j]])) * mpf(float(x)) for p, x in zip(ca["body_pos"][b], ca["jnt_axis"][j])]
+    assert max(abs(x - w) for x, w in zip(Pc.xpos(b), want)) < 1e-17
+    assert Pc.xmat(b) == [[1, 0, 0], [0, 1, 0], [0, 0, 1]]
+    saved = ca["jnt_type"]
+    ca["jnt_type"] = np.where(np.arange(len(saved)) == j, rr.JOINT_TYPES["ball"], saved)
+    try:
+        with pytest.raises(NotImplementedError):
+            rr.Kinematics(cart)                              # a ball joint
+    finally:
+        ca["jnt_type"] = saved
 
 
 def test_reference_com_velocity_is_the_mass_weighted_body_velocity():
