@@ -923,15 +923,16 @@ QLS_ATTR double line_search(const QuadModel& m_in, int leg, const QRows R, CS cs
     const auto* vp = QREBIND_PRIVATE(double, &Vs_in[0][0]);
     QUNROLL for (int d = 0; d < 4; d++) QUNROLL for (int k = 0; k < 6; k++) Vs[d][k] = vp[6 * d + k];
   }
-  QDiag dg;
-  diag_prepare(L, R, hl, dg);
-  const bool any_limit = qw_any(R.lm_side[0] != 0 || R.lm_side[1] != 0 || R.lm_side[2] != 0);
   QLine ql[kQLineSlots];
   QLine qx[BEYOND ? kQMaxCon - kQLineSlots : 1];
   QPROF(pf, 40);
   const bool beyond = BEYOND && qd_or(ncon > kQLineSlots ? 1 : 0) != 0;
   rows_line_prepare<MULTI, BEYOND>(m, cs, ncon, Vs, pmask, beyond, ql, qx);
   const int nslot_wave = qw_max(ncon < kQLineSlots ? ncon : kQLineSlots);
+  // (the diagonal rows AFTER the contacts' coefficients: their 30 numbers are then not alive while the records are walked -- round 12)
+  QDiag dg;
+  diag_prepare(L, R, hl, dg);
+  const bool any_limit = qw_any(R.lm_side[0] != 0 || R.lm_side[1] != 0 || R.lm_side[2] != 0);
   QPROF(pf, 41);
   double lo = 0, hi = -1, alpha = 0, d1, d2;
   rows_line<BEYOND>(dg, any_limit, ncon, 0.0, beyond, nslot_wave, ql, qx, d1, d2);
@@ -1167,14 +1168,17 @@ QD int newton_body(const QuadModel& m, const QuadLeg& L, const QKin& kin, const 
       }
       rows_X(m, cs, nstat, X, nshallow);
       Arrow H;
-      load_arrow(ms, H);
-
+      // M from the store in two parts (round 12): the leg block first, which the diagonal rows' branches add to; the couplings and the
+      // trunk block only behind those branches, so that their 39 numbers are not carried through them
+      QUNROLL for (int i = 0; i < 6; i++) H.l[i] = qms_l(ms, i);
       QUNROLL for (int i = 0; i < 6; i++) H.l[i] += Hl_rel[i];
       QUNROLL for (int r = 0; r < 3; r++) QUNROLL for (int c = 0; c < 3; c++) H.ab[r][c] = Hab_rel[r][c];
       QUNROLL for (int j = 0; j < 3; j++) {
         if (L.floss[j] > 0) { const double x = R.fl_jar[j]; if (x > -L.floss_R[j] * L.floss[j] && x < L.floss_R[j] * L.floss[j]) H.l[tri(j, j)] += L.floss_D[j]; }
         if (R.lm_side[j] != 0 && R.lm_jar[j] < 0) H.l[tri(j, j)] += R.lm_D[j];
       }
+      QUNROLL for (int j = 0; j < 3; j++) QUNROLL for (int k = 0; k < 6; k++) H.b[j][k] = qms_b(ms, j, k);
+      QUNROLL for (int i = 0; i < 21; i++) H.t[i] = qms_t(ms, i);
       hessian_common(m, kin, cs, nstat, X, nshallow, H);
       QPROF(pf, 9);
       bool pd;
@@ -1197,6 +1201,9 @@ QD int newton_body(const QuadModel& m, const QuadLeg& L, const QKin& kin, const 
       const double alpha = qw_any(ncon > kQLineSlots) ? line_search_beyond<GENERAL>(m, leg, R, cs, ncon, hl[0], hl[1], hl[2], Vs, pmask, q1, q2, gtol, pf)
                                                       : line_search<GENERAL, false>(m, leg, R, cs, ncon, hl[0], hl[1], hl[2], Vs, pmask, q1, q2, gtol, pf);
       QPROF(pf, 11);
+      // the rows' pass first, the Gauss term after it (round 12): the pass reads neither the new point nor M (qacc - qacc_smooth), so
+      // the difference, the product with M and its dot are not alive across the contact loop
+      const double rowcost = rows_eval<GENERAL>(m, L, kin, R, cs, ncon, kEvalStep, hl, Vs, alpha, fc_l, fc_t, pmask);
       QUNROLL for (int j = 0; j < 3; j++) al[j] += alpha * hl[j];
       QUNROLL for (int k = 0; k < 6; k++) at[k] += alpha * ht[k];
       // the Gauss term at the new point, as the oracle evaluates it: from M (qacc - qacc_smooth) recomputed
@@ -1205,13 +1212,7 @@ QD int newton_body(const QuadModel& m, const QuadLeg& L, const QKin& kin, const 
       QUNROLL for (int k = 0; k < 6; k++) dt[k] = at[k] - st[k];
       arrow_mul_s(ms, dl, dt, Mal, Mat);
       const double gauss = 0.5 * arrow_dot(dl, dt, Mal, Mat);
-#ifdef QEXP_VE
-      double Ve[4][6];  // (the chain velocities again)
-      chain_velocity(kin, hl, ht, Ve);
-      const double newcost = gauss + rows_eval<GENERAL>(m, L, kin, R, cs, ncon, kEvalStep, hl, Ve, alpha, fc_l, fc_t, pmask);
-#else
-      const double newcost = gauss + rows_eval<GENERAL>(m, L, kin, R, cs, ncon, kEvalStep, hl, Vs, alpha, fc_l, fc_t, pmask);
-#endif
+      const double newcost = gauss + rowcost;
       improvement = cost - newcost;
       cost = newcost;
     }
