@@ -459,6 +459,34 @@ int mjpcx_ce_update_batched(mjpcx_ctx* ctx, int num_envs, int n_elite, int skip_
 int mjpcx_best_batched(mjpcx_ctx* ctx, int num_envs, int ref_candidate, int32_t* index, double* best_return,
                        double* ref_return, double* spline_values);
 
+/* The MPPI (model predictive path integral) update, segmented: where mjpcx_best_batched takes the argmin and mjpcx_ce_update_batched
+ * the mean of the n_elite best, this takes the softmin -- every candidate's spline weighted by exp(-(R - R_min) / temperature). One
+ * launch sequence (two kernels) and one sync, over the n_per_env stored returns R[i] and spline parameters p[i][j] (j < P*nu) of every
+ * environment of the last batched rollout (mjpcx_rollout_noise_batched, _splines_batched or _noise_ensemble). The failure words are
+ * not consulted, as in mjpcx_best: a failed rollout's 1e6 loses by itself. Per environment e, with lambda = temperature[e]:
+ *   index, best_return: the argmin in mjpcx_topk's order (ascending, ties to the lower index, NaN last) as a LOCAL index and its
+ *     return beta -- exactly what mjpcx_best_batched gives. valid = 1 iff beta is a number below +inf.
+ *   w[i] = 0 if R[i] is NaN; 1 if R[i] == beta (ties at the minimum, +-0, beta = -inf); otherwise exp(-((R[i] - beta) / lambda)): one
+ *     fp64 subtraction, one fp64 division by lambda, the negation and the device library's double-precision exp. valid == 0: every
+ *     w[i] = 0.
+ *   eta = sum w[i], Q = sum w[i]^2, S[j] = sum w[i] p[i][j]: fp64 (the node cast to double first in a 32-bit context), each over
+ *     the candidates in index order in the shape of mjpcx_elite_moments' sums -- 256 strided partial sums from zero, then a halving
+ *     tree; products and additions round separately (no fma); no atomics.
+ *   weight_sum = eta (>= 1 when valid: the winner weighs 1), effective_samples = eta * eta / Q, mean (E x P*nu) = S[j] / eta.
+ *     valid == 0: weight_sum = effective_samples = 0 and mean is the spline of ref_candidate (NaN when ref_candidate == -1).
+ *   ref_return = R[ref_candidate] (-1: skipped, NaN).
+ *   weights (E x n_per_env, may be NULL): every w[i].
+ * Any output but index may be NULL. Deterministic: two calls on the same rollout give the same bits, and environment e's outputs do
+ * not depend on num_envs or on the other environments' data. With the timer on (mjpcx_timing_reset) the call counts as one launch
+ * whose first kernel is the weights kernel. Validated before any device call: MJPCX_EINVAL when the last rollout was not a batched one
+ * of num_envs environments, when a temperature is not finite or is <= 0 (the message names the environment), or when ref_candidate
+ * is outside -1..n_per_env-1; MJPCX_ESTATE when the last rollout was pruned (stored partial returns are no returns: the rule of
+ * mjpcx_ce_update_batched); MJPCX_EUNSUPPORTED on a context sharded with mjpcx_comm_init. */
+int mjpcx_mppi_update_batched(mjpcx_ctx* ctx, int num_envs, const double* temperature /* E */, int ref_candidate,
+                              int32_t* index, double* best_return, double* ref_return, double* weight_sum,
+                              double* effective_samples, int32_t* valid, double* mean /* E x P*nu */,
+                              double* weights /* E x n or NULL */);
+
 /* An ensemble: ONE set of n candidates rolled out under M hypotheses about one robot, in the batched launch of M environments.
  * Hypothesis h is environment h of the preceding mjpcx_set_states(M, ...): its state, its task row if mjpcx_set_task_params_batched
  * gave one, its residual state, and its model if mjpcx_set_models_batched(M, ...) gave one. The hypotheses share node_times (P),

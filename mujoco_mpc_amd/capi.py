@@ -38,6 +38,7 @@ EXPORTS = [
     "mjpcx_set_pruning_batched", "mjpcx_prune_stats_batched",
     "mjpcx_set_prune_rank", "mjpcx_rank_bound_batched",
     "mjpcx_rollout_noise_ensemble", "mjpcx_ensemble_best",
+    "mjpcx_mppi_update_batched",
 ]
 
 MAX_HYPOTHESES = 32                           # MJPCX_MAX_HYPOTHESES of mjpcx_ensemble_best
@@ -92,6 +93,7 @@ def lib():
         L.mjpcx_rollout_sample_gradient_batched.argtypes = [vp] + [C.c_int] * 6 + [c_f64p, c_f64p, C.c_double, C.c_uint64, C.c_int, c_f64p, c_f64p]
         L.mjpcx_sample_gradient_update_batched.argtypes = ([vp] + [C.c_int] * 3 + [C.c_double] * 4 + [c_i32p, c_i32p] + [c_f64p] * 5)
         L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
+        L.mjpcx_mppi_update_batched.argtypes = [vp, C.c_int, c_f64p, C.c_int, c_i32p] + [c_f64p] * 4 + [c_i32p, c_f64p, c_f64p]
         L.mjpcx_rollout_noise_ensemble.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_ensemble_best.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_i32p] + [C.POINTER(C.c_double)] * 2 + [c_f64p] * 3
         L.mjpcx_rollout_noise_batched_ce.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
@@ -465,6 +467,27 @@ class Context:
         self._chk(lib().mjpcx_best_batched(self.handle, E, int(ref_candidate), as_i32p(idx), as_f64p(br), as_f64p(rr),
                                            as_f64p(sp) if with_spline else None))
         return idx, br, rr, sp
+
+    def mppi_update_batched(self, num_envs, temperature, ref_candidate=-1, want_weights=False):
+        """the MPPI update of every environment in one launch sequence / one sync (mjpcx_mppi_update_batched): dict of index (E: the
+        argmin, local), best_return, ref_return (NaN without a ref_candidate), weight_sum, effective_samples (E), valid (E: the best
+        return is a number below +inf), mean (E x P x nu: the splines weighted by exp(-(R - best) / temperature[e]); an invalid
+        environment's is ref_candidate's spline) and, want_weights, weights (E x n; else None). temperature: E values, or one for all."""
+        E = int(num_envs)
+        Ea = max(E, 1)
+        temp = np.ascontiguousarray(temperature, dtype=np.float64).reshape(-1)
+        if temp.size == 1:
+            temp = np.full(Ea, temp[0])
+        if temp.size != Ea:
+            raise ValueError(f"mppi_update_batched: {temp.size} temperatures for {E} environments")
+        out = dict(index=np.zeros(Ea, np.int32), best_return=np.zeros(Ea), ref_return=np.zeros(Ea), weight_sum=np.zeros(Ea),
+                   effective_samples=np.zeros(Ea), valid=np.zeros(Ea, np.int32), mean=np.zeros((Ea, self.P, self.nu)),
+                   weights=np.zeros((Ea, max(self.N // Ea, 1))) if want_weights else None)
+        self._chk(lib().mjpcx_mppi_update_batched(self.handle, E, as_f64p(temp), int(ref_candidate), as_i32p(out["index"]),
+                                                  as_f64p(out["best_return"]), as_f64p(out["ref_return"]), as_f64p(out["weight_sum"]),
+                                                  as_f64p(out["effective_samples"]), as_i32p(out["valid"]), as_f64p(out["mean"]),
+                                                  as_f64p(out["weights"]) if want_weights else None))
+        return out
 
     def rollout_noise_ensemble(self, n, horizon, interp, node_times, nominal, noise_spec, num_hypotheses):
         """ONE set of n candidates under num_hypotheses hypotheses (the environments of the preceding set_states, with their task rows and

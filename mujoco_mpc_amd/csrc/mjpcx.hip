@@ -27,6 +27,7 @@
 #include "rank_bound.h"
 #include "wave_argmin.h"
 #include "ensemble_best.h"
+#include "mppi_update.h"
 #include "limb_launch.h"
 #include "wave32_launch.h"
 #include <type_traits>
@@ -828,6 +829,7 @@ struct mjpcx_ctx {
   DevBuf d_grad;       // workspace of mjpcx_gradient_step_batched / mjpcx_ilqg_step_batched: inputs, every intermediate, the result block
   PinnedBlock h_grad;  // its pinned [inputs | result block] (those calls end in a sync)
   DevBuf d_states, d_actions, d_times, d_residual, d_costs, d_trace, d_ret, d_fail, d_sort, d_stage;
+  DevBuf d_mppi;  // mjpcx_mppi_update_batched: every environment's [weight sum | weights] between its two kernels (mppi_update.h)
   bool traj_candidate_major = false;  // layout of the last rollout's Trajectory buffers (true: wavefront-per-candidate kernels)
   int nsite_model = 0;
   int N = 0, H = 0, P = 0;  // shape of the last rollout
@@ -2241,7 +2243,7 @@ void mjpcx_destroy(mjpcx_ctx* c) {
   c->wh.release();
   DevBuf* bufs[] = {&c->d_nodes, &c->d_in_nodes, &c->d_grad, &c->d_ilqg, &c->d_ilqg_out, &c->d_work, &c->d_ovf, &c->d_qmodel, &c->d_qtab, &c->d_qstats, &c->d_qstamps, &c->d_qwave, &c->d_qovf, &c->d_qclass, &c->d_park_rec, &c->d_resume, &c->d_resume_groups, &c->d_limb, &c->d_comm_send, &c->d_comm_recv,
                     &c->d_states, &c->d_actions, &c->d_times, &c->d_residual, &c->d_costs, &c->d_trace, &c->d_ret,
-                    &c->d_fail, &c->d_sort, &c->d_stage};
+                    &c->d_fail, &c->d_sort, &c->d_stage, &c->d_mppi};
   for (DevBuf* b : bufs) b->release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -2655,6 +2657,60 @@ int mjpcx_best_batched(mjpcx_ctx* c, int E, int ref_candidate, int32_t* index, d
     if (ref_return) ref_return[e] = r->ref_return;
     if (spline_values) std::memcpy(spline_values + (size_t)e * np, r->spline, (size_t)np * 8);
   }
+  return MJPCX_OK;
+}
+
+int mjpcx_mppi_update_batched(mjpcx_ctx* c, int E, const double* temperature, int ref_candidate, int32_t* index, double* best_return, double* ref_return,
+                              double* weight_sum, double* effective_samples, int32_t* valid, double* mean, double* weights) {
+  const std::string who = "mjpcx_mppi_update_batched: ";
+  if (!c || !index || !temperature) return fail(c, MJPCX_EINVAL, who + "null argument");
+  if (c->comm_world > 1) return fail(c, MJPCX_EUNSUPPORTED, who + "not implemented on a context sharded with mjpcx_comm_init");
+  if (!c->have_rollout) return fail(c, MJPCX_ESTATE, "no rollout has been run");
+  if (E < 1 || c->env_n < 1 || (long long)E * c->env_n != c->N)
+    return fail(c, MJPCX_EINVAL, who + "the last rollout was not a batched one of " + std::to_string(E) + " environments");
+  const int n = c->env_n;
+  for (int e = 0; e < E; e++)
+    if (!std::isfinite(temperature[e]) || !(temperature[e] > 0))
+      return fail(c, MJPCX_EINVAL, who + "the temperature of environment " + std::to_string(e) + " is " + std::to_string(temperature[e]) + "; it must be finite and > 0");
+  if (ref_candidate < -1 || ref_candidate >= n)
+    return fail(c, MJPCX_EINVAL, who + "ref_candidate = " + std::to_string(ref_candidate) + " outside -1.." + std::to_string(n - 1));
+  if (c->last_pruned) return fail(c, MJPCX_ESTATE, who + kPrunedRanking);  // (stored partial returns are no returns: the rule of mjpcx_ce_update_batched)
+  HIPCHK(c, hipSetDevice(c->device));
+  const int np = c->P * c->nu;
+  // the mapped block: E records, the E temperatures (the host writes them, mppi_weights_kernel reads them), then the E x n weights if asked for
+  const size_t rec = kMppiHeader + (size_t)np * 8, off_temp = rec * E, off_w = off_temp + (size_t)E * 8;
+  static_assert(offsetof(MppiRecord, mean) == kMppiHeader, "the record of mppi_weights_kernel");
+  HIPCHK(c, c->result.reserve(off_w + (weights ? (size_t)E * n * 8 : 0)));
+  HIPCHK(c, c->d_mppi.reserve((size_t)E * (n + 1) * 8));
+  std::memcpy((char*)c->result.p + off_temp, temperature, (size_t)E * 8);
+  // (with the timer on this call is one of its launches: its first kernel, the weights, is what mjpcx_timing_read_main singles out)
+  hipEvent_t e1 = nullptr;
+  int rc = begin_rollout_timing(c, &e1);
+  if (rc != MJPCX_OK) return rc;
+  hipLaunchKernelGGL(mppi_weights_kernel, dim3(E), dim3(256), 0, c->stream, (const double*)c->d_ret.p, (const double*)((char*)c->result.dev + off_temp), n,
+                     ref_candidate, (double*)c->d_mppi.p, (unsigned char*)c->result.dev, (unsigned)rec,
+                     weights ? (double*)((char*)c->result.dev + off_w) : (double*)nullptr);
+  HIPCHK(c, hipGetLastError());
+  if (c->timing && c->cur_main) { HIPCHK(c, hipEventRecord(c->cur_main, c->stream)); c->cur_main = nullptr; }
+  by_precision(c, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((mppi_mean_kernel<T>), dim3(np, E), dim3(256), 0, c->stream, (const T*)c->d_nodes.p, (const double*)c->d_mppi.p, c->N, n, ref_candidate,
+                       (unsigned char*)c->result.dev, (unsigned)rec);
+  });
+  HIPCHK(c, hipGetLastError());
+  if (c->timing) HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int e = 0; e < E; e++) {
+    const MppiRecord* r = (const MppiRecord*)((const char*)c->result.p + rec * e);
+    index[e] = r->best_index;
+    if (best_return) best_return[e] = r->best_return;
+    if (ref_return) ref_return[e] = r->ref_return;
+    if (weight_sum) weight_sum[e] = r->weight_sum;
+    if (effective_samples) effective_samples[e] = r->effective_samples;
+    if (valid) valid[e] = r->valid;
+    if (mean) std::memcpy(mean + (size_t)e * np, r->mean, (size_t)np * 8);
+  }
+  if (weights) std::memcpy(weights, (const char*)c->result.p + off_w, (size_t)E * n * 8);
   return MJPCX_OK;
 }
 

@@ -1329,6 +1329,112 @@ class GpuSampleGradientPlanner:
         return self.fleet.num_parameters()
 
 
+class GpuBatchMPPIPlanner(GpuBatchSamplingPlanner):
+    """MPPI (model predictive path integral control) for `num_envs` environments on ONE context: Predictive Sampling's plan launch,
+    unchanged -- the same noise, seeds (seed + e) and candidates, local candidate 0 the un-noised nominal -- followed by the softmin in
+    place of the argmin (`mppi_update_batched`, one sync): member e's new policy is the mean of ALL its candidates' splines, the
+    nominal's among them, weighted by exp(-(R - R_min) / temperature[e]). As the temperature goes to 0 this is Predictive Sampling, as
+    it grows the plain mean of the candidates.
+
+    `temperature`: a scalar or one value per environment, on the scale of the task's returns; settable between plan steps. None: read
+    from the model's custom numeric `mppi_temperature` in `initialize` (ValueError when the model has none: there is no default that
+    fits every task). Every return is needed, so there is no `pruning` here. A member whose best return is NaN or +inf (`valid` 0)
+    keeps its policy. `best_trajectory(env)` is the rollout of the member's LOWEST-RETURN candidate (`winner`), not of the averaged
+    policy, which was never rolled out; `nominal_trajectory` rolls the averaged policies out. Per member after a plan: `best_return`,
+    `nominal_return`, `improvement` (as Predictive Sampling's), `effective_samples` ((sum w)^2 / sum w^2), `weight_sum`, `valid`."""
+
+    def __init__(self, num_envs, device=0, precision=64, seed=0, temperature=None, backend_factory=None):
+        super().__init__(num_envs, device, precision, seed, backend_factory)
+        del self.pruning
+        self._temperature = None
+        self._temperature_given = temperature is not None
+        if temperature is not None:
+            self.temperature = temperature
+
+    @property
+    def temperature(self):
+        """the E temperatures (None before `initialize` when none was given)"""
+        return self._temperature
+
+    @temperature.setter
+    def temperature(self, value):
+        t = np.asarray(value, dtype=np.float64).reshape(-1)
+        if t.size == 1:
+            t = np.full(self.num_envs, t[0])
+        if t.size != self.num_envs:
+            raise ValueError(f"{t.size} temperatures for {self.num_envs} environments")
+        if not (np.all(np.isfinite(t)) and np.all(t > 0)):
+            raise ValueError(f"temperature {t.tolist()}: every value must be finite and > 0")
+        self._temperature, self._temperature_given = t.copy(), True
+
+    def initialize(self, model, task: Task):
+        super().initialize(model, task)
+        if not self._temperature_given:
+            if "mppi_temperature" not in model.numeric:
+                raise ValueError(f"{type(self).__name__}: no temperature given and the model has no custom numeric mppi_temperature "
+                                 "(its right value is on the scale of the task's returns)")
+            self.temperature = model.get_number("mppi_temperature")
+            self._temperature_given = False     # (the model's: read again by the next initialize)
+
+    def optimize_policy(self, horizon, pool=None):
+        t0 = self._launch(horizon)
+        out = self.ctx.mppi_update_batched(self.num_envs, self._temperature, 0)
+        # (a member that is not valid: its resampled nominal, whatever the context made of candidate 0's spline)
+        values = [out["mean"][e] if out["valid"][e] else p.policy.plan.values() for e, p in enumerate(self.envs)]
+        self._finish(t0, [([out["index"][e]], [out["best_return"][e]], 0, values[e]) for e in range(self.num_envs)])
+        for e, p in enumerate(self.envs):
+            p.best_return, p.nominal_return = float(out["best_return"][e]), float(out["ref_return"][e])
+            p.improvement = max(p.nominal_return - p.best_return, 0.0)
+            p.effective_samples, p.weight_sum = float(out["effective_samples"][e]), float(out["weight_sum"][e])
+            p.valid = int(out["valid"][e])
+
+
+class GpuMPPIPlanner:
+    """MPPI for one robot: GpuBatchMPPIPlanner with ONE environment -- the same code, so a fleet's member e IS this planner with seed
+    s + e. The candidate count must be a multiple of 64. `best_trajectory()` is the lowest-return candidate's rollout."""
+    winner, improvement, best_return, nominal_return = (_member_attr(k) for k in ("winner", "improvement", "best_return", "nominal_return"))
+    effective_samples, weight_sum, valid = (_member_attr(k) for k in ("effective_samples", "weight_sum", "valid"))
+    policy, previous_policy, noise_exploration = (_member_attr(k) for k in ("policy", "previous_policy", "noise_exploration"))
+    iteration, ctx, model, task, num_trajectory_ = (_fleet_attr(k) for k in ("iteration", "ctx", "model", "task", "num_trajectory_"))
+
+    def __init__(self, device=0, precision=64, seed=0, temperature=None, backend_factory=None):
+        self.fleet = GpuBatchMPPIPlanner(1, device, precision, seed, temperature, backend_factory)
+        self.seed = seed
+
+    @property
+    def temperature(self):
+        t = self.fleet.temperature
+        return None if t is None else float(t[0])
+
+    @temperature.setter
+    def temperature(self, value):
+        self.fleet.temperature = value
+
+    def initialize(self, model, task: Task):
+        self.fleet.initialize(model, task)
+
+    def allocate(self):
+        self.fleet.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.fleet.reset(horizon, initial_repeated_action)
+
+    def set_state(self, state: State):
+        self.fleet.set_states([state])
+
+    def optimize_policy(self, horizon, pool=None):
+        self.fleet.optimize_policy(horizon, pool)
+
+    def action_from_policy(self, action, state, time, use_previous=False):
+        return self.fleet.action_from_policy(0, action, state, time, use_previous)
+
+    def best_trajectory(self):
+        return self.fleet.best_trajectory(0)
+
+    def num_parameters(self):
+        return self.fleet.num_parameters()
+
+
 class GpuCrossEntropyPlanner(_ContextOwner):
     """mjpc::CrossEntropyPlanner (mjpc/planners/cross_entropy/planner.{h,cc}) with the candidate
     fan-out, the sort and the elite statistics on the GPU. Differences forced by SURVEY F4/F5 as for

@@ -51,6 +51,14 @@ step as above (set_states, rollout_noise_batched, best_batched); (b) "ensemble":
 default E: the mean). The same launch over E x n rollouts with the noise stream shared, and ensemble_best in place of best_batched: the
 expectation is equal times. Default shape 8 x 2048 on the A1, H = 100, fp64; default output profiles/batch_sweep_ensemble.jsonl.
 
+--planner mppi: the MPPI plan step against the unpruned Predictive Sampling plan step of the same fleet. Two variants alternating in one
+session on one context, from the same states and nominal, for --rounds rounds (default 2) of --steps timed steps each: (a) "sampling":
+set_states, rollout_noise_batched, best_batched; (b) "mppi": set_states, rollout_noise_batched, mppi_update_batched. The launch is the same;
+the update differs. Afterwards the update alone, --steps times under the context's timer: its two kernels' time (timing_read) and its first
+kernel's, the weights (timing_read_main). --temperature X (default: the spread of environment 0's returns in the first warm-up launch over
+10; the time does not depend on it). MPPI needs every return, so it cannot prune: the PRUNED sampling step (--planner sampling --prune) is
+faster than either side here. Default shapes 8 x 2048 and 1 x 16384 on the A1, H = 100, fp64; default output profiles/batch_sweep_mppi.jsonl.
+
 --mixed-params: every environment plans with task weights, norm parameters, residual parameters and risk of its own (sampling and
 cross_entropy: set_task_params_batched after set_states, and the plain set_task_params of the same row before every sequential plan
 step; gradient and ilqg: the fleet planner's set_tasks, and every sequential planner on its own task). The kernels do the same work
@@ -207,6 +215,75 @@ def sweep_ensemble(name, precision, H, shapes, steps, warmup, out, tail=None, mo
         out.flush()
         if models:
             ctx.set_models_batched(None)
+    ctx.close()
+
+
+MPPI_SHAPES = [("QuadrupedFlat", 64, 100, [(8, 2048), (1, 16384)])]
+
+
+def sweep_mppi(name, precision, H, shapes, steps, warmup, out, temperature=None, rounds=2):
+    task = load_task(name)
+    m = task.model
+    rng = np.random.default_rng(1)
+    ctx = capi.Context(task.packed_model(), task.packed(), 0, precision)
+    P = int(m.get_number("sampling_spline_points", 6))
+    interp = int(m.get_number("sampling_representation", capi.SPLINE_CUBIC))
+    std = float(m.get_number("sampling_exploration", 0.1))
+    dt = m.get_number("agent_timestep", m.timestep)
+    times1 = np.arange(P) * ((H - 1) * dt / max(P - 1, 1))
+    for E, n in shapes:
+        states, clocks, mocap = initial(task, name, E, rng)
+        times, nominal = np.stack([times1] * E), np.zeros((E, P, m.nu))
+        it = [0]
+        lam = [temperature]
+        last = {}
+
+        def launch():
+            ctx.set_states(states, clocks, mocap)
+            ctx.rollout_noise_batched(n, H, interp, times, nominal, capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_envs=E)
+
+        def sampling():
+            it[0] += 1
+            launch()
+            ctx.best_batched(E, 0)
+
+        def mppi():
+            launch()
+            if lam[0] is None:
+                r = ctx.returns()[0][:n]
+                r = r[np.isfinite(r) & (r < 1e6)]
+                lam[0] = max(float(r.max() - r.min()) / 10.0, 1e-12)
+            last.update(ctx.mppi_update_batched(E, lam[0], 0))
+
+        for _ in range(warmup):
+            sampling()
+            mppi()
+        per_round = []
+        for _ in range(rounds):
+            ta, tb = [], []
+            for _ in range(steps):   # alternating: both sides see the same clocks and the same neighbours on the machine
+                t0 = time.perf_counter(); sampling(); t1 = time.perf_counter(); mppi(); t2 = time.perf_counter()
+                ta.append((t1 - t0) * 1e3)
+                tb.append((t2 - t1) * 1e3)
+            per_round.append({"sampling_ms": stats(ta), "mppi_ms": stats(tb)})
+        # the update alone on the last launch: wall time, and its kernels' under the context's timer
+        tu = []
+        ctx.timing_reset()
+        for _ in range(steps):
+            t0 = time.perf_counter(); ctx.mppi_update_batched(E, lam[0], 0); tu.append((time.perf_counter() - t0) * 1e3)
+        first_ms, _ = ctx.timing_read_main()
+        both_ms, calls = ctx.timing_read()
+        med = lambda k: [r[k]["median"] for r in per_round]
+        rec = {"planner": "mppi", "task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps, "warmup": warmup,
+               "rounds": per_round, "temperature": lam[0], "kernel": ctx.kernel_name.split(" (")[0],
+               "effective_samples": [float(x) for x in last["effective_samples"]],
+               "ratio_mppi_over_sampling": [float(b / a) for a, b in zip(med("sampling_ms"), med("mppi_ms"))],
+               "sampling_spread_between_rounds_ms": float(max(med("sampling_ms")) - min(med("sampling_ms"))),
+               "update_call_ms": stats(tu), "update_kernels_ms": both_ms / max(calls, 1), "update_weights_kernel_ms": first_ms / max(calls, 1),
+               "update_mean_kernel_ms": (both_ms - first_ms) / max(calls, 1)}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+        out.flush()
     ctx.close()
 
 
@@ -717,11 +794,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "ilqs", "robust", "sample_gradient", "ensemble"], default="sampling")
+    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "ilqs", "robust", "sample_gradient", "ensemble", "mppi"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
     ap.add_argument("--mixed-params", action="store_true", help="every environment its own task weights, parameters and risk")
     ap.add_argument("--mixed-models", action="store_true", help="sampling, cross_entropy, ensemble: every environment its own model (payload, friction, actuator strength)")
     ap.add_argument("--tail", type=int, default=None, help="--planner ensemble: the score is the mean of the `tail` largest returns (default: all, the mean)")
+    ap.add_argument("--temperature", type=float, default=None, help="--planner mppi: the temperature (default: a tenth of the spread of the first launch's returns)")
+    ap.add_argument("--rounds", type=int, default=2, help="--planner mppi: rounds of --steps alternating timed steps")
     ap.add_argument("--robust", default="16x4", help="--planner robust: candidates x repetitions")
     ap.add_argument("--gradient-candidates", type=int, default=32, help="--planner sample_gradient: gradient candidates per environment")
     ap.add_argument("--prune", action="store_true", help="--planner sampling, cross_entropy: the batched side prunes and parks per environment (set_pruning_batched; "
@@ -731,19 +810,22 @@ def main():
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl", "ilqs": "batch_sweep_ilqs.jsonl", "robust": "batch_sweep_robust.jsonl",
-                                                       "sample_gradient": "batch_sweep_sample_gradient.jsonl", "ensemble": "batch_sweep_ensemble.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
+                                                       "sample_gradient": "batch_sweep_sample_gradient.jsonl", "ensemble": "batch_sweep_ensemble.jsonl", "mppi": "batch_sweep_mppi.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
     keep = None if a.shapes is None else {tuple(int(x) for x in sh.split("x")) for sh in a.shapes.split(",")}
     if a.steps < 10:
         raise SystemExit("batch_sweep.py: at least 10 timed steps")
     with open(a.out, "w") as out:
         for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES, "ilqs": ILQS_SHAPES, "robust": ROBUST_SHAPES,
-                                             "sample_gradient": SAMPLE_GRADIENT_SHAPES, "ensemble": ENSEMBLE_SHAPES}.get(a.planner, SHAPES):
+                                             "sample_gradient": SAMPLE_GRADIENT_SHAPES, "ensemble": ENSEMBLE_SHAPES, "mppi": MPPI_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
             if keep is not None and a.only == name and a.planner in ("sampling", "cross_entropy"):   # (--only with --shapes: also shapes outside the default list, e.g. 16x1024)
                 shapes += [sh for sh in sorted(keep) if sh not in shapes]
             if shapes and (a.only is None or a.only == name):
                 if a.planner == "ensemble":
                     sweep_ensemble(name, precision, H, shapes, a.steps, a.warmup, out, a.tail, a.mixed_models)
+                    continue
+                if a.planner == "mppi":
+                    sweep_mppi(name, precision, H, shapes, a.steps, a.warmup, out, a.temperature, a.rounds)
                     continue
                 if a.mixed_models and (a.planner not in ("sampling", "cross_entropy") or name == "Cartpole"):
                     if a.planner not in ("sampling", "cross_entropy"):
