@@ -1,7 +1,8 @@
 """An independent reference for the task residuals (test infrastructure, CPU only; not a conftest).
 
 Nothing here shares arithmetic with the kernels, the oracle or the emulators:
-- forward kinematics composes homogeneous transforms [R p; 0 1] down the body tree from the model's arrays (free, hinge and slide joints);
+- forward kinematics composes homogeneous transforms [R p; 0 1] down the body tree from the model's arrays (free, ball, hinge and slide
+  joints; the inertial frame is the body's times body_iquat);
 - velocities are central differences of POSITIONS along q(eps) = q (+) eps v, eps = 1e-15 in 50-digit arithmetic (no spatial algebra, no cvel);
 - the ground under a point is the closed-form height of each group-0 geom on the vertical line through it: the plane's equation, the
   sphere's z_c +- sqrt(r^2 - dx^2 - dy^2), and for a box the six face planes cut by the line, kept where the cut lies on the face;
@@ -76,7 +77,11 @@ def transform(R, p):
 
 
 def t_mul(A, Bm):
-    return [[sum(A[i][k] * Bm[k][j] for k in range(4)) for j in range(4)] for i in range(4)]
+    """the product of two transforms [R p; 0 1]: the last rows are 0 0 0 1, so their terms are left out (the same numbers, bit for bit)"""
+    out = [[A[i][0] * Bm[0][j] + A[i][1] * Bm[1][j] + A[i][2] * Bm[2][j] for j in range(4)] for i in range(3)]
+    for i in range(3):
+        out[i][3] = out[i][3] + A[i][3]
+    return out + [[0, 0, 0, 1]]
 
 
 def t_point(T, p):
@@ -108,14 +113,21 @@ class Kinematics:
         self.jnt_type = [int(v) for v in a["jnt_type"]]
         self.qadr, self.dadr = [int(v) for v in a["jnt_qposadr"]], [int(v) for v in a["jnt_dofadr"]]
         for t in self.jnt_type:
-            if t not in (JOINT_TYPES["free"], JOINT_TYPES["hinge"], JOINT_TYPES["slide"]):
-                raise NotImplementedError(f"joint type {t}: the reference kinematics knows free, hinge and slide joints")
+            if t not in JOINT_TYPES.values():
+                raise NotImplementedError(f"joint type {t}: the reference kinematics knows free, ball, hinge and slide joints")
         self.body_T = [pose(B, B.vec(a["body_pos"][b]), B.vec(a["body_quat"][b])) for b in range(self.nbody)]
         self.body_q = [q_unit(B, B.vec(a["body_quat"][b])) for b in range(self.nbody)]
         self.ipos = [B.vec(v) for v in a["body_ipos"]]
+        self.iquat = [q_unit(B, B.vec(v)) for v in a["body_iquat"]]
         self.mass = B.vec(a["body_mass"])
         self.jnt_pos, self.jnt_axis = [B.vec(v) for v in a["jnt_pos"]], [B.vec(v) for v in a["jnt_axis"]]
         self.qpos0 = B.vec(a["qpos0"])
+        # per joint, what no qpos changes: the unit axis and the transforms to the anchor and back
+        one = q_matrix(B.vec([1, 0, 0, 0]))
+        self.axis_unit = [[v / B.sqrt(sum(w * w for w in ax)) for v in ax] if any(ax) else ax for ax in self.jnt_axis]
+        self.to_anchor = [transform(one, p) for p in self.jnt_pos]
+        self.from_anchor = [transform(one, [-v for v in p]) for p in self.jnt_pos]
+        self.one = one
 
     def name(self, kind, name):
         return self.m.names[kind].index(name)
@@ -145,22 +157,21 @@ class Kinematics:
             if self.jnt_type[j] == JOINT_TYPES["free"]:
                 Qb = q_unit(B, q[adr + 3:adr + 7])
                 Tb = transform(q_matrix(Qb), q[adr:adr + 3])
+            elif self.jnt_type[j] == JOINT_TYPES["ball"]:
+                qj = q_unit(B, q[adr:adr + 4])               # the turn about the anchor, in the body's frame (qpos0's turn is in body_quat)
+                Tb = t_mul(t_mul(t_mul(Tb, self.to_anchor[j]), transform(q_matrix(qj), B.vec([0, 0, 0]))), self.from_anchor[j])
+                Qb = q_mul(Qb, qj)
             elif self.jnt_type[j] == JOINT_TYPES["slide"]:
-                ax = self.jnt_axis[j]
-                n = B.sqrt(sum(v * v for v in ax))
-                Tb = t_mul(Tb, transform(q_matrix(B.vec([1, 0, 0, 0])), [v / n * (q[adr] - self.qpos0[adr]) for v in ax]))
+                Tb = t_mul(Tb, transform(self.one, [v * (q[adr] - self.qpos0[adr]) for v in self.axis_unit[j]]))
             else:
-                ax = self.jnt_axis[j]
-                n = B.sqrt(sum(v * v for v in ax))
-                qj = q_rotvec(B, [v / n * (q[adr] - self.qpos0[adr]) for v in ax])
-                zero, anchor = B.vec([0, 0, 0]), self.jnt_pos[j]
-                Tb = t_mul(t_mul(t_mul(Tb, transform(q_matrix(B.vec([1, 0, 0, 0])), anchor)), transform(q_matrix(qj), zero)),
-                           transform(q_matrix(B.vec([1, 0, 0, 0])), [-v for v in anchor]))
+                qj = q_rotvec(B, [v * (q[adr] - self.qpos0[adr]) for v in self.axis_unit[j]])
+                Tb = t_mul(t_mul(t_mul(Tb, self.to_anchor[j]), transform(q_matrix(qj), B.vec([0, 0, 0]))), self.from_anchor[j])
                 Qb = q_mul(Qb, qj)
         return Tb, Qb
 
     def displaced(self, qpos, qvel, eps):
-        """q (+) eps v: a free joint moves by eps v_lin in the world and turns by eps omega in its own frame, a hinge by eps v"""
+        """q (+) eps v: a free joint moves by eps v_lin in the world and turns by eps omega in its own frame, a ball joint turns by eps omega
+        in its own frame, a hinge or a slide moves by eps v"""
         B = self.B
         q, v = B.vec(qpos), B.vec(qvel)
         for j, t in enumerate(self.jnt_type):
@@ -169,6 +180,8 @@ class Kinematics:
                 for k in range(3):
                     q[qa + k] = q[qa + k] + eps * v[da + k]
                 q[qa + 3:qa + 7] = q_mul(q_unit(B, q[qa + 3:qa + 7]), q_rotvec(B, [eps * v[da + 3 + k] for k in range(3)]))
+            elif t == JOINT_TYPES["ball"]:
+                q[qa:qa + 4] = q_mul(q_unit(B, q[qa:qa + 4]), q_rotvec(B, [eps * v[da + k] for k in range(3)]))
             else:
                 q[qa] = q[qa] + eps * v[da]
         return q
@@ -192,6 +205,11 @@ class Pose:
 
     def xipos(self, b):
         return t_point(self.T[b], self.kin.ipos[b])
+
+    def ximat(self, b):
+        """the inertial frame's rotation: the body's frame times body_iquat"""
+        R, Ri = t_rot(self.T[b]), q_matrix(self.kin.iquat[b])
+        return [[sum(R[i][k] * Ri[k][j] for k in range(3)) for j in range(3)] for i in range(3)]
 
     def site_xpos(self, s):
         a = self.kin.m.arrays

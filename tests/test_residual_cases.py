@@ -71,13 +71,40 @@ def test_reference_kinematics_self_checks():
     want = [mpf(float(p)) + mpf(float(q[ck.qadr[j]])) * mpf(float(x)) for p, x in zip(ca["body_pos"][b], ca["jnt_axis"][j])]
     assert max(abs(x - w) for x, w in zip(Pc.xpos(b), want)) < 1e-17
     assert Pc.xmat(b) == [[1, 0, 0], [0, 1, 0], [0, 0, 1]]
-    saved = ca["jnt_type"]
-    ca["jnt_type"] = np.where(np.arange(len(saved)) == j, rr.JOINT_TYPES["ball"], saved)
+    # a ball joint: the trunk's free joint read as a ball about an anchor off the body's origin. The body turns about the anchor by
+    # Rodrigues' formula for the angle t about the unit axis n, composed by hand: R = cos t I + (1 - cos t) n n^T + sin t [n]x, and
+    # its origin sits at body_pos + anchor - R anchor; body_iquat turns the inertial frame on top of that
+    trunk, jt = kin.name("body", "trunk"), int(np.flatnonzero(np.asarray(a["jnt_type"]) == rr.JOINT_TYPES["free"])[0])
+    saved = {k: a[k] for k in ("jnt_type", "jnt_pos", "body_iquat")}
+    anchor, iq = np.array([0.05, -0.02, 0.03]), np.array([0.8, 0.2, 0.4, -0.4])
+    a["jnt_type"] = np.where(np.arange(len(saved["jnt_type"])) == jt, rr.JOINT_TYPES["ball"], saved["jnt_type"])
+    a["jnt_pos"], a["body_iquat"] = np.array(saved["jnt_pos"], float), np.array(saved["body_iquat"], float)
+    a["jnt_pos"][jt], a["body_iquat"][trunk] = anchor, iq
     try:
-        with pytest.raises(NotImplementedError):
-            rr.Kinematics(cart)                              # a ball joint
+        bk = rr.Kinematics(kin.m)
+        t, n = mpf(0.9), [mpf(2) / 7, mpf(-3) / 7, mpf(6) / 7]
+        qb = np.array(a["qpos0"], float).tolist()
+        adr = bk.qadr[jt]
+        qb = rr.MP.vec(qb)
+        qb[adr:adr + 4] = [M.cos(t / 2)] + [M.sin(t / 2) * v for v in n]
+        cross = [[0, -n[2], n[1]], [n[2], 0, -n[0]], [-n[1], n[0], 0]]
+        R = [[M.cos(t) * (i == j_) + (1 - M.cos(t)) * n[i] * n[j_] + M.sin(t) * cross[i][j_] for j_ in range(3)] for i in range(3)]
+        Pb = bk.forward(qb, None)
+        am = rr.MP.vec(anchor)
+        want = [mpf(float(a["body_pos"][trunk][i])) + am[i] - sum(R[i][k] * am[k] for k in range(3)) for i in range(3)]
+        assert max(abs(x - w) for x, w in zip(Pb.xpos(trunk), want)) < 1e-40
+        assert max(abs(Pb.xmat(trunk)[i][k] - R[i][k]) for i in range(3) for k in range(3)) < 1e-40
+        Ri = rr.q_matrix(rr.q_unit(rr.MP, rr.MP.vec(iq)))
+        RRi = [[sum(R[i][k] * Ri[k][j_] for k in range(3)) for j_ in range(3)] for i in range(3)]
+        assert max(abs(Pb.ximat(trunk)[i][k] - RRi[i][k]) for i in range(3) for k in range(3)) < 1e-40
+        # and q (+) eps v turns a ball in its own frame: after a turn by s about the same axis the angle is t + s
+        vel = [0.0] * kin.m.nv
+        vel[bk.dadr[jt]:bk.dadr[jt] + 3] = [float(x) for x in n]
+        qs = bk.displaced(qb, vel, mpf(0.25))
+        assert max(abs(x - w) for x, w in zip(qs[adr:adr + 4], [M.cos((t + 0.25) / 2)] + [M.sin((t + 0.25) / 2) * mpf(float(v)) for v in n])) < 1e-15
     finally:
-        ca["jnt_type"] = saved
+        for k, v in saved.items():
+            a[k] = v
 
 
 def test_reference_com_velocity_is_the_mass_weighted_body_velocity():
