@@ -588,6 +588,92 @@ int mjpcx_sample_gradient_update_batched(mjpcx_ctx* ctx, int num_envs, int num_g
                                          double* best_return, double* nominal_return, double* improvement, double* spline_values,
                                          double* gradient);
 
+/* CMA-ES (covariance matrix adaptation evolution strategy) for E environments, beside the reference's planners: the search distribution
+ * N(m, sigma^2 D C D) over the d = num_nodes x nu spline parameters (j = node * nu + actuator) lives in the context and is advanced on
+ * the device. D = diag(s_k), s_k = 0.5 (hi_k - lo_k) the half control range of actuator k, so sigma and C are in normalised
+ * coordinates. Per environment the context holds sigma (the step size), C (d x d, symmetric), A (its lower Cholesky factor, C = A A^T),
+ * the evolution paths p_sigma and p_c, and generation (the updates applied since the state was set) -- all fp64 whatever the context's
+ * precision. The mean m is NOT in the context: it is the nominal spline, which the host owns and resamples at every plan step's node
+ * times. A plan step is mjpcx_rollout_cma_batched, then mjpcx_cma_update_batched, which ends in the step's ONE sync; no candidate
+ * spline, no normal and no covariance crosses the host.
+ * The variant is the Cholesky form with positive recombination weights, no eigendecomposition. Deviations, on purpose:
+ *   - the sigma path uses A^-1 where Hansen's tutorial has C^-1/2: A^-1 (m' - m) / sigma is exactly the weighted mean z_w of the
+ *     ranked standard normals, so p_sigma accumulates z_w (a rotation of the tutorial's vector: the same length distribution);
+ *   - C, A, the paths and sigma are not shifted in time when the node times move on between plan steps (mjpcx_ce_update_batched's
+ *     variance is not either);
+ *   - candidate 0, the mean itself, is rolled out and can be the argmin, but is not ranked: the update sees candidates 1..n-1.
+ *
+ * mjpcx_cma_set_state_batched sets the state of num_envs environments of num_params = d parameters: sigma[E]; C (E x d x d, row-major;
+ * NULL: the identity), p_sigma and p_c (E x d; NULL: zeros); generation = 0. C is factored on the device by the update's routine
+ * (below, with pivot_floor = 0). A setup call: it synchronises. MJPCX_EINVAL: a sigma that is not finite or is <= 0, a path or C that is
+ * not finite, a C that is not symmetric (C[a][b] != C[b][a]) or not positive definite (a pivot <= 0) -- the message names the
+ * environment, and no state is set afterwards --, d not a multiple of nu. MJPCX_EUNSUPPORTED: d > MJPCX_CMA_MAX_PARAMS (the message
+ * names d: the dense factor is built in LDS; a separable variant for wider models is not implemented), or a sharded context. */
+#define MJPCX_CMA_MAX_PARAMS 128
+int mjpcx_cma_set_state_batched(mjpcx_ctx* ctx, int num_envs, int num_params, const double* sigma /* E */, const double* C,
+                                const double* p_sigma, const double* p_c);
+/* The state as it stands: sigma[E], generation[E], C and A (E x d x d; A has zeros above the diagonal), p_sigma and p_c (E x d). Any
+ * output may be NULL. Synchronises. MJPCX_ESTATE when no state of this num_envs and num_params is set. */
+int mjpcx_cma_get_state_batched(mjpcx_ctx* ctx, int num_envs, int num_params, double* sigma, int64_t* generation, double* C,
+                                double* A, double* p_sigma, double* p_c);
+
+/* The candidates, written on the device, and their batched rollout; nothing is read back, no sync. m = nominal_values (E x P x nu).
+ * Local candidate 0 is m as given (not clamped). Candidate c = 1..n-1 of environment e, in fp64 with every product and sum rounded
+ * on its own (no fma):
+ *   z[j]  = gaussian_pair(seed + e, c, j >> 1, iteration)[j & 1]            (the counters of mjpcx_rollout_sample_gradient_batched)
+ *   y[a]  = sum_{b <= a} A[a][b] * z[b], b ascending, starting from 0.0
+ *   node  = clamp(m[a] + (sigma * s_k) * y[a], lo_k, hi_k), k = a % nu, s_k = 0.5 * (hi_k - lo_k), cast to the context's type.
+ * Environment e of a call equals a one-environment call with seed + e, bit for bit. Afterwards the context's last rollout is a batched
+ * one of E x n: every getter works on it. Validation and error codes as mjpcx_rollout_noise_batched, plus MJPCX_ESTATE when no state
+ * of num_envs environments and num_nodes x nu parameters is set. mjpcx_set_pruning_batched does not apply. With the timer on
+ * (mjpcx_timing_reset) the call is one launch whose first kernel is the candidate kernel: mjpcx_timing_read_main gives its time. */
+int mjpcx_rollout_cma_batched(mjpcx_ctx* ctx, int num_envs, int n_per_env, int horizon, int num_nodes, int interpolation,
+                              const double* node_times /* E x P */, const double* nominal_values /* E x P x nu */, uint64_t seed,
+                              int iteration);
+
+/* The constants of an update; the host computes all of them (Hansen's defaults: planners.cma_parameters), so the device only adds,
+ * multiplies and divides, takes square roots and one exp. */
+typedef struct mjpcx_cma_params {
+  int32_t mu;            /* ranked candidates, 1..n-1 */
+  const double* weights; /* mu recombination weights, each > 0, best first (summing to 1 is the caller's business) */
+  double c_sigma, d_sigma, c_c, c_one, c_mu, mu_eff, chi;
+  double sigma_min, sigma_max; /* sigma is clamped to this range */
+  double pivot_floor;    /* a pivot of the factorisation must exceed pivot_floor * C'[a][a]; otherwise the covariance restarts */
+} mjpcx_cma_params;
+
+/* The update after mjpcx_rollout_cma_batched: one launch sequence, one sync, over the stored returns R[0..n) of every environment.
+ * The state used is the context's as it stands at this call; it is advanced in place (a second call advances it again). With
+ * fp64 operations in exactly this order, every product and sum rounded on its own:
+ *   order    candidates 1..n-1 in mjpcx_topk's order (ascending, ties to the lower index, NaN last); (i) is the i-th of them, i < mu.
+ *   valid    = none of the mu best is NaN. valid == 0: state and generation stay untouched, mean = nominal_values, sigma as it was.
+ *   z_(i), y_(i)  re-drawn from the counter and multiplied as in the rollout (y_(i) unclamped).
+ *   z_w[j]   = sum_i w_i * z_(i)[j] over the ranks: 256 strided partial sums from 0.0 (partial t takes ranks t, t + 256, ...), then the
+ *              halving tree sum[t] += sum[t + s], s = 128 .. 1 -- the shape of mjpcx_sample_gradient_update_batched's sums.
+ *   y_w[a]   = sum_{b <= a} A[a][b] * z_w[b], as above.
+ *   mean[a]  = clamp(m[a] + (sigma * s_k) * y_w[a], lo_k, hi_k)
+ *   p_sigma[j] <- ((1 - c_sigma) * p_sigma[j]) + (sqrt((c_sigma * (2 - c_sigma)) * mu_eff) * z_w[j])         (the host's square root)
+ *   norm     = sqrt(sum_j p_sigma[j] * p_sigma[j]), j ascending from 0.0
+ *   h_sigma  = [ norm / sqrt(1 - (1 - c_sigma)^(2 g)) < (1.4 + 2 / (d + 1)) * chi ], g = generation + 1      (both sides' constants the host's)
+ *   p_c[a]   <- ((1 - c_c) * p_c[a]) + (h * y_w[a]), h = h_sigma ? sqrt((c_c * (2 - c_c)) * mu_eff) : 0
+ *   C'[a][b] = ((decay * C[a][b]) + c_one * (p_c[a] * p_c[b])) + c_mu * S[a][b] for a >= b, mirrored, with
+ *              decay = ((1 - c_one) - c_mu) [+ (c_one * c_c) * (2 - c_c) when h_sigma == 0] and
+ *              S[a][b] = sum_i (w_i * y_(i)[a]) * y_(i)[b] in the tree shape above.
+ *   sigma'   = clamp(sigma * exp((c_sigma / d_sigma) * ((norm / chi) - 1)), sigma_min, sigma_max)
+ *   A'       by columns b = 0..d-1: acc = sum_{k < b} A'[a][k] * A'[b][k], k ascending from 0.0; s = C'[a][b] - acc; the diagonal needs
+ *            s > pivot_floor * C'[b][b] and is sqrt(s); below it A'[a][b] = s / A'[b][b].
+ *   restart  a failed pivot: C = A = I, both paths zero, sigma' kept, restarted = 1 (the generation still counts).
+ * Outputs per environment: index (the argmin over ALL n returns, candidate 0 included, LOCAL), best_return, nominal_return = R[0],
+ * improvement = max(R[0] - best_return, 0), valid, restarted, sigma (the new one), mean (E x d), order (E x mu, may be NULL). Any
+ * output but index may be NULL. Deterministic, no atomics: two calls from the same state and rollout give the same bits; environment
+ * e's outputs do not depend on num_envs or on the other environments. With the timer on the call counts as one launch whose first
+ * kernel is the ranking. MJPCX_EINVAL: the last rollout was not a mjpcx_rollout_cma_batched of num_envs environments (or the state
+ * was set for another shape since); mu outside 1..n-1; c_one + c_mu > 1; a constant or weight that is not finite or is outside its
+ * range (weights, d_sigma, mu_eff, chi, sigma_min > 0; c_sigma, c_c in (0, 1]; c_one, c_mu, pivot_floor >= 0; sigma_max >= sigma_min).
+ * MJPCX_ESTATE when the last rollout was pruned; MJPCX_EUNSUPPORTED on a sharded context. */
+int mjpcx_cma_update_batched(mjpcx_ctx* ctx, int num_envs, const mjpcx_cma_params* params, int32_t* index, double* best_return,
+                             double* nominal_return, double* improvement, int32_t* valid, int32_t* restarted, double* sigma,
+                             double* mean /* E x P*nu */, int32_t* order /* E x mu or NULL */);
+
 /* Block until everything queued on the context's stream has finished. */
 int mjpcx_sync(mjpcx_ctx* ctx);
 

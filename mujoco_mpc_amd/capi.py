@@ -39,10 +39,21 @@ EXPORTS = [
     "mjpcx_set_prune_rank", "mjpcx_rank_bound_batched",
     "mjpcx_rollout_noise_ensemble", "mjpcx_ensemble_best",
     "mjpcx_mppi_update_batched",
+    "mjpcx_cma_set_state_batched", "mjpcx_cma_get_state_batched", "mjpcx_rollout_cma_batched", "mjpcx_cma_update_batched",
 ]
 
 MAX_HYPOTHESES = 32                           # MJPCX_MAX_HYPOTHESES of mjpcx_ensemble_best
 SG_COMPUTE_WEIGHTS, SG_ZERO_GRADIENT = 1, 2   # MJPCX_SG_* flags of mjpcx_sample_gradient_update_batched
+CMA_MAX_PARAMS = 128                          # MJPCX_CMA_MAX_PARAMS of mjpcx_cma_set_state_batched
+
+
+class MjpcxCmaParams(C.Structure):
+    """mjpcx_cma_params (include/mjpcx.h)"""
+    _fields_ = ([("mu", C.c_int32), ("weights", C.POINTER(C.c_double))] +
+                [(k, C.c_double) for k in ("c_sigma", "d_sigma", "c_c", "c_one", "c_mu", "mu_eff", "chi", "sigma_min", "sigma_max", "pivot_floor")])
+
+
+CMA_CONSTANTS = tuple(f[0] for f in MjpcxCmaParams._fields_[2:])
 
 _LIB = None
 
@@ -94,6 +105,11 @@ def lib():
         L.mjpcx_sample_gradient_update_batched.argtypes = ([vp] + [C.c_int] * 3 + [C.c_double] * 4 + [c_i32p, c_i32p] + [c_f64p] * 5)
         L.mjpcx_best_batched.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p, c_f64p]
         L.mjpcx_mppi_update_batched.argtypes = [vp, C.c_int, c_f64p, C.c_int, c_i32p] + [c_f64p] * 4 + [c_i32p, c_f64p, c_f64p]
+        L.mjpcx_cma_set_state_batched.argtypes = [vp, C.c_int, C.c_int] + [c_f64p] * 4
+        L.mjpcx_cma_get_state_batched.argtypes = [vp, C.c_int, C.c_int, c_f64p, C.POINTER(C.c_int64)] + [c_f64p] * 4
+        L.mjpcx_rollout_cma_batched.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.c_uint64, C.c_int]
+        L.mjpcx_cma_update_batched.argtypes = ([vp, C.c_int, C.POINTER(MjpcxCmaParams), c_i32p] + [c_f64p] * 3 + [c_i32p, c_i32p, c_f64p, c_f64p,
+                                                                                                                  c_i32p])
         L.mjpcx_rollout_noise_ensemble.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
         L.mjpcx_ensemble_best.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_i32p] + [C.POINTER(C.c_double)] * 2 + [c_f64p] * 3
         L.mjpcx_rollout_noise_batched_ce.argtypes = [vp] + [C.c_int] * 5 + [c_f64p, c_f64p, c_f64p, C.POINTER(MjpcxNoiseSpec)]
@@ -487,6 +503,67 @@ class Context:
                                                   as_f64p(out["best_return"]), as_f64p(out["ref_return"]), as_f64p(out["weight_sum"]),
                                                   as_f64p(out["effective_samples"]), as_i32p(out["valid"]), as_f64p(out["mean"]),
                                                   as_f64p(out["weights"]) if want_weights else None))
+        return out
+
+    def cma_set_state_batched(self, num_envs, num_params, sigma, C_=None, p_sigma=None, p_c=None):
+        """the CMA-ES state of every environment (mjpcx_cma_set_state_batched): sigma E (or one for all), C E x d x d (None: the identity),
+        p_sigma / p_c E x d (None: zeros); C is factored on the device, generation = 0"""
+        E, d = int(num_envs), int(num_params)
+        sig = _f(sigma).reshape(-1)
+        if sig.size == 1:
+            sig = np.full(max(E, 1), sig[0])
+        opt = []
+        for name, a, size in (("C", C_, E * d * d), ("p_sigma", p_sigma, E * d), ("p_c", p_c, E * d)):
+            a = None if a is None else _f(a)
+            if a is not None and a.size != max(size, 0):
+                raise ValueError(f"cma_set_state_batched: {name} of {a.size} entries for {E} environments x {d} parameters")
+            opt.append(a)
+        if sig.size != max(E, 1):
+            raise ValueError(f"cma_set_state_batched: {sig.size} step sizes for {E} environments")
+        self._chk(lib().mjpcx_cma_set_state_batched(self.handle, E, d, as_f64p(sig), *[as_f64p(a) if a is not None else None for a in opt]))
+
+    def cma_get_state_batched(self, num_envs, num_params):
+        """dict of sigma (E), generation (E), C, A (E x d x d), p_sigma, p_c (E x d) as the context holds them"""
+        E, d = int(num_envs), int(num_params)
+        Ea, da = max(E, 1), max(d, 1)
+        out = dict(sigma=np.zeros(Ea), generation=np.zeros(Ea, np.int64), C=np.zeros((Ea, da, da)), A=np.zeros((Ea, da, da)),
+                   p_sigma=np.zeros((Ea, da)), p_c=np.zeros((Ea, da)))
+        self._chk(lib().mjpcx_cma_get_state_batched(self.handle, E, d, as_f64p(out["sigma"]), out["generation"].ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    as_f64p(out["C"]), as_f64p(out["A"]), as_f64p(out["p_sigma"]), as_f64p(out["p_c"])))
+        return out
+
+    def rollout_cma_batched(self, n_per_env, horizon, interp, node_times, nominal, seed=0, iteration=0, num_envs=None):
+        """the CMA-ES candidates, generated on the device from the context's state, and their rollout (mjpcx_rollout_cma_batched):
+        node_times E x P, nominal (the mean) E x P x nu; local candidate 0 the mean, c >= 1 clamp(mean + sigma s (A z)) with the normals of
+        (seed + e, c, pair, iteration)"""
+        nt, nom = _f(node_times), _f(nominal)
+        E = int(num_envs) if num_envs is not None else (nt.shape[0] if nt.ndim == 2 else 1)
+        P = nt.size // E if E > 0 else nt.size
+        n = int(n_per_env)
+        assert E < 1 or nom.size == E * P * self.nu
+        self._chk(lib().mjpcx_rollout_cma_batched(self.handle, E, n, int(horizon), P, int(interp), as_f64p(nt), as_f64p(nom), int(seed), int(iteration)))
+        self.N, self.H, self.P, self.n_per_env = E * n, int(horizon), P, n
+
+    def cma_update_batched(self, num_envs, params, want_order=False):
+        """the CMA-ES update of every environment after rollout_cma_batched, one launch sequence / one sync (mjpcx_cma_update_batched).
+        params: dict of mu, weights (mu) and the constants CMA_CONSTANTS (planners.cma_parameters plus sigma_min, sigma_max, pivot_floor).
+        -> dict of index (E: the argmin over all candidates, local), best_return, nominal_return, improvement, valid, restarted, sigma
+        (E), mean (E x P x nu) and, want_order, order (E x mu; else None). The distribution itself stays in the context."""
+        E, mu = int(num_envs), int(params["mu"])
+        Ea = max(E, 1)
+        w = np.ascontiguousarray(params["weights"], dtype=np.float64).reshape(-1)
+        if w.size != max(mu, 0):
+            raise ValueError(f"cma_update_batched: {w.size} weights for mu = {mu}")
+        if w.size == 0:
+            w = np.zeros(1)
+        prm = MjpcxCmaParams(mu, as_f64p(w), *[float(params[k]) for k in CMA_CONSTANTS])
+        out = dict(index=np.zeros(Ea, np.int32), best_return=np.zeros(Ea), nominal_return=np.zeros(Ea), improvement=np.zeros(Ea),
+                   valid=np.zeros(Ea, np.int32), restarted=np.zeros(Ea, np.int32), sigma=np.zeros(Ea), mean=np.zeros((Ea, max(self.P, 1), self.nu)),
+                   order=np.zeros((Ea, max(mu, 1)), np.int32) if want_order else None)
+        self._chk(lib().mjpcx_cma_update_batched(self.handle, E, C.byref(prm), as_i32p(out["index"]), as_f64p(out["best_return"]),
+                                                 as_f64p(out["nominal_return"]), as_f64p(out["improvement"]), as_i32p(out["valid"]),
+                                                 as_i32p(out["restarted"]), as_f64p(out["sigma"]), as_f64p(out["mean"]),
+                                                 as_i32p(out["order"]) if want_order else None))
         return out
 
     def rollout_noise_ensemble(self, n, horizon, interp, node_times, nominal, noise_spec, num_hypotheses):

@@ -1435,6 +1435,250 @@ class GpuMPPIPlanner:
         return self.fleet.num_parameters()
 
 
+def cma_parameters(d, lam):
+    """Hansen's default strategy parameters (The CMA Evolution Strategy: A Tutorial, table 1, positive weights only) for d parameters
+    and lam ranked candidates: dict of mu = lam // 2, weights (mu, w_i proportional to ln((lam + 1) / 2) - ln i, summing to 1),
+    mu_eff, c_sigma, d_sigma, c_c, c_one, c_mu = min(1 - c_one, .), chi = E|N(0, I_d)|."""
+    d, lam = int(d), int(lam)
+    mu = lam // 2
+    if d < 1 or mu < 1:
+        raise ValueError(f"cma_parameters: d = {d}, lam = {lam}; needs d >= 1 and lam >= 2")
+    raw = np.array([math.log((lam + 1) / 2.0) - math.log(i) for i in range(1, mu + 1)])
+    w = raw / raw.sum()
+    mu_eff = float(1.0 / np.sum(w * w))
+    c_sigma = (mu_eff + 2.0) / (d + mu_eff + 5.0)
+    d_sigma = 1.0 + 2.0 * max(0.0, math.sqrt((mu_eff - 1.0) / (d + 1.0)) - 1.0) + c_sigma
+    c_c = (4.0 + mu_eff / d) / (d + 4.0 + 2.0 * mu_eff / d)
+    c_one = 2.0 / ((d + 1.3) ** 2 + mu_eff)
+    c_mu = min(1.0 - c_one, 2.0 * (mu_eff - 2.0 + 1.0 / mu_eff) / ((d + 2.0) ** 2 + mu_eff))
+    chi = math.sqrt(d) * (1.0 - 1.0 / (4.0 * d) + 1.0 / (21.0 * d * d))
+    return dict(mu=mu, weights=w, mu_eff=mu_eff, c_sigma=c_sigma, d_sigma=d_sigma, c_c=c_c, c_one=c_one, c_mu=c_mu, chi=chi)
+
+
+def cma_lower_times(A, z):
+    """y[..., a] = sum_{b <= a} A[a][b] z[..., b], b ascending from 0.0, every product and sum rounded on its own: the candidates' and
+    the update's matrix-vector product (cma_row, csrc/cma_update.h)"""
+    A, z = np.asarray(A, dtype=np.float64), np.asarray(z, dtype=np.float64)
+    y = np.zeros(z.shape)
+    for b in range(A.shape[0]):
+        y[..., b:] += z[..., b:b + 1] * A[b:, b]
+    return y
+
+
+def cma_factor(C, pivot_floor=0.0):
+    """The lower Cholesky factor by columns in the device's order (cma_factor, csrc/cma_update.h): acc = sum_{k < b} A[a][k] A[b][k]
+    ascending from 0.0, s = C[a][b] - acc, the diagonal needs s > pivot_floor * C[b][b] and is sqrt(s), below it s / A[b][b].
+    -> A, or None when a pivot fails."""
+    C = np.asarray(C, dtype=np.float64)
+    d = C.shape[0]
+    A = np.zeros((d, d))
+    for b in range(d):
+        acc = np.zeros(d - b)
+        for k in range(b):
+            acc += A[b:, k] * A[b, k]
+        s = C[b:, b] - acc
+        if not s[0] > pivot_floor * C[b, b]:
+            return None
+        A[b, b] = np.sqrt(s[0])
+        A[b + 1:, b] = s[1:] / A[b, b]
+    return A
+
+
+def cma_candidates(nominal, z, sigma, A, ctrlrange):
+    """The n candidates of mjpcx_rollout_cma_batched in its order of operations: row 0 the mean as given, row c >= 1
+    clamp(m + (sigma s) (A z[c])), s the half control range; nominal d (parameter j belongs to actuator j % nu), z n x d."""
+    m = np.asarray(nominal, dtype=np.float64).reshape(-1)
+    b = np.asarray(ctrlrange, dtype=np.float64).reshape(-1, 2)
+    lo, hi = np.resize(b[:, 0], m.size), np.resize(b[:, 1], m.size)
+    step = np.float64(sigma) * (0.5 * (hi - lo))
+    out = np.maximum(lo, np.minimum(hi, m + step * cma_lower_times(A, np.asarray(z, dtype=np.float64).reshape(-1, m.size))))
+    out[0] = m
+    return out
+
+
+def cma_update(returns, nominal, z, state, params, ctrlrange):
+    """The CMA-ES update of one environment in the device's order of operations -- the single statement of the arithmetic of
+    mjpcx_cma_update_batched (include/mjpcx.h), next to sample_gradient_update. `returns` n, `nominal` the mean's d parameters, `z` the
+    standard normals n x d of the candidates (row 0 is not read), `state` dict of sigma, C, A, p_sigma, p_c, generation, `params`
+    cma_parameters' dict plus sigma_min, sigma_max, pivot_floor. The Cholesky form: p_sigma accumulates z_w = A^-1 (m' - m) / sigma
+    where Hansen's tutorial has C^-1/2 (m' - m) / sigma.
+    -> dict of order (the mu best of candidates 1..n-1: ascending, ties to the lower index, NaN last), index (the argmin over all n),
+    best_return, nominal_return, improvement, valid, restarted, sigma, mean, z_w, y_w, y (mu x d), S, C_new (before a restart), h_sigma,
+    state (the new one; the old one untouched when not valid)."""
+    ret = np.asarray(returns, dtype=np.float64).reshape(-1)
+    m = np.asarray(nominal, dtype=np.float64).reshape(-1)
+    n, d, mu = ret.size, m.size, int(params["mu"])
+    if not 1 <= mu <= n - 1:
+        raise ValueError(f"mu = {mu} outside 1..{n - 1}")
+    w = np.asarray(params["weights"], dtype=np.float64).reshape(-1)
+    order = (np.lexsort((np.arange(1, n), ret[1:])) + 1)[:mu]
+    index = int(np.lexsort((np.arange(n), ret))[0])
+    gain = ret[0] - ret[index]
+    sigma = np.float64(state["sigma"])
+    out = dict(order=order, index=index, best_return=ret[index], nominal_return=ret[0], improvement=float(gain) if gain > 0 else 0.0,
+               valid=int(not np.isnan(ret[order]).any()), restarted=0, sigma=float(sigma), mean=m.copy(), state=state)
+    if not out["valid"]:
+        return out
+    A, C = np.asarray(state["A"], dtype=np.float64), np.asarray(state["C"], dtype=np.float64)
+    cs, cc, c1, cmu = (np.float64(params[k]) for k in ("c_sigma", "c_c", "c_one", "c_mu"))
+    mu_eff, chi = np.float64(params["mu_eff"]), np.float64(params["chi"])
+    b = np.asarray(ctrlrange, dtype=np.float64).reshape(-1, 2)
+    lo, hi = np.resize(b[:, 0], d), np.resize(b[:, 1], d)
+    zs = np.asarray(z, dtype=np.float64).reshape(n, d)[order]
+    y = cma_lower_times(A, zs)
+    z_w = strided_tree_sum(w[:, None] * zs)
+    y_w = cma_lower_times(A, z_w)
+    mean = np.maximum(lo, np.minimum(hi, m + (sigma * (0.5 * (hi - lo))) * y_w))
+    p_sigma = (1.0 - cs) * np.asarray(state["p_sigma"], dtype=np.float64) + np.sqrt((cs * (2.0 - cs)) * mu_eff) * z_w
+    n2 = np.float64(0.0)
+    for v in p_sigma:
+        n2 = n2 + v * v
+    norm = np.sqrt(n2)
+    g = int(state["generation"]) + 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h_sigma = bool(norm / np.float64(math.sqrt(1.0 - math.pow(1.0 - float(cs), 2.0 * g))) < (1.4 + 2.0 / (d + 1.0)) * chi)
+    hc = np.sqrt((cc * (2.0 - cc)) * mu_eff) if h_sigma else np.float64(0.0)
+    p_c = (1.0 - cc) * np.asarray(state["p_c"], dtype=np.float64) + hc * y_w
+    decay = (1.0 - c1) - cmu
+    if not h_sigma:
+        decay = decay + (c1 * cc) * (2.0 - cc)
+    S = strided_tree_sum((w[:, None] * y)[:, :, None] * y[:, None, :])
+    full = (decay * C + c1 * (p_c[:, None] * p_c[None, :])) + cmu * S
+    C_new = np.tril(full) + np.tril(full, -1).T           # the entries a >= b, mirrored
+    grown = sigma * np.exp((cs / np.float64(params["d_sigma"])) * ((norm / chi) - 1.0))
+    sigma_new = float(min(max(grown, np.float64(params["sigma_min"])), np.float64(params["sigma_max"])))
+    A_new = cma_factor(C_new, float(params["pivot_floor"]))
+    new = dict(sigma=sigma_new, generation=g)
+    if A_new is None:
+        new.update(C=np.eye(d), A=np.eye(d), p_sigma=np.zeros(d), p_c=np.zeros(d))
+    else:
+        new.update(C=C_new, A=A_new, p_sigma=p_sigma, p_c=p_c)
+    out.update(restarted=int(A_new is None), sigma=sigma_new, mean=mean, z_w=z_w, y_w=y_w, y=y, S=np.tril(S) + np.tril(S, -1).T, C_new=C_new,
+               h_sigma=int(h_sigma), norm=float(norm), state=new)
+    return out
+
+
+class GpuBatchCMAESPlanner(GpuBatchSamplingPlanner):
+    """CMA-ES (covariance matrix adaptation) for `num_envs` environments on ONE context, the search distribution on the device: where
+    Predictive Sampling, Cross-Entropy and MPPI search with a diagonal distribution, this one learns the d x d covariance of the
+    d = spline points x nu parameters -- actuators correlated across a gait, knots correlated in time -- and its own step size. A plan
+    step is `generations` times: the host resample of every nominal (the mean), one `set_states`, one `rollout_cma_batched` (the
+    candidates mean + sigma s A z are written on the device; candidate 0 is the mean), one `cma_update_batched` and ONE sync; the
+    returned mean is the member's new policy and the next generation's nominal. Covariance, factor, paths and step size never leave
+    the context. Member e plans exactly like GpuCMAESPlanner(seed = s + e), which is this class with one environment.
+
+    The Cholesky form with positive weights and Hansen's default parameters (`cma_parameters`; lam = num_trajectory_ - 1, the mean is
+    not ranked). Coordinates are normalised by the half control range, so `sigma0` is a fraction of it; None: the model's
+    `sampling_exploration`. sigma stays within [sigma_min, sigma_max]. The state starts at sigma0, C = I and zero paths in `allocate`,
+    `reset`, and whenever the number of spline points changes; it is NOT shifted in time between plan steps (Cross-Entropy's variance
+    is not either). d is at most capi.CMA_MAX_PARAMS = 128 (the A1 with up to 10 spline points); the Humanoid's 336 are refused.
+    Every return is needed, so there is no `pruning` here. A member whose mu best returns hold a NaN (`valid` 0) keeps its policy and
+    its distribution. `best_trajectory(env)` is the rollout of the member's LOWEST-RETURN candidate (`winner`), not of the new mean,
+    which was never rolled out. Per member after a plan: `sigma`, `best_return`, `nominal_return`, `improvement`, `restarted`, `valid`,
+    `winner`."""
+    pivot_floor = 1.0e-12     # a pivot of the factorisation must exceed this share of its diagonal entry, else C restarts at I
+
+    def __init__(self, num_envs, device=0, precision=64, seed=0, sigma0=None, sigma_min=1.0e-6, sigma_max=2.0, generations=1,
+                 backend_factory=None):
+        super().__init__(num_envs, device, precision, seed, backend_factory)
+        del self.pruning
+        self.sigma0, self.sigma_min, self.sigma_max, self.generations = sigma0, float(sigma_min), float(sigma_max), int(generations)
+        self._state_for = None    # (context, d) the context's CMA state was set for
+        self._defaults = None     # ((d, n), cma_parameters(d, n - 1))
+        for p in self.envs:
+            p.sigma, p.restarted, p.valid = None, 0, 1
+
+    def _reset_own(self):
+        super()._reset_own()
+        self._state_for = None
+
+    def allocate(self):
+        super().allocate()
+        self._state_for = None
+
+    def _sigma0(self):
+        s = self.envs[0].noise_exploration[0] if self.sigma0 is None else self.sigma0
+        s = np.asarray(s, dtype=np.float64).reshape(-1)
+        return np.full(self.num_envs, s[0]) if s.size == 1 else s
+
+    def _enqueue(self, horizon, prune):
+        n = self.num_trajectory_
+        plans = [p.policy.plan for p in self.envs]
+        d = plans[0].size() * self.model.nu
+        if d > capi.CMA_MAX_PARAMS:
+            raise ValueError(f"{type(self).__name__}: {d} parameters ({plans[0].size()} spline points x {self.model.nu} actuators); the dense "
+                             f"covariance is kept for at most {capi.CMA_MAX_PARAMS}")
+        self._push_states()
+        if self._state_for is None or self._state_for[0] is not self.ctx or self._state_for[1] != d:
+            self.ctx.cma_set_state_batched(self.num_envs, d, self._sigma0())
+            self._state_for = (self.ctx, d)
+        self._pruned = False
+        self.ctx.rollout_cma_batched(n, horizon, plans[0].interpolation(), np.stack([pl.times() for pl in plans]),
+                                     np.stack([pl.values() for pl in plans]), seed=self.seed, iteration=self.iteration, num_envs=self.num_envs)
+        self._last = "plan"
+        self._n = n
+
+    def cma_params(self, d):
+        """the update's constants for d parameters and the current candidate count (Hansen's defaults, computed once per shape)"""
+        key = (d, self.num_trajectory_)
+        if self._defaults is None or self._defaults[0] != key:
+            self._defaults = (key, cma_parameters(d, self.num_trajectory_ - 1))
+        return dict(self._defaults[1], sigma_min=self.sigma_min, sigma_max=self.sigma_max, pivot_floor=self.pivot_floor)
+
+    def optimize_policy(self, horizon, pool=None):
+        if self.generations < 1:
+            raise ValueError(f"{type(self).__name__}: generations = {self.generations}; at least one")
+        for _ in range(self.generations):
+            t0 = self._launch(horizon)
+            out = self.ctx.cma_update_batched(self.num_envs, self.cma_params(self._state_for[1]))
+            # (a member that is not valid: its resampled nominal)
+            values = [out["mean"][e] if out["valid"][e] else p.policy.plan.values() for e, p in enumerate(self.envs)]
+            self._finish(t0, [([out["index"][e]], [out["best_return"][e]], 0, values[e]) for e in range(self.num_envs)])
+            for e, p in enumerate(self.envs):
+                p.best_return, p.nominal_return = float(out["best_return"][e]), float(out["nominal_return"][e])
+                p.improvement = float(out["improvement"][e])
+                p.sigma, p.restarted, p.valid = float(out["sigma"][e]), int(out["restarted"][e]), int(out["valid"][e])
+
+
+class GpuCMAESPlanner:
+    """CMA-ES for one robot: GpuBatchCMAESPlanner with ONE environment -- the same code, so a fleet's member e IS this planner with
+    seed s + e. The candidate count must be a multiple of 64, the mean included. `best_trajectory()` is the lowest-return candidate's
+    rollout."""
+    winner, improvement, best_return, nominal_return = (_member_attr(k) for k in ("winner", "improvement", "best_return", "nominal_return"))
+    sigma, restarted, valid = (_member_attr(k) for k in ("sigma", "restarted", "valid"))
+    policy, previous_policy, noise_exploration = (_member_attr(k) for k in ("policy", "previous_policy", "noise_exploration"))
+    iteration, ctx, model, task, num_trajectory_ = (_fleet_attr(k) for k in ("iteration", "ctx", "model", "task", "num_trajectory_"))
+    sigma0, sigma_min, sigma_max, generations = (_fleet_attr(k) for k in ("sigma0", "sigma_min", "sigma_max", "generations"))
+
+    def __init__(self, device=0, precision=64, seed=0, sigma0=None, sigma_min=1.0e-6, sigma_max=2.0, generations=1, backend_factory=None):
+        self.fleet = GpuBatchCMAESPlanner(1, device, precision, seed, sigma0, sigma_min, sigma_max, generations, backend_factory)
+        self.seed = seed
+
+    def initialize(self, model, task: Task):
+        self.fleet.initialize(model, task)
+
+    def allocate(self):
+        self.fleet.allocate()
+
+    def reset(self, horizon, initial_repeated_action=None):
+        self.fleet.reset(horizon, initial_repeated_action)
+
+    def set_state(self, state: State):
+        self.fleet.set_states([state])
+
+    def optimize_policy(self, horizon, pool=None):
+        self.fleet.optimize_policy(horizon, pool)
+
+    def action_from_policy(self, action, state, time, use_previous=False):
+        return self.fleet.action_from_policy(0, action, state, time, use_previous)
+
+    def best_trajectory(self):
+        return self.fleet.best_trajectory(0)
+
+    def num_parameters(self):
+        return self.fleet.num_parameters()
+
+
 class GpuCrossEntropyPlanner(_ContextOwner):
     """mjpc::CrossEntropyPlanner (mjpc/planners/cross_entropy/planner.{h,cc}) with the candidate
     fan-out, the sort and the elite statistics on the GPU. Differences forced by SURVEY F4/F5 as for

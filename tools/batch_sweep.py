@@ -51,6 +51,13 @@ step as above (set_states, rollout_noise_batched, best_batched); (b) "ensemble":
 default E: the mean). The same launch over E x n rollouts with the noise stream shared, and ensemble_best in place of best_batched: the
 expectation is equal times. Default shape 8 x 2048 on the A1, H = 100, fp64; default output profiles/batch_sweep_ensemble.jsonl.
 
+--planner cmaes: the CMA-ES plan step (set_states, rollout_cma_batched, cma_update_batched; Hansen's defaults, sigma0 the model's
+sampling_exploration, the returned mean the next nominal, the distribution moving on from step to step; once with sigma free in
+[1e-6, 2] and once with sigma held at sampling_exploration) against the unpruned Predictive Sampling plan step of the same fleet,
+alternating as for --planner mppi; then the candidate kernel (the first kernel of the rollout's launch) and the update alone under the
+context's timer. Default shapes as for mppi; default output
+profiles/batch_sweep_cmaes.jsonl.
+
 --planner mppi: the MPPI plan step against the unpruned Predictive Sampling plan step of the same fleet. Two variants alternating in one
 session on one context, from the same states and nominal, for --rounds rounds (default 2) of --steps timed steps each: (a) "sampling":
 set_states, rollout_noise_batched, best_batched; (b) "mppi": set_states, rollout_noise_batched, mppi_update_batched. The launch is the same;
@@ -281,6 +288,86 @@ def sweep_mppi(name, precision, H, shapes, steps, warmup, out, temperature=None,
                "sampling_spread_between_rounds_ms": float(max(med("sampling_ms")) - min(med("sampling_ms"))),
                "update_call_ms": stats(tu), "update_kernels_ms": both_ms / max(calls, 1), "update_weights_kernel_ms": first_ms / max(calls, 1),
                "update_mean_kernel_ms": (both_ms - first_ms) / max(calls, 1)}
+        print(json.dumps(rec), flush=True)
+        out.write(json.dumps(rec) + "\n")
+        out.flush()
+    ctx.close()
+
+
+def sweep_cmaes(name, precision, H, shapes, steps, warmup, out, rounds=2):
+    """the CMA-ES plan step against the unpruned Predictive Sampling plan step of the same fleet, alternating (as sweep_mppi), in two
+    variants one after the other: "adaptive" (sigma free in [1e-6, 2], as the planner's defaults) and "fixed_sigma" (sigma held at the
+    model's sampling_exploration, so the candidates are as far from the mean as Predictive Sampling's: the cost of the mechanism alone).
+    As in the planner the returned mean is the next step's nominal; the states stay where they are."""
+    from mujoco_mpc_amd.planners import cma_parameters
+    task = load_task(name)
+    m = task.model
+    rng = np.random.default_rng(1)
+    ctx = capi.Context(task.packed_model(), task.packed(), 0, precision)
+    P = int(m.get_number("sampling_spline_points", 6))
+    interp = int(m.get_number("sampling_representation", capi.SPLINE_CUBIC))
+    std = float(m.get_number("sampling_exploration", 0.1))
+    dt = m.get_number("agent_timestep", m.timestep)
+    times1 = np.arange(P) * ((H - 1) * dt / max(P - 1, 1))
+    d = P * m.nu
+    for E, n in shapes:
+        states, clocks, mocap = initial(task, name, E, rng)
+        times, zeros = np.stack([times1] * E), np.zeros((E, P, m.nu))
+        defaults = cma_parameters(d, n - 1)
+        rec = {"planner": "cmaes", "task": name, "precision": precision, "horizon": H, "num_envs": E, "n_per_env": n, "steps": steps, "warmup": warmup,
+               "num_params": d, "mu": int(defaults["mu"]), "kernel": ctx.kernel_name.split(" (")[0], "sigma0": std}
+        for variant, lo, hi in (("adaptive", 1e-6, 2.0), ("fixed_sigma", std, std)):
+            prm = dict(defaults, sigma_min=lo, sigma_max=hi, pivot_floor=1e-12)
+            it = [0]
+            last = {}
+            mean = [zeros.copy()]
+            ctx.set_states(states, clocks, mocap)
+            ctx.cma_set_state_batched(E, d, std)
+
+            def sampling():
+                it[0] += 1
+                ctx.set_states(states, clocks, mocap)
+                ctx.rollout_noise_batched(n, H, interp, times, zeros, capi.make_noise_spec(seed=7, iteration=it[0], std0=std), num_envs=E)
+                ctx.best_batched(E, 0)
+
+            def cmaes():
+                ctx.set_states(states, clocks, mocap)
+                ctx.rollout_cma_batched(n, H, interp, times, mean[0], seed=7, iteration=it[0], num_envs=E)
+                last.update(ctx.cma_update_batched(E, prm))
+                mean[0] = last["mean"].copy()
+
+            for _ in range(warmup):
+                sampling()
+                cmaes()
+            per_round = []
+            for _ in range(rounds):
+                ta, tb, sig = [], [], []
+                for _ in range(steps):   # alternating: both sides see the same clocks and the same neighbours on the machine
+                    t0 = time.perf_counter(); sampling(); t1 = time.perf_counter(); cmaes(); t2 = time.perf_counter()
+                    ta.append((t1 - t0) * 1e3)
+                    tb.append((t2 - t1) * 1e3)
+                    sig.append(float(np.max(last["sigma"])))
+                per_round.append({"sampling_ms": stats(ta), "cmaes_ms": stats(tb), "largest_sigma": stats(sig)})
+            # the candidate kernel: the first kernel of the rollout's launch under the context's timer
+            ctx.timing_reset()
+            for _ in range(steps):
+                ctx.set_states(states, clocks, mocap)
+                ctx.rollout_cma_batched(n, H, interp, times, mean[0], seed=7, iteration=it[0], num_envs=E)
+            cand_ms, _ = ctx.timing_read_main()
+            launch_ms, launches = ctx.timing_read()
+            # the update alone on the last launch (the distribution moves on with every call): wall time, and its kernels' under the context's timer
+            tu = []
+            ctx.timing_reset()
+            for _ in range(steps):
+                t0 = time.perf_counter(); ctx.cma_update_batched(E, prm); tu.append((time.perf_counter() - t0) * 1e3)
+            first_ms, _ = ctx.timing_read_main()
+            all_ms, calls = ctx.timing_read()
+            med = lambda k: [r[k]["median"] for r in per_round]
+            rec[variant] = {"rounds": per_round, "sigma": [float(x) for x in last["sigma"]], "restarted": [int(x) for x in last["restarted"]],
+                            "ratio_cmaes_over_sampling": [float(b / a) for a, b in zip(med("sampling_ms"), med("cmaes_ms"))],
+                            "sampling_spread_between_rounds_ms": float(max(med("sampling_ms")) - min(med("sampling_ms"))),
+                            "update_call_ms": stats(tu), "update_kernels_ms": all_ms / max(calls, 1), "update_rank_kernel_ms": first_ms / max(calls, 1),
+                            "candidate_kernel_ms": cand_ms / max(launches, 1), "rollout_launch_kernels_ms": launch_ms / max(launches, 1)}
         print(json.dumps(rec), flush=True)
         out.write(json.dumps(rec) + "\n")
         out.flush()
@@ -794,13 +881,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "ilqs", "robust", "sample_gradient", "ensemble", "mppi"], default="sampling")
+    ap.add_argument("--planner", choices=["sampling", "cross_entropy", "gradient", "ilqg", "ilqs", "robust", "sample_gradient", "ensemble", "mppi", "cmaes"], default="sampling")
     ap.add_argument("--shapes", default=None, help="comma-separated ExN filter, e.g. 8x2048,1x16384")
     ap.add_argument("--mixed-params", action="store_true", help="every environment its own task weights, parameters and risk")
     ap.add_argument("--mixed-models", action="store_true", help="sampling, cross_entropy, ensemble: every environment its own model (payload, friction, actuator strength)")
     ap.add_argument("--tail", type=int, default=None, help="--planner ensemble: the score is the mean of the `tail` largest returns (default: all, the mean)")
     ap.add_argument("--temperature", type=float, default=None, help="--planner mppi: the temperature (default: a tenth of the spread of the first launch's returns)")
-    ap.add_argument("--rounds", type=int, default=2, help="--planner mppi: rounds of --steps alternating timed steps")
+    ap.add_argument("--rounds", type=int, default=2, help="--planner mppi, cmaes: rounds of --steps alternating timed steps")
     ap.add_argument("--robust", default="16x4", help="--planner robust: candidates x repetitions")
     ap.add_argument("--gradient-candidates", type=int, default=32, help="--planner sample_gradient: gradient candidates per environment")
     ap.add_argument("--prune", action="store_true", help="--planner sampling, cross_entropy: the batched side prunes and parks per environment (set_pruning_batched; "
@@ -810,13 +897,13 @@ def main():
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"cross_entropy": "batch_sweep_ce.jsonl", "gradient": "batch_sweep_gradient.jsonl", "ilqg": "batch_sweep_ilqg.jsonl", "ilqs": "batch_sweep_ilqs.jsonl", "robust": "batch_sweep_robust.jsonl",
-                                                       "sample_gradient": "batch_sweep_sample_gradient.jsonl", "ensemble": "batch_sweep_ensemble.jsonl", "mppi": "batch_sweep_mppi.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
+                                                       "sample_gradient": "batch_sweep_sample_gradient.jsonl", "ensemble": "batch_sweep_ensemble.jsonl", "mppi": "batch_sweep_mppi.jsonl", "cmaes": "batch_sweep_cmaes.jsonl"}.get(a.planner, "batch_sweep.jsonl"))
     keep = None if a.shapes is None else {tuple(int(x) for x in sh.split("x")) for sh in a.shapes.split(",")}
     if a.steps < 10:
         raise SystemExit("batch_sweep.py: at least 10 timed steps")
     with open(a.out, "w") as out:
         for name, precision, H, shapes in {"gradient": GRADIENT_SHAPES, "ilqg": ILQG_SHAPES, "ilqs": ILQS_SHAPES, "robust": ROBUST_SHAPES,
-                                             "sample_gradient": SAMPLE_GRADIENT_SHAPES, "ensemble": ENSEMBLE_SHAPES, "mppi": MPPI_SHAPES}.get(a.planner, SHAPES):
+                                             "sample_gradient": SAMPLE_GRADIENT_SHAPES, "ensemble": ENSEMBLE_SHAPES, "mppi": MPPI_SHAPES, "cmaes": MPPI_SHAPES}.get(a.planner, SHAPES):
             shapes = [sh for sh in shapes if keep is None or sh in keep]
             if keep is not None and a.only == name and a.planner in ("sampling", "cross_entropy"):   # (--only with --shapes: also shapes outside the default list, e.g. 16x1024)
                 shapes += [sh for sh in sorted(keep) if sh not in shapes]
@@ -826,6 +913,9 @@ def main():
                     continue
                 if a.planner == "mppi":
                     sweep_mppi(name, precision, H, shapes, a.steps, a.warmup, out, a.temperature, a.rounds)
+                    continue
+                if a.planner == "cmaes":
+                    sweep_cmaes(name, precision, H, shapes, a.steps, a.warmup, out, a.rounds)
                     continue
                 if a.mixed_models and (a.planner not in ("sampling", "cross_entropy") or name == "Cartpole"):
                     if a.planner not in ("sampling", "cross_entropy"):
